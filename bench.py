@@ -6,9 +6,15 @@ devices (L = 80, model llama_3_70b/online, kv "4bit"), each swept over all 9 k-c
 table (resident in HBM, 16 rotating copies > the Infinity Cache) through the whole reference path -- the
 lowering of every (fleet, k) (halda_p_solver.py:59-338), the exact solves (:340-353) and the argmin over k
 with the reference's tie rule (:391-414). The K timed steps are ONE group launch (halda_fleets_group_launch
--> halda_sweep_steps_kernel), bit-identical per batch to K launches (checked before timing).
+-> halda_sweep_steps_kernel), bit-identical per batch to K launches (checked before timing with --full).
 
-The ONE JSON line (compact_line: <= 3.5 KB) carries beside the headline: the roofline of the headline's
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline needs and no more: the fleets' table
+(build_table: worker processes), its resident copies, W warm-up steps, the K timed steps, then ONE JSON line
+of the contract's keys (headline_record). `--dump-outputs DIR` writes what the last timed step left in its
+result arrays (best_k, obj_value, w, n) as DIR/<name>.npy: the inputs are seeded, so two builds can be
+compared output for output. Everything below is measured with `--full` only.
+
+With `--full` the ONE JSON line (compact_line: <= 3.5 KB) carries beside the headline: the roofline of the headline's
 launch (HBM and VALU issue), the CPU baseline (the oracle -- reference lowering + scipy / HiGHS 1.8.0 -- on
 the host cores, pinned), the per-batch launches, latency mode, the C5 stream, the public batch API, the
 milp() replacement on a pre-lowered CSR batch (solve_only), config C2 (4096 M = 16 fleets, k > 1 MILPs),
@@ -79,6 +85,40 @@ def load_model():
     from distilp_amd.synth import load_model_dict
 
     return ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
+
+
+def _table_shard(job):
+    """Worker of build_table: the packed table of the fleets of `seeds` as plain arrays."""
+    from distilp_amd.solver.fleets import BYTE_FIELDS, F64_FIELDS, fleet_table
+
+    seeds, M = job
+    t = fleet_table(build_fleets(seeds, M), load_model())
+    return t.sizes(), {f: np.array(getattr(t, f)) for f in ("os_class", "flags") + F64_FIELDS + BYTE_FIELDS}
+
+
+def build_table(seeds, M: int, procs: int):
+    """fleet_table(build_fleets(seeds, M), model) made by `procs` worker processes: each makes and packs
+    a contiguous share of the seeds (a device's entries depend on its own fleet alone), the shares are
+    joined in seed order -- the same table, bit for bit (tests/test_bench_line.py). The workers never
+    touch the GPU and are started before this process initialises it. A plain run keeps only the table:
+    validating 262,144 synthetic DeviceProfiles in one process is most of the bench's set-up time."""
+    from concurrent.futures import ProcessPoolExecutor
+    from multiprocessing import get_context
+
+    from distilp_amd.solver.fleets import FleetTable
+
+    seeds = list(seeds)
+    procs = max(1, min(procs, len(seeds)))
+    cut = [len(seeds) * i // procs for i in range(procs + 1)]
+    jobs = [(seeds[a:b], M) for a, b in zip(cut, cut[1:])]
+    if procs == 1:
+        parts = [_table_shard(jobs[0])]
+    else:
+        with ProcessPoolExecutor(procs, mp_context=get_context("spawn")) as pool:
+            parts = list(pool.map(_table_shard, jobs))
+    sizes = np.concatenate([p[0] for p in parts])
+    dev_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    return FleetTable(dev_off=dev_off, **{f: np.concatenate([p[1][f] for p in parts]) for f in parts[0][1]})
 
 
 def build_workload(rank: int, fleets: int, M: int, ks=None):
@@ -792,6 +832,58 @@ def compact_line(full: dict) -> dict:
     return line
 
 
+def headline_record(args, world, rccl_world, n_fleets_rank, n_k, n_sw, total, el_sweep, n_opt=None, rounded=True):
+    """The contract's keys of the result line, from the headline's timed region alone: `total` instances in
+    `el_sweep` seconds over args.steps steps. `n_opt` (feasible instances per step, counted by --full's
+    solve-only leg) is left out of `config` when not given. `rounded`: ms_per_step as the printed line
+    carries it (6 significant digits)."""
+    strong = args.scaling == "strong"
+    ms = el_sweep / args.steps * 1e3
+    config = {
+        "workload": (f"C3: {n_fleets_rank if not strong else C3_FLEETS} M={args.M} fleets x {n_k} k "
+                     f"per {'GPU' if not strong else 'node'} (L=80, llama_3_70b/online, kv 4bit), one "
+                     "k-sweep per step from HBM-resident tables"),
+        "instances_per_step_per_gpu": n_fleets_rank * n_k,
+        "feasible_per_step_per_gpu": n_opt,
+        "parallelism": f"dp{world}",
+        "rccl_world_size": rccl_world,
+        "resident_copies": n_sw,
+    }
+    if n_opt is None:
+        del config["feasible_per_step_per_gpu"]
+    return {
+        "metric": METRIC,
+        "value": total / el_sweep,
+        "unit": "instances/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": _g(ms, 6) if rounded else ms,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded C3 fleets, distilp_amd/synth.py)",
+        "config": config,
+    }
+
+
+def dump_outputs(folder: str, out: dict, rank: int = 0) -> None:
+    """--dump-outputs: the result arrays the last timed step left on the device (a table's `out`: best_k and
+    obj_value per fleet, w and n per device -- what a caller of the launch receives), each as
+    <folder>/<name>.npy in float64 (the int32 arrays are exact in it); 4.3 MB for the C3 batch. Ranks
+    above 0 write <name>.rank<r>.npy. An array above its share of 64 MB (a --fleets far beyond C3's) is
+    written as a fixed sample of its entries (seed 0, ascending index)."""
+    d = Path(folder)
+    d.mkdir(parents=True, exist_ok=True)
+    cap = (64 << 20) // (8 * len(out))  # entries per array
+    for name, t in out.items():
+        arr = t.cpu().numpy().astype(np.float64)
+        if arr.size > cap:
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.size, cap, replace=False))]
+        np.save(d / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), arr)
+
+
 def launch_ranks(args) -> int:
     """--gpus N from a plain `python bench.py`: start N ranks (one process per GPU) with
     torch.distributed.run before this process touches the GPU, relay their output and exit code."""
@@ -826,8 +918,16 @@ def main():
     ap.add_argument("--no-c2", action="store_true", help="skip the config-2 leg (4096 M = 16 fleets)")
     ap.add_argument("--no-latency", action="store_true", help="skip the latency-mode leg")
     ap.add_argument("--ks", type=str, default="", help="diagnostic: comma-separated k-candidates instead of C3's")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline, the roofline, the per-batch launches, path B "
+                         "(solve_only), C2, latency mode, the C5 stream, the batch API, time to optimal and, on "
+                         "several GPUs, the 200-step and strong-scaling regions (DESIGN.md §5)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step left in its table's result arrays (best_k, obj_value, w, "
+                         "n: what a caller of the group launch receives) as DIR/<name>.npy, float64")
     ap.add_argument("--full-json", type=str, default="",
-                    help="also write the detailed record (every leg's figures, per-launch times) to this file")
+                    help="with --full: also write the detailed record (every leg's figures, per-launch times) to "
+                         "this file")
     ap.add_argument("--cpu-baseline-child", action="store_true")
     ap.add_argument("--cpu-core", type=int, default=0)
     ap.add_argument("--cpu-first", type=int, default=0)
@@ -848,8 +948,15 @@ def main():
         return 2
 
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_base = run_cpu_baseline(args.cpu_budget, args.M)  # before any GPU work, in child processes
+
+    ks = [int(k) for k in args.ks.split(",")] if args.ks else KS_L80
+    strong_head = args.scaling == "strong"
+    seeds = fleet_seeds(args, rank, world, strong_head)
+    if not args.full:
+        # the headline needs the fleets' field table alone: made by worker processes, before any GPU work
+        table = build_table(seeds, args.M, len(usable_cores()[0]) // world)
 
     import torch
     import torch.distributed as dist
@@ -881,12 +988,10 @@ def main():
     from distilp_amd.solver.lower import lower_fleet
 
     t_setup = time.perf_counter()
-    ks = [int(k) for k in args.ks.split(",")] if args.ks else KS_L80
     model = load_model()
-    strong_head = args.scaling == "strong"
-    seeds = fleet_seeds(args, rank, world, strong_head)
-    fleets = build_fleets(seeds, args.M)
-    table = fleet_table(fleets, model)
+    if args.full:  # the other legs need the DeviceProfile objects too (path B's lowering, the batch API)
+        fleets = build_fleets(seeds, args.M)
+        table = fleet_table(fleets, model)
     ctx = get_context(local)
     stream = torch.cuda.Stream(dev)
     sref = stream.cuda_stream
@@ -927,18 +1032,19 @@ def main():
         rot1.launch(turn[0], k)
         turn[0] += k
 
-    # ---- solve-only leg: the same fleets lowered on the host, CSR batch resident in HBM
-    lowered = [lower_fleet(devs, model, "4bit") for devs in fleets]
-    batch, refs = assemble(lowered, [ks] * len(lowered))
-    n_so = args.copies or 2
-    copies = [to_device(batch, torch, dev) for _ in range(n_so)]
-    cptrs = [({f: t.data_ptr() for f, t in k.items()}, {f: t.data_ptr() for f, t in o.items()}) for k, o in copies]
-    # the lowering's own verdicts: the bound-infeasible k's (M > W = L / k), computed with the lowering
-    # (set-up, like the CSR) and handed to halda_solve_batch_device_settled, which then reads none of
-    # their rows; every step still writes all results
-    settled = settled_instances(batch)
-    settled_dev = torch.from_numpy(settled).to(dev)
-    hint = [settled_dev.data_ptr()]
+    # ---- solve-only leg: the same fleets lowered on the host, CSR batch resident in HBM (--full)
+    if args.full:
+        lowered = [lower_fleet(devs, model, "4bit") for devs in fleets]
+        batch, refs = assemble(lowered, [ks] * len(lowered))
+        n_so = args.copies or 2
+        copies = [to_device(batch, torch, dev) for _ in range(n_so)]
+        cptrs = [({f: t.data_ptr() for f, t in k.items()}, {f: t.data_ptr() for f, t in o.items()}) for k, o in copies]
+        # the lowering's own verdicts: the bound-infeasible k's (M > W = L / k), computed with the lowering
+        # (set-up, like the CSR) and handed to halda_solve_batch_device_settled, which then reads none of
+        # their rows; every step still writes all results
+        settled = settled_instances(batch)
+        settled_dev = torch.from_numpy(settled).to(dev)
+        hint = [settled_dev.data_ptr()]
 
     def solve_step():
         # consecutive batches alternate over the streams too (per-stream scratch: the next batch's
@@ -957,41 +1063,65 @@ def main():
     # prepared launches (halda_fleets_plan_create) are set-up, not steps
     for t in sweeps:
         t.plan(ctx)
-    rot2, rot1 = PlanRotation(sweeps, ctx, srefs), PlanRotation(sweeps, ctx, [sref])
     group = PlanGroup(sweeps, ctx)
-    # warm-up and sanity: the sweep's per-fleet answers equal the solve-only leg's k = 1 solves (at least
-    # one warm-up step per stream, so that no stream meets its first launch inside a timed region)
-    for _ in range(max(args.warmup, len(srefs))):
-        sweep_step()
-        solve_step()
-    torch.cuda.synchronize(dev)
-    st = copies[(turn[1] - 1) % n_so][1]["status"].cpu().numpy()
-    n_opt, n_inf = int((st == 0).sum()), int((st == 2).sum())
-    if n_opt + n_inf != batch.n_inst:
-        raise RuntimeError(f"unexpected statuses: {np.unique(st, return_counts=True)}")
-    bk = sweeps[0].out["best_k"].cpu().numpy()
-    if not (bk > 0).all():
-        raise RuntimeError("a fleet without a feasible k in the sweep")
-    # the group launch leaves every copy's results bit-identical to its own per-batch launch (checked on
-    # the first copy; every group launch in this process has K steps, so a kernel trace averages alike)
-    ref = {k: v.cpu().numpy().copy() for k, v in sweeps[0].out.items()}
-    for v in sweeps[0].out.values():
-        v.zero_()
-    torch.cuda.synchronize(dev)  # the zeroing (torch's stream) before the launch on sref
-    turn[0] = 0
-    sweep_group(args.steps)
-    torch.cuda.synchronize(dev)
-    for k, v in sweeps[0].out.items():
-        if not np.array_equal(v.cpu().numpy(), ref[k]):
-            raise RuntimeError(f"group launch: {k} differs from the per-batch launch")
+    if args.full:
+        rot2, rot1 = PlanRotation(sweeps, ctx, srefs), PlanRotation(sweeps, ctx, [sref])
+        # warm-up and sanity: the sweep's per-fleet answers equal the solve-only leg's k = 1 solves (at least
+        # one warm-up step per stream, so that no stream meets its first launch inside a timed region)
+        for _ in range(max(args.warmup, len(srefs))):
+            sweep_step()
+            solve_step()
+        torch.cuda.synchronize(dev)
+        st = copies[(turn[1] - 1) % n_so][1]["status"].cpu().numpy()
+        n_opt, n_inf = int((st == 0).sum()), int((st == 2).sum())
+        if n_opt + n_inf != batch.n_inst:
+            raise RuntimeError(f"unexpected statuses: {np.unique(st, return_counts=True)}")
+        bk = sweeps[0].out["best_k"].cpu().numpy()
+        if not (bk > 0).all():
+            raise RuntimeError("a fleet without a feasible k in the sweep")
+        # the group launch leaves every copy's results bit-identical to its own per-batch launch (checked on
+        # the first copy; every group launch in this process has K steps, so a kernel trace averages alike)
+        ref = {k: v.cpu().numpy().copy() for k, v in sweeps[0].out.items()}
+        for v in sweeps[0].out.values():
+            v.zero_()
+        torch.cuda.synchronize(dev)  # the zeroing (torch's stream) before the launch on sref
+        turn[0] = 0
+        sweep_group(args.steps)
+        torch.cuda.synchronize(dev)
+        for k, v in sweeps[0].out.items():
+            if not np.array_equal(v.cpu().numpy(), ref[k]):
+                raise RuntimeError(f"group launch: {k} differs from the per-batch launch")
 
     ctx.set_timing(False)  # no per-launch instrumentation events inside the timed regions
+    if not args.full:
+        # with --full the checks above have run the timed region's own launch (K batches) once; a plain run
+        # does so here, untimed, so that both meet the region with the same first-launch costs behind them
+        # (host side: the first K-batch enqueue took 16-48 us against 5 us once warm)
+        sweep_group(args.steps)
+        torch.cuda.synchronize(dev)
     # the headline's own warm-up right before its timed region: W untimed steps as one group launch (the
     # checks above left the GPU idle for milliseconds of host work)
     sweep_group(max(args.warmup, 1))
     torch.cuda.synchronize(dev)
     R = Ranks(dist, world, lambda: torch.cuda.synchronize(dev), dev)
+    last = sweeps[(turn[0] + args.steps - 1) % n_sw]  # the copy the last timed step writes
     el_sweep = timed(None, args.steps, R, tag="headline", many=sweep_group)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last.out, rank)
+    n_fleets_rank = table.n_fleets
+    inst_rank = n_fleets_rank * len(ks)
+    total = inst_rank * world * args.steps if not strong_head else C3_FLEETS * len(ks) * args.steps
+    n_fleets_total = (n_fleets_rank * world if not strong_head else C3_FLEETS) * args.steps
+    if not args.full:
+        if rank == 0:
+            line = headline_record(args, world, rccl_world, n_fleets_rank, len(ks), n_sw, total, el_sweep)
+            line["launch"] = {"persistent": group.persistent, "launches_per_region": 1 if group.persistent else args.steps}
+            line["host_enqueue_ms_per_step"] = _g(HOST_ENQUEUE["headline"] / args.steps * 1e3, 3)
+            line["fleets_per_s"] = _g(n_fleets_total / el_sweep)
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
     # each rank's device time of its group launch: HIP events on its stream around the same region run
     # once more right after (events recorded inside the headline region would put two host-side event
     # records in front of its one launch: ~0.4 us per step at K = 20)
@@ -1067,10 +1197,7 @@ def main():
     alg = algorithmic_bytes(lowered, refs, len(ks))
     alg_so = algorithmic_bytes(lowered, refs, len(ks), settled)
 
-    inst_rank = len(fleets) * len(ks)
-    total = inst_rank * world * args.steps if not strong_head else C3_FLEETS * len(ks) * args.steps
     value = total / el_sweep
-    n_fleets_total = (len(fleets) * world if not strong_head else C3_FLEETS) * args.steps
     c2 = lat = None
     if world == 1 and not args.no_c2:
         c2 = c2_leg(args, torch, dev, ctx, model, stream, srefs)
@@ -1080,28 +1207,8 @@ def main():
         c5 = c5_stream(model, args.M) if (world == 1 and not args.no_tto) else None
         bapi = batch_api(model, fleets) if (world == 1 and not args.no_tto) else None
         full = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "instances/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": el_sweep / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (seeded C3 fleets, distilp_amd/synth.py)",
-            "config": {
-                "workload": (f"C3: {len(fleets) if not strong_head else C3_FLEETS} M={args.M} fleets x {len(ks)} k "
-                             f"per {'GPU' if not strong_head else 'node'} (L=80, llama_3_70b/online, kv 4bit), one "
-                             "k-sweep per step from HBM-resident tables"),
-                "instances_per_step_per_gpu": inst_rank,
-                "feasible_per_step_per_gpu": n_opt,
-                "parallelism": f"dp{world}",
-                "rccl_world_size": rccl_world,
-                "resident_copies": n_sw,
-            },
+            **headline_record(args, world, rccl_world, n_fleets_rank, len(ks), n_sw, total, el_sweep, n_opt,
+                              rounded=False),
             "roofline": group_roofline(group_ms, args.steps, alg["halda_sweep_kernel"], len(fleets),
                                        roofline(fl_mean, alg, pmc_traffic, sweep_ev_ms)),
             "cpu_baseline": cpu_base,

@@ -15,13 +15,13 @@ export TMPDIR=/tmp
 sha256sum distilp_amd/libhalda.so | cut -d' ' -f1 > "$OUT/lib_sha256"
 echo "[prof] trace"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$OUT/trace" -o run -- \
-    python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-tto --streams 1 > "$OUT/trace_bench.json" 2> "$OUT/trace.err"
+    python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-tto --streams 1 > "$OUT/trace_bench.json" 2> "$OUT/trace.err"
 echo "[prof] fetch"
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -T --output-format csv -d "$OUT/pmc_fetch" -o run -- \
-    python3 bench.py --steps 20 --warmup 1 --no-cpu-baseline --no-tto --no-latency > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
+    python3 bench.py --full --steps 20 --warmup 1 --no-cpu-baseline --no-tto --no-latency > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
 echo "[prof] write"
 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace -T --output-format csv -d "$OUT/pmc_write" -o run -- \
-    python3 bench.py --steps 20 --warmup 1 --no-cpu-baseline --no-tto --no-latency > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
+    python3 bench.py --full --steps 20 --warmup 1 --no-cpu-baseline --no-tto --no-latency > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
 echo "[prof] calib"
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/calib" -o run -- \
     ./build/hbm_calib > "$OUT/calib.json" 2> "$OUT/calib.err"

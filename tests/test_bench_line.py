@@ -99,6 +99,42 @@ def test_compact_line_fits_and_ends_with_the_metric_figures():
     assert eight["weak_200"]["ms_per_step"] is not None and eight["config"]["rccl_world_size"] == 8
 
 
+def test_plain_line_is_the_contract_keys_of_the_full_record():
+    """A plain run's line (headline_record) carries the same leading keys, with the same values, as the
+    --full record does; only `feasible_per_step_per_gpu` (counted by a --full leg) is missing."""
+    import argparse
+
+    import bench
+
+    args = argparse.Namespace(steps=20, warmup=5, scaling="weak", M=64)
+    total, el = 36864 * 20, 1.5e-4
+    plain = bench.headline_record(args, 1, 1, 4096, 9, 16, total, el)
+    full = bench.headline_record(args, 1, 1, 4096, 9, 16, total, el, n_opt=4096, rounded=False)
+    assert list(plain) == list(full) == list(bench.compact_line(_full(1)))[:13]
+    assert plain["value"] == full["value"] == total / el and plain["unit"] == "instances/s"
+    assert plain["ms_per_step"] == 0.0075 and abs(full["ms_per_step"] - 0.0075) < 1e-15
+    assert plain["higher_is_better"] is True and plain["dtype"] == "f64" and plain["metric"] == bench.METRIC
+    assert "feasible_per_step_per_gpu" not in plain["config"]
+    assert list(full["config"]) == list(_full(1)["config"]) and full["config"] == _full(1)["config"]
+    assert {k: v for k, v in full["config"].items() if k != "feasible_per_step_per_gpu"} == plain["config"]
+
+
+def test_build_table_by_workers_is_the_one_piece_table():
+    """bench.build_table (worker processes, each packing a share of the seeds) joins bit for bit the table
+    that fleet_table makes of all the fleets at once, for shares of unequal size."""
+    import bench
+    from distilp_amd.solver.fleets import BYTE_FIELDS, F64_FIELDS, fleet_table
+
+    seeds, M = list(range(5, 16)), 7
+    one = fleet_table(bench.build_fleets(seeds, M), bench.load_model())
+    for procs in (1, 3):
+        tab = bench.build_table(seeds, M, procs)
+        assert tab.n_fleets == len(seeds) and tab.n_devices == len(seeds) * M
+        for f in ("dev_off", "os_class", "flags") + F64_FIELDS + BYTE_FIELDS:
+            a, b = getattr(one, f), getattr(tab, f)
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (procs, f)
+
+
 def test_valu_issue_prices_fp64_apart():
     import bench
 
