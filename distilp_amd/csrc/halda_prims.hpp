@@ -6,7 +6,14 @@
 
 constexpr int kRows = 4;            // capacity rows per device (link, RAM/Metal cap, <= 2 VRAM)
 constexpr int kMaxRowNnz = 8;       // widest HALDA row (cycle rows: 6 device cols + z + C)
-constexpr double kSlackEps = 1e-9;  // a capacity row counts as met within 1e-9 layers (oracle: same)
+// A capacity row's integer slack s >= u w + v n + ceil(-rhs / b' - kSlackEps): the row counts as met while it is
+// short by at most 1e-6 layers, HiGHS's integrality tolerance on the reference's integer slack columns
+// (tests/golden/boundary.json brackets the flip between 0.9e-6 and 1.1e-6 layers on every row kind; a probe at
+// b' = 523,282,022 put it between 520 and 530 B; the oracle carries the same value, oracle/milp_oracle.py
+// SLACK_EPS). A row without a slack column (the link row n - w <= 0) has no integer column to absorb a
+// shortfall: it keeps its own relative tolerance kRowEps.
+constexpr double kSlackEps = 1e-6;
+constexpr double kRowEps = 1e-9;
 constexpr double kInf = __builtin_huge_val();
 constexpr int kK1MaxM = 64;         // widest fleet the k = 1 fast path takes (lane = device)
 

@@ -845,7 +845,7 @@ __device__ inline int decode_cap_row(const WaveCtx &w, const Inst &I, int nnz, d
     rb |= u * v > 0;  // L-natural convexity: w and n may be coupled only through w - n
     if (rb) return 1;
     const double kk = slack >= 0 ? ceil(-rhs / beta - kSlackEps)
-                                 : floor((rhs + kSlackEps * fmax(1.0, fabs(rhs))) / scale);
+                                 : floor((rhs + kRowEps * fmax(1.0, fabs(rhs))) / scale);
     if (!(fabs(kk) < 1e8)) return 1;
     const int q = atomicAdd(&w.cnt[dev], 1) & 0xff;
     if (q >= kRows) return 1;

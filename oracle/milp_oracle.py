@@ -34,6 +34,12 @@ import numpy as np
 HERE = Path(__file__).resolve().parent
 EXACT_LIB = HERE / "build" / "libhalda_exact.so"
 
+# A capacity row counts as met while it is short by at most SLACK_EPS layers: HiGHS's integrality
+# tolerance on the reference's integer slack columns. tests/golden/boundary.json brackets the
+# reference's flip between 0.9e-6 and 1.1e-6 layers on every row kind (a probe at b' = 523,282,022
+# put it between 520 and 530 B short). libhalda: kSlackEps.
+SLACK_EPS = 1e-6
+
 # The coefficient helpers (alpha/beta/xi, b', kappa, sets) are pure scalar
 # restatements of dense_common.py; the oracle re-derives them independently.
 
@@ -234,7 +240,8 @@ def highs_solve(prob, mip_gap: Optional[float] = 1e-4, relax: bool = False):
     return milp(c=prob["c"], integrality=integ, bounds=Bounds(prob["lb"], prob["ub"]), constraints=cons, options=opts)
 
 
-def halda_solve_oracle(devs, model, k_candidates=None, mip_gap=1e-4, kv_bits="8bit", solver="highs"):
+def halda_solve_oracle(devs, model, k_candidates=None, mip_gap=1e-4, kv_bits="8bit", solver="highs",
+                       eps: float = SLACK_EPS):
     """k-sweep (halda_p_solver.py:369-436) with either HiGHS or the exact C solver.
 
     Returns (best dict or None, per_k list). Prints nothing."""
@@ -253,7 +260,7 @@ def halda_solve_oracle(devs, model, k_candidates=None, mip_gap=1e-4, kv_bits="8b
             res = highs_solve(prob, mip_gap)
             ok, x, extra = res.success, (res.x if res.success else None), {}
         else:
-            st, x, b1, b2, nodes = exact_solve(prob)
+            st, x, b1, b2, nodes = exact_solve(prob, eps)
             ok, extra = st == 0, {"margin": b2 - b1, "nodes": nodes}
         if not ok:
             per_k.append({"k": k, "success": False})
@@ -287,7 +294,7 @@ def _load_exact():
     return _lib
 
 
-def exact_solve(prob, eps: float = 1e-9):
+def exact_solve(prob, eps: float = SLACK_EPS):
     """(status, x, best_obj_lin, second_best_obj_lin, dp_runs). status 0 ok, 2 infeasible, <0 unsupported."""
     lib = _load_exact()
     A = np.ascontiguousarray(np.vstack([prob["A_ub"], prob["A_eq"]]), dtype=np.float64)

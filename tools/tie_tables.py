@@ -15,6 +15,8 @@ sys.path.insert(0, str(REPO / "tools"))
 
 
 def tables(p, M, W):
+    from oracle.milp_oracle import SLACK_EPS  # the slack rule's tolerance, in layers (the oracle's constant)
+
     A, b, c, lb, ub = p["A_ub"], p["b_ub"], p["c"], p["lb"], p["ub"]
     iC, R1 = 7 * M, W - M + 1
     G, H = np.full((M, R1), np.inf), np.full((M, R1), np.inf)
@@ -35,7 +37,7 @@ def tables(p, M, W):
                         ok = ok and act <= b[r] + 1e-9 * max(1, abs(b[r]))
                         continue
                     j = sl[0] * M + i
-                    x[j] = max(x[j], math.ceil((act - b[r]) / -A[r, j] - 1e-9))
+                    x[j] = max(x[j], math.ceil((act - b[r]) / -A[r, j] - SLACK_EPS))
                 for blk in range(2, 6):
                     j = blk * M + i
                     x[j] = max(x[j], lb[j])
