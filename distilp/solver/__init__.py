@@ -1,6 +1,8 @@
 """Alias of distilp_amd.solver (reference API: distilp.solver.halda_solve / HALDAResult)."""
 
 from distilp_amd.solver import HALDAResult, ILPResult, halda_solve, halda_solve_batch  # noqa: F401
+from distilp_amd.solver import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
+                                halda_solve_subfleets)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

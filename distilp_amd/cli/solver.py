@@ -11,6 +11,8 @@ Same surface and output as the reference CLI (src/cli/solver.py:15-237):
     --time-limit / --max-iters / --sdisk-threshold / --k-candidates are accepted
     and ignored, as in the reference;
   * --quiet / --verbose / --save-solution formats of :176-235.
+Beyond the reference: --leave-one-out prints, after the unchanged output above, one line per device with
+the best k and objective of the fleet without it.
 """
 
 from __future__ import annotations
@@ -22,7 +24,7 @@ from pathlib import Path
 from typing import List, Tuple
 
 from ..common import DeviceProfile, ModelProfile, ModelProfileSplit
-from ..solver import halda_solve
+from ..solver import halda_leave_one_out, halda_solve
 
 
 def load_device_profile(device_path: str) -> DeviceProfile:
@@ -59,6 +61,14 @@ def load_from_profile_folder(profile_path: str):
     return load_devices_and_model(device_files, str(model_file))
 
 
+def leave_one_out_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: float) -> List[str]:
+    """--leave-one-out: one line per dropped device -- its name, then the best k and obj_value of the fleet
+    without it (halda_leave_one_out, kv_bits "4bit" like the solve above)."""
+    res = halda_leave_one_out(devices, model, mip_gap=mip_gap, kv_bits="4bit")
+    return [f"without {d.name}: " + ("infeasible" if r is None else f"k={r.k}, obj={r.obj_value:.6f}")
+            for d, r in zip(devices, res)]
+
+
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Run HALDA solver for distributed LLM inference optimization",
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -77,6 +87,8 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--verbose", action="store_true", help="Verbose output including device and model summaries")
     o.add_argument("--save-solution", help="Save solution to JSON file")
     o.add_argument("--no-plot", action="store_true", help="Disable plotting of k vs objective curve")
+    o.add_argument("--leave-one-out", action="store_true",
+                   help="After the solution, print the best k and objective of the fleet without each device")
     return p
 
 
@@ -128,6 +140,9 @@ def main(argv=None) -> int:
             json.dump(payload, f, indent=2)
         if not args.quiet:
             print(f"\nSolution saved to: {args.save_solution}")
+    if args.leave_one_out:
+        for line in leave_one_out_lines(devices, model, args.mip_gap):
+            print(line)
     return 0
 
 

@@ -319,11 +319,15 @@ static void *worker(void *arg) {
 static int pack_threads(Py_ssize_t nd) {
     const char *e = getenv("HALDA_PACK_THREADS");
     if (e && *e) return atoi(e);
-    if (nd < 8192) return 1;
+    if (nd < 1024) return 1;
     cpu_set_t cs;
     int n = 1;
     if (sched_getaffinity(0, sizeof(cs), &cs) == 0) n = CPU_COUNT(&cs);
-    return n < 16 ? n : 16;
+    n = n < 16 ? n : 16;
+    /* 1,024 .. 8,191 devices (the parents of a leave-one-out call, subfleets.py): a thread per 512 devices,
+     * which a thread's start is worth; from 8,192 on every thread, as before */
+    if (nd < 8192 && n > nd / 512) n = (int)(nd / 512);
+    return n;
 }
 
 /* 1: packed in parallel; 0: not attempted / given up (the caller packs serially); -1: error set */
@@ -680,6 +684,105 @@ done:
     return ret;
 }
 
+/* consts_items(f64, b64, u8, off, parent, sub_off, sub_idx, fout, f_out_b1, b_in, b_out, V, out, cls_out,
+ *              heads_out) -> None
+ * consts for the items of a packed table (subfleets.py): item i is the fleet of devices off[parent[i]] +
+ * sub_idx[sub_off[i] .. sub_off[i + 1] - 1] in list order. out[0..2][i] are the constants consts gives for
+ * that fleet materialised -- the same scalar loops over the listed devices, kappa's head the first listed
+ * device with the head flag, else the first listed one -- cls_out the listed devices' classes in list
+ * order (the materialised table's os_class) and heads_out[i] the head's device index in the parent table.
+ * Nothing of the size of the listed devices is built but cls_out. ValueError for an index out of range
+ * or an empty list. */
+static PyObject *consts_items(PyObject *self, PyObject *args) {
+    (void)self;
+    Py_buffer bf, bi, bu, bo, bp, bso, bsi, bout, bcls, bheads;
+    int fout;
+    double f_out_b1, b_in, b_out, V;
+    if (!PyArg_ParseTuple(args, "y*y*y*y*y*y*y*pddddw*w*w*", &bf, &bi, &bu, &bo, &bp, &bso, &bsi, &fout, &f_out_b1,
+                          &b_in, &b_out, &V, &bout, &bcls, &bheads))
+        return NULL;
+    PyObject *ret = NULL;
+    const Py_ssize_t nd = bu.len / 2, nf = bo.len / 8 - 1, n = bp.len / 4;
+    const int64_t *off = (const int64_t *)bo.buf, *so = (const int64_t *)bso.buf;
+    const int32_t *par = (const int32_t *)bp.buf, *idx = (const int32_t *)bsi.buf;
+    int bad = nf < 0 || bf.len < 80 * nd || bi.len < 48 * nd || bso.len < 8 * (n + 1) || bout.len < 24 * n ||
+              bheads.len < 8 * n || (n > 0 && (so[0] != 0 || so[n] < 0 || bsi.len < 4 * so[n] || bcls.len < so[n]));
+    if (!bad) {
+        const double *f64 = (const double *)bf.buf, *b64 = (const double *)bi.buf;
+        const uint8_t *cls = (const uint8_t *)bu.buf, *flg = cls + nd;
+        const double *scpu = f64, *Tc = f64 + 2 * nd, *r2v = f64 + 6 * nd, *v2r = f64 + 7 * nd, *tcomm = f64 + 8 * nd,
+                     *sd = f64 + 9 * nd;
+        const double *ram = b64, *ccpu = b64 + nd, *swap = b64 + 5 * nd;
+        double *out = (double *)bout.buf;
+        uint8_t *co = (uint8_t *)bcls.buf;
+        int64_t *ho = (int64_t *)bheads.buf;
+        Py_BEGIN_ALLOW_THREADS /* plain arrays only, held by the buffers above */
+        for (Py_ssize_t i = 0; i < n && !bad; ++i) {
+            const int64_t a = so[i], b = so[i + 1];
+            if (par[i] < 0 || par[i] >= nf || b <= a || b > so[n]) {
+                bad = 1;
+                break;
+            }
+            const int64_t base = off[par[i]], M = off[par[i] + 1] - base;
+            if (base < 0 || M < 0 || base + M > nd) {
+                bad = 1;
+                break;
+            }
+            int64_t h = -1;
+            for (int64_t j = a; j < b; ++j) {
+                if (idx[j] < 0 || idx[j] >= M) {
+                    bad = 1;
+                    break;
+                }
+                const int64_t g = base + idx[j];
+                co[j] = cls[g];
+                if (h < 0 && (flg[g] & HEAD)) h = g;
+            }
+            if (bad) break;
+            if (h < 0) h = base + idx[a];
+            double t = 0.0, x = 0.0;
+            for (int64_t j = a; j < b; ++j) t += tcomm[base + idx[j]];
+            for (int64_t j = a; j < b; ++j) {
+                const int64_t g = base + idx[j];
+                x += (r2v[g] + v2r[g]) * ((flg[g] & UMA) ? 0.0 : 1.0);
+            }
+            double total = 0.0;
+            if (fout && (flg[h] & CPU_RATE)) total = scpu[h] > 0.0 ? 0.0 + f_out_b1 / scpu[h] : 0.0;
+            total += (b_in / V + b_out) / Tc[h];
+            total += b_in / (V * sd[h]);
+            total += b_out / sd[h];
+            double tail = 0.0;
+            for (int pass = 1; pass <= 3; pass += 2)
+                for (int64_t j = a; j < b; ++j) {
+                    const int64_t g = base + idx[j];
+                    if (cls[g] == pass) tail += ((ccpu[g] - ram[g]) - swap[g]) / sd[g];
+                }
+            out[i] = t;
+            out[n + i] = x;
+            out[2 * n + i] = total + tail;
+            ho[i] = h;
+        }
+        Py_END_ALLOW_THREADS
+    }
+    if (bad) {
+        PyErr_SetString(PyExc_ValueError, "consts_items: buffers too small, an index out of range or an empty list");
+    } else {
+        Py_INCREF(Py_None);
+        ret = Py_None;
+    }
+    PyBuffer_Release(&bf);
+    PyBuffer_Release(&bi);
+    PyBuffer_Release(&bu);
+    PyBuffer_Release(&bo);
+    PyBuffer_Release(&bp);
+    PyBuffer_Release(&bso);
+    PyBuffer_Release(&bsi);
+    PyBuffer_Release(&bout);
+    PyBuffer_Release(&bcls);
+    PyBuffer_Release(&bheads);
+    return ret;
+}
+
 /* results(cls, x, row, k, obj, off, os_class) -> list
  * The HALDAResult of every fleet of a solved batch (halda._batch_on_gpu), built without Python
  * bytecode per fleet: fleet f's winner row starts at x[row[f]] (-1: no feasible k -> None), w = the
@@ -917,6 +1020,8 @@ done:
 static PyMethodDef methods[] = {{"pack", pack, METH_VARARGS, "Pack fleets of DeviceProfile into the fleet table."},
                                 {"consts", consts, METH_VARARGS, "Per-fleet obj_value constants of a packed table."},
                                 {"results", results, METH_VARARGS, "HALDAResult per fleet of a solved batch."},
+                                {"consts_items", consts_items, METH_VARARGS,
+                                 "Per-item obj_value constants, classes and heads of index lists into a packed table."},
                                 {"sets", sets_of, METH_VARARGS, "M1 / M2 / M3 device index lists of a class row."},
                                 {NULL, NULL, 0, NULL}};
 

@@ -156,6 +156,10 @@ struct Ctx {
     bool have_last = false;
     void *fleet_scratch = nullptr;  // lowered batch + results of halda_solve_fleets
     size_t fleet_scratch_bytes = 0;
+    uint8_t *sub_tab = nullptr;     // halda_solve_subfleets: the expanded table of the expansion route
+    size_t sub_tab_bytes = 0;
+    int sub_path = 0;               // halda_set_subfleets_path: 0 automatic, 1 always expand
+    int sub_route = 0;              // the last halda_solve_subfleets call: 1 fused, 2 expansion (0: none yet)
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -1186,6 +1190,7 @@ void halda_free(void *ctx) {
     if (c->hb_flag) (void)hipFree(c->hb_flag);
     if (c->fleet_scratch) (void)hipFree(c->fleet_scratch);
     if (c->gtab) (void)hipFree(c->gtab);
+    if (c->sub_tab) (void)hipFree(c->sub_tab);
     for (auto &x : c->sws) {
         if (x.fflag) (void)hipFree(x.fflag);
         if (x.cls) (void)hipFree(x.cls);
@@ -1962,6 +1967,255 @@ int halda_solve_fleets_host(void *ctx, const halda_model *model, const halda_fle
         HIP_TRY(down(out_h->x, o_x, 8 * xs));
         HIP_TRY(down(out_h->c, o_c, 8 * xs));
     }
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- sub-fleets of a resident table
+// halda_solve_subfleets: items (parent fleet, index list) solved as the fleets of their listed devices.
+// Fused route: every item of one length M' <= kK1MaxM and a batch of n_items fleets of M' devices planned
+// as the register sweep alone (plan_sweep's kRegAlone: no table launch, nothing flagged -- the condition
+// group_check uses) -> halda_sweep_subfleets_kernel gathers the fields per wave, no expanded table.
+// Expansion route (everything else, and every call on path 1): halda_expand_subfleets_kernel writes the
+// listed devices as a compact table into the context's grow-only sub_tab, whose dev_off is the items'
+// sub_off, and the ordinary halda_solve_fleets runs on it into the caller's out. sub_tab is per context:
+// a call that uses it runs after the previous user of the context's shared scratch on another stream
+// (order_after_previous), like the global tables.
+int halda_set_subfleets_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "sub-fleets path must be 0 (automatic) or 1 (always expand)");
+    c->sub_path = path;
+    return HALDA_OK;
+}
+
+int halda_last_subfleets_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->sub_route;
+    return HALDA_OK;
+}
+
+// total: sub_off[n_items] when the caller knows it (the host variant), -1 to read it back where needed
+static int solve_subfleets(void *ctx, const halda_model *model, const halda_fleets *table,
+                           const halda_subfleets *items, const int32_t *ks, int32_t n_k, halda_fleet_result *out,
+                           void *stream, int64_t total) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !table || !items || !ks || !out)
+        return fail(HALDA_E_ARG, "NULL ctx/model/table/items/ks/out");
+    const halda_subfleets &I = *items;
+    if (I.n_items <= 0) return HALDA_OK;
+    if (!I.parent || !I.sub_off || !I.sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (table->n_fleets <= 0) return fail(HALDA_E_ARG, "halda_solve_subfleets: the table has no fleets");
+    // the items seen as a batch of fleets: the table's arrays under the items' count and length summary
+    halda_fleets V = *table;
+    V.n_fleets = I.n_items;
+    V.min_devices = I.min_devices;
+    V.max_devices = I.max_devices;
+    {
+        const int rc = check_fleets_args(model, &V, ks, n_k, out);
+        if (rc != HALDA_OK) return rc;
+    }
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const SubArgs S{I.parent, I.sub_off, I.sub_idx};
+    if (c->sub_path == 0 && c->fleets_fused && n_k <= 64 && I.min_devices == I.max_devices &&
+        I.max_devices <= kK1MaxM) {
+        SweepPlan p;
+        const int rc = plan_sweep(c, *model, V, ks, n_k, *out, &p);
+        if (rc != HALDA_OK) return rc;
+        if (p.kind == kRegAlone && !p.A.k1dp) {
+            SweepArgs &A = p.A;
+            A.fflag = nullptr;  // the register sweep alone never flags
+            A.hb_flag = c->hb_flag;
+            A.launch_id = ++c->launch_id;
+            A.want = 0;
+            c->fleet_timed = false;
+            c->have_lowered = false;
+            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+            hipLaunchKernelGGL(halda_sweep_subfleets_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, S);
+            HIP_TRY(hipGetLastError());
+            if (c->timing) {
+                HIP_TRY(hipEventRecord(c->evf1, s));
+                c->fleet_timed = true;
+            }
+            c->fleet_two = false;
+            c->fleet_reg_alone = true;
+            c->fleet_seg = false;
+            c->fleet_kslot = false;
+            c->last_fleet_fused = true;
+            c->sub_route = 1;
+            return HALDA_OK;
+        }
+    }
+    // expansion: the listed devices as a compact table (16 double and 2 byte arrays of nd entries)
+    int64_t nd = total >= 0 ? total : int64_t(I.n_items) * I.max_devices;
+    if (total < 0 && I.min_devices != I.max_devices) {
+        HIP_TRY(hipMemcpyAsync(&nd, I.sub_off + I.n_items, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (nd < int64_t(I.n_items) * I.min_devices || nd > int64_t(I.n_items) * I.max_devices)
+            return fail(HALDA_E_ARG, "halda_subfleets: sub_off[n_items] does not fit min_devices / max_devices");
+    }
+    const size_t nd8 = (size_t(nd) * 8 + 255) & ~size_t(255), nd1 = (size_t(nd) + 255) & ~size_t(255);
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sub_tab, &c->sub_tab_bytes, 16 * nd8 + 2 * nd1);
+        if (rc != HALDA_OK) return rc;
+    }
+    ExpandOut E;
+    for (int a = 0; a < 16; ++a) E.f[a] = reinterpret_cast<double *>(c->sub_tab + nd8 * size_t(a));
+    E.os_class = c->sub_tab + 16 * nd8;
+    E.flags = E.os_class + nd1;
+    hipLaunchKernelGGL(halda_expand_subfleets_kernel, dim3(unsigned((I.n_items + 3) / 4)), dim3(256), 0, s, *table, S,
+                       int(I.n_items), E);
+    HIP_TRY(hipGetLastError());
+    halda_fleets X = V;
+    X.dev_off = I.sub_off;
+    X.os_class = E.os_class;
+    X.flags = E.flags;
+    X.scpu_b1 = E.f[0]; X.sgpu_b1 = E.f[1]; X.T_cpu = E.f[2]; X.T_gpu = E.f[3]; X.t_kvcpy_cpu = E.f[4];
+    X.t_kvcpy_gpu = E.f[5]; X.t_ram2vram = E.f[6]; X.t_vram2ram = E.f[7]; X.t_comm = E.f[8]; X.s_disk = E.f[9];
+    X.d_avail_ram = E.f[10]; X.c_cpu = E.f[11]; X.c_gpu = E.f[12]; X.d_avail_cuda = E.f[13];
+    X.d_avail_metal = E.f[14]; X.swap = E.f[15];
+    c->sub_route = 2;
+    return halda_solve_fleets(ctx, model, &X, ks, n_k, out, s);
+}
+
+int halda_solve_subfleets(void *ctx, const halda_model *model, const halda_fleets *table,
+                          const halda_subfleets *items, const int32_t *ks, int32_t n_k, halda_fleet_result *out,
+                          void *stream) {
+    return solve_subfleets(ctx, model, table, items, ks, n_k, out, stream, -1);
+}
+
+int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                               const halda_subfleets *ih, const int32_t *ks, int32_t n_k, halda_fleet_result *out_h) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !ih || !ks || !out_h) return fail(HALDA_E_ARG, "NULL ctx/model/table/items/ks/out");
+    if (ih->n_items <= 0) return HALDA_OK;
+    if (!ih->parent || !ih->sub_off || !ih->sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (th->n_fleets <= 0 || !th->dev_off) return fail(HALDA_E_ARG, "halda_solve_subfleets_host: empty table");
+    if (n_k <= 0) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (!out_h->best_k || !out_h->obj_value || !out_h->w || !out_h->n)
+        return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf], n = ih->n_items;
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    // the items: parents and device indices in range, no empty list, the length summary
+    if (ih->sub_off[0] != 0) return fail(HALDA_E_ARG, "halda_subfleets: sub_off[0] must be 0");
+    int64_t lmin = INT64_MAX, lmax = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t p = ih->parent[i], a = ih->sub_off[i], len = ih->sub_off[i + 1] - a;
+        if (p < 0 || p >= nf)
+            return fail(HALDA_E_ARG, "halda_subfleets: item " + std::to_string(i) + " has parent " + std::to_string(p) +
+                                         " outside the table's " + std::to_string(nf) + " fleets");
+        if (len < 1) return fail(HALDA_E_ARG, "halda_subfleets: item " + std::to_string(i) + " has an empty list");
+        const int64_t Mp = th->dev_off[p + 1] - th->dev_off[p];
+        for (int64_t j = 0; j < len; ++j) {
+            const int64_t d = ih->sub_idx[a + j];
+            if (d < 0 || d >= Mp)
+                return fail(HALDA_E_ARG, "halda_subfleets: item " + std::to_string(i) + " lists device " +
+                                             std::to_string(d) + " of a parent with " + std::to_string(Mp) + " devices");
+        }
+        lmin = std::min(lmin, len);
+        lmax = std::max(lmax, len);
+    }
+    if (lmax > 4096) return fail(HALDA_E_ARG, "halda_subfleets: a list of more than 4096 devices");
+    // a summary that is given must be tight: the dense x / c layout strides by max_devices
+    if ((ih->min_devices || ih->max_devices) && (lmin != ih->min_devices || lmax != ih->max_devices))
+        return fail(HALDA_E_ARG, "halda_subfleets: min_devices / max_devices are not the lists' shortest and longest "
+                                 "length (" + std::to_string(lmin) + ", " + std::to_string(lmax) + ")");
+    const int64_t tot = ih->sub_off[n];
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
+    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16),
+                 o_par = take(4 * n), o_soff = take(8 * (n + 1)), o_sidx = take(4 * tot);
+    const bool xsel = out_h->x_off && (out_h->x || out_h->c);
+    const size_t o_xoff = xsel ? take(8 * size_t(n) * n_k) : 0;
+    const size_t o_bk = take(4 * n), o_obj = take(8 * n), o_w = take(4 * tot), o_n = take(4 * tot),
+                 o_obk = take(8 * n * n_k), o_st = take(4 * n * n_k);
+    // x / c extent: the dense layout, or the caller's compact one (x_off, host memory)
+    size_t xs = size_t(n) * n_k * (7 * size_t(lmax) + 1);
+    if (xsel) {
+        int64_t ext = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t N = 7 * (ih->sub_off[i + 1] - ih->sub_off[i]) + 1;
+            for (int j = 0; j < n_k; ++j) {
+                const int64_t a = out_h->x_off[i * n_k + j];
+                if (a >= 0) ext = std::max(ext, a + N);
+            }
+        }
+        xs = size_t(ext);
+    }
+    const size_t o_x = out_h->x ? take(8 * xs) : 0, o_c = out_h->c ? take(8 * xs) : 0;
+    if (off > c->scratch_bytes) {
+        if (c->scratch) HIP_TRY(hipFree(c->scratch));
+        c->scratch = nullptr;
+        c->scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&c->scratch, off));
+        c->scratch_bytes = off;
+    }
+    char *base = static_cast<char *>(c->scratch);
+    // in: the parent table and the item arrays, one copy per array straight from the caller's memory (a
+    // DMA where it is page-locked, halda_host_alloc)
+    auto up = [&](size_t o, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    const double *f64[16] = {th->scpu_b1, th->sgpu_b1, th->T_cpu, th->T_gpu, th->t_kvcpy_cpu, th->t_kvcpy_gpu,
+                             th->t_ram2vram, th->t_vram2ram, th->t_comm, th->s_disk, th->d_avail_ram, th->c_cpu,
+                             th->c_gpu, th->d_avail_cuda, th->d_avail_metal, th->swap};
+    if (!th->os_class || !th->flags) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    for (int a = 0; a < 16; ++a)
+        if (!f64[a]) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    HIP_TRY(up(o_doff, th->dev_off, 8 * (nf + 1)));
+    HIP_TRY(up(o_cls, th->os_class, nd));
+    HIP_TRY(up(o_fl, th->flags, nd));
+    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
+    HIP_TRY(up(o_par, ih->parent, 4 * n));
+    HIP_TRY(up(o_soff, ih->sub_off, 8 * (n + 1)));
+    HIP_TRY(up(o_sidx, ih->sub_idx, 4 * tot));
+    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * size_t(n) * n_k));
+    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
+    halda_fleets d = *th;
+    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
+    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
+    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
+    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
+    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
+    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
+    d.d_avail_metal = F64(14); d.swap = F64(15);
+    halda_subfleets di = *ih;
+    di.min_devices = int32_t(lmin);
+    di.max_devices = int32_t(lmax);
+    di.parent = reinterpret_cast<const int32_t *>(base + o_par);
+    di.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
+    di.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
+    halda_fleet_result r;
+    r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+    r.obj_value = reinterpret_cast<double *>(base + o_obj);
+    r.w = reinterpret_cast<int32_t *>(base + o_w);
+    r.n = reinterpret_cast<int32_t *>(base + o_n);
+    r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
+    r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
+    r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
+    r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
+    r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
+    {
+        const int rc = solve_subfleets(ctx, model, &d, &di, ks, n_k, &r, s, tot);  // no read-back of the total
+        if (rc != HALDA_OK) return rc;
+    }
+    auto dn = [&](void *dst, size_t o, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIP_TRY(dn(out_h->best_k, o_bk, 4 * n));
+    HIP_TRY(dn(out_h->obj_value, o_obj, 8 * n));
+    HIP_TRY(dn(out_h->w, o_w, 4 * tot));
+    HIP_TRY(dn(out_h->n, o_n, 4 * tot));
+    HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n * n_k));
+    HIP_TRY(dn(out_h->status, o_st, 4 * n * n_k));
+    HIP_TRY(dn(out_h->x, o_x, 8 * xs));
+    HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+    HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
 }
 

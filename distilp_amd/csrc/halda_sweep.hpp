@@ -1175,6 +1175,78 @@ __global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_STEPS_WAVES) void h
                                           &cur);
 }
 
+// ---------------------------------------------------------------- sub-fleets of a resident table
+// An item is (parent fleet of the table, list of local device indices): the fleet of the listed devices in
+// list order (halda_solve_subfleets). The item arrays as the kernels see them.
+struct SubArgs {
+    const int32_t *parent;   // [n_items]
+    const int64_t *sub_off;  // [n_items + 1]
+    const int32_t *sub_idx;  // [sub_off[n_items]]
+};
+
+__device__ inline int sload_i32(const int32_t *p) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) int32_t *>(reinterpret_cast<uintptr_t>(p));
+}
+
+// halda_sweep_subfleets_kernel: the fused route -- one wave per item, every item of A.uM <= kK1MaxM listed
+// devices (A.F is the parent table with n_fleets = the item count; the host sends only shapes whose
+// register sweep needs no table launch). The item's parent, list offset and the parent's first device are
+// wave-uniform reads through the scalar cache (the item arrays and dev_off are read-only to the kernel);
+// lane j's list entry is the wave's first vector round trip, the 18 fields of device dev_off[parent] +
+// idx the second (issued together, as load_fields does). From there on the item is a fleet handed to
+// sweep_fleet with its fields prefetched (kPre), exactly as the steps kernel and the resident wave hand
+// theirs: the same code on the same fields as halda_sweep_kernel runs on the materialised table, so the
+// same bits. pre.d0 is the item's offset in the w / n outputs (sub_off lays them out).
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_subfleets_kernel(
+    SweepArgs A, SubArgs S) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    if (i >= A.F.n_fleets) return;
+    const int lane = int(threadIdx.x & 63);
+    const int M = A.uM;
+    const int64_t so = sload_i64(S.sub_off + i);
+    const int64_t base = sload_i64(A.F.dev_off + sload_i32(S.parent + i));
+    const int idx = S.sub_idx[so + (lane < M ? lane : 0)];
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    SweepPre pre;
+    const bool kl = lane < A.n_k;
+    pre.kj = A.ks[kl ? lane : 0];
+    pre.Wj = kl ? A.Ws[lane] : 0;
+    pre.d0 = so;
+    pre.mf = load_fields(A.F, base + idx);
+    sweep_fleet<false, false, Wave, true, true>(A, A.F, A.out, i, w, Wave(lane), &pre);
+}
+
+// halda_expand_subfleets_kernel: the expansion route -- one wave per item copies the 18 fields of its
+// listed devices into a compact fleet table E whose dev_off is sub_off itself (item i owns entries
+// sub_off[i] .. sub_off[i + 1] - 1); lists longer than a wave take several passes. The ordinary sweep
+// then runs on E.
+struct ExpandOut {
+    uint8_t *os_class, *flags;
+    double *f[16];  // the table's double fields in halda_fleets order (scpu_b1 .. swap)
+};
+
+__global__ __launch_bounds__(256) void halda_expand_subfleets_kernel(halda_fleets T, SubArgs S, int n_items,
+                                                                       ExpandOut E) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * 4 + int(threadIdx.x >> 6));
+    if (i >= n_items) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t so = sload_i64(S.sub_off + i);
+    const int len = int(sload_i64(S.sub_off + i + 1) - so);
+    const int64_t base = sload_i64(T.dev_off + sload_i32(S.parent + i));
+    for (int j = lane; j < len; j += 64) {
+        const int64_t g = base + S.sub_idx[so + j], o = so + j;
+        const DevFields d = load_fields(T, g);
+        E.os_class[o] = uint8_t(d.cls);
+        E.flags[o] = uint8_t(d.flags);
+        E.f[0][o] = d.scpu; E.f[1][o] = d.sgpu; E.f[2][o] = d.Tc; E.f[3][o] = d.Tg; E.f[4][o] = d.tkc;
+        E.f[5][o] = d.tkg; E.f[6][o] = d.r2v; E.f[7][o] = d.v2r; E.f[8][o] = d.tcomm; E.f[9][o] = d.sdisk;
+        E.f[10][o] = d.ram; E.f[11][o] = d.ccpu; E.f[12][o] = d.cgpu; E.f[13][o] = d.cuda; E.f[14][o] = d.metal;
+        E.f[15][o] = d.swap;
+    }
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the

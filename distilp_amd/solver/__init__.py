@@ -3,7 +3,10 @@
 from .coefficients import HALDAResult, ILPResult
 from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
+from .subfleets import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
+                        halda_solve_subfleets)
 
-__all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "HALDAResult", "ILPResult"]
+__all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solve_subfleets", "halda_leave_one_out",
+           "halda_leave_one_out_batch", "halda_select_devices", "HALDAResult", "ILPResult"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

@@ -189,6 +189,22 @@ def halda_solve(
     return result
 
 
+def _batch_k_list(model: ModelProfile, k_candidates: Optional[Iterable[int]]) -> List[int]:
+    """The k list of the batch entries (halda_solve_batch, subfleets.py): halda_solve's, without its print
+    of the factors of L (valid_factors_of_L prints; the batch entries print nothing)."""
+    if k_candidates:
+        return sorted({_as_k(k) for k in k_candidates})
+    L = model.L
+    return sorted({d for d in range(1, L) if L % d == 0}) if L > 1 else []
+
+
+def _positive_ks(Ks: List[int]) -> List[int]:
+    """The k that reach the GPU; k = 0 raises where the reference divides by it."""
+    if any(k == 0 for k in Ks):
+        raise ZeroDivisionError("integer division or modulo by zero")  # W = L // k (halda_p_solver.py:72)
+    return [k for k in Ks if k > 0]  # k < 0: W < 0, HiGHS reports infeasible
+
+
 def _batch_on_gpu(fleets: Sequence[List[DeviceProfile]], model: ModelProfile, Ks: List[int], kv_factor: float,
                   device: int, _multi=None) -> List[Optional[HALDAResult]]:
     """Many fleets' k-sweeps in ONE halda_solve_fleets call (the fused sweep from the packed
@@ -198,25 +214,31 @@ def _batch_on_gpu(fleets: Sequence[List[DeviceProfile]], model: ModelProfile, Ks
     length runs numpy's 1-D dot loop per row, the bits of `float(c.dot(x))` -- + sum t_comm + sum xi +
     kappa in the reference's own order (fleets.fleet_constants); best k by ascending k and strict "<"
     (:407, the first minimum); w, n = int(round(x)) of the winner. None where no k is feasible."""
-    if any(k == 0 for k in Ks):
-        raise ZeroDivisionError("integer division or modulo by zero")  # W = L // k (halda_p_solver.py:72)
+    pos = _positive_ks(Ks)
     fleets = fleets if isinstance(fleets, list) else list(fleets)
     if not fleets:
         return []
-    pos = [k for k in Ks if k > 0]  # k < 0: W < 0, HiGHS reports infeasible
     # the table and the results are this thread's reusable workspace: everything returned is built from
     # them below (Python ints / floats), nothing keeps a view
     table = fleet_table(fleets, model, _reuse=True)
     if not pos:
         return [None] * len(fleets)
     res = solve_table(table, model, pos, kv_factor, device, want_x="open", _multi=_multi, _reuse=True)
+    return _batch_results(table, res, pos, model)
+
+
+def _batch_results(table, res, pos: List[int], model: ModelProfile, consts=None) -> List[Optional[HALDAResult]]:
+    """_batch_on_gpu's host half: `res` (want_x="open") of the packed `table` swept over `pos` into one
+    HALDAResult per fleet (None where no k is feasible), the objectives formed as described there.
+    subfleets.halda_solve_subfleets runs it on its items: `table` then holds only what is read here
+    (n_fleets, sizes(), dev_off, os_class) and `consts` the items' (sum t_comm, sum xi, kappa)."""
     st = res.status
     bad = (st != STATUS_OPTIMAL) & (st != STATUS_INFEASIBLE)
     if bad.any():
         f, j = map(int, np.argwhere(bad)[0])
         raise RuntimeError(f"libhalda rejected the (fleet {f}, k={pos[j]}) MILP with status {int(st[f, j])}: "
                            "the lowered MILP does not have the HALDA structure")
-    t_sum, x_sum, kappa = fleet_constants(table, model)
+    t_sum, x_sum, kappa = consts if consts is not None else fleet_constants(table, model)
     nf, nk = table.n_fleets, len(pos)
     sizes = table.sizes()
     opt = st == STATUS_OPTIMAL
@@ -280,11 +302,7 @@ def halda_solve_batch(
 
     Returns one HALDAResult per fleet, or None where no k is feasible (where
     `halda_solve` would raise). Prints nothing."""
-    if k_candidates:
-        Ks = sorted({_as_k(k) for k in k_candidates})
-    else:
-        L = model.L
-        Ks = sorted({d for d in range(1, L) if L % d == 0}) if L > 1 else []
+    Ks = _batch_k_list(model, k_candidates)
     kv_factor = kv_bits_to_factor(kv_bits)
     if not Ks:
         return [None] * len(fleets)

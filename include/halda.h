@@ -292,6 +292,59 @@ int halda_last_fleet_ms(void *ctx, double *ms8);
 int halda_solve_fleets_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
                             int32_t n_k, halda_fleet_result *out);
 
+/* ------------------------------------------------------------------------
+ * Sub-fleets of a resident table: leave-one-out and what-if.
+ *
+ * An item is (parent fleet f of `table`, index list s): s holds local device indices into fleet f, each
+ * in [0, M_f), in any order, repeats allowed. Its meaning is the fleet [devs_f[j] for j in s], in that
+ * order (so kappa's head is the first listed device with HALDA_DEV_HEAD, else the first listed device),
+ * and every output of item i equals, bit for bit, what halda_solve_fleets writes for fleet i of a table
+ * that holds the listed devices materialised. `out` is an ordinary halda_fleet_result over the items:
+ * best_k / obj_value per item, w / n laid out by sub_off, obj_by_k / status per (item, k), x / c dense
+ * with the items' max_devices or compact through x_off over (item, k).
+ *
+ * Two routes, one contract (halda_set_subfleets_path). When every item has the same length M' <= 64 and
+ * a batch of n_items fleets of M' devices would run as the register sweep alone (no table launch), one
+ * wave per item reads its index list and gathers its devices' fields straight from the parent table
+ * (halda_sweep_subfleets_kernel): no expanded table exists. Every other call first copies the listed
+ * devices into a compact table in context scratch (halda_expand_subfleets_kernel; grow-only, 130 bytes
+ * per listed device) and runs halda_solve_fleets on it.
+ * ------------------------------------------------------------------------ */
+typedef struct halda_subfleets {
+    int32_t n_items;
+    int32_t min_devices, max_devices;   /* over the items' list lengths */
+    const int32_t *parent;              /* [n_items] fleet of the table */
+    const int64_t *sub_off;             /* [n_items + 1], sub_off[0] = 0 */
+    const int32_t *sub_idx;             /* [sub_off[n_items]] local device indices within the parent */
+} halda_subfleets;
+
+/* Asynchronous on `stream` (NULL = the context's stream); table, items and out hold device arrays, ks is
+ * host memory as for halda_solve_fleets. A parent or device index out of range, an empty list, a
+ * sub_off[0] != 0 or list lengths outside [min_devices, max_devices] are the caller's error (not checked,
+ * as settled flags are not). With mixed list lengths the call reads sub_off[n_items] back to size its
+ * scratch (it waits for `stream` once). */
+int halda_solve_subfleets(void *ctx, const halda_model *model, const halda_fleets *table,
+                          const halda_subfleets *items, const int32_t *ks, int32_t n_k, halda_fleet_result *out,
+                          void *stream);
+
+/* Synchronous variant on HOST arrays: only the parent table and the item arrays cross PCIe on the way in.
+ * Validates the items (parent and device indices in range, no empty list, sub_off ascending from 0, the
+ * length summary, which must be the lists' shortest and longest length exactly: the dense x / c layout
+ * strides by max_devices) and returns HALDA_E_ARG with a message in halda_last_error otherwise;
+ * min_devices = max_devices = 0 lets it compute the summary itself. It knows sub_off[n_items], so it
+ * never reads it back. */
+int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_fleets *table,
+                               const halda_subfleets *items, const int32_t *ks, int32_t n_k,
+                               halda_fleet_result *out);
+
+/* Which route the context's last halda_solve_subfleets / _host call took: 1 the fused route
+ * (halda_sweep_subfleets_kernel), 2 the expansion route, 0 when none ran yet. */
+int halda_last_subfleets_route(void *ctx, int *route);
+
+/* How halda_solve_subfleets runs: 0 automatic (default: the fused route where it applies), 1 always
+ * expand (test path: the fused route is compared against it). HALDA_E_ARG for any other path. */
+int halda_set_subfleets_path(void *ctx, int path);
+
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */
 int halda_resident_release(void *ctx);
