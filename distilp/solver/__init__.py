@@ -3,6 +3,7 @@
 from distilp_amd.solver import HALDAResult, ILPResult, halda_solve, halda_solve_batch  # noqa: F401
 from distilp_amd.solver import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
                                 halda_solve_subfleets)
+from distilp_amd.solver import halda_context_sweep, halda_solve_variants, model_grid  # noqa: F401
 
 __all__ = ["halda_solve", "HALDAResult"]
 

@@ -12,7 +12,8 @@ Same surface and output as the reference CLI (src/cli/solver.py:15-237):
     and ignored, as in the reference;
   * --quiet / --verbose / --save-solution formats of :176-235.
 Beyond the reference: --leave-one-out prints, after the unchanged output above, one line per device with
-the best k and objective of the fleet without it.
+the best k and objective of the fleet without it. --kv-sweep / --n-kv-sweep print, after that, one line per
+(n_kv, kv_bits) point of the grid: the best k and objective of the fleet for that model variant.
 """
 
 from __future__ import annotations
@@ -21,10 +22,10 @@ import argparse
 import json
 import sys
 from pathlib import Path
-from typing import List, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 from ..common import DeviceProfile, ModelProfile, ModelProfileSplit
-from ..solver import halda_leave_one_out, halda_solve
+from ..solver import halda_context_sweep, halda_leave_one_out, halda_solve
 
 
 def load_device_profile(device_path: str) -> DeviceProfile:
@@ -69,6 +70,17 @@ def leave_one_out_lines(devices: List[DeviceProfile], model: ModelProfile, mip_g
             for d, r in zip(devices, res)]
 
 
+def variant_sweep_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: float,
+                        kv_sweep: Optional[Sequence[str]], n_kv_sweep: Optional[Sequence[int]]) -> List[str]:
+    """--kv-sweep / --n-kv-sweep: one line per grid point, n_kv outermost -- n_kv, kv_bits, then the best k and
+    obj_value of the fleet for that variant (halda_context_sweep). Either flag alone sweeps that axis at the
+    model's other value: the model's n_kv, or the "4bit" of the solve above."""
+    rows = halda_context_sweep(devices, model, n_kv_sweep or None, tuple(kv_sweep) if kv_sweep else ("4bit",),
+                               mip_gap=mip_gap)
+    return [f"n_kv={n}, kv_bits={kv}: " + ("infeasible" if r is None else f"k={r.k}, obj={r.obj_value:.6f}")
+            for n, kv, r in rows]
+
+
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Run HALDA solver for distributed LLM inference optimization",
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -89,6 +101,10 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--no-plot", action="store_true", help="Disable plotting of k vs objective curve")
     o.add_argument("--leave-one-out", action="store_true",
                    help="After the solution, print the best k and objective of the fleet without each device")
+    o.add_argument("--kv-sweep", nargs="+", metavar="BITS", choices=("4bit", "8bit", "fp16", "bf16"),
+                   help="After the solution, print the best k and objective at each KV precision (e.g. 4bit 8bit fp16)")
+    o.add_argument("--n-kv-sweep", nargs="+", type=int, metavar="N",
+                   help="After the solution, print the best k and objective at each context length n_kv")
     return p
 
 
@@ -142,6 +158,9 @@ def main(argv=None) -> int:
             print(f"\nSolution saved to: {args.save_solution}")
     if args.leave_one_out:
         for line in leave_one_out_lines(devices, model, args.mip_gap):
+            print(line)
+    if args.kv_sweep or args.n_kv_sweep:
+        for line in variant_sweep_lines(devices, model, args.mip_gap, args.kv_sweep, args.n_kv_sweep):
             print(line)
     return 0
 

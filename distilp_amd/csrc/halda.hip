@@ -160,6 +160,10 @@ struct Ctx {
     size_t sub_tab_bytes = 0;
     int sub_path = 0;               // halda_set_subfleets_path: 0 automatic, 1 always expand
     int sub_route = 0;              // the last halda_solve_subfleets call: 1 fused, 2 expansion (0: none yet)
+    uint8_t *var_desc = nullptr;    // halda_solve_variants: the fused route's per-variant models (SweepModel)
+    size_t var_desc_bytes = 0;
+    int var_path = 0;               // halda_set_variants_path: 0 automatic, 1 always loop
+    int var_route = 0;              // the last halda_solve_variants call: 1 fused, 2 loop (0: none yet)
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -1191,6 +1195,7 @@ void halda_free(void *ctx) {
     if (c->fleet_scratch) (void)hipFree(c->fleet_scratch);
     if (c->gtab) (void)hipFree(c->gtab);
     if (c->sub_tab) (void)hipFree(c->sub_tab);
+    if (c->var_desc) (void)hipFree(c->var_desc);
     for (auto &x : c->sws) {
         if (x.fflag) (void)hipFree(x.fflag);
         if (x.cls) (void)hipFree(x.cls);
@@ -2213,6 +2218,258 @@ int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_
     HIP_TRY(dn(out_h->n, o_n, 4 * tot));
     HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n * n_k));
     HIP_TRY(dn(out_h->status, o_st, 4 * n * n_k));
+    HIP_TRY(dn(out_h->x, o_x, 8 * xs));
+    HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- model variants of one table
+// halda_solve_variants: one fleet table solved for n_var models (the same L, has_f_q and has_f_out: what
+// the packed table and the plan's shapes depend on), outputs variant-major, slice v bit for bit what
+// halda_solve_fleets(&models[v]) writes.
+// Loop route (the specification; every call on path 1): n_var calls of halda_solve_fleets on the caller's
+// stream, the output pointers moved to the variant's slice.
+// Fused route: one launch, blockIdx.y the variant, for the two plans in which one wave owns one fleet from
+// start to end -- kRegAlone with one fleet size <= kK1MaxM (halda_sweep_variants_kernel) and kTablesAlone
+// (halda_sweep_tables_variants_kernel). The plan is that of one variant (plan_sweep reads only L of the
+// model, and compares the fleet count alone with kSweepSmallBatch). The variants' models go into the
+// context's grow-only var_desc with the stream; var_desc is per context, so the call runs after the
+// previous user of the context's shared scratch on another stream (order_after_previous).
+int halda_set_variants_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "variants path must be 0 (automatic) or 1 (always loop)");
+    c->var_path = path;
+    return HALDA_OK;
+}
+
+int halda_last_variants_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->var_route;
+    return HALDA_OK;
+}
+
+static int check_variants(const halda_model *models, int32_t n_var) {
+    if (n_var < 1 || n_var > 65535) return fail(HALDA_E_ARG, "n_var must be in 1..65535");
+    for (int32_t v = 1; v < n_var; ++v) {
+        if (models[v].L != models[0].L)
+            return fail(HALDA_E_ARG, "halda_solve_variants: variant " + std::to_string(v) + " has L = " +
+                                         std::to_string(models[v].L) + ", variant 0 has L = " +
+                                         std::to_string(models[0].L));
+        if (!models[v].has_f_q != !models[0].has_f_q || !models[v].has_f_out != !models[0].has_f_out)
+            return fail(HALDA_E_ARG, "halda_solve_variants: variant " + std::to_string(v) +
+                                         " differs from variant 0 in has_f_q / has_f_out");
+    }
+    return HALDA_OK;
+}
+
+// total: dev_off[n_fleets] when the caller knows it (the host variant), -1 to read it back where needed
+static int solve_variants(void *ctx, const halda_model *models, int32_t n_var, const halda_fleets *fleets,
+                          const int32_t *ks, int32_t n_k, halda_fleet_result *out, void *stream, int64_t total) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !models || !fleets || !ks || !out) return fail(HALDA_E_ARG, "NULL ctx/models/fleets/ks/out");
+    {
+        const int rc = check_variants(models, n_var);
+        if (rc != HALDA_OK) return rc;
+    }
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    for (int32_t v = 0; v < n_var; ++v) {
+        const int rc = check_fleets_args(&models[v], fleets, ks, n_k, out);
+        if (rc != HALDA_OK) return rc;
+    }
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const int64_t nf = F.n_fleets;
+    // the fused kernels index fleets and (fleet, k) instances over all variants with 32 bits
+    if (c->var_path == 0 && c->fleets_fused && n_k <= 64 && int64_t(n_var) * nf * n_k < (int64_t(1) << 31)) {
+        SweepPlan p;
+        const int rc = plan_sweep(c, models[0], F, ks, n_k, *out, &p);
+        if (rc != HALDA_OK) return rc;
+        const bool reg = p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM && !p.A.k1dp;
+        if (reg || p.kind == kTablesAlone) {
+            std::vector<SweepModel> h{size_t(n_var), SweepModel{}};
+            for (int32_t v = 0; v < n_var; ++v) {
+                static_cast<halda_model &>(h[v]) = models[v];
+                h[v].bvo = model_bvo(models[v]);
+            }
+            {
+                int rc2 = order_after_previous(c, s);
+                if (rc2 == HALDA_OK) rc2 = grow(&c->var_desc, &c->var_desc_bytes, sizeof(SweepModel) * h.size());
+                if (rc2 != HALDA_OK) return rc2;
+            }
+            // (pageable source: the copy is staged before the call returns)
+            HIP_TRY(hipMemcpyAsync(c->var_desc, h.data(), sizeof(SweepModel) * h.size(), hipMemcpyHostToDevice, s));
+            const VarArgs V{reinterpret_cast<const SweepModel *>(c->var_desc)};
+            SweepArgs &A = p.A;
+            A.fflag = nullptr;  // neither plan flags: one launch, nothing behind it
+            A.hb_flag = c->hb_flag;
+            A.launch_id = ++c->launch_id;
+            A.want = 0;
+            c->fleet_timed = false;
+            c->have_lowered = false;
+            if (reg) {
+                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+                hipLaunchKernelGGL(halda_sweep_variants_kernel, dim3(p.grid1, unsigned(n_var)), dim3(p.block1), 0, s, A,
+                                   V);
+            } else {
+                A.uM = 0;  // every extent from dev_off (the kernel moves its view of it per variant)
+                const void *fn = reinterpret_cast<const void *>(halda_sweep_tables_variants_kernel);
+                HIP_TRY(Ctx::ensure_lds(fn, p.lds));
+                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+                hipLaunchKernelGGL(halda_sweep_tables_variants_kernel, dim3(p.grid1, unsigned(n_var)), dim3(64),
+                                   size_t(p.lds), s, A, V);
+            }
+            HIP_TRY(hipGetLastError());
+            if (c->timing) {
+                HIP_TRY(hipEventRecord(c->evf1, s));
+                c->fleet_timed = true;
+            }
+            c->fleet_two = false;
+            c->fleet_reg_alone = reg;
+            c->fleet_seg = false;
+            c->fleet_kslot = false;
+            c->last_fleet_fused = true;
+            c->var_route = 1;
+            return HALDA_OK;
+        }
+    }
+    // the loop: variant v's slice of every output
+    int64_t nd = total;
+    if (nd < 0 && n_var > 1) {
+        HIP_TRY(hipMemcpyAsync(&nd, F.dev_off + nf, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (nd < 0) return fail(HALDA_E_ARG, "halda_fleets: dev_off[n_fleets] < 0");
+    }
+    const int64_t xstride = 7 * int64_t(std::max(F.max_devices, 1)) + 1;
+    c->var_route = 2;
+    for (int64_t v = 0; v < n_var; ++v) {
+        halda_fleet_result o = *out;
+        o.best_k += v * nf;
+        o.obj_value += v * nf;
+        if (v) {
+            o.w += v * nd;
+            o.n += v * nd;
+        }
+        if (o.obj_by_k) o.obj_by_k += v * nf * n_k;
+        if (o.status) o.status += v * nf * n_k;
+        if (o.x_off) {
+            o.x_off += v * nf * n_k;  // absolute offsets into the one x / c
+        } else {
+            if (o.x) o.x += v * nf * n_k * xstride;
+            if (o.c) o.c += v * nf * n_k * xstride;
+        }
+        const int rc = halda_solve_fleets(ctx, &models[v], fleets, ks, n_k, &o, s);
+        if (rc != HALDA_OK) return rc;
+    }
+    return HALDA_OK;
+}
+
+int halda_solve_variants(void *ctx, const halda_model *models, int32_t n_var, const halda_fleets *fleets,
+                         const int32_t *ks, int32_t n_k, halda_fleet_result *out, void *stream) {
+    return solve_variants(ctx, models, n_var, fleets, ks, n_k, out, stream, -1);
+}
+
+int halda_solve_variants_host(void *ctx, const halda_model *models, int32_t n_var, const halda_fleets *fh,
+                              const int32_t *ks, int32_t n_k, halda_fleet_result *out_h) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !models || !fh || !ks || !out_h) return fail(HALDA_E_ARG, "NULL ctx/models/fleets/ks/out");
+    {
+        const int rc = check_variants(models, n_var);
+        if (rc != HALDA_OK) return rc;
+    }
+    if (fh->n_fleets <= 0) return HALDA_OK;
+    if (!fh->dev_off) return fail(HALDA_E_ARG, "halda_fleets.dev_off is NULL");
+    if (n_k <= 0 || n_k > 1024) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (!out_h->best_k || !out_h->obj_value || !out_h->w || !out_h->n)
+        return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
+    const int64_t nf = fh->n_fleets, nd = fh->dev_off[nf], nv = n_var;
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    const double *f64[16] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu, fh->t_kvcpy_gpu,
+                             fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk, fh->d_avail_ram, fh->c_cpu,
+                             fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
+    if (!fh->os_class || !fh->flags) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    for (int a = 0; a < 16; ++a)
+        if (!f64[a]) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
+    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16);
+    const bool xsel = out_h->x_off && (out_h->x || out_h->c);
+    const size_t n_inst = size_t(nv) * nf * n_k;
+    const size_t o_xoff = xsel ? take(8 * n_inst) : 0;
+    const size_t o_bk = take(4 * nv * nf), o_obj = take(8 * nv * nf), o_w = take(4 * nv * nd), o_n = take(4 * nv * nd),
+                 o_obk = take(8 * n_inst), o_st = take(4 * n_inst);
+    // x / c extent: the dense layout over (variant, fleet, k), or the caller's compact one (x_off, host memory)
+    size_t xs = n_inst * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
+    if (xsel) {
+        int64_t ext = 0;
+        for (int64_t v = 0; v < nv; ++v)
+            for (int64_t f = 0; f < nf; ++f) {
+                const int64_t N = 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1;
+                for (int j = 0; j < n_k; ++j) {
+                    const int64_t a = out_h->x_off[(v * nf + f) * n_k + j];
+                    if (a >= 0) ext = std::max(ext, a + N);
+                }
+            }
+        xs = size_t(ext);
+    }
+    const size_t o_x = out_h->x ? take(8 * xs) : 0, o_c = out_h->c ? take(8 * xs) : 0;
+    if (off > c->scratch_bytes) {
+        if (c->scratch) HIP_TRY(hipFree(c->scratch));
+        c->scratch = nullptr;
+        c->scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&c->scratch, off));
+        c->scratch_bytes = off;
+    }
+    char *base = static_cast<char *>(c->scratch);
+    // in: the table, once, one copy per array straight from the caller's memory (a DMA where it is
+    // page-locked, halda_host_alloc)
+    auto up = [&](size_t o, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(up(o_doff, fh->dev_off, 8 * (nf + 1)));
+    HIP_TRY(up(o_cls, fh->os_class, nd));
+    HIP_TRY(up(o_fl, fh->flags, nd));
+    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
+    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * n_inst));
+    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
+    halda_fleets d = *fh;
+    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
+    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
+    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
+    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
+    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
+    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
+    d.d_avail_metal = F64(14); d.swap = F64(15);
+    halda_fleet_result r;
+    r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+    r.obj_value = reinterpret_cast<double *>(base + o_obj);
+    r.w = reinterpret_cast<int32_t *>(base + o_w);
+    r.n = reinterpret_cast<int32_t *>(base + o_n);
+    r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
+    r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
+    r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
+    r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
+    r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
+    {
+        const int rc = solve_variants(ctx, models, n_var, &d, ks, n_k, &r, s, nd);  // no read-back of the total
+        if (rc != HALDA_OK) return rc;
+    }
+    // out: only the variants' slices
+    auto dn = [&](void *dst, size_t o, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIP_TRY(dn(out_h->best_k, o_bk, 4 * nv * nf));
+    HIP_TRY(dn(out_h->obj_value, o_obj, 8 * nv * nf));
+    HIP_TRY(dn(out_h->w, o_w, 4 * nv * nd));
+    HIP_TRY(dn(out_h->n, o_n, 4 * nv * nd));
+    HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n_inst));
+    HIP_TRY(dn(out_h->status, o_st, 4 * n_inst));
     HIP_TRY(dn(out_h->x, o_x, 8 * xs));
     HIP_TRY(dn(out_h->c, o_c, 8 * xs));
     HIP_TRY(hipStreamSynchronize(s));

@@ -687,15 +687,16 @@ struct SweepPre {
 // F / O: the batch's table and results (the kernel arguments' A.F / A.out, or one batch of a steps
 // launch); kPre: the fleet's fields come prefetched in *pre (every fleet has A.uM <= kK1MaxM devices);
 // kXC = false: the x / c outputs are compiled out (the caller guarantees outs has none); kLds: A is in
-// LDS (the resident wave), its uniform fields arrive in vector registers.
+// LDS (the resident wave), its uniform fields arrive in vector registers. Mo: the model the fleet is
+// solved for -- the launch's own A.Mo (the overload below), or one variant of a variants launch
+// (halda_sweep_variants_kernel), which shares everything else of A.
 template <bool kTables, bool kGlobal, class SG = Wave, bool kPre = false, bool kXC = !kPre, bool kLds = false>
 __device__ void sweep_fleet(const SweepArgs &A, const halda_fleets &F, const FleetOut &O, int f, const WaveCtx &w,
-                            const SG &sg, const SweepPre *pre = nullptr) {
+                            const SG &sg, const SweepPre *pre, const SweepModel &Mo) {
     constexpr int S = SG::S;
     constexpr bool kSeg = S < 64;
     constexpr bool kFirst = !kTables || kSeg;  // a first launch: flags what it leaves to the table launch
     const int lane = sg.sl;  // device index within the fleet
-    const SweepModel &Mo = A.Mo;
     HALDA_SSTAMP(0, __builtin_amdgcn_s_memtime());
     HALDA_SSTAMP(7, __builtin_amdgcn_s_memrealtime());
     // lane j: k_j and W_j = L / k_j (kernel arguments; their loads are issued with the fields')
@@ -903,7 +904,7 @@ __device__ void sweep_fleet(const SweepArgs &A, const halda_fleets &F, const Fle
                 I.iC = 7 * M;
                 I.R1 = W - M + 1;
                 I.RS = odd_stride(I.R1);
-                const FieldSrc src{&A.Mo, &F, regs ? &me : nullptr, d0, W, sg.base};
+                const FieldSrc src{&Mo, &F, regs ? &me : nullptr, d0, W, sg.base};
                 int64_t nodes = 0;
                 const bool too_large =
                     M > A.mmax || I.R1 > A.r1max || int64_t(M) * I.RS > (kc > 0.0 ? A.tab_kc : A.tab);
@@ -1022,8 +1023,18 @@ __device__ void sweep_fleet(const SweepArgs &A, const halda_fleets &F, const Fle
     HALDA_SSTAMP(8, __builtin_amdgcn_s_memrealtime());
 }
 
+template <bool kTables, bool kGlobal, class SG = Wave, bool kPre = false, bool kXC = !kPre, bool kLds = false>
+__device__ inline void sweep_fleet(const SweepArgs &A, const halda_fleets &F, const FleetOut &O, int f,
+                                   const WaveCtx &w, const SG &sg, const SweepPre *pre = nullptr) {
+    sweep_fleet<kTables, kGlobal, SG, kPre, kXC, kLds>(A, F, O, f, w, sg, pre, A.Mo);
+}
+
+// Mo: the model of every fleet of the launch (A.Mo, or a variant's); fo: added to the fleet index handed
+// to sweep_fleet, the index of the fleet's outputs (0 but for a variants launch, see
+// halda_sweep_tables_variants_kernel).
 template <bool kTables, bool kGlobal>
-__device__ inline void sweep_body(const SweepArgs &A, const SweepBatch &B, unsigned char *slice_base) {
+__device__ inline void sweep_body(const SweepArgs &A, const SweepBatch &B, unsigned char *slice_base,
+                                  const SweepModel &Mo, int fo) {
     const int lane = threadIdx.x;
     if (A.want == 1 && __hip_atomic_load(A.hb_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.launch_id)
         return;
@@ -1052,9 +1063,14 @@ __device__ inline void sweep_body(const SweepArgs &A, const SweepBatch &B, unsig
         while (todo) {
             const int bit = __builtin_ctzll(todo);
             todo &= todo - 1;
-            sweep_fleet<kTables, kGlobal>(A, B.F, B.out, int(b + int64_t(bit) * S), w, Wave(lane));
+            sweep_fleet<kTables, kGlobal>(A, B.F, B.out, int(b + int64_t(bit) * S) + fo, w, Wave(lane), nullptr, Mo);
         }
     }
+}
+
+template <bool kTables, bool kGlobal>
+__device__ inline void sweep_body(const SweepArgs &A, const SweepBatch &B, unsigned char *slice_base) {
+    sweep_body<kTables, kGlobal>(A, B, slice_base, A.Mo, 0);
 }
 
 #ifndef HALDA_SWEEP_WAVES_PER_SIMD
@@ -1247,6 +1263,58 @@ __global__ __launch_bounds__(256) void halda_expand_subfleets_kernel(halda_fleet
     }
 }
 
+// ---------------------------------------------------------------- model variants of one table
+// halda_solve_variants: one fleet table solved for n_var models in one launch, blockIdx.y the variant.
+// The variants share the table, the k list, L (so every W = L / k and the plan's shapes) and has_f_q /
+// has_f_out; everything else of the model is per variant: the call's SweepModel array (bvo formed on the
+// host per variant, as A.Mo.bvo is) in context scratch, read-only to the kernel, so a wave reads its
+// variant's model through the scalar cache, as the steps kernels read their batch's descriptor.
+// The outputs are variant-major, which is the layout of a batch of n_var * n_fleets fleets: variant v's
+// fleet f is output fleet v * n_fleets + f for best_k / obj_value / obj_by_k / status / x / c / x_off
+// (sweep_fleet's fleet index), and its devices' w / n lie at v * dev_off[n_fleets] + their table index.
+struct VarArgs {
+    const SweepModel *models;  // [n_var]
+};
+
+__device__ inline SweepModel var_model(const VarArgs &V, int v) {
+    const __attribute__((address_space(4))) SweepModel &m =
+        reinterpret_cast<const __attribute__((address_space(4))) SweepModel *>(uintptr_t(V.models))[v];
+    SweepModel o;
+    o.f_q_b1 = m.f_q_b1; o.f_out_b1 = m.f_out_b1; o.has_f_q = m.has_f_q; o.has_f_out = m.has_f_out;
+    o.b_prime = m.b_prime; o.b_layer = m.b_layer; o.b_in = m.b_in; o.b_out = m.b_out; o.V = m.V; o.L = m.L;
+    o.bvo = m.bvo;
+    return o;
+}
+
+// halda_sweep_variants_kernel: the register form -- one wave per (variant, fleet), every fleet of
+// A.uM <= kK1MaxM devices and a plan that needs no table launch (the host checks both). The fleet's fields
+// are loaded as halda_sweep_kernel loads them and handed to the same sweep_fleet (kPre, as the sub-fleet
+// kernel hands its gathered fields), with the variant's model: the same code on the same fields and
+// model as that variant's own halda_sweep_kernel launch, so the same bits. pre.d0 is where the fleet's
+// w / n go.
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_variants_kernel(
+    SweepArgs A, VarArgs V) {
+    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    const int nf = A.F.n_fleets;
+    if (f >= nf) return;
+    const int v = int(blockIdx.y);
+    const int lane = int(threadIdx.x & 63);
+    const int M = A.uM;
+    const int64_t base = sload_i64(A.F.dev_off), nd = sload_i64(A.F.dev_off + nf);
+    const SweepModel Mo = var_model(V, v);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    SweepPre pre;
+    const bool kl = lane < A.n_k;
+    pre.kj = A.ks[kl ? lane : 0];
+    pre.Wj = kl ? A.Ws[lane] : 0;
+    const int64_t d0 = base + int64_t(f) * M;
+    pre.d0 = int64_t(v) * nd + d0;
+    pre.mf = load_fields(A.F, d0 + (lane < M ? lane : 0));
+    sweep_fleet<false, false, Wave, true, true>(A, A.F, A.out, v * nf + f, w, Wave(lane), &pre, Mo);
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the
@@ -1323,6 +1391,26 @@ __global__ __launch_bounds__(64) void halda_resident_kernel(ResidentArgs R) {
 __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_tables_kernel(SweepArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     sweep_body<true, false>(A, batch_of(A), smem);
+}
+
+// halda_sweep_tables_variants_kernel: the table form of a variants launch (a small batch whose one launch
+// is halda_sweep_tables_kernel) -- grid (the table kernel's own, n_var), every workgroup the table
+// kernel's loop over the fleets with its variant's model. The host sends A.uM = 0, so sweep_fleet takes a
+// fleet's extent from dev_off alone; the wave's view of dev_off is moved back by the variant's fleet offset
+// v * n_fleets, so that the output fleet index sweep_fleet is handed addresses the fleet's own entry, and
+// its view of w / n forward by v * dev_off[n_fleets].
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_tables_variants_kernel(SweepArgs A,
+                                                                                                       VarArgs V) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int v = int(blockIdx.y), nf = A.F.n_fleets;
+    const int64_t nd = sload_i64(A.F.dev_off + nf);
+    const SweepModel Mo = var_model(V, v);
+    halda_fleets F = A.F;
+    F.dev_off -= int64_t(v) * nf;
+    FleetOut O = A.out;
+    O.w += int64_t(v) * nd;
+    O.n += int64_t(v) * nd;
+    sweep_body<true, false>(A, SweepBatch{F, O, nullptr}, smem, Mo, v * nf);
 }
 
 __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_big_kernel(SweepArgs A) {

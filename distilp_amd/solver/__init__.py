@@ -5,8 +5,10 @@ from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
 from .subfleets import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
                         halda_solve_subfleets)
+from .variants import halda_context_sweep, halda_solve_variants, model_grid  # noqa: F401
 
 __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solve_subfleets", "halda_leave_one_out",
-           "halda_leave_one_out_batch", "halda_select_devices", "HALDAResult", "ILPResult"]
+           "halda_leave_one_out_batch", "halda_select_devices", "halda_solve_variants", "halda_context_sweep",
+           "model_grid", "HALDAResult", "ILPResult"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

@@ -86,7 +86,9 @@ EXPORTS = ("halda_version", "halda_init", "halda_solve_batch", "halda_solve_batc
            "halda_fleets_plan_free", "halda_solve_fleets_sharded_emulated", "halda_fleets_plan_launch_many",
            "halda_fleets_group_create", "halda_fleets_group_launch", "halda_fleets_group_free",
            "halda_resident_release", "halda_host_alloc", "halda_host_free", "halda_solve_subfleets",
-           "halda_solve_subfleets_host", "halda_set_subfleets_path", "halda_last_subfleets_route")
+           "halda_solve_subfleets_host", "halda_set_subfleets_path", "halda_last_subfleets_route",
+           "halda_solve_variants", "halda_solve_variants_host", "halda_set_variants_path",
+           "halda_last_variants_route")
 
 _lib = None
 _lib_lock = threading.Lock()

@@ -345,6 +345,48 @@ int halda_last_subfleets_route(void *ctx, int *route);
  * expand (test path: the fused route is compared against it). HALDA_E_ARG for any other path. */
 int halda_set_subfleets_path(void *ctx, int path);
 
+/* ------------------------------------------------------------------------
+ * Model variants of one table: which KV precision and context length can this fleet serve?
+ *
+ * halda_solve_variants solves one fleet table for n_var models in one call. The packed table does not
+ * depend on the variant (it reads the model's quantization and whether f_q / f_out carry "b_1"), so
+ * the variants must share L, has_f_q and has_f_out; every other field (b_prime -- kv_bits and n_kv --,
+ * b_layer, b_in, b_out, V, f_q_b1, f_out_b1) is per variant. Outputs are variant-major: with
+ * nf = n_fleets and nd = dev_off[nf], best_k / obj_value hold n_var * nf entries (variant v, fleet f at
+ * v * nf + f), w / n hold n_var * nd (variant v's block at v * nd), obj_by_k / status n_var * nf * n_k,
+ * x / c are dense with stride 7 max_devices + 1 over (v, f, k), or compact through an x_off of
+ * n_var * nf * n_k entries (element offsets into the one x / c, -1: not wanted). Slice v of every output
+ * equals, bit for bit, what halda_solve_fleets(ctx, &models[v], fleets, ks, n_k, ...) writes.
+ *
+ * Two routes, one contract (halda_set_variants_path). Where halda_solve_fleets would run one launch in
+ * which a wave owns a fleet from start to end -- the register sweep alone over fleets of one size <= 64
+ * (halda_sweep_variants_kernel), or a small batch's table kernel alone (at most 64 fleets, whatever
+ * n_var: halda_sweep_tables_variants_kernel) -- the variants run as ONE launch, blockIdx.y the variant,
+ * each wave reading its variant's model from a per-call array in context scratch. Every other shape
+ * (gated launches, the k-slot and segment kernels, global tables, more than 64 k, the CSR pipeline) is
+ * a loop of n_var halda_solve_fleets calls on the caller's stream with the output pointers moved.
+ * ------------------------------------------------------------------------ */
+
+/* Asynchronous on `stream` (NULL = the context's stream); models and ks are host memory, fleets and out
+ * hold device arrays. HALDA_E_ARG (nothing launched) when n_var < 1 or n_var > 65535, or when the models
+ * do not all share L, has_f_q and has_f_out. On the loop route a call with n_var > 1 reads
+ * dev_off[n_fleets] back to place the w / n slices (it waits for `stream` once). */
+int halda_solve_variants(void *ctx, const halda_model *models, int32_t n_var, const halda_fleets *fleets,
+                         const int32_t *ks, int32_t n_k, halda_fleet_result *out, void *stream);
+
+/* Synchronous variant on HOST arrays: the table crosses PCIe once on the way in, the n_var result slices
+ * on the way out. It knows dev_off[n_fleets], so it never reads it back. */
+int halda_solve_variants_host(void *ctx, const halda_model *models, int32_t n_var, const halda_fleets *fleets,
+                              const int32_t *ks, int32_t n_k, halda_fleet_result *out);
+
+/* Which route the context's last halda_solve_variants / _host call took: 1 fused (one launch), 2 the
+ * per-variant loop, 0 when none ran yet. */
+int halda_last_variants_route(void *ctx, int *route);
+
+/* How halda_solve_variants runs: 0 automatic (default: the fused route where it applies), 1 always loop
+ * (test path: the fused route is compared against it). HALDA_E_ARG for any other path. */
+int halda_set_variants_path(void *ctx, int path);
+
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */
 int halda_resident_release(void *ctx);
