@@ -4,6 +4,8 @@ from distilp_amd.solver import HALDAResult, ILPResult, halda_solve, halda_solve_
 from distilp_amd.solver import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
                                 halda_solve_subfleets)
 from distilp_amd.solver import halda_context_sweep, halda_solve_variants, model_grid  # noqa: F401
+from distilp_amd.solver import (PlanEvaluation, Replacement, evaluate_plan_np, halda_evaluate_plan,  # noqa: F401
+                                halda_evaluate_plans_batch, halda_replace_or_keep, halda_replace_or_keep_batch)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

@@ -14,6 +14,9 @@ Same surface and output as the reference CLI (src/cli/solver.py:15-237):
 Beyond the reference: --leave-one-out prints, after the unchanged output above, one line per device with
 the best k and objective of the fleet without it. --kv-sweep / --n-kv-sweep print, after that, one line per
 (n_kv, kv_bits) point of the grid: the best k and objective of the fleet for that model variant.
+--evaluate-solution FILE prints, last, the plan of a --save-solution JSON priced on the current fleet and its
+regret / moved layers against the solution above; a file that does not name exactly the current devices is an
+error (exit status 2).
 """
 
 from __future__ import annotations
@@ -25,7 +28,8 @@ from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
 
 from ..common import DeviceProfile, ModelProfile, ModelProfileSplit
-from ..solver import halda_context_sweep, halda_leave_one_out, halda_solve
+from ..solver import halda_context_sweep, halda_evaluate_plan, halda_leave_one_out, halda_solve
+from ..solver.plans import replacement
 
 
 def load_device_profile(device_path: str) -> DeviceProfile:
@@ -81,6 +85,38 @@ def variant_sweep_lines(devices: List[DeviceProfile], model: ModelProfile, mip_g
             for n, kv, r in rows]
 
 
+class SolutionMismatch(ValueError):
+    """A --evaluate-solution file that does not describe the current fleet."""
+
+
+def load_incumbent(path: str, devices: List[DeviceProfile]) -> Tuple[int, List[int], List[int]]:
+    """--evaluate-solution FILE: the (k, w, n) of a --save-solution JSON, matched to the current fleet by device
+    name. SolutionMismatch when a name of the file is not in the fleet or a device of the fleet not in the file."""
+    sol = json.loads(Path(path).read_text())
+    dist = sol["layer_distribution"]
+    names = [d.name for d in devices]
+    extra = [n for n in dist if n not in names]
+    if extra:
+        raise SolutionMismatch(f"{path}: device(s) not in the current fleet: {', '.join(extra)}")
+    missing = [n for n in names if n not in dist]
+    if missing:
+        raise SolutionMismatch(f"{path}: no entry for device(s) of the current fleet: {', '.join(missing)}")
+    if int(sol["k"]) <= 0:
+        raise SolutionMismatch(f"{path}: k = {sol['k']} must be positive")
+    return int(sol["k"]), [int(dist[n]["w"]) for n in names], [int(dist[n]["n"]) for n in names]
+
+
+def incumbent_lines(devices: List[DeviceProfile], model: ModelProfile, plan, result) -> List[str]:
+    """--evaluate-solution: the incumbent priced on the current fleet (halda_evaluate_plan, kv_bits "4bit" like
+    the solve above), then its regret against the solution printed above and the layers that would move."""
+    k, w, _ = plan
+    ev = halda_evaluate_plan(devices, model, *plan, kv_bits="4bit")
+    rep = replacement(ev, plan, result)
+    first = (f"incumbent: k={k}, obj={ev.obj_value:.6f}" if ev.feasible
+             else f"incumbent: infeasible ({', '.join(ev.reasons)})")
+    return [first, f"regret={rep.regret:.6f}, moved_layers={rep.moved_layers}"]
+
+
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Run HALDA solver for distributed LLM inference optimization",
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -105,6 +141,9 @@ def _parser() -> argparse.ArgumentParser:
                    help="After the solution, print the best k and objective at each KV precision (e.g. 4bit 8bit fp16)")
     o.add_argument("--n-kv-sweep", nargs="+", type=int, metavar="N",
                    help="After the solution, print the best k and objective at each context length n_kv")
+    o.add_argument("--evaluate-solution", metavar="FILE",
+                   help="After the solution, price the plan of a --save-solution JSON on this fleet: its objective "
+                        "(or why it is infeasible), its regret against the solution and the layers that would move")
     return p
 
 
@@ -124,6 +163,14 @@ def main(argv=None) -> int:
         parser.error("--devices requires --model")
     else:
         parser.error("Either --profile or both --devices and --model must be provided.")
+
+    incumbent = None
+    if args.evaluate_solution:
+        try:
+            incumbent = load_incumbent(args.evaluate_solution, devices)
+        except (SolutionMismatch, OSError, KeyError, TypeError, ValueError) as e:
+            print(f"error: --evaluate-solution: {e}", file=sys.stderr)
+            return 2
 
     if args.verbose:
         print(f"\n{bar}\nLoaded {len(devices)} device(s):\n{bar}")
@@ -161,6 +208,9 @@ def main(argv=None) -> int:
             print(line)
     if args.kv_sweep or args.n_kv_sweep:
         for line in variant_sweep_lines(devices, model, args.mip_gap, args.kv_sweep, args.n_kv_sweep):
+            print(line)
+    if incumbent is not None:
+        for line in incumbent_lines(devices, model, incumbent, result):
             print(line)
     return 0
 

@@ -164,6 +164,8 @@ struct Ctx {
     size_t var_desc_bytes = 0;
     int var_path = 0;               // halda_set_variants_path: 0 automatic, 1 always loop
     int var_route = 0;              // the last halda_solve_variants call: 1 fused, 2 loop (0: none yet)
+    int plans_path = 0;             // halda_set_plans_path: 0 automatic, 1 always two launches, 2 fused where it applies
+    int plans_route = 0;            // the last halda_solve_fleets_plans call: 1 fused, 2 two launches (0: none yet)
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -2474,6 +2476,311 @@ int halda_solve_variants_host(void *ctx, const halda_model *models, int32_t n_va
     HIP_TRY(dn(out_h->c, o_c, 8 * xs));
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- a caller's plan priced on the table
+// halda_eval_plans: fleet f's plan (k, w, n) evaluated on the table (halda_eval_plans_kernel, any shape).
+// halda_solve_fleets_plans: the k-sweep of the table plus the evaluation of the incumbent plans.
+// Two-launch route (the default, every shape): halda_eval_plans_kernel, then halda_solve_fleets, both on the
+// caller's stream. Fused route (path 2): where the sweep is the register launch alone over fleets of one size
+// <= kK1MaxM (kRegAlone, the sub-fleet and variants kernels' gate), ONE launch of halda_sweep_plans_kernel --
+// each wave prices its fleet's plan on the fields it loads for the sweep.
+int halda_set_plans_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path < 0 || path > 2)
+        return fail(HALDA_E_ARG, "plans path must be 0 (automatic), 1 (always two launches) or 2 (fused where it applies)");
+    c->plans_path = path;
+    return HALDA_OK;
+}
+
+int halda_last_plans_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->plans_route;
+    return HALDA_OK;
+}
+
+// Argument checks of the plan entries, before any HIP call (HALDA_OK: go on).
+static int check_plans_args(const void *ctx, const halda_model *model, const halda_fleets *fleets,
+                            const halda_plans *plans, const halda_plan_result *out, const char *who) {
+    if (!ctx || !model || !fleets || !plans || !out)
+        return fail(HALDA_E_ARG, std::string(who) + ": NULL ctx/model/fleets/plans/out");
+    if (fleets->n_fleets < 0) return fail(HALDA_E_ARG, std::string(who) + ": n_fleets < 0");
+    if (!plans->k || !plans->w || !plans->n) return fail(HALDA_E_ARG, std::string(who) + ": halda_plans has a NULL array");
+    if (!out->status || !out->obj_value)
+        return fail(HALDA_E_ARG, std::string(who) + ": halda_plan_result needs status and obj_value");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    return HALDA_OK;
+}
+
+static int check_plans_table(const halda_fleets &F) {
+    if (F.min_devices < 1 || F.max_devices < F.min_devices || F.max_devices > 4096)
+        return fail(HALDA_E_ARG, "halda_fleets: need 1 <= min_devices <= max_devices <= 4096");
+    if (!F.dev_off || !F.os_class || !F.flags || !F.scpu_b1 || !F.sgpu_b1 || !F.T_cpu || !F.T_gpu ||
+        !F.t_kvcpy_cpu || !F.t_kvcpy_gpu || !F.t_ram2vram || !F.t_vram2ram || !F.t_comm || !F.s_disk ||
+        !F.d_avail_ram || !F.c_cpu || !F.c_gpu || !F.d_avail_cuda || !F.d_avail_metal || !F.swap)
+        return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    return HALDA_OK;
+}
+
+static PlanArgs plan_args(const halda_fleets &F, const halda_plans &P, const halda_plan_result &O) {
+    PlanArgs E = {};
+    E.k = P.k; E.w = P.w; E.n = P.n;
+    E.status = O.status; E.obj_value = O.obj_value; E.cycle = O.cycle; E.bottleneck = O.bottleneck;
+    E.reason = O.reason; E.x = O.x; E.c = O.c; E.x_off = O.x_off;
+    E.xstride = 7 * int64_t(std::max(F.max_devices, 1)) + 1;
+    E.outs = (O.x ? kOutX : 0) | (O.c ? kOutC : 0) | (O.cycle ? kPlanOutCycle : 0) |
+             (O.bottleneck ? kPlanOutBott : 0) | (O.reason ? kPlanOutReason : 0);
+    return E;
+}
+
+static int launch_eval_plans(const halda_model &model, const halda_fleets &F, const PlanArgs &E, hipStream_t s) {
+    EvalArgs A;
+    static_cast<halda_model &>(A.Mo) = model;
+    A.Mo.bvo = model_bvo(model);
+    A.F = F;
+    A.E = E;
+    hipLaunchKernelGGL(halda_eval_plans_kernel, dim3(unsigned((int64_t(F.n_fleets) + 3) / 4)), dim3(256), 0, s, A);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+int halda_eval_plans(void *ctx, const halda_model *model, const halda_fleets *fleets, const halda_plans *plans,
+                     halda_plan_result *out, void *stream) {
+    {
+        const int rc = check_plans_args(ctx, model, fleets, plans, out, "halda_eval_plans");
+        if (rc != HALDA_OK) return rc;
+    }
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets == 0) return HALDA_OK;
+    {
+        const int rc = check_plans_table(F);
+        if (rc != HALDA_OK) return rc;
+    }
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    return launch_eval_plans(*model, F, plan_args(F, *plans, *out), s);
+}
+
+int halda_solve_fleets_plans(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                             int32_t n_k, const halda_plans *plans, halda_plan_result *eval_out,
+                             halda_fleet_result *out, void *stream) {
+    {
+        const int rc = check_plans_args(ctx, model, fleets, plans, eval_out, "halda_solve_fleets_plans");
+        if (rc != HALDA_OK) return rc;
+    }
+    if (!ks || !out) return fail(HALDA_E_ARG, "halda_solve_fleets_plans: NULL ks/out");
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets == 0) return HALDA_OK;
+    {
+        const int rc = check_fleets_args(model, fleets, ks, n_k, out);
+        if (rc != HALDA_OK) return rc;
+    }
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const PlanArgs E = plan_args(F, *plans, *eval_out);
+    // automatic = two launches: the fused launch measured 7 % ahead of them on C3's shape, inside the
+    // box-to-box spread, so it stays behind path 2
+    if (c->plans_path == 2 && c->fleets_fused && n_k <= 64) {
+        SweepPlan p;
+        const int rc = plan_sweep(c, *model, F, ks, n_k, *out, &p);
+        if (rc != HALDA_OK) return rc;
+        if (p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM && !p.A.k1dp) {
+            SweepArgs &A = p.A;
+            A.fflag = nullptr;  // the register sweep alone never flags
+            A.hb_flag = c->hb_flag;
+            A.launch_id = ++c->launch_id;
+            A.want = 0;
+            c->fleet_timed = false;
+            c->have_lowered = false;
+            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+            hipLaunchKernelGGL(halda_sweep_plans_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, E);
+            HIP_TRY(hipGetLastError());
+            if (c->timing) {
+                HIP_TRY(hipEventRecord(c->evf1, s));
+                c->fleet_timed = true;
+            }
+            c->fleet_two = false;
+            c->fleet_reg_alone = true;
+            c->fleet_seg = false;
+            c->fleet_kslot = false;
+            c->last_fleet_fused = true;
+            c->plans_route = 1;
+            return HALDA_OK;
+        }
+    }
+    {
+        const int rc = launch_eval_plans(*model, F, E, s);
+        if (rc != HALDA_OK) return rc;
+    }
+    c->plans_route = 2;
+    return halda_solve_fleets(ctx, model, fleets, ks, n_k, out, s);
+}
+
+// The host variants: the table, the plans (and x_off) cross PCIe once on the way in, the results on the way
+// out, through the context's staging scratch. out_h == nullptr: the evaluation alone.
+static int plans_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks, int32_t n_k,
+                      const halda_plans *ph, halda_plan_result *eh, halda_fleet_result *out_h) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int64_t nf = fh->n_fleets;
+    if (nf == 0) return HALDA_OK;
+    if (!fh->dev_off) return fail(HALDA_E_ARG, "halda_fleets.dev_off is NULL");
+    {
+        const int rc = check_plans_table(*fh);
+        if (rc != HALDA_OK) return rc;
+    }
+    if (out_h) {
+        if (n_k <= 0 || n_k > 1024) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+        if (!out_h->best_k || !out_h->obj_value || !out_h->w || !out_h->n)
+            return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
+    }
+    const int64_t nd = fh->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    const double *f64[16] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu, fh->t_kvcpy_gpu,
+                             fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk, fh->d_avail_ram, fh->c_cpu,
+                             fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
+    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16);
+    // the plans and the evaluation's outputs
+    const size_t o_pk = take(4 * nf), o_pw = take(4 * nd), o_pn = take(4 * nd);
+    const size_t o_est = take(4 * nf), o_eobj = take(8 * nf), o_ecyc = take(8 * nf), o_ebot = take(4 * nf),
+                 o_erea = take(4 * nf);
+    const bool exsel = eh->x_off && (eh->x || eh->c);
+    const size_t o_exoff = exsel ? take(8 * nf) : 0;
+    size_t exs = size_t(nf) * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
+    if (exsel) {
+        int64_t ext = 0;
+        for (int64_t f = 0; f < nf; ++f) {
+            const int64_t a = eh->x_off[f];
+            if (a >= 0) ext = std::max(ext, a + 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1);
+        }
+        exs = size_t(ext);
+    }
+    const size_t o_ex = eh->x ? take(8 * exs) : 0, o_ec = eh->c ? take(8 * exs) : 0;
+    // the sweep's outputs
+    const size_t n_inst = out_h ? size_t(nf) * n_k : 0;
+    const bool xsel = out_h && out_h->x_off && (out_h->x || out_h->c);
+    const size_t o_xoff = xsel ? take(8 * n_inst) : 0;
+    const size_t o_bk = take(4 * nf), o_obj = take(8 * nf), o_w = take(4 * nd), o_n = take(4 * nd),
+                 o_obk = take(8 * n_inst), o_st = take(4 * n_inst);
+    size_t xs = n_inst * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
+    if (xsel) {
+        int64_t ext = 0;
+        for (int64_t f = 0; f < nf; ++f) {
+            const int64_t N = 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1;
+            for (int j = 0; j < n_k; ++j) {
+                const int64_t a = out_h->x_off[f * n_k + j];
+                if (a >= 0) ext = std::max(ext, a + N);
+            }
+        }
+        xs = size_t(ext);
+    }
+    const size_t o_x = out_h && out_h->x ? take(8 * xs) : 0, o_c = out_h && out_h->c ? take(8 * xs) : 0;
+    if (off > c->scratch_bytes) {
+        if (c->scratch) HIP_TRY(hipFree(c->scratch));
+        c->scratch = nullptr;
+        c->scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&c->scratch, off));
+        c->scratch_bytes = off;
+    }
+    char *base = static_cast<char *>(c->scratch);
+    auto up = [&](size_t o, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(up(o_doff, fh->dev_off, 8 * (nf + 1)));
+    HIP_TRY(up(o_cls, fh->os_class, nd));
+    HIP_TRY(up(o_fl, fh->flags, nd));
+    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
+    HIP_TRY(up(o_pk, ph->k, 4 * nf));
+    HIP_TRY(up(o_pw, ph->w, 4 * nd));
+    HIP_TRY(up(o_pn, ph->n, 4 * nd));
+    if (exsel) HIP_TRY(up(o_exoff, eh->x_off, 8 * nf));
+    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * n_inst));
+    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
+    halda_fleets d = *fh;
+    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
+    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
+    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
+    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
+    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
+    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
+    d.d_avail_metal = F64(14); d.swap = F64(15);
+    halda_plans dp;
+    dp.k = reinterpret_cast<const int32_t *>(base + o_pk);
+    dp.w = reinterpret_cast<const int32_t *>(base + o_pw);
+    dp.n = reinterpret_cast<const int32_t *>(base + o_pn);
+    halda_plan_result de;
+    de.status = reinterpret_cast<int32_t *>(base + o_est);
+    de.obj_value = reinterpret_cast<double *>(base + o_eobj);
+    de.cycle = eh->cycle ? reinterpret_cast<double *>(base + o_ecyc) : nullptr;
+    de.bottleneck = eh->bottleneck ? reinterpret_cast<int32_t *>(base + o_ebot) : nullptr;
+    de.reason = eh->reason ? reinterpret_cast<int32_t *>(base + o_erea) : nullptr;
+    de.x = eh->x ? reinterpret_cast<double *>(base + o_ex) : nullptr;
+    de.c = eh->c ? reinterpret_cast<double *>(base + o_ec) : nullptr;
+    de.x_off = exsel ? reinterpret_cast<const int64_t *>(base + o_exoff) : nullptr;
+    if (out_h) {
+        halda_fleet_result r;
+        r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+        r.obj_value = reinterpret_cast<double *>(base + o_obj);
+        r.w = reinterpret_cast<int32_t *>(base + o_w);
+        r.n = reinterpret_cast<int32_t *>(base + o_n);
+        r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
+        r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
+        r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
+        r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
+        r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
+        const int rc = halda_solve_fleets_plans(ctx, model, &d, ks, n_k, &dp, &de, &r, s);
+        if (rc != HALDA_OK) return rc;
+    } else {
+        const int rc = halda_eval_plans(ctx, model, &d, &dp, &de, s);
+        if (rc != HALDA_OK) return rc;
+    }
+    auto dn = [&](void *dst, size_t o, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIP_TRY(dn(eh->status, o_est, 4 * nf));
+    HIP_TRY(dn(eh->obj_value, o_eobj, 8 * nf));
+    HIP_TRY(dn(eh->cycle, o_ecyc, 8 * nf));
+    HIP_TRY(dn(eh->bottleneck, o_ebot, 4 * nf));
+    HIP_TRY(dn(eh->reason, o_erea, 4 * nf));
+    HIP_TRY(dn(eh->x, o_ex, 8 * exs));
+    HIP_TRY(dn(eh->c, o_ec, 8 * exs));
+    if (out_h) {
+        HIP_TRY(dn(out_h->best_k, o_bk, 4 * nf));
+        HIP_TRY(dn(out_h->obj_value, o_obj, 8 * nf));
+        HIP_TRY(dn(out_h->w, o_w, 4 * nd));
+        HIP_TRY(dn(out_h->n, o_n, 4 * nd));
+        HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n_inst));
+        HIP_TRY(dn(out_h->status, o_st, 4 * n_inst));
+        HIP_TRY(dn(out_h->x, o_x, 8 * xs));
+        HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+int halda_eval_plans_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const halda_plans *plans,
+                          halda_plan_result *out) {
+    const int rc = check_plans_args(ctx, model, fleets, plans, out, "halda_eval_plans_host");
+    if (rc != HALDA_OK) return rc;
+    return plans_host(ctx, model, fleets, nullptr, 0, plans, out, nullptr);
+}
+
+int halda_solve_fleets_plans_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                                  int32_t n_k, const halda_plans *plans, halda_plan_result *eval_out,
+                                  halda_fleet_result *out) {
+    const int rc = check_plans_args(ctx, model, fleets, plans, eval_out, "halda_solve_fleets_plans_host");
+    if (rc != HALDA_OK) return rc;
+    if (!ks || !out) return fail(HALDA_E_ARG, "halda_solve_fleets_plans_host: NULL ks/out");
+    return plans_host(ctx, model, fleets, ks, n_k, plans, eval_out, out);
 }
 
 // ---------------------------------------------------------------- several GPUs, one process

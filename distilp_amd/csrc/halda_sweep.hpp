@@ -1315,6 +1315,259 @@ __global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIM
     sweep_fleet<false, false, Wave, true, true>(A, A.F, A.out, v * nf + f, w, Wave(lane), &pre, Mo);
 }
 
+// ---------------------------------------------------------------- a caller's plan priced on the table
+// halda_eval_plans: fleet f's plan (k, w[M], n[M]) evaluated on the fleet's records at W = L / k -- the
+// least slacks (rec_slacks), the device cost (rec_try's expression), the cycle time (dev_cycle) and the
+// objective sweep_fleet forms, on the caller's (w, n) instead of on the minimiser.
+// reason bits of an infeasible plan:
+constexpr int kPlanSumW = 1;     // sum w != W
+constexpr int kPlanRangeW = 2;   // some w_i outside [1, W]
+constexpr int kPlanRangeN = 4;   // some n_i outside its interval (rec_interval at w_i)
+constexpr int kPlanSlack = 8;    // a slack over its bound: setok false, or the VRAM slack over nhi
+constexpr int kPlanRecord = 16;  // record rejected (bad / rec_nanx), or W >= 1e6: HALDA_STATUS_UNSUPPORTED
+constexpr int kPlanNone = 32;    // k <= 0: no plan
+// PlanArgs.outs: the optional outputs wanted (kOutX / kOutC and these)
+constexpr int kPlanOutCycle = 32, kPlanOutBott = 64, kPlanOutReason = 128;
+
+struct PlanArgs {
+    const int32_t *k, *w, *n;  // halda_plans
+    int32_t *status;           // halda_plan_result
+    double *obj_value, *cycle;
+    int32_t *bottleneck, *reason;
+    double *x, *c;
+    const int64_t *x_off;
+    int64_t xstride;  // dense x / c: 7 max_devices + 1 per fleet
+    int outs;
+};
+
+// One device of a plan: its reason bits, and where it has none its cost g (rec_try's term order), least
+// slacks s, least cycle time H and z as sweep_fleet forms them for a solved k. W is 0 for a plan without
+// a usable k (every w is then out of range); the n checks are made only where w_i is in [1, W] < 1e6, so
+// no sum below can leave the int range whatever the caller's w / n hold.
+struct PlanDev {
+    double g, H, z;
+    int s[4];
+    int reason;
+};
+
+__device__ inline PlanDev plan_dev(FieldRec &r, int bad, int W, int wl, int n) {
+    PlanDev d;
+    d.g = 0.0; d.H = 0.0; d.z = 0.0;
+    d.s[0] = d.s[1] = d.s[2] = d.s[3] = 0;
+    r.W = W;
+    int reason = (bad || rec_nanx(r)) ? kPlanRecord : 0;
+    const bool wok = wl >= 1 && wl <= W;
+    if (!wok) reason |= kPlanRangeW;
+    if (wok) {
+        int nL, nU;
+        rec_interval(r, wl, nL, nU);
+        const bool hs = r.Kset != kNoRow;
+        const bool setok = !(hs && (r.cls == 1 || r.cls == 2)) || max(0, wl + r.Kset) <= W;
+        const int nhi = r.gpu ? W : 0;
+        if (!(n >= nL && n <= nU)) reason |= kPlanRangeN;
+        if (!setok || (r.Kvram != kNoRow && n > nhi - r.Kvram)) reason |= kPlanSlack;
+    }
+    d.reason = reason;
+    if (reason == 0) {
+        rec_slacks(r, wl, n, d.s);
+        const double pv = rec_pv(r), pvo = rec_own(r) ? pv : 0.0;
+        const int sc = max(0, wl - (r.cls == 3 ? n : 0) + r.Kset);
+        double g = r.alpha * double(wl);
+        g = g + r.b * double(n);
+        g = g + pvo * double(sc);
+        g = g + pv * double(d.s[3]);
+        d.g = g;
+        double P, Q;
+        dev_cycle(r, wl, n, d.s, P, Q);
+        d.z = Q > P ? 0.5 * (Q - P) : 0.0;
+        d.H = Q >= P ? 0.5 * (P + Q) : P;
+    }
+    return d;
+}
+
+// Column i of the plan's x / c (put_xc's layout [w|n|s1|s2|s3|t|z|C]); zeros for a plan that is not feasible.
+__device__ inline void plan_put_xc(const PlanArgs &E, int64_t at, int M, int i, bool feas, int wl, int n,
+                                   const PlanDev &d, const FieldRec &r) {
+    if (E.outs & kOutX) {
+        double *x = E.x + at;
+        x[i] = feas ? double(wl) : 0.0; x[M + i] = feas ? double(n) : 0.0;
+        x[2 * M + i] = double(feas ? d.s[0] : 0); x[3 * M + i] = double(feas ? d.s[1] : 0);
+        x[4 * M + i] = double(feas ? d.s[2] : 0); x[5 * M + i] = double(feas ? d.s[3] : 0);
+        x[6 * M + i] = feas ? d.z : 0.0;
+    }
+    if (E.outs & kOutC) {
+        double *c = E.c + at;
+        c[i] = feas ? r.alpha : 0.0; c[M + i] = feas ? r.b : 0.0; c[2 * M + i] = feas ? r.p_bp : 0.0;
+        c[3 * M + i] = feas ? r.p_b : 0.0; c[4 * M + i] = feas ? r.p_bp : 0.0;
+        c[5 * M + i] = feas ? rec_pv(r) : 0.0; c[6 * M + i] = 0.0;
+    }
+}
+
+// The fleet's verdict from the OR of its devices' reason bits, sum w (a double: exact for any int32 w) and k.
+__device__ inline int plan_reason(int dev_bits, double wsum, int k, int W) {
+    if (k <= 0) return kPlanNone;
+    int reason = dev_bits;
+    if (!(W < 1000000)) reason |= kPlanRecord;
+    if (wsum != double(W)) reason |= kPlanSumW;
+    return reason;
+}
+
+__device__ inline void plan_store(const PlanArgs &E, int f, int64_t at, int M, int lane, int reason, double obj,
+                                  double C, double hraw, int bott, int k) {
+    const bool feas = reason == 0;
+    if (lane == 0) {
+        E.status[f] = feas ? HALDA_STATUS_OPTIMAL
+                           : (reason & kPlanRecord) ? HALDA_STATUS_UNSUPPORTED : HALDA_STATUS_INFEASIBLE;
+        E.obj_value[f] = feas ? obj : kInf;
+        if (E.outs & kPlanOutCycle) E.cycle[f] = feas ? C : kInf;
+        if (E.outs & kPlanOutBott) E.bottleneck[f] = feas && hraw > 0.0 ? bott : -1;
+        if (E.outs & kPlanOutReason) E.reason[f] = reason;
+        if (at >= 0 && (E.outs & kOutX)) E.x[at + 7 * M] = feas ? C : 0.0;
+        if (at >= 0 && (E.outs & kOutC)) E.c[at + 7 * M] = feas ? double(k - 1) : 0.0;
+    }
+}
+
+__device__ inline int64_t plan_xc_at(const PlanArgs &E, int f) {
+    if (!(E.outs & kOutXC)) return -1;
+    return E.x_off ? E.x_off[f] : int64_t(f) * E.xstride;
+}
+
+// A fleet of M <= 64 devices, lane = device, its fields (mf), plan entries (pw, pn) and k already loaded.
+// The objective is added in sweep_fleet<.., Wave>'s order: sum_f64(g) + kc hmax, + tsum, + xsum, + kappa
+// (fleet_offsets_regs's constants), so a plan that is a sweep's own (k, w, n) gets the sweep's bits.
+__device__ inline void eval_plan_regs(const SweepModel &Mo, const PlanArgs &E, int f, int M, const Wave &sg,
+                                      const DevFields &mf, int k, int pw, int pn) {
+    const int lane = sg.sl;
+    const bool act = lane < M;
+    int bad = 0;
+    FieldRec r = field_rec(Mo, mf, bad);
+    const int Wk = k > 0 ? Mo.L / k : 0;
+    const int W = Wk < 1000000 ? Wk : 0;
+    const PlanDev d = plan_dev(r, bad, W, pw, pn);
+    const int reason = plan_reason(sg.or_i(act ? d.reason : 0), sg.sum_f64(act ? double(pw) : 0.0), k, Wk);
+    const bool feas = reason == 0;
+    double tsum, xsum, kappa;
+    fleet_offsets_regs<Wave, false>(Mo, mf, M, sg, tsum, xsum, kappa);
+    const double hraw = sg.max_f64(act && feas ? d.H : -kInf);
+    const double C = fmax(0.0, hraw);
+    const int bott = sg.lowest(act && d.H == hraw);
+    double obj = sg.sum_f64(act ? d.g : 0.0) + double(k - 1) * C;
+    obj = obj + tsum;
+    obj = obj + xsum;
+    obj = obj + kappa;
+    const int64_t at = plan_xc_at(E, f);
+    if (at >= 0 && act) plan_put_xc(E, at, M, lane, feas, pw, pn, d, r);
+    plan_store(E, f, at, M, lane, reason, obj, C, hraw, bott, k);
+}
+
+// A fleet wider than a wave: 64-device chunks, the partial sums, max and its lowest device carried in
+// registers (a lane's devices come in ascending order, so a strict ">" keeps the lowest), the constants
+// from fleet_offsets_tree -- the table path's order in sweep_fleet. x / c need the fleet's verdict first:
+// a second pass over the chunks rebuilds each device's values (no per-device state is kept).
+__device__ inline void eval_plan_wide(const SweepModel &Mo, const halda_fleets &F, const PlanArgs &E, int f,
+                                      int64_t d0, int M, const Wave &sg, int k) {
+    const int lane = sg.sl;
+    const int Wk = k > 0 ? Mo.L / k : 0;
+    const int W = Wk < 1000000 ? Wk : 0;
+    double gs = 0.0, ws = 0.0, hm = -kInf;
+    int bits = 0, bi = 0x7fffffff;
+    for (int i = lane; i < M; i += 64) {
+        int bad = 0;
+        const DevFields mf = load_fields(F, d0 + i);
+        const int pw = E.w[d0 + i], pn = E.n[d0 + i];
+        FieldRec r = field_rec(Mo, mf, bad);
+        const PlanDev d = plan_dev(r, bad, W, pw, pn);
+        bits |= d.reason;
+        ws += double(pw);
+        gs += d.g;
+        if (d.reason == 0 && d.H > hm) {
+            hm = d.H;
+            bi = i;
+        }
+    }
+    const int reason = plan_reason(sg.or_i(bits), sg.sum_f64(ws), k, Wk);
+    const bool feas = reason == 0;
+    double tsum, xsum, kappa;
+    fleet_offsets_tree(Mo, F, d0, M, lane, tsum, xsum, kappa);
+    const double hraw = sg.max_f64(hm);
+    const double C = fmax(0.0, hraw);
+    const int bott = sg.imin(hm == hraw ? bi : 0x7fffffff);
+    double obj = sg.sum_f64(gs) + double(k - 1) * C;
+    obj = obj + tsum;
+    obj = obj + xsum;
+    obj = obj + kappa;
+    const int64_t at = plan_xc_at(E, f);
+    if (at >= 0)
+        for (int i = lane; i < M; i += 64) {
+            int bad = 0;
+            const int pw = E.w[d0 + i], pn = E.n[d0 + i];
+            FieldRec r = field_rec(Mo, load_fields(F, d0 + i), bad);
+            const PlanDev d = plan_dev(r, bad, W, pw, pn);
+            plan_put_xc(E, at, M, i, feas, pw, pn, d, r);
+        }
+    plan_store(E, f, at, M, lane, reason, obj, C, hraw, bott, k);
+}
+
+struct EvalArgs {
+    SweepModel Mo;
+    halda_fleets F;
+    PlanArgs E;
+};
+
+// halda_eval_plans_kernel: the general route -- one wave per fleet, four per workgroup, any fleet size.
+// The fleet's extent and the plan's k are wave-uniform reads through the scalar cache (read-only to the
+// kernel); the plan's w / n are two 4-byte loads issued with the 18 field loads. No LDS.
+__global__ __launch_bounds__(256) void halda_eval_plans_kernel(EvalArgs A) {
+    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * 4 + int(threadIdx.x >> 6));
+    if (f >= A.F.n_fleets) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t d0 = sload_i64(A.F.dev_off + f);
+    const int M = int(sload_i64(A.F.dev_off + f + 1) - d0);
+    const int k = sload_i32(A.E.k + f);
+    const Wave sg(lane);
+    if (M <= 0) {  // no devices: nothing to read
+        plan_store(A.E, f, -1, 0, lane, k <= 0 ? kPlanNone : kPlanSumW, kInf, kInf, 0.0, -1, k);
+        return;
+    }
+    if (M <= kK1MaxM) {
+        const int64_t g = d0 + (lane < M ? lane : 0);
+        const DevFields mf = load_fields(A.F, g);
+        const int pw = A.E.w[g], pn = A.E.n[g];
+        eval_plan_regs(A.Mo, A.E, f, M, sg, mf, k, pw, pn);
+    } else {
+        eval_plan_wide(A.Mo, A.F, A.E, f, d0, M, sg, k);
+    }
+}
+
+// halda_sweep_plans_kernel: the fused route -- the register sweep of a batch of fleets of one size
+// A.uM <= kK1MaxM that needs no table launch (the host checks both), with the incumbent plan priced on the
+// sweep's own field loads: the wave loads its fleet's fields once (the plan's w / n with them), evaluates
+// the plan and stores its outputs, and only then hands the same fields to the unedited sweep_fleet (kPre,
+// as the sub-fleet and variants kernels hand theirs) -- nothing of the evaluation is live across the sweep.
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_plans_kernel(
+    SweepArgs A, PlanArgs E) {
+    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    if (f >= A.F.n_fleets) return;
+    const int lane = int(threadIdx.x & 63);
+    const int M = A.uM;
+    const int64_t base = sload_i64(A.F.dev_off);
+    const int k = sload_i32(E.k + f);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    SweepPre pre;
+    const bool kl = lane < A.n_k;
+    pre.kj = A.ks[kl ? lane : 0];
+    pre.Wj = kl ? A.Ws[lane] : 0;
+    pre.d0 = base + int64_t(f) * M;
+    const int64_t g = pre.d0 + (lane < M ? lane : 0);
+    pre.mf = load_fields(A.F, g);
+    const int pw = E.w[g], pn = E.n[g];
+    const Wave sg(lane);
+    eval_plan_regs(A.Mo, E, f, M, sg, pre.mf, k, pw, pn);
+    sweep_fleet<false, false, Wave, true, true>(A, A.F, A.out, f, w, sg, &pre);
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the

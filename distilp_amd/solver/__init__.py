@@ -3,12 +3,16 @@
 from .coefficients import HALDAResult, ILPResult
 from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
+from .plans import (PlanEvaluation, Replacement, evaluate_plan_np, halda_evaluate_plan,  # noqa: F401
+                    halda_evaluate_plans_batch, halda_replace_or_keep, halda_replace_or_keep_batch)
 from .subfleets import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
                         halda_solve_subfleets)
 from .variants import halda_context_sweep, halda_solve_variants, model_grid  # noqa: F401
 
 __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solve_subfleets", "halda_leave_one_out",
            "halda_leave_one_out_batch", "halda_select_devices", "halda_solve_variants", "halda_context_sweep",
-           "model_grid", "HALDAResult", "ILPResult"]
+           "model_grid", "halda_evaluate_plan", "halda_evaluate_plans_batch", "halda_replace_or_keep",
+           "halda_replace_or_keep_batch", "evaluate_plan_np", "PlanEvaluation", "Replacement", "HALDAResult",
+           "ILPResult"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

@@ -64,6 +64,44 @@ class HaldaFleetResultC(ctypes.Structure):
                 ("x", ctypes.c_void_p), ("c", ctypes.c_void_p), ("x_off", ctypes.c_void_p)]
 
 
+class HaldaPlansC(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_void_p), ("w", ctypes.c_void_p), ("n", ctypes.c_void_p)]
+
+
+class HaldaPlanResultC(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_void_p), ("obj_value", ctypes.c_void_p), ("cycle", ctypes.c_void_p),
+                ("bottleneck", ctypes.c_void_p), ("reason", ctypes.c_void_p), ("x", ctypes.c_void_p),
+                ("c", ctypes.c_void_p), ("x_off", ctypes.c_void_p)]
+
+
+def _bind_plans(lib):
+    """The plan entries' prototypes (halda_eval_plans .. halda_set_plans_path), on top of _bind's."""
+    lib = _bind(lib)
+    if getattr(lib, "_plans_bound", False):
+        return lib
+    P = ctypes.POINTER
+    lib.halda_eval_plans.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaPlansC),
+                                     P(HaldaPlanResultC), ctypes.c_void_p]
+    lib.halda_eval_plans.restype = ctypes.c_int
+    lib.halda_eval_plans_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaPlansC),
+                                          P(HaldaPlanResultC)]
+    lib.halda_eval_plans_host.restype = ctypes.c_int
+    lib.halda_solve_fleets_plans.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
+                                             ctypes.c_int32, P(HaldaPlansC), P(HaldaPlanResultC),
+                                             P(HaldaFleetResultC), ctypes.c_void_p]
+    lib.halda_solve_fleets_plans.restype = ctypes.c_int
+    lib.halda_solve_fleets_plans_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
+                                                  ctypes.c_int32, P(HaldaPlansC), P(HaldaPlanResultC),
+                                                  P(HaldaFleetResultC)]
+    lib.halda_solve_fleets_plans_host.restype = ctypes.c_int
+    lib.halda_last_plans_route.argtypes = [ctypes.c_void_p, P(ctypes.c_int)]
+    lib.halda_last_plans_route.restype = ctypes.c_int
+    lib.halda_set_plans_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.halda_set_plans_path.restype = ctypes.c_int
+    lib._plans_bound = True
+    return lib
+
+
 def _bind(lib):
     if getattr(lib, "_fleets_bound", False):
         return lib
@@ -848,6 +886,48 @@ class DeviceFleetTable:
         if rc != 0:
             raise RuntimeError(f"halda_solve_fleets failed ({rc}): {last_error(lib)}")
 
+    def set_plans(self, k=None, w=None, n=None) -> None:
+        """Give the table its resident plan: device tensors plan_k [n_fleets], plan_w / plan_n [n_devices]
+        (int32; zeros, "no plan", where not given) and the evaluation's result buffers plan_out -- buffers of
+        their own, next to what the constructor allocated. A streaming caller rewrites plan_k / plan_w /
+        plan_n in place between launches (e.g. copies out["best_k"] / ["w"] / ["n"] into them)."""
+        import torch
+
+        dev = self.out["best_k"].device
+        nf, nd = self.table.n_fleets, self.table.n_devices
+
+        def tensor(a, size):
+            if a is None:
+                return torch.zeros(size, dtype=torch.int32, device=dev)
+            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))
+            if t.numel() != size:
+                raise ValueError(f"plan array of {t.numel()} entries, expected {size}")
+            return t.to(device=dev, dtype=torch.int32).contiguous().clone()
+
+        self.plan_k, self.plan_w, self.plan_n = tensor(k, nf), tensor(w, nd), tensor(n, nd)
+        self.plan_out = {"status": torch.empty(nf, dtype=torch.int32, device=dev),
+                         "obj_value": torch.empty(nf, dtype=torch.float64, device=dev),
+                         "cycle": torch.empty(nf, dtype=torch.float64, device=dev),
+                         "bottleneck": torch.empty(nf, dtype=torch.int32, device=dev),
+                         "reason": torch.empty(nf, dtype=torch.int32, device=dev)}
+        o = self.plan_out
+        self._plans_c = HaldaPlansC(self.plan_k.data_ptr(), self.plan_w.data_ptr(), self.plan_n.data_ptr())
+        self._plan_res = HaldaPlanResultC(o["status"].data_ptr(), o["obj_value"].data_ptr(), o["cycle"].data_ptr(),
+                                          o["bottleneck"].data_ptr(), o["reason"].data_ptr(), None, None, None)
+
+    def launch_with_plans(self, ctx, stream: int) -> None:
+        """Enqueue the k-sweep of every fleet and the evaluation of the resident plan on `stream`
+        (halda_solve_fleets_plans): self.out as launch() leaves it, self.plan_out the incumbents' evaluation."""
+        if getattr(self, "_plans_c", None) is None:
+            self.set_plans()
+        lib = _bind_plans(ctx.lib)
+        with ctx._lock:
+            rc = lib.halda_solve_fleets_plans(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
+                                              self.ks.ctypes.data, len(self.ks), ctypes.byref(self._plans_c),
+                                              ctypes.byref(self._plan_res), ctypes.byref(self.res),
+                                              ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"halda_solve_fleets_plans failed ({rc}): {last_error(lib)}")
 
 
 class RcclComm:

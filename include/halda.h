@@ -387,6 +387,84 @@ int halda_last_variants_route(void *ctx, int *route);
  * (test path: the fused route is compared against it). HALDA_E_ARG for any other path. */
 int halda_set_variants_path(void *ctx, int path);
 
+/* ------------------------------------------------------------------------
+ * A deployed plan priced on the fleet as it is now: evaluate, regret, keep or move.
+ *
+ * A plan for fleet f of M devices is (k[f], w[M], n[M]) (w / n in the table's device layout). Under
+ * `model` it is evaluated at W = L / k on the device records the sweep builds. It is feasible when
+ * k > 0, sum w = W, every 1 <= w_i <= W, every n_i lies in the interval its capacity rows leave at w_i
+ * (0 <= n_i <= min(w_i, nhi) with nhi = W on a device with a usable GPU, else 0, narrowed by the VRAM
+ * and the class-3 RAM row), no integer slack exceeds its bound, and no record is rejected. Its
+ * objective is then sum_i g_i + (k - 1) C + the fleet's constants, with the least integer slacks at
+ * (w_i, n_i), g_i the device's cost, H_i its least cycle time and C = max(0, max_i H_i): for the
+ * (best_k, w, n) a halda_solve_fleets call returned, the obj_value that call returned (bit for bit on
+ * fleets of at most 64 devices against the one-fleet-per-wave sweep; within 1e-12 relative otherwise).
+ *
+ * Per fleet: status HALDA_STATUS_OPTIMAL (feasible), _INFEASIBLE, or _UNSUPPORTED (a record the sweep
+ * would reject, or W >= 1e6); obj_value and cycle (C) are +inf unless feasible; bottleneck is the
+ * lowest device index with H_i = max H, -1 when not feasible or max H <= 0; reason is a bit mask:
+ *    1  sum w != W                         2  some w_i outside [1, W]
+ *    4  some n_i outside its interval (n_i > 0 without a usable GPU, n_i > w_i, ...)
+ *    8  a slack over its bound (the class-1 / class-2 RAM slack at w_i, or the VRAM slack at n_i)
+ *   16  record rejected                   32  k <= 0: "no plan" (nothing else is looked at)
+ * Bits 4 and 8 are looked at on the devices whose w_i is in range. Bit 32 lets a sweep's own
+ * best_k / w / n be fed back as the plan even for fleets where no k was feasible.
+ * x / c (optional) hold the plan's 7 M + 1 columns [w|n|s1|s2|s3|t|z|C] as the sweep's x / c hold
+ * them for a solved k (c[C] = k - 1), zeros for a plan that is not feasible: dense with stride
+ * 7 max_devices + 1 per fleet, or compact through an x_off of n_fleets element offsets (-1: not
+ * written).
+ * ------------------------------------------------------------------------ */
+typedef struct halda_plans {
+    const int32_t *k;      /* [n_fleets] */
+    const int32_t *w, *n;  /* [dev_off[n_fleets]] device layout */
+} halda_plans;
+
+typedef struct halda_plan_result {
+    int32_t *status;     /* [n_fleets] HALDA_STATUS_* */
+    double *obj_value;   /* [n_fleets] */
+    double *cycle;       /* [n_fleets]; may be NULL */
+    int32_t *bottleneck; /* [n_fleets]; may be NULL */
+    int32_t *reason;     /* [n_fleets]; may be NULL */
+    double *x, *c;       /* may be NULL */
+    const int64_t *x_off; /* [n_fleets] or NULL (dense) */
+} halda_plan_result;
+
+/* Asynchronous on `stream` (NULL = the context's stream); every array is device memory. One launch
+ * (halda_eval_plans_kernel: one wave per fleet, any fleet size). The plan arrays are only read: they
+ * may be the best_k / w / n arrays an earlier halda_solve_fleets on the same stream wrote. */
+int halda_eval_plans(void *ctx, const halda_model *model, const halda_fleets *fleets, const halda_plans *plans,
+                     halda_plan_result *out, void *stream);
+
+/* Synchronous variant on HOST arrays (x_off host memory too). */
+int halda_eval_plans_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const halda_plans *plans,
+                          halda_plan_result *out);
+
+/* The k-sweep of the table and the evaluation of the incumbent plans in one call: `out` equals, bit for
+ * bit, what halda_solve_fleets writes, `eval_out` what halda_eval_plans writes. Two routes, one contract
+ * (halda_set_plans_path). By default the call runs halda_eval_plans and then halda_solve_fleets on
+ * `stream` (any shape). On path 2, where the sweep is the register launch alone over fleets of one size
+ * <= 64 (the sub-fleet and variants kernels' gate), it is ONE launch (halda_sweep_plans_kernel: each wave
+ * prices its fleet's plan on the fields it loads for the sweep, so the table is read once); measured 7 %
+ * ahead of the two launches on 4,096 fleets of 64 devices, inside the box-to-box spread, hence not the
+ * default. This entry writes the sweep's outputs: plan arrays that alias
+ * out->best_k / w / n are the caller's error here (not checked). */
+int halda_solve_fleets_plans(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                             int32_t n_k, const halda_plans *plans, halda_plan_result *eval_out,
+                             halda_fleet_result *out, void *stream);
+
+/* Synchronous variant on HOST arrays: the table crosses PCIe once for both. */
+int halda_solve_fleets_plans_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                                  int32_t n_k, const halda_plans *plans, halda_plan_result *eval_out,
+                                  halda_fleet_result *out);
+
+/* Which route the context's last halda_solve_fleets_plans / _host call took: 1 fused (one launch), 2 the
+ * evaluation launch then the sweep, 0 when none ran yet. */
+int halda_last_plans_route(void *ctx, int *route);
+
+/* How halda_solve_fleets_plans runs: 0 automatic (default: two launches), 1 always two launches, 2 the
+ * fused route where it applies (two launches elsewhere). HALDA_E_ARG for any other path. */
+int halda_set_plans_path(void *ctx, int path);
+
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */
 int halda_resident_release(void *ctx);

@@ -1,0 +1,368 @@
+"""A deployed plan priced on the fleet (distilp_amd/solver/plans.py): the NumPy specification against the
+reference's recorded plans and the oracle's fixed-column answers, the reason bits, the keep-or-move logic, the
+CLI flag and the ABI surface. No GPU."""
+
+import contextlib
+import io
+import json
+import math
+
+import numpy as np
+import pytest
+
+from distilp_amd.solver import _libhalda as lh
+from distilp_amd.solver import plans as pl
+from distilp_amd.solver.coefficients import HALDAResult, b_prime
+from distilp_amd.solver.fleets import DEV_CUDA_OK, fleet_table
+from distilp_amd.solver.lower import kv_bits_to_factor
+
+from .conftest import GOLDEN, REPO
+from .helpers import fixture_fleet, synth_devices
+from .test_abi import declared_functions, kernel_resources
+
+SYNTH_M = (1, 2, 3, 4, 8, 16, 32, 64)
+N_RECORDED = 1096  # every successful per-k plan of the synthetic goldens
+TOL = 1e-9  # the project's objective tolerance (relative, floor 1)
+
+
+def close(a, b):
+    return abs(a - b) <= TOL * max(1.0, abs(b))
+
+
+def recorded_plans(synth_golden):
+    """(M, seed, device dicts, k, w, n, obj_value) of every successful per-k plan of the synthetic goldens."""
+    for M in SYNTH_M:
+        for fl in synth_golden[M]["fleets"]:
+            for rec in fl["per_k"]:
+                if rec["success"]:
+                    yield M, fl["seed"], fl["devices"], rec["k"], rec["w"], rec["n"], rec["obj_value"]
+
+
+def test_recorded_plans_reproduce_the_reference_objective(synth_golden, llama_online_model):
+    count, tabs = 0, {}
+    for M, seed, dicts, k, w, n, obj in recorded_plans(synth_golden):
+        if (M, seed) not in tabs:
+            tabs[(M, seed)] = fleet_table([synth_devices(M, seed, dicts)], llama_online_model)
+        e = pl.evaluate_plan_np(tabs[(M, seed)], llama_online_model, 0, k, w, n, 0.5)
+        assert e.feasible and e.reason == 0, (M, seed, k, e.reason)
+        assert close(e.obj_value, obj), (M, seed, k, e.obj_value, obj)
+        assert e.cycle >= 0.0 and (e.bottleneck >= 0) == (e.cycle > 0.0)
+        count += 1
+    assert count == N_RECORDED  # none left out
+
+
+def test_fixture_results_reproduce_the_reference_objective(fixtures_golden):
+    fx = fixtures_golden["fixtures"]
+    assert len(fx) == 24
+    for key, f in fx.items():
+        devs, model = fixture_fleet(f["folder"])
+        r = f["result"]
+        e = pl.evaluate_plan_np(fleet_table([devs], model), model, 0, r["k"], r["w"], r["n"],
+                                kv_bits_to_factor(f["kv_bits"]))
+        assert e.feasible, (key, e.reason)
+        assert close(e.obj_value, r["obj_value"]), (key, e.obj_value, r["obj_value"])
+
+
+@pytest.fixture(scope="module")
+def neighbour_cases():
+    return json.loads((GOLDEN / "plans.json").read_text())
+
+
+def test_neighbour_golden_is_data_with_both_classes(neighbour_cases):
+    cases = neighbour_cases["cases"]
+    assert {c["M"] for c in cases} == {2, 3, 4, 8, 16, 64}
+    assert {c["kind"] for c in cases} == {"move", "n_plus", "n_minus"}
+    feas = sum(c["success"] for c in cases)
+    assert feas >= 0.25 * len(cases) and len(cases) - feas >= 0.25 * len(cases), (feas, len(cases))
+    per_plan = {}
+    for c in cases:
+        per_plan[(c["M"], c["seed"], c["k"])] = per_plan.get((c["M"], c["seed"], c["k"]), 0) + 1
+    assert min(per_plan.values()) >= 6
+    for c in cases:
+        assert set(c) == {"M", "seed", "k", "kind", "w", "n", "success", "objective_value"}
+        assert (c["objective_value"] is not None) == c["success"]
+
+
+def test_neighbour_plans_match_the_oracle_with_fixed_columns(neighbour_cases, llama_online_model):
+    tabs = {}
+    for c in neighbour_cases["cases"]:
+        key = (c["M"], c["seed"])
+        if key not in tabs:
+            tabs[key] = fleet_table([synth_devices(*key)], llama_online_model)
+        e = pl.evaluate_plan_np(tabs[key], llama_online_model, 0, c["k"], c["w"], c["n"], 0.5)
+        assert e.feasible == c["success"], (key, c["k"], c["kind"], e.reason)
+        if c["success"]:
+            assert close(e.obj_value, c["objective_value"]), (key, c["k"], e.obj_value, c["objective_value"])
+        else:
+            assert e.reason != 0 and e.obj_value == math.inf and e.bottleneck == -1
+
+
+# ------------------------------------------------------------------ reason bits
+@pytest.fixture(scope="module")
+def base_plan(synth_golden, llama_online_model):
+    """A 16-device synthetic fleet with a CUDA class-3 device and a device without a usable GPU, its table and
+    its recorded k = 1 plan."""
+    for fl in synth_golden[16]["fleets"]:
+        devs = synth_devices(16, fl["seed"], fl["devices"])
+        t = fleet_table([devs], llama_online_model)
+        rec = next((r for r in fl["per_k"] if r["success"] and r["k"] == 1), None)
+        r = pl.plan_records(t, llama_online_model, 0, 0.5)
+        cuda3 = np.flatnonzero(((t.flags & DEV_CUDA_OK) != 0) & (t.os_class == 3))
+        nogpu = np.flatnonzero(~r["gpu"])
+        if rec is not None and len(cuda3) and len(nogpu):
+            return devs, t, rec, int(cuda3[0]), int(nogpu[0])
+    pytest.fail("no synthetic 16-device fleet with a CUDA class-3 device and a CPU-only device")
+
+
+def reason_of(t, model, k, w, n):
+    e = pl.evaluate_plan_np(t, model, 0, k, w, n, 0.5)
+    assert (e.reason == 0) == e.feasible
+    return e
+
+
+def test_every_reason_bit_is_produced(base_plan, llama_online_model):
+    devs, t, rec, cuda3, nogpu = base_plan
+    model, W = llama_online_model, llama_online_model.L
+    w, n = list(rec["w"]), list(rec["n"])
+    assert reason_of(t, model, 1, w, n).reason == 0
+    # sum w != W alone: one layer more on a device that keeps its n
+    w2 = list(w)
+    w2[nogpu] += 1
+    assert reason_of(t, model, 1, w2, n).reason & pl.REASON_SUM_W
+    # w_i = 0 and w_i > W
+    w2 = list(w)
+    w2[nogpu] = 0
+    e = reason_of(t, model, 1, w2, n)
+    assert e.reason & pl.REASON_RANGE_W and "w_out_of_range" in pl.reason_names(e.reason)
+    w2 = list(w)
+    w2[nogpu] = W + 1
+    assert reason_of(t, model, 1, w2, n).reason & pl.REASON_RANGE_W
+    # n_i > w_i
+    n2 = list(n)
+    n2[cuda3] = w[cuda3] + 1
+    assert reason_of(t, model, 1, w, n2).reason & pl.REASON_RANGE_N
+    # n_i = 1 on a device without a usable GPU (linux_cpu)
+    assert devs[nogpu].os_type == "linux" and not devs[nogpu].has_cuda
+    n2 = list(n)
+    n2[nogpu] = 1
+    assert reason_of(t, model, 1, w, n2).reason == pl.REASON_RANGE_N
+    # a VRAM-slack overflow: the CUDA device's c_gpu takes W layers' worth of VRAM, so t >= n + W > W
+    bp = float(b_prime(model, kv_bits_k=0.5))
+    t2 = fleet_table([devs], model)
+    cg = t2.c_gpu.copy()
+    cg[cuda3] = t2.d_avail_cuda[cuda3] + bp * W
+    t2.c_gpu = cg
+    n2 = list(n)
+    n2[cuda3] = max(1, n[cuda3])
+    e = reason_of(t2, model, 1, w, n2)
+    assert e.reason & pl.REASON_SLACK and e.status == lh.STATUS_INFEASIBLE
+    # k = 0: "no plan", nothing else looked at
+    e = reason_of(t, model, 0, [0] * 16, [0] * 16)
+    assert e.reason == pl.REASON_NO_PLAN and pl.reason_names(e.reason) == ("no_plan",)
+
+
+def test_rejected_record_is_unsupported(base_plan, llama_online_model):
+    """Bit 16: a record the packer admits but field_rec rejects (a cycle-row constant beyond 1e300)."""
+    devs, _, rec, _, _ = base_plan
+    devs = list(devs)
+    devs[3] = devs[3].model_copy(update={"t_comm": 1e301})
+    t = fleet_table([devs], llama_online_model)  # the packer admits it
+    e = pl.evaluate_plan_np(t, llama_online_model, 0, 1, rec["w"], rec["n"], 0.5)
+    assert e.reason & pl.REASON_RECORD and e.status == lh.STATUS_UNSUPPORTED
+    assert e.obj_value == math.inf and e.bottleneck == -1
+
+
+def test_wrong_lengths_and_bad_k_raise_before_any_gpu_call(base_plan, llama_online_model):
+    devs, t, rec, _, _ = base_plan
+    with pytest.raises(ValueError):
+        pl.evaluate_plan_np(t, llama_online_model, 0, 1, rec["w"][:-1], rec["n"], 0.5)
+    with pytest.raises(ValueError):
+        pl.evaluate_plan_np(t, llama_online_model, 0, 1, rec["w"], rec["n"] + [0], 0.5)
+    # the GPU entries: ValueError, not the missing-GPU error a call would give here
+    with pytest.raises(ValueError):
+        pl.halda_evaluate_plan(devs, llama_online_model, 1, rec["w"][:-1], rec["n"])
+    with pytest.raises(ValueError):
+        pl.halda_evaluate_plan(devs, llama_online_model, 0, rec["w"], rec["n"])
+    with pytest.raises(ValueError):
+        pl.halda_evaluate_plans_batch([devs], llama_online_model, [])
+    with pytest.raises(ValueError):
+        pl.halda_replace_or_keep(devs, llama_online_model, (1, rec["w"], rec["n"][:-1]))
+    with pytest.raises(ValueError):
+        pl.halda_replace_or_keep(devs, llama_online_model, (-1, rec["w"], rec["n"]))
+
+
+# ------------------------------------------------------------------ keep or move
+def _ev(obj):
+    ok = obj is not None
+    return pl.PlanEvaluation(ok, obj if ok else math.inf, 1.0 if ok else math.inf, 0 if ok else None,
+                             () if ok else ("sum_w",), 0 if ok else 2, 0 if ok else 1)
+
+
+def _best(w, obj):
+    return HALDAResult.model_construct(w=list(w), n=[0] * len(w), k=1, obj_value=obj, sets={})
+
+
+def test_replacement_logic(monkeypatch, llama_online_model):
+    devs = synth_devices(2, 0)
+    seen = {}
+
+    def fake(fleets, model, plans, Ks, kv_factor, device):
+        seen["plans"], seen["Ks"] = plans, Ks
+        return [_best([30, 50], 10.0)] * len(fleets), seen["evals"]
+
+    monkeypatch.setattr(pl, "_solve_and_evaluate", fake)
+    # a feasible incumbent that is worse: regret, moved layers, replace at rel_tol = 0, kept at a wide rel_tol
+    seen["evals"] = [_ev(10.5)]
+    r = pl.halda_replace_or_keep(devs, llama_online_model, (1, [40, 40], [0, 0]), k_candidates=[1, 2])
+    assert seen["plans"] == [(1, [40, 40], [0, 0])] and seen["Ks"] == [1, 2]
+    assert r.regret == 0.5 and r.moved_layers == 20 and r.replace and r.best.w == [30, 50]
+    r = pl.halda_replace_or_keep(devs, llama_online_model, (1, [40, 40], [0, 0]), rel_tol=0.1)
+    assert r.regret == 0.5 and not r.replace  # 0.5 <= 0.1 * max(1, 10)
+    r = pl.halda_replace_or_keep(devs, llama_online_model, (1, [40, 40], [0, 0]), rel_tol=0.04)
+    assert r.replace  # 0.5 > 0.04 * 10
+    # the incumbent is the optimum: zero regret, nothing moves, kept
+    seen["evals"] = [_ev(10.0)]
+    r = pl.halda_replace_or_keep(devs, llama_online_model, _best([30, 50], 10.0))
+    assert seen["plans"] == [(1, [30, 50], [0, 0])]
+    assert r.regret == 0.0 and r.moved_layers == 0 and not r.replace
+    # an infeasible incumbent: infinite regret, replaced whatever rel_tol
+    seen["evals"] = [_ev(None)]
+    r = pl.halda_replace_or_keep(devs, llama_online_model, (2, [20, 20], [0, 0]), rel_tol=1e9)
+    assert r.regret == math.inf and r.replace and r.moved_layers == 40
+    # none yet
+    r = pl.halda_replace_or_keep(devs, llama_online_model, None)
+    assert seen["plans"] == [None] and r.regret == math.inf and r.replace and r.moved_layers == 0
+    # no best: nothing to move to
+    monkeypatch.setattr(pl, "_solve_and_evaluate", lambda *a: ([None], [_ev(None)]))
+    r = pl.halda_replace_or_keep(devs, llama_online_model, None)
+    assert r.best is None and not r.replace and r.regret == math.inf
+    # the batch form keeps fleet order
+    monkeypatch.setattr(pl, "_solve_and_evaluate",
+                        lambda fleets, *a: ([_best([30, 50], 10.0), None], [_ev(11.0), _ev(None)]))
+    rs = pl.halda_replace_or_keep_batch([devs, devs], llama_online_model, [(1, [40, 40], [0, 0]), None])
+    assert [x.replace for x in rs] == [True, False] and rs[0].regret == 1.0
+
+
+def test_plan_arrays_pack_none_as_no_plan(llama_online_model):
+    t = fleet_table([synth_devices(2, 0), synth_devices(3, 0)], llama_online_model)
+    k, w, n = pl._plan_arrays(t, [None, (2, [10, 20, 10], [1, 2, 3])], allow_none=True)
+    assert k.tolist() == [0, 2] and w.tolist() == [0, 0, 10, 20, 10] and n.tolist() == [0, 0, 1, 2, 3]
+    assert k.dtype == w.dtype == n.dtype == np.int32
+    with pytest.raises(ValueError):
+        pl._plan_arrays(t, [None, (2, [10, 20, 10], [1, 2, 3])], allow_none=False)
+
+
+# ------------------------------------------------------------------ CLI
+@pytest.fixture
+def in_repo(monkeypatch):
+    monkeypatch.chdir(REPO)
+
+
+def _solution(tmp_path, dist, k=2, name="sol.json"):
+    p = tmp_path / name
+    p.write_text(json.dumps({"k": k, "objective_value": 1.0, "layer_distribution": dist, "sets": {}}))
+    return str(p)
+
+
+def test_cli_evaluate_solution_flag(in_repo, tmp_path, monkeypatch):
+    from distilp_amd.cli import solver as cli
+
+    args = cli._parser().parse_args(["--profile", "llama_3_70b/online", "--evaluate-solution", "x.json"])
+    assert args.evaluate_solution == "x.json"
+    assert cli._parser().parse_args(["--profile", "hermes_70b"]).evaluate_solution is None
+    devs, _ = cli.load_from_profile_folder("llama_3_70b/online")
+    # names are matched, whatever the file's order
+    good = _solution(tmp_path, {"Omers-MBP-32193": {"w": 27, "n": 26}, "Mac": {"w": 13, "n": 12}})
+    assert cli.load_incumbent(good, devs) == (2, [13, 27], [12, 26])
+    # a name missing from the fleet, a device missing from the file, no file: message and exit status 2
+    for dist in ({"Mac": {"w": 13, "n": 13}, "Other": {"w": 27, "n": 27}, "Omers-MBP-32193": {"w": 1, "n": 1}},
+                 {"Mac": {"w": 40, "n": 40}}):
+        err = io.StringIO()
+        with contextlib.redirect_stderr(err), contextlib.redirect_stdout(io.StringIO()):
+            rc = cli.main(["--profile", "llama_3_70b/online", "--no-plot", "--evaluate-solution",
+                           _solution(tmp_path, dist, name="bad.json")])
+        assert rc == 2 and "--evaluate-solution" in err.getvalue()
+    with contextlib.redirect_stderr(io.StringIO()), contextlib.redirect_stdout(io.StringIO()):
+        assert cli.main(["--profile", "llama_3_70b/online", "--evaluate-solution", str(tmp_path / "none.json")]) == 2
+    # with the solve and the evaluation stubbed: stdout without the flag is unchanged, the flag adds two lines
+    res = HALDAResult.model_construct(w=[13, 27], n=[13, 27], k=2, obj_value=1.5,
+                                      sets={"M1": [], "M2": [0, 1], "M3": []})
+    monkeypatch.setattr(cli, "halda_solve", lambda *a, **kw: res)
+    seen = {}
+
+    def fake_eval(devices, model, k, w, n, kv_bits="8bit"):
+        seen["plan"] = (k, w, n, kv_bits)
+        return pl.PlanEvaluation(True, 1.75, 0.5, 1)
+
+    monkeypatch.setattr(cli, "halda_evaluate_plan", fake_eval)
+
+    def run(argv):
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            assert cli.main(argv) == 0
+        return buf.getvalue()
+
+    base = ["--profile", "llama_3_70b/online", "--no-plot", "--quiet"]
+    plain = run(base)
+    assert plain == "k=2, obj=1.500000\nMac: 13\nOmers-MBP-32193: 27\n"
+    assert run(base + ["--evaluate-solution", good]) == (plain + "incumbent: k=2, obj=1.750000\n"
+                                                         "regret=0.250000, moved_layers=0\n")
+    assert seen["plan"] == (2, [13, 27], [12, 26], "4bit")
+    monkeypatch.setattr(cli, "halda_evaluate_plan", lambda *a, **kw: pl.PlanEvaluation(
+        False, math.inf, math.inf, None, ("sum_w", "n_out_of_range"), 2, 5))
+    assert run(base + ["--evaluate-solution", good]).endswith(
+        "incumbent: infeasible (sum_w, n_out_of_range)\nregret=inf, moved_layers=0\n")
+
+
+# ------------------------------------------------------------------ ABI surface
+NEW_ENTRIES = ("halda_eval_plans", "halda_eval_plans_host", "halda_solve_fleets_plans",
+               "halda_solve_fleets_plans_host", "halda_last_plans_route", "halda_set_plans_path")
+
+
+def test_header_and_exports_declare_the_plan_entries():
+    declared = declared_functions()
+    assert declared == sorted(lh.EXPORTS)
+    for name in NEW_ENTRIES:
+        assert name in declared, name
+
+
+def test_plan_entries_reject_bad_arguments_before_any_hip_call():
+    import ctypes
+
+    from distilp_amd.solver.fleets import (HaldaFleetResultC, HaldaFleetsC, HaldaModelC, HaldaPlanResultC,
+                                           HaldaPlansC, _bind_plans)
+
+    if not lh.LIB_PATH.exists():
+        pytest.fail(f"{lh.LIB_PATH} not built (run __graft_entry__.build())")
+    lib = _bind_plans(lh.load_library())
+    m, fs, p, o, r = HaldaModelC(), HaldaFleetsC(), HaldaPlansC(), HaldaPlanResultC(), HaldaFleetResultC()
+    m.L = 80
+    ks = (ctypes.c_int32 * 1)(1)
+    fake_ctx = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(8)))  # checked, never dereferenced
+    B = ctypes.byref
+    assert lib.halda_eval_plans(None, B(m), B(fs), B(p), B(o), None) == -22
+    assert "halda_eval_plans" in lh.last_error(lib)
+    assert lib.halda_eval_plans_host(None, B(m), B(fs), B(p), B(o)) == -22
+    assert lib.halda_eval_plans(fake_ctx, None, B(fs), B(p), B(o), None) == -22
+    assert lib.halda_eval_plans(fake_ctx, B(m), B(fs), None, B(o), None) == -22
+    assert lib.halda_eval_plans(fake_ctx, B(m), B(fs), B(p), None, None) == -22
+    fs.n_fleets = -1
+    assert lib.halda_eval_plans(fake_ctx, B(m), B(fs), B(p), B(o), None) == -22
+    assert "n_fleets" in lh.last_error(lib)
+    fs.n_fleets = 1
+    assert lib.halda_eval_plans(fake_ctx, B(m), B(fs), B(p), B(o), None) == -22  # NULL plan arrays
+    assert lib.halda_solve_fleets_plans(None, B(m), B(fs), ks, 1, B(p), B(o), B(r), None) == -22
+    assert lib.halda_solve_fleets_plans_host(fake_ctx, B(m), B(fs), ks, 1, None, B(o), B(r)) == -22
+    assert lib.halda_set_plans_path(None, 0) == -22
+    assert lib.halda_last_plans_route(None, None) == -22
+
+
+def test_plan_kernels_use_no_scratch(tmp_path):
+    if not lh.LIB_PATH.exists():
+        pytest.fail(f"{lh.LIB_PATH} not built (run __graft_entry__.build())")
+    res = kernel_resources(tmp_path)
+    for name in ("halda_eval_plans_kernel", "halda_sweep_plans_kernel"):
+        assert name in res, name
+        assert res[name]["private_segment_fixed_size"] == 0 and res[name]["vgpr_spill_count"] == 0, (name, res[name])
+    # the kernels it rides on keep their figures (tests/test_abi.py holds the budgets)
+    assert res["halda_sweep_kernel"]["private_segment_fixed_size"] == 0
