@@ -16,7 +16,9 @@ the best k and objective of the fleet without it. --kv-sweep / --n-kv-sweep prin
 (n_kv, kv_bits) point of the grid: the best k and objective of the fleet for that model variant.
 --evaluate-solution FILE prints, last, the plan of a --save-solution JSON priced on the current fleet and its
 regret / moved layers against the solution above; a file that does not name exactly the current devices is an
-error (exit status 2).
+error (exit status 2). --max-move D (with --evaluate-solution) adds one line after those: the best plan at that
+plan's k at most D layers per device away from it, `within D: k=..., obj=..., moved_layers=...`, or
+`within D: infeasible`.
 """
 
 from __future__ import annotations
@@ -117,6 +119,19 @@ def incumbent_lines(devices: List[DeviceProfile], model: ModelProfile, plan, res
     return [first, f"regret={rep.regret:.6f}, moved_layers={rep.moved_layers}"]
 
 
+def within_line(devices: List[DeviceProfile], model: ModelProfile, plan, max_move: int) -> str:
+    """--max-move D: the best plan at the incumbent's k at most D layers per device away from it
+    (halda_solve_bounded inside move_bounds' box), or "infeasible" when the box holds no plan."""
+    from ..solver.bounds import halda_solve_bounded_batch, move_bounds
+
+    k, w, _ = plan
+    r = halda_solve_bounded_batch([devices], model, [move_bounds(w, max_move)], [k], kv_bits="4bit")[0]
+    if r is None:
+        return f"within {max_move}: infeasible"
+    moved = sum(abs(int(a) - int(b)) for a, b in zip(r.w, w))
+    return f"within {max_move}: k={r.k}, obj={r.obj_value:.6f}, moved_layers={moved}"
+
+
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Run HALDA solver for distributed LLM inference optimization",
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -144,6 +159,9 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--evaluate-solution", metavar="FILE",
                    help="After the solution, price the plan of a --save-solution JSON on this fleet: its objective "
                         "(or why it is infeasible), its regret against the solution and the layers that would move")
+    o.add_argument("--max-move", type=int, metavar="D",
+                   help="With --evaluate-solution: also print the best plan at that plan's k that moves at most D "
+                        "layers per device away from it")
     return p
 
 
@@ -164,6 +182,10 @@ def main(argv=None) -> int:
     else:
         parser.error("Either --profile or both --devices and --model must be provided.")
 
+    if args.max_move is not None and not args.evaluate_solution:
+        parser.error("--max-move requires --evaluate-solution")
+    if args.max_move is not None and args.max_move < 0:
+        parser.error("--max-move must be >= 0")
     incumbent = None
     if args.evaluate_solution:
         try:
@@ -212,6 +234,8 @@ def main(argv=None) -> int:
     if incumbent is not None:
         for line in incumbent_lines(devices, model, incumbent, result):
             print(line)
+        if args.max_move is not None:
+            print(within_line(devices, model, incumbent, args.max_move))
     return 0
 
 

@@ -166,6 +166,8 @@ struct Ctx {
     int var_route = 0;              // the last halda_solve_variants call: 1 fused, 2 loop (0: none yet)
     int plans_path = 0;             // halda_set_plans_path: 0 automatic, 1 always two launches, 2 fused where it applies
     int plans_route = 0;            // the last halda_solve_fleets_plans call: 1 fused, 2 two launches (0: none yet)
+    int bounds_path = 0;            // halda_set_bounds_path: 0 automatic, 1 always general, 2 fused where it applies
+    int bounds_route = 0;           // the last halda_solve_fleets_bounded call: 1 fused, 2 general (0: none yet)
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -1402,6 +1404,9 @@ int replan(FleetsPlan *P) {
 
 extern "C" {
 
+static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, const int32_t *ks, int32_t n_k,
+                      halda_fleet_result *out, hipStream_t s, const halda_bounds *bounds);
+
 int halda_solve_fleets(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
                        int32_t n_k, halda_fleet_result *out, void *stream) {
     Ctx *c = static_cast<Ctx *>(ctx);
@@ -1415,10 +1420,18 @@ int halda_solve_fleets(void *ctx, const halda_model *model, const halda_fleets *
     int cur_dev = -1;
     if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    const int32_t *kh = ks;
     // the fused sweep orders itself: per-stream scratch slots, and order_after_previous before a launch
     // on the context's global tables
     if (c->fleets_fused && n_k <= 64) return sweep_fleets(c, *model, F, ks, n_k, *out, s);
+    return fleets_csr(c, model, F, ks, n_k, out, s, nullptr);
+}
+
+// The CSR pipeline of halda_solve_fleets (the arguments checked, the device set): the batch lowered on the
+// GPU, then screened, solved and picked. bounds != nullptr (halda_solve_fleets_bounded's general route):
+// the w columns' bounds of the lowered batch are overwritten before the solve.
+static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, const int32_t *ks, int32_t n_k,
+                      halda_fleet_result *out, hipStream_t s, const halda_bounds *bounds) {
+    const int32_t *kh = ks;
     {
         const int rc = order_after_previous(c, s);  // fleet_scratch / last_lowered are per context
         if (rc != HALDA_OK) return rc;
@@ -1472,7 +1485,15 @@ int halda_solve_fleets(void *ctx, const halda_model *model, const halda_fleets *
     hipLaunchKernelGGL(halda_lower_kernel, dim3(unsigned(F.n_fleets)), dim3(64), 0, s, *model, F, ks_dev, int(n_k), D,
                        O);
     HIP_TRY(hipGetLastError());
-    // the lowered batch and its shape summary (R = W - M with lb(w) = 1 on every device)
+    if (bounds && (bounds->w_min || bounds->w_max)) {
+        // same stream, behind the lowering: one wave per instance rewrites its M w bounds
+        const BoundArgs Bd{bounds->w_min, bounds->w_max};
+        hipLaunchKernelGGL(halda_bound_cols_kernel, dim3(unsigned((n_inst + 3) / 4)), dim3(256), 0, s, F, Bd, ks_dev,
+                           int(n_k), int(model->L), int64_t(D.cols), O.col_lb, O.col_ub);
+        HIP_TRY(hipGetLastError());
+    }
+    // the lowered batch and its shape summary (R = W - M with lb(w) = 1 on every device: bounds only
+    // raise sum lb, so the slices sized here hold every bounded instance too)
     halda_batch b = {};
     b.n_inst = int32_t(n_inst);
     b.max_cols = int32_t(D.cols);
@@ -2781,6 +2802,182 @@ int halda_solve_fleets_plans_host(void *ctx, const halda_model *model, const hal
     if (rc != HALDA_OK) return rc;
     if (!ks || !out) return fail(HALDA_E_ARG, "halda_solve_fleets_plans_host: NULL ks/out");
     return plans_host(ctx, model, fleets, ks, n_k, plans, eval_out, out);
+}
+
+// ---------------------------------------------------------------- the k-sweep within per-device layer bounds
+// halda_solve_fleets_bounded: every (fleet, k) instance with its w columns' bounds narrowed to
+// [max(1, w_min_i), min(W, w_max_i)]. General route (the specification, every shape): fleets_csr with the
+// bounds -- halda_lower_kernel, halda_bound_cols_kernel, then the screen / k = 1 / general / big kernels
+// and halda_pick_kernel unchanged. Fused route: where the sweep is the register launch alone over fleets of
+// one size <= kK1MaxM (kRegAlone: the sub-fleet, variants and plans kernels' gate), ONE launch of
+// halda_sweep_bounds_kernel; bounds only shrink R and the set of open k, so no fleet is handed back.
+int halda_set_bounds_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path < 0 || path > 2)
+        return fail(HALDA_E_ARG, "bounds path must be 0 (automatic), 1 (always general) or 2 (fused where it applies)");
+    c->bounds_path = path;
+    return HALDA_OK;
+}
+
+int halda_last_bounds_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->bounds_route;
+    return HALDA_OK;
+}
+
+int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                               int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fleets || !ks || !out)
+        return fail(HALDA_E_ARG, "halda_solve_fleets_bounded: NULL ctx/model/fleets/ks/out");
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    {
+        const int rc = check_fleets_args(model, fleets, ks, n_k, out);
+        if (rc != HALDA_OK) return rc;
+    }
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const halda_bounds none = {nullptr, nullptr};
+    const halda_bounds &B = bounds ? *bounds : none;
+    // automatic = fused where admissible: one launch against the general route's lowering, patch, screen,
+    // solve and pick launches
+    if (c->bounds_path != 1 && c->fleets_fused && n_k <= 64) {
+        SweepPlan p;
+        const int rc = plan_sweep(c, *model, F, ks, n_k, *out, &p);
+        if (rc != HALDA_OK) return rc;
+        if (p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM) {
+            SweepArgs &A = p.A;
+            A.fflag = nullptr;  // the register sweep alone never flags
+            A.hb_flag = c->hb_flag;
+            A.launch_id = ++c->launch_id;
+            A.want = 0;
+            c->fleet_timed = false;
+            c->have_lowered = false;
+            const BoundArgs Bd{B.w_min, B.w_max};
+            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+            hipLaunchKernelGGL(halda_sweep_bounds_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, Bd);
+            HIP_TRY(hipGetLastError());
+            if (c->timing) {
+                HIP_TRY(hipEventRecord(c->evf1, s));
+                c->fleet_timed = true;
+            }
+            c->fleet_two = false;
+            c->fleet_reg_alone = true;
+            c->fleet_seg = false;
+            c->fleet_kslot = false;
+            c->last_fleet_fused = true;
+            c->bounds_route = 1;
+            return HALDA_OK;
+        }
+    }
+    c->bounds_route = 2;
+    return fleets_csr(c, model, F, ks, n_k, out, s, &B);
+}
+
+// The host variant: the table, the bounds (and x_off) cross PCIe once on the way in, the results on the way
+// out, through the context's staging scratch.
+int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks,
+                                    int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out_h) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fh || !ks || !out_h)
+        return fail(HALDA_E_ARG, "halda_solve_fleets_bounded_host: NULL ctx/model/fleets/ks/out");
+    const int64_t nf = fh->n_fleets;
+    if (nf <= 0) return HALDA_OK;
+    {
+        const int rc = check_fleets_args(model, fh, ks, n_k, out_h);
+        if (rc != HALDA_OK) return rc;
+    }
+    const int64_t nd = fh->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    const double *f64[16] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu, fh->t_kvcpy_gpu,
+                             fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk, fh->d_avail_ram, fh->c_cpu,
+                             fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int32_t *bmin = bounds ? bounds->w_min : nullptr, *bmax = bounds ? bounds->w_max : nullptr;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
+    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16);
+    const size_t o_bmin = take(4 * nd), o_bmax = take(4 * nd);
+    const size_t n_inst = size_t(nf) * n_k;
+    const bool xsel = out_h->x_off && (out_h->x || out_h->c);
+    const size_t o_xoff = xsel ? take(8 * n_inst) : 0;
+    const size_t o_bk = take(4 * nf), o_obj = take(8 * nf), o_w = take(4 * nd), o_n = take(4 * nd),
+                 o_obk = take(8 * n_inst), o_st = take(4 * n_inst);
+    size_t xs = n_inst * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
+    if (xsel) {
+        int64_t ext = 0;
+        for (int64_t f = 0; f < nf; ++f) {
+            const int64_t N = 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1;
+            for (int j = 0; j < n_k; ++j) {
+                const int64_t a = out_h->x_off[f * n_k + j];
+                if (a >= 0) ext = std::max(ext, a + N);
+            }
+        }
+        xs = size_t(ext);
+    }
+    const size_t o_x = out_h->x ? take(8 * xs) : 0, o_c = out_h->c ? take(8 * xs) : 0;
+    if (off > c->scratch_bytes) {
+        if (c->scratch) HIP_TRY(hipFree(c->scratch));
+        c->scratch = nullptr;
+        c->scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&c->scratch, off));
+        c->scratch_bytes = off;
+    }
+    char *base = static_cast<char *>(c->scratch);
+    auto up = [&](size_t o, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(up(o_doff, fh->dev_off, 8 * (nf + 1)));
+    HIP_TRY(up(o_cls, fh->os_class, nd));
+    HIP_TRY(up(o_fl, fh->flags, nd));
+    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
+    if (bmin) HIP_TRY(up(o_bmin, bmin, 4 * nd));
+    if (bmax) HIP_TRY(up(o_bmax, bmax, 4 * nd));
+    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * n_inst));
+    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
+    halda_fleets d = *fh;
+    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
+    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
+    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
+    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
+    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
+    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
+    d.d_avail_metal = F64(14); d.swap = F64(15);
+    halda_bounds db;
+    db.w_min = bmin ? reinterpret_cast<const int32_t *>(base + o_bmin) : nullptr;
+    db.w_max = bmax ? reinterpret_cast<const int32_t *>(base + o_bmax) : nullptr;
+    halda_fleet_result r;
+    r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+    r.obj_value = reinterpret_cast<double *>(base + o_obj);
+    r.w = reinterpret_cast<int32_t *>(base + o_w);
+    r.n = reinterpret_cast<int32_t *>(base + o_n);
+    r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
+    r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
+    r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
+    r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
+    r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
+    {
+        const int rc = halda_solve_fleets_bounded(ctx, model, &d, ks, n_k, &db, &r, s);
+        if (rc != HALDA_OK) return rc;
+    }
+    auto dn = [&](void *dst, size_t o, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIP_TRY(dn(out_h->best_k, o_bk, 4 * nf));
+    HIP_TRY(dn(out_h->obj_value, o_obj, 8 * nf));
+    HIP_TRY(dn(out_h->w, o_w, 4 * nd));
+    HIP_TRY(dn(out_h->n, o_n, 4 * nd));
+    HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n_inst));
+    HIP_TRY(dn(out_h->status, o_st, 4 * n_inst));
+    HIP_TRY(dn(out_h->x, o_x, 8 * xs));
+    HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
 }
 
 // ---------------------------------------------------------------- several GPUs, one process

@@ -1568,6 +1568,249 @@ __global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIM
     sweep_fleet<false, false, Wave, true, true>(A, A.F, A.out, f, w, sg, &pre);
 }
 
+// ---------------------------------------------------------------- per-device layer bounds
+// halda_solve_fleets_bounded: the k-sweep with the w columns' bounds narrowed from [1, W] to
+// [lo_i, hi_i] = [max(1, w_min_i), min(W, w_max_i)]; n, the slacks, z, C and every row
+// stay as they are. Either array may be absent (nullptr: no bound on that side).
+struct BoundArgs {
+    const int32_t *w_min, *w_max;  // halda_bounds: [dev_off[n_fleets]] device layout
+};
+
+// Capped bound sums: every open W is < 1e6 < kBoundCap, so sum min(b_i, kBoundCap) compares with W as the
+// uncapped sum does, and 4096 capped terms of a lane's share / 64 lane sums stay inside an int.
+constexpr int kBoundCap = 1 << 24;
+
+// The general route's patch of a lowered batch (halda_lower_kernel's layout: instance (f, j) has its
+// columns at (f n_k + j) cols, the w columns first): one wave per instance, lane = column, col_lb / col_ub
+// of the M w columns overwritten with lo / hi. lo is capped at W + 1 (any lo > W is infeasible by itself,
+// the screen's rule), so the screen's integer sum of the lower bounds stays small.
+__global__ __launch_bounds__(256) void halda_bound_cols_kernel(halda_fleets F, BoundArgs Bd, const int32_t *ks, int n_k,
+                                                               int L, int64_t cols, double *col_lb, double *col_ub) {
+    const int64_t inst = int64_t(blockIdx.x) * 4 + int(threadIdx.x >> 6);
+    if (inst >= int64_t(F.n_fleets) * n_k) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t f = inst / n_k;
+    const int j = int(inst - f * n_k);
+    const int64_t d0 = F.dev_off[f];
+    const int M = int(F.dev_off[f + 1] - d0);
+    const int W = L / ks[j];
+    const int64_t co = inst * cols;
+    for (int i = lane; i < M; i += 64) {
+        const int lo = max(1, Bd.w_min ? Bd.w_min[d0 + i] : 0);
+        const int hi = Bd.w_max ? Bd.w_max[d0 + i] : 0x7fffffff;
+        col_lb[co + i] = lo > W ? double(W) + 1.0 : double(lo);
+        col_ub[co + i] = double(min(W, hi));
+    }
+}
+
+// The compact record with its w bounds: k1_alloc, k1_dp and the splits read a record's bounds through
+// rec_wlo / rec_whi and its broadcast form through bcast() / core(), so the register greedy and its exact
+// DP fallback run on [wlo, whi] unedited (split_first / split_second fall back to split_full where the
+// lower bound is not 1). With wlo = 1, whi = W every value equals the FieldRec's.
+struct UBoundRec : UFieldRec {
+    int wlo, whi;
+    __device__ inline const UBoundRec &core() const { return *this; }
+};
+
+struct BoundRec : FieldRec {
+    int wlo, whi;
+    template <class SG>
+    __device__ inline UBoundRec bcast(const SG &sg, int src) const {
+        UBoundRec o;
+        static_cast<UFieldRec &>(o) = FieldRec::bcast(sg, src);
+        o.wlo = sg.bcast(wlo, src);
+        o.whi = sg.bcast(whi, src);
+        return o;
+    }
+    __device__ inline const BoundRec &core() const { return *this; }
+};
+
+__device__ inline int rec_wlo(const BoundRec &r) { return r.wlo; }
+__device__ inline int rec_whi(const BoundRec &r) { return r.whi; }
+__device__ inline int rec_wlo(const UBoundRec &r) { return r.wlo; }
+__device__ inline int rec_whi(const UBoundRec &r) { return r.whi; }
+
+// One fleet of M = A.uM <= kK1MaxM devices (lane = device) under its bounds, its fields (mf), the lane's
+// k_j / W_j and the lane's w_min / w_max already loaded. The host sends only batches the register sweep
+// takes alone (plan_sweep's kRegAlone): every k > 1 has W < M <= sum lo, so an open instance is k = 1 with
+// R = W - sum lo < kDpLanes, solved by k1_alloc and, for what the greedy does not take, k1_dp -- both
+// exact. The settled verdicts, the objective's order of additions and every store follow sweep_fleet, so
+// bounds that never bind give the sweep's bits.
+__device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveCtx &w, const Wave &sg,
+                                          const DevFields &mf, int64_t d0, int kj, int Wj, int wmn, int wmx) {
+    const FleetOut &O = A.out;
+    const int lane = sg.sl;
+    const bool kl = lane < A.n_k;
+    const int M = A.uM;
+    const int outs = A.outs;
+    const bool act = lane < M;
+    BoundRec me = {};
+    int bad = 0;
+    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
+    bad = act ? bad : 0;
+    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
+    fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
+    bad = sg.any(bad != 0) ? 1 : 0;
+    // lo_i = max(1, w_min_i); hi_i = min(W, w_max_i). sum lo > W, some lo_i > hi_i and sum hi < W are
+    // bound-infeasible. A lo_i > W already gives sum lo > W (every lo >= 1), so the crossing test needs
+    // w_max alone; and where no bound crosses (every w_max_i >= lo_i >= 1) sum min(W, w_max_i) < W exactly
+    // when sum w_max_i < W: all three tests are formed once, for every k of the call.
+    const int lo = min(max(1, wmn), kBoundCap);
+    const int sumlo = sg.sum_i(act ? lo : 0);
+    const int sumhi = sg.sum_i(act ? min(max(wmx, 0), kBoundCap) : 0);
+    const bool cross = sg.any(act && lo > wmx);
+    double best = kInf;
+    int best_k = 0;
+    constexpr int kOpen = 1000;
+    int stj = kOpen;
+    if (!(Wj < 1000000)) stj = HALDA_STATUS_UNSUPPORTED;
+    else if (sumlo > Wj) stj = HALDA_STATUS_INFEASIBLE;  // sum lb(w) > W (without bounds: M > W)
+    else if (bad) stj = HALDA_STATUS_UNSUPPORTED;
+    else if (cross || sumhi < Wj) stj = HALDA_STATUS_INFEASIBLE;
+    if (kl && stj != kOpen) {
+        const int64_t inst = int64_t(f) * A.n_k + lane;
+        if (outs & kOutObk) O.obj_by_k[inst] = kInf;
+        if (outs & kOutSt) O.status[inst] = stj;
+    }
+    if ((outs & kOutXZ) && (outs & kOutXC)) {  // x / c of a settled instance are zero
+        uint64_t settled = sg.bits(kl && stj != kOpen);
+        const int N = 7 * M + 1;
+        while (settled) {
+            const int j = __builtin_ctzll(settled);
+            settled &= settled - 1;
+            const int64_t at = xc_at(A, int64_t(f) * A.n_k + j);
+            if (at >= 0)
+                for (int cc = lane; cc < N; cc += 64) {
+                    if (outs & kOutX) O.x[at + cc] = 0.0;
+                    if (outs & kOutC) O.c[at + cc] = 0.0;
+                }
+        }
+    }
+    uint64_t todo = sg.bits(kl && stj == kOpen);
+    while (todo) {
+        const int j = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        opaque_rec(me);
+        const int k = sg.bcast(kj, j);
+        const int W = sg.bcast(Wj, j);
+        const int64_t inst = int64_t(f) * A.n_k + j;
+        const double kc = double(k - 1);
+        const int R = W - sumlo;
+        int st;
+        double obj = kInf;
+        bool improved = false;
+        int rc = K1_FALLBACK, e = 0, rounds = 0, nE = 0;
+        double gE = 0.0;
+        bool haveE = true;  // gE / nE hold the split at w = lo + e (k1_alloc), else split here
+        me.W = W;
+        me.wlo = lo;
+        me.whi = min(W, wmx);
+        // k = 1, or R = 0 (every w_i = lo_i is forced): the allocation that minimises sum g is the answer
+        if (k == 1 || R == 0) {
+            if (!A.k1dp) rc = k1_alloc(me, M, R, sg, e, rounds, gE, nE);
+            if (rc == K1_FALLBACK && R < kDpLanes) {
+                rc = k1_dp(me, M, R, sg, e, w.dparg);
+                haveE = false;
+            }
+        }
+        if (rc == K1_INFEASIBLE) {
+            st = HALDA_STATUS_INFEASIBLE;
+        } else if (rc == K1_OK) {
+            double g = 0.0, H = 0.0, z = 0.0;
+            int n = 0, sl[4] = {0, 0, 0, 0};
+            const int wl = lo + e;
+            const bool need_h = kc != 0.0 || (outs & kOutX);
+            if (act) {
+                if (haveE) {
+                    g = gE;
+                    n = nE;
+                    rec_slacks(me, wl, n, sl);
+                } else {
+                    split_full(me, wl, g, n, sl);
+                }
+                if (need_h) {
+                    double P, Q;
+                    dev_cycle(me, wl, n, sl, P, Q);
+                    z = Q > P ? 0.5 * (Q - P) : 0.0;
+                    H = Q >= P ? 0.5 * (P + Q) : P;
+                }
+            }
+            const double hmax = need_h ? fmax(0.0, sg.max_f64(act ? H : 0.0)) : 0.0;
+            obj = sg.sum_f64(act ? g : 0.0) + kc * hmax;
+            obj = obj + tsum;
+            obj = obj + xsum;
+            obj = obj + kappa;
+            st = HALDA_STATUS_OPTIMAL;
+            improved = obj < best;
+            if (act) {
+                if (outs & kOutXC) put_xc(A, O, inst, M, lane, wl, n, sl, z, me);
+                if (improved) {
+                    O.w[d0 + lane] = wl;
+                    O.n[d0 + lane] = n;
+                }
+            }
+            if (lane == 0 && (outs & kOutXC)) {
+                const int64_t at = xc_at(A, inst);
+                if (at >= 0 && (outs & kOutX)) O.x[at + 7 * M] = hmax;
+                if (at >= 0 && (outs & kOutC)) O.c[at + 7 * M] = kc;
+            }
+        } else {
+            // k > 1 with room, or R + 1 > kDpLanes: not a batch the host sends here (the general route's)
+            st = HALDA_STATUS_UNSUPPORTED;
+        }
+        if (improved) {
+            best = obj;
+            best_k = k;
+        }
+        if ((outs & kOutXZ) && st != HALDA_STATUS_OPTIMAL) {  // x / c of a non-optimal instance are zero
+            const int N = 7 * M + 1;
+            const int64_t at = xc_at(A, inst);
+            if (at >= 0)
+                for (int cc = lane; cc < N; cc += 64) {
+                    if (outs & kOutX) O.x[at + cc] = 0.0;
+                    if (outs & kOutC) O.c[at + cc] = 0.0;
+                }
+        }
+        if (lane == 0) {
+            if (outs & kOutObk) O.obj_by_k[inst] = st == HALDA_STATUS_OPTIMAL ? obj : kInf;
+            if (outs & kOutSt) O.status[inst] = st;
+        }
+    }
+    if (lane == 0) {
+        O.best_k[f] = best_k;
+        O.obj_value[f] = best;
+    }
+    if (best_k == 0 && act) {
+        O.w[d0 + lane] = 0;
+        O.n[d0 + lane] = 0;
+    }
+}
+
+// halda_sweep_bounds_kernel: the fused route -- the register sweep of a batch of fleets of one size
+// A.uM <= kK1MaxM that needs no table launch (the host checks both: the sub-fleet, variants and plans
+// kernels' gate), under per-device bounds. One wave per fleet, kSweepWavesPerBlock per workgroup, lane =
+// device; the lane's w_min / w_max are two 4-byte loads issued with the 18 field loads.
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_bounds_kernel(
+    SweepArgs A, BoundArgs Bd) {
+    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    if (f >= A.F.n_fleets) return;
+    const int lane = int(threadIdx.x & 63);
+    const int M = A.uM;
+    const int64_t base = sload_i64(A.F.dev_off);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    const bool kl = lane < A.n_k;
+    const int kj = A.ks[kl ? lane : 0];
+    const int Wj = kl ? A.Ws[lane] : 0;
+    const int64_t d0 = base + int64_t(f) * M;
+    const int64_t g = d0 + (lane < M ? lane : 0);
+    const DevFields mf = load_fields(A.F, g);
+    const int wmn = Bd.w_min ? Bd.w_min[g] : 0;
+    const int wmx = Bd.w_max ? Bd.w_max[g] : 0x7fffffff;
+    sweep_fleet_bounds(A, f, w, Wave(lane), mf, d0, kj, Wj, wmn, wmx);
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the

@@ -89,7 +89,9 @@ EXPORTS = ("halda_version", "halda_init", "halda_solve_batch", "halda_solve_batc
            "halda_solve_subfleets_host", "halda_set_subfleets_path", "halda_last_subfleets_route",
            "halda_solve_variants", "halda_solve_variants_host", "halda_set_variants_path",
            "halda_last_variants_route", "halda_eval_plans", "halda_eval_plans_host", "halda_solve_fleets_plans",
-           "halda_solve_fleets_plans_host", "halda_last_plans_route", "halda_set_plans_path")
+           "halda_solve_fleets_plans_host", "halda_last_plans_route", "halda_set_plans_path",
+           "halda_solve_fleets_bounded", "halda_solve_fleets_bounded_host", "halda_last_bounds_route",
+           "halda_set_bounds_path")
 
 _lib = None
 _lib_lock = threading.Lock()

@@ -1,0 +1,235 @@
+"""The k-sweep within per-device layer bounds (libhalda `halda_solve_fleets_bounded`): caps, pins, bounded moves.
+
+`halda_replace_or_keep` reports how many layers the new optimum would move, but the caller cannot limit it.
+Here the caller narrows the bounds of the `w` columns of every fixed-k MILP from `[1, W]` to
+`[max(1, w_min_i), min(W, w_max_i)]`: "at most D layers per device away from the running plan"
+(`move_bounds`, `halda_replace_within`), "device 3 takes at most 6 layers" (a cap), "devices 0 and 1 stay as
+they are" (a pin, `w_min_i = w_max_i`). Everything else of the MILP is unchanged: the other devices' n are
+re-optimised, and bounds on n are not offered.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import math
+import numbers
+from dataclasses import dataclass
+from typing import Iterable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from ..common import DeviceProfile, ModelProfile
+from ._libhalda import get_context, last_error
+from .coefficients import HALDAResult
+from .fleets import (FleetSolve, FleetTable, HaldaBoundsC, HaldaFleetResultC, _bind_bounds, _host_struct,
+                     fleet_table, model_struct, open_x_offsets)
+from .halda import _batch_k_list, _batch_results, _positive_ks
+from .lower import kv_bits_to_factor
+from .plans import Incumbent, PlanEvaluation, _as_plan, halda_replace_or_keep_batch
+
+INT32_MAX = 2**31 - 1
+Bounds = Optional[Tuple[Optional[Sequence[int]], Optional[Sequence[int]]]]
+
+
+def set_bounds_path(ctx, path: int) -> None:
+    """halda_set_bounds_path on a HaldaContext: 0 automatic, 1 always the general route, 2 the fused launch
+    where it applies."""
+    lib = _bind_bounds(ctx.lib)
+    rc = lib.halda_set_bounds_path(ctx.ctx, int(path))
+    if rc != 0:
+        raise RuntimeError(f"halda_set_bounds_path failed ({rc}): {last_error(lib)}")
+
+
+def last_bounds_route(ctx) -> str:
+    """The route of the context's last halda_solve_fleets_bounded call: "fused", "general" or "none"."""
+    lib = _bind_bounds(ctx.lib)
+    r = ctypes.c_int(0)
+    rc = lib.halda_last_bounds_route(ctx.ctx, ctypes.byref(r))
+    if rc != 0:
+        raise RuntimeError(f"halda_last_bounds_route failed ({rc}): {last_error(lib)}")
+    return ("none", "fused", "general")[r.value]
+
+
+def _int_list(a, what: str, M: int) -> List[int]:
+    try:
+        a = list(a)
+    except TypeError:
+        raise ValueError(f"{what}: {a!r} is neither an integer nor a sequence of integers") from None
+    if len(a) != M:
+        raise ValueError(f"{what} of {len(a)} entries for a fleet of {M} devices")
+    for v in a:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f"{what}: {v!r} is not an integer")
+    return [int(v) for v in a]
+
+
+def check_bounds(w_min, w_max, M: int) -> Tuple[Optional[List[int]], Optional[List[int]]]:
+    """(w_min, w_max) as int lists (None: no bound on that side). ValueError for a wrong length, a non-integer
+    entry or w_min_i < 1; w_max_i < w_min_i is not an error (the instance is infeasible)."""
+    lo = None if w_min is None else _int_list(w_min, "w_min", M)
+    hi = None if w_max is None else _int_list(w_max, "w_max", M)
+    if lo is not None and any(v < 1 for v in lo):
+        raise ValueError("w_min: every entry must be >= 1")
+    return lo, hi
+
+
+def move_bounds(w0: Sequence[int], max_move: Union[int, Sequence[int]]) -> Tuple[List[int], List[int]]:
+    """The box of plans at most `max_move` layers per device away from w0: (max(1, w0 - D), w0 + D), D an int
+    or one per device."""
+    w0 = _int_list(w0, "w0", len(list(w0)))
+    if isinstance(max_move, numbers.Integral) and not isinstance(max_move, bool):
+        D = [int(max_move)] * len(w0)
+    else:
+        D = _int_list(max_move, "max_move", len(w0))
+    if any(d < 0 for d in D):
+        raise ValueError("max_move must be >= 0")
+    return [max(1, w - d) for w, d in zip(w0, D)], [w + d for w, d in zip(w0, D)]
+
+
+def bounds_arrays(table: FleetTable, bounds: Sequence[Bounds]) -> Tuple[np.ndarray, np.ndarray]:
+    """(w_min, w_max) int32 in the table's device layout: 0 / INT32_MAX ("no bound") where a fleet has none;
+    entries beyond the int32 range are clipped to it (they bind no more than the range's ends)."""
+    nf, nd = table.n_fleets, table.n_devices
+    if len(bounds) != nf:
+        raise ValueError(f"{len(bounds)} bounds for {nf} fleets")
+    lo, hi = np.zeros(nd, np.int32), np.full(nd, INT32_MAX, np.int32)
+    sizes = table.sizes()
+    for f, b in enumerate(bounds):
+        if b is None:
+            continue
+        w_min, w_max = check_bounds(b[0], b[1], int(sizes[f]))
+        a = int(table.dev_off[f])
+        if w_min is not None:
+            lo[a:a + len(w_min)] = np.clip(w_min, 0, INT32_MAX)
+        if w_max is not None:
+            hi[a:a + len(w_max)] = np.clip(w_max, -INT32_MAX, INT32_MAX)
+    return lo, hi
+
+
+def solve_bounded_table(table: FleetTable, model: ModelProfile, pos: List[int], w_min: Optional[np.ndarray],
+                        w_max: Optional[np.ndarray], kv_factor: float, device: int = 0) -> FleetSolve:
+    """One halda_solve_fleets_bounded_host call on a packed table: the bounded sweep's FleetSolve
+    (want_x="open")."""
+    ctx = get_context(device)
+    lib = _bind_bounds(ctx.lib)
+    nf, nd, nk = table.n_fleets, table.n_devices, len(pos)
+    xsel = open_x_offsets(table, model, pos)
+    ext = int(np.max(xsel + np.repeat(7 * table.sizes() + 1, nk), initial=0)) if (xsel >= 0).any() else 0
+    fbuf, ibuf = np.zeros(nf + nf * nk + 2 * ext), np.zeros(nf + 2 * nd + nf * nk, np.int32)
+    pf, pi = fbuf.ctypes.data, ibuf.ctypes.data
+    o1, o2 = nf, nf + nf * nk
+    out = FleetSolve(best_k=ibuf[:nf], obj_value=fbuf[:nf], w=ibuf[nf:nf + nd], n=ibuf[nf + nd:nf + 2 * nd],
+                     obj_by_k=fbuf[o1:o2].reshape(nf, nk), status=ibuf[nf + 2 * nd:].reshape(nf, nk), ks=pos,
+                     x=fbuf[o2:o2 + ext], c=fbuf[o2 + ext:], x_off=xsel)
+    r = HaldaFleetResultC(pi, pf, pi + 4 * nf, pi + 4 * (nf + nd), pf + 8 * o1, pi + 4 * (nf + 2 * nd), pf + 8 * o2,
+                          pf + 8 * (o2 + ext), xsel.ctypes.data)
+    fs, keep = _host_struct(table)
+    lo = None if w_min is None else np.ascontiguousarray(w_min, np.int32)
+    hi = None if w_max is None else np.ascontiguousarray(w_max, np.int32)
+    bd = HaldaBoundsC(None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data)
+    karr = np.asarray(pos, np.int32)
+    m = model_struct(model, kv_factor)
+    with ctx._lock:
+        rc = lib.halda_solve_fleets_bounded_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
+                                                 ctypes.byref(bd), ctypes.byref(r))
+    del keep
+    if rc != 0:
+        raise RuntimeError(f"halda_solve_fleets_bounded_host failed ({rc}): {last_error(lib)}")
+    return out
+
+
+def halda_solve_bounded_batch(fleets: Sequence[Sequence[DeviceProfile]], model: ModelProfile,
+                              bounds: Sequence[Bounds], k_candidates: Optional[Iterable[int]] = None,
+                              kv_bits: str = "8bit", device: int = 0) -> List[Optional[HALDAResult]]:
+    """Many fleets, each within its own bounds (`bounds[f]` = (w_min, w_max), either None, or None for no
+    bounds), in ONE GPU call. One HALDAResult per fleet, None where no k is feasible within the bounds."""
+    kv_factor = kv_bits_to_factor(kv_bits)
+    fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
+    if len(bounds) != len(fleets):
+        raise ValueError(f"{len(bounds)} bounds for {len(fleets)} fleets")
+    for devs, b in zip(fleets, bounds):  # the argument errors before any packing or GPU call
+        if b is not None:
+            check_bounds(b[0], b[1], len(devs))
+    if k_candidates is not None and not isinstance(k_candidates, (list, tuple)):
+        k_candidates = list(k_candidates)
+    Ks = _batch_k_list(model, k_candidates)
+    if not fleets:
+        return []
+    if not Ks:
+        return [None] * len(fleets)
+    pos = _positive_ks(Ks)
+    table = fleet_table(fleets, model)
+    if not pos:
+        return [None] * len(fleets)
+    lo, hi = bounds_arrays(table, bounds)
+    res = solve_bounded_table(table, model, pos, lo, hi, kv_factor, device)
+    return _batch_results(table, res, pos, model)
+
+
+def halda_solve_bounded(devs: Sequence[DeviceProfile], model: ModelProfile, w_min: Optional[Sequence[int]] = None,
+                        w_max: Optional[Sequence[int]] = None, k_candidates: Optional[Iterable[int]] = None,
+                        kv_bits: str = "8bit", device: int = 0) -> HALDAResult:
+    """halda_solve with every device's layer count kept in [w_min_i, w_max_i]; RuntimeError, as halda_solve
+    raises it, when no k is feasible within the bounds."""
+    devs = list(devs)
+    b = None if w_min is None and w_max is None else (w_min, w_max)
+    r = halda_solve_bounded_batch([devs], model, [b], k_candidates, kv_bits, device)[0]
+    if r is None:
+        raise RuntimeError("No feasible MILP found for any k this round.")
+    return r
+
+
+@dataclass(frozen=True)
+class ReplacementWithin:
+    """halda_replace_within's answer: halda_replace_or_keep's fields, and `within` -- the best plan at the
+    incumbent's k at most max_move layers per device away from it (None where the box holds no plan) --
+    with regret_within = incumbent.obj_value - within.obj_value, moved_layers_within and
+    gap_to_free = within.obj_value - best.obj_value (what the move budget costs; inf without `within`)."""
+
+    incumbent: PlanEvaluation
+    best: Optional[HALDAResult]
+    regret: float
+    moved_layers: int
+    replace: bool
+    within: Optional[HALDAResult]
+    regret_within: float
+    moved_layers_within: int
+    gap_to_free: float
+
+
+def halda_replace_within_batch(fleets: Sequence[Sequence[DeviceProfile]], model: ModelProfile,
+                               incumbents: Sequence[Incumbent], max_move: Union[int, Sequence[int]],
+                               kv_bits: str = "8bit", rel_tol: float = 0.0, device: int = 0
+                               ) -> List[ReplacementWithin]:
+    """Per fleet: halda_replace_or_keep (the incumbent priced, the free optimum), then the best plan inside
+    the move box around the incumbent at the incumbent's k -- one bounded call per distinct incumbent k."""
+    fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
+    base = halda_replace_or_keep_batch(fleets, model, incumbents, rel_tol, kv_bits, None, device)
+    plans = [_as_plan(p) for p in incumbents]
+    within: List[Optional[HALDAResult]] = [None] * len(fleets)
+    by_k = {}
+    for f, p in enumerate(plans):
+        if p is not None:
+            by_k.setdefault(int(p[0]), []).append(f)
+    for k, fs in sorted(by_k.items()):
+        boxes = [move_bounds(plans[f][1], max_move) for f in fs]
+        got = halda_solve_bounded_batch([fleets[f] for f in fs], model, boxes, [k], kv_bits, device)
+        for f, r in zip(fs, got):
+            within[f] = r
+    out = []
+    for b, p, wi in zip(base, plans, within):
+        moved = 0 if wi is None or p is None else int(sum(abs(int(a) - int(c)) for a, c in zip(wi.w, p[1])))
+        if wi is None:
+            rw = -math.inf if b.incumbent.feasible else math.inf
+        else:
+            rw = b.incumbent.obj_value - wi.obj_value if b.incumbent.feasible else math.inf
+        gap = math.inf if wi is None or b.best is None else wi.obj_value - b.best.obj_value
+        out.append(ReplacementWithin(b.incumbent, b.best, b.regret, b.moved_layers, b.replace, wi, rw, moved, gap))
+    return out
+
+
+def halda_replace_within(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent,
+                         max_move: Union[int, Sequence[int]], kv_bits: str = "8bit", rel_tol: float = 0.0,
+                         device: int = 0) -> ReplacementWithin:
+    """halda_replace_within_batch for one fleet."""
+    return halda_replace_within_batch([list(devs)], model, [incumbent], max_move, kv_bits, rel_tol, device)[0]

@@ -102,6 +102,30 @@ def _bind_plans(lib):
     return lib
 
 
+class HaldaBoundsC(ctypes.Structure):
+    _fields_ = [("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p)]
+
+
+def _bind_bounds(lib):
+    """The bounded-sweep entries' prototypes (halda_solve_fleets_bounded .. halda_set_bounds_path)."""
+    lib = _bind(lib)
+    if getattr(lib, "_bounds_bound", False):
+        return lib
+    P = ctypes.POINTER
+    lib.halda_solve_fleets_bounded.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
+                                               ctypes.c_int32, P(HaldaBoundsC), P(HaldaFleetResultC), ctypes.c_void_p]
+    lib.halda_solve_fleets_bounded.restype = ctypes.c_int
+    lib.halda_solve_fleets_bounded_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
+                                                    ctypes.c_int32, P(HaldaBoundsC), P(HaldaFleetResultC)]
+    lib.halda_solve_fleets_bounded_host.restype = ctypes.c_int
+    lib.halda_last_bounds_route.argtypes = [ctypes.c_void_p, P(ctypes.c_int)]
+    lib.halda_last_bounds_route.restype = ctypes.c_int
+    lib.halda_set_bounds_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.halda_set_bounds_path.restype = ctypes.c_int
+    lib._bounds_bound = True
+    return lib
+
+
 def _bind(lib):
     if getattr(lib, "_fleets_bound", False):
         return lib
@@ -928,6 +952,39 @@ class DeviceFleetTable:
                                               ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"halda_solve_fleets_plans failed ({rc}): {last_error(lib)}")
+
+    def set_bounds(self, w_min=None, w_max=None) -> None:
+        """Give the table its resident per-device layer bounds: device tensors bound_min / bound_max
+        [n_devices] (int32; zeros / INT32_MAX, "no bound", where not given), buffers of their own. A streaming
+        caller rewrites them in place between launches."""
+        import torch
+
+        dev = self.out["best_k"].device
+        nd = self.table.n_devices
+
+        def tensor(a, fill):
+            if a is None:
+                return torch.full((nd,), fill, dtype=torch.int32, device=dev)
+            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))
+            if t.numel() != nd:
+                raise ValueError(f"bounds array of {t.numel()} entries, expected {nd}")
+            return t.to(device=dev, dtype=torch.int32).contiguous().clone()
+
+        self.bound_min, self.bound_max = tensor(w_min, 0), tensor(w_max, 2**31 - 1)
+        self._bounds_c = HaldaBoundsC(self.bound_min.data_ptr(), self.bound_max.data_ptr())
+
+    def launch_with_bounds(self, ctx, stream: int) -> None:
+        """Enqueue the k-sweep of every fleet within the resident bounds on `stream`
+        (halda_solve_fleets_bounded): self.out as launch() leaves it."""
+        if getattr(self, "_bounds_c", None) is None:
+            self.set_bounds()
+        lib = _bind_bounds(ctx.lib)
+        with ctx._lock:
+            rc = lib.halda_solve_fleets_bounded(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
+                                                self.ks.ctypes.data, len(self.ks), ctypes.byref(self._bounds_c),
+                                                ctypes.byref(self.res), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"halda_solve_fleets_bounded failed ({rc}): {last_error(lib)}")
 
 
 class RcclComm:

@@ -465,6 +465,48 @@ int halda_last_plans_route(void *ctx, int *route);
  * fused route where it applies (two launches elsewhere). HALDA_E_ARG for any other path. */
 int halda_set_plans_path(void *ctx, int path);
 
+/* ------------------------------------------------------------------------
+ * The k-sweep within per-device layer bounds: caps, pins and bounded moves.
+ *
+ * Two optional int32 arrays in the table's device layout narrow the w columns of every (fleet, k)
+ * instance from [1, W] to [lo_i, hi_i], W = L / k:
+ *    lo_i = max(1, w_min_i)   (a zero-filled array, or w_min == NULL: no lower bound)
+ *    hi_i = min(W, w_max_i)   (INT32_MAX, or w_max == NULL: no upper bound)
+ * The same arrays apply to every k of the call (a caller with a move budget around an incumbent passes
+ * the incumbent's k alone). The answer is that of the reference's fixed-k MILP with only the bounds of
+ * the w columns replaced: n, the slacks, z, C and every row are as in halda_solve_fleets, the other
+ * devices' n are re-optimised, a device with lo = hi is pinned in w only, and the best k is picked by
+ * the same rule (ascending k, strict "<"). An instance is HALDA_STATUS_INFEASIBLE when sum lo > W
+ * (without bounds: M > W), when some lo_i > hi_i, or when sum hi < W; W >= 1e6 and rejected records
+ * stay HALDA_STATUS_UNSUPPORTED. With no bounds, or with bounds that never bind (w_min <= 1,
+ * w_max >= W), every output equals halda_solve_fleets' bit for bit. Bounds on n are not offered.
+ * ------------------------------------------------------------------------ */
+typedef struct halda_bounds {
+    const int32_t *w_min, *w_max; /* [dev_off[n_fleets]] device layout; either may be NULL */
+} halda_bounds;
+
+/* Asynchronous on `stream` (NULL = the context's stream); every array is device memory (ks: host).
+ * Writes into `out` exactly the fields halda_solve_fleets writes. Two routes, one contract
+ * (halda_set_bounds_path). General route (every shape): the batch is lowered on the GPU
+ * (halda_lower_kernel), halda_bound_cols_kernel overwrites the w columns' bounds, and the CSR pipeline
+ * solves it. Fused route: where the sweep is the register launch alone over fleets of one size <= 64
+ * (the sub-fleet, variants and plans kernels' gate: no k > 1 has L / k >= M, and L - M + 1 <= 64 at
+ * k = 1), ONE launch of halda_sweep_bounds_kernel, one wave per fleet. */
+int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                               int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out, void *stream);
+
+/* Synchronous variant on HOST arrays (x_off host memory too): the table and the bounds cross PCIe once. */
+int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                                    int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out);
+
+/* Which route the context's last halda_solve_fleets_bounded / _host call took: 1 fused (one launch),
+ * 2 general (lowering, bounds, CSR pipeline), 0 when none ran yet. */
+int halda_last_bounds_route(void *ctx, int *route);
+
+/* How halda_solve_fleets_bounded runs: 0 automatic, 1 always general, 2 the fused route where it
+ * applies (general elsewhere). HALDA_E_ARG for any other path. */
+int halda_set_bounds_path(void *ctx, int path);
+
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */
 int halda_resident_release(void *ctx);
