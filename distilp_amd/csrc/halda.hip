@@ -166,8 +166,10 @@ struct Ctx {
     int var_route = 0;              // the last halda_solve_variants call: 1 fused, 2 loop (0: none yet)
     int plans_path = 0;             // halda_set_plans_path: 0 automatic, 1 always two launches, 2 fused where it applies
     int plans_route = 0;            // the last halda_solve_fleets_plans call: 1 fused, 2 two launches (0: none yet)
-    int bounds_path = 0;            // halda_set_bounds_path: 0 automatic, 1 always general, 2 fused where it applies
-    int bounds_route = 0;           // the last halda_solve_fleets_bounded call: 1 fused, 2 general (0: none yet)
+    int bounds_path = 0;            // halda_set_bounds_path: 0 automatic, 1 always general, 2 fused where it applies,
+                                    // 3 fused, else the table launch, where they apply
+    int bounds_route = 0;           // the last halda_solve_fleets_bounded call: 1 fused, 2 general, 3 table launch
+                                    // (0: none yet)
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -2811,11 +2813,15 @@ int halda_solve_fleets_plans_host(void *ctx, const halda_model *model, const hal
 // and halda_pick_kernel unchanged. Fused route: where the sweep is the register launch alone over fleets of
 // one size <= kK1MaxM (kRegAlone: the sub-fleet, variants and plans kernels' gate), ONE launch of
 // halda_sweep_bounds_kernel; bounds only shrink R and the set of open k, so no fleet is handed back.
+// Table route (path 3 only, where the fused route does not apply): fleets of 1 .. kK1MaxM devices whose
+// unbounded table slice fits the LDS budget, ONE launch of halda_sweep_bounds_tables_kernel on that slice
+// (sum lo >= M, so it holds every bounded instance; nothing is handed back either).
 int halda_set_bounds_path(void *ctx, int path) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c) return fail(HALDA_E_ARG, "NULL ctx");
-    if (path < 0 || path > 2)
-        return fail(HALDA_E_ARG, "bounds path must be 0 (automatic), 1 (always general) or 2 (fused where it applies)");
+    if (path < 0 || path > 3)
+        return fail(HALDA_E_ARG, "bounds path must be 0 (automatic), 1 (always general), 2 (fused where it applies) or "
+                                 "3 (fused, else the table launch, where they apply)");
     c->bounds_path = path;
     return HALDA_OK;
 }
@@ -2871,6 +2877,35 @@ int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_
             c->fleet_kslot = false;
             c->last_fleet_fused = true;
             c->bounds_route = 1;
+            return HALDA_OK;
+        }
+        if (c->bounds_path == 3 && F.min_devices >= 1 && F.max_devices <= kK1MaxM && p.slice <= kLdsBudget) {
+            SweepArgs &A = p.A;
+            A.fflag = nullptr;  // every fleet is solved here: nothing is flagged or handed back
+            A.hb_flag = c->hb_flag;
+            A.launch_id = ++c->launch_id;
+            A.want = 0;
+            c->fleet_timed = false;
+            c->have_lowered = false;
+            const void *fn = reinterpret_cast<const void *>(halda_sweep_bounds_tables_kernel);
+            int per_cu = 0;
+            HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
+            const unsigned grid =
+                unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(p.nf))));
+            const BoundArgs Bd{B.w_min, B.w_max};
+            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+            hipLaunchKernelGGL(halda_sweep_bounds_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bd);
+            HIP_TRY(hipGetLastError());
+            if (c->timing) {
+                HIP_TRY(hipEventRecord(c->evf1, s));
+                c->fleet_timed = true;
+            }
+            c->fleet_two = false;
+            c->fleet_reg_alone = false;
+            c->fleet_seg = false;
+            c->fleet_kslot = false;
+            c->last_fleet_fused = true;
+            c->bounds_route = 3;
             return HALDA_OK;
         }
     }

@@ -1811,6 +1811,256 @@ __global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIM
     sweep_fleet_bounds(A, f, w, Wave(lane), mf, d0, kj, Wj, wmn, wmx);
 }
 
+// The table route of the bounded sweep (route 3): fleets of any sizes 1 .. kK1MaxM under their bounds, every
+// k, in one launch with the table kernel's LDS slice. What the register route leaves to the general route --
+// k > 1 with room, R + 1 > kDpLanes, small fleets of a long model -- is solved here by the table machinery
+// on bounded records: table_entry builds w = wlo + e and masks w > whi, the DP sees only R1 = W - sum lo + 1
+// and the tables. The slice is the one plan_sweep sizes for the unbounded batch: sum lo >= M, so every
+// bounded R1 fits it. No fleet is handed back (A.want = 0: no flag bytes, no hand-back flag, no scratch), and
+// the waves share nothing, so launches on different streams need no ordering between them.
+
+// Device records for table_pass: lane i holds device i's record with its bounds (M <= 64), other lanes
+// fetch it by shuffle, wlo / whi with the record.
+struct BoundSrc {
+    using Rec = BoundRec;
+    const BoundRec *me;
+    __device__ inline void load(BoundRec &r, const WaveCtx &, int i) const {
+        static_cast<FieldRec &>(r) = me->shfl(i);
+        r.wlo = __shfl(me->wlo, i);
+        r.whi = __shfl(me->whi, i);
+    }
+};
+
+// One fleet of M <= kK1MaxM devices (lane = device) under its bounds. The settled verdicts are
+// sweep_fleet_bounds' (formed once for every k); an open k follows the table branch of
+// sweep_fleet<true, false> on a BoundRec with R = W - sum lo: k1_alloc where that branch takes it (k = 1, or
+// R = 0 where every w_i = lo_i is forced), else the tables and the DP, the objective in that branch's order
+// of additions. Bounds that never bind therefore give halda_sweep_tables_kernel's bits. A.k1dp (the test
+// path) sends every instance to the tables.
+__device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const BoundArgs &Bd, int f, const WaveCtx &w,
+                                                 const Wave &sg) {
+    const FleetOut &O = A.out;
+    const int lane = sg.sl;
+    const bool kl = lane < A.n_k;
+    const int kj = A.ks[kl ? lane : 0];
+    const int Wj = kl ? A.Ws[lane] : 0;
+    // the fleet's extent through the scalar cache (dev_off is read-only to the kernel)
+    const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
+    const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
+    const int outs = A.outs;
+    const bool act = lane < M;
+    const int64_t g0 = d0 + (act ? lane : 0);
+    const DevFields mf = load_fields(A.F, g0);
+    const int wmn = Bd.w_min ? Bd.w_min[g0] : 0;
+    const int wmx = Bd.w_max ? Bd.w_max[g0] : 0x7fffffff;
+    BoundRec me = {};
+    int bad = 0;
+    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
+    bad = act ? bad : 0;
+    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
+    fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
+    bad = sg.any(bad != 0) ? 1 : 0;
+    // the three bound tests from the capped integer sums and the ballot, once for every k (sweep_fleet_bounds)
+    const int lo = min(max(1, wmn), kBoundCap);
+    const int sumlo = sg.sum_i(act ? lo : 0);
+    const int sumhi = sg.sum_i(act ? min(max(wmx, 0), kBoundCap) : 0);
+    const bool cross = sg.any(act && lo > wmx);
+    double best = kInf;
+    int best_k = 0;
+    constexpr int kOpen = 1000;
+    int stj = kOpen;
+    if (!(Wj < 1000000)) stj = HALDA_STATUS_UNSUPPORTED;
+    else if (sumlo > Wj) stj = HALDA_STATUS_INFEASIBLE;  // sum lb(w) > W (without bounds: M > W)
+    else if (bad) stj = HALDA_STATUS_UNSUPPORTED;
+    else if (cross || sumhi < Wj) stj = HALDA_STATUS_INFEASIBLE;
+    if (kl && stj != kOpen) {
+        const int64_t inst = int64_t(f) * A.n_k + lane;
+        if (outs & kOutObk) O.obj_by_k[inst] = kInf;
+        if (outs & kOutSt) O.status[inst] = stj;
+    }
+    if ((outs & kOutXZ) && (outs & kOutXC)) {  // x / c of a settled instance are zero
+        uint64_t settled = sg.bits(kl && stj != kOpen);
+        const int N = 7 * M + 1;
+        while (settled) {
+            const int j = __builtin_ctzll(settled);
+            settled &= settled - 1;
+            const int64_t at = xc_at(A, int64_t(f) * A.n_k + j);
+            if (at >= 0)
+                for (int cc = lane; cc < N; cc += 64) {
+                    if (outs & kOutX) O.x[at + cc] = 0.0;
+                    if (outs & kOutC) O.c[at + cc] = 0.0;
+                }
+        }
+    }
+    uint64_t todo = sg.bits(kl && stj == kOpen);
+    while (todo) {
+        const int j = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        opaque_rec(me);
+        const int k = sg.bcast(kj, j);
+        const int W = sg.bcast(Wj, j);
+        const int64_t inst = int64_t(f) * A.n_k + j;
+        const double kc = double(k - 1);
+        const int R = W - sumlo;
+        int st;
+        double obj = kInf;
+        bool improved = false;
+        int rc = K1_FALLBACK, e = 0, rounds = 0, nE = 0;
+        double gE = 0.0;
+        me.W = W;
+        me.wlo = lo;
+        me.whi = min(W, wmx);
+        // k = 1: the register greedy; R = 0: every w_i = lo_i is forced, so the same code gives the solution
+        // for any k (the output adds (k - 1) max_i H_i)
+        if ((k == 1 || R == 0) && (HALDA_SWEEP_TABLE_K1 || R == 0) && !A.k1dp)
+            rc = k1_alloc(me, M, R, sg, e, rounds, gE, nE);
+        if (rc == K1_INFEASIBLE) {
+            st = HALDA_STATUS_INFEASIBLE;
+        } else if (rc == K1_OK) {
+            double g = 0.0, H = 0.0, z = 0.0;
+            int n = 0, sl[4] = {0, 0, 0, 0};
+            const int wl = lo + e;
+            const bool need_h = kc != 0.0 || (outs & kOutX);
+            if (act) {
+                g = gE;
+                n = nE;
+                rec_slacks(me, wl, n, sl);
+                if (need_h) {
+                    double P, Q;
+                    dev_cycle(me, wl, n, sl, P, Q);
+                    z = Q > P ? 0.5 * (Q - P) : 0.0;
+                    H = Q >= P ? 0.5 * (P + Q) : P;
+                }
+            }
+            const double hmax = need_h ? fmax(0.0, sg.max_f64(act ? H : 0.0)) : 0.0;
+            obj = sg.sum_f64(act ? g : 0.0) + kc * hmax;
+            obj = obj + tsum;
+            obj = obj + xsum;
+            obj = obj + kappa;
+            st = HALDA_STATUS_OPTIMAL;
+            improved = obj < best;
+            if (act) {
+                if (outs & kOutXC) put_xc(A, O, inst, M, lane, wl, n, sl, z, me);
+                if (improved) {
+                    O.w[d0 + lane] = wl;
+                    O.n[d0 + lane] = n;
+                }
+            }
+            if (lane == 0 && (outs & kOutXC)) {
+                const int64_t at = xc_at(A, inst);
+                if (at >= 0 && (outs & kOutX)) O.x[at + 7 * M] = hmax;
+                if (at >= 0 && (outs & kOutC)) O.c[at + 7 * M] = kc;
+            }
+        } else {
+            Inst I = {};
+            I.inst = int(inst);
+            I.M = M;
+            I.W = W;
+            I.Wd = double(W);
+            I.kc = kc;
+            I.iC = 7 * M;
+            I.R1 = R + 1;
+            I.RS = odd_stride(I.R1);
+            int64_t nodes = 0;
+            // a guard: the host sizes the slice from the unbounded batch, which holds every bounded instance
+            const bool too_large = M > A.mmax || I.R1 > A.r1max || int64_t(M) * I.RS > (kc > 0.0 ? A.tab_kc : A.tab);
+            int feas = 1;
+            if (!too_large) {
+                table_pass<64>(BoundSrc{&me}, w, I, lane);
+                wave_sync();
+                feas = dp_pass(w, I, lane, nodes) ? 1 : 0;
+            }
+            if (too_large) {
+                st = HALDA_STATUS_TOO_LARGE;
+            } else if (!feas) {
+                st = HALDA_STATUS_INFEASIBLE;
+            } else {
+                // solution: per device (w, n, least slacks, z), sum of costs, largest cycle time
+                double gs = 0.0, hmax = 0.0;
+                int wl = 0, n = 0;
+                if (act) {
+                    wl = lo + w.st0[lane];
+                    double gd = 0.0, P, Q;
+                    int sl[4] = {0, 0, 0, 0};
+                    split_full(me, wl, gd, n, sl);
+                    dev_cycle(me, wl, n, sl, P, Q);
+                    gs += gd;
+                    hmax = fmax(hmax, Q >= P ? 0.5 * (P + Q) : P);
+                    if (outs & kOutXC) put_xc(A, O, inst, M, lane, wl, n, sl, Q > P ? 0.5 * (Q - P) : 0.0, me);
+                }
+                hmax = sg.max_f64(hmax);
+                obj = sg.sum_f64(gs) + kc * hmax;
+                obj = obj + tsum;
+                obj = obj + xsum;
+                obj = obj + kappa;
+                st = HALDA_STATUS_OPTIMAL;
+                improved = obj < best;
+                if (improved && act) {
+                    O.w[d0 + lane] = wl;
+                    O.n[d0 + lane] = n;
+                }
+                if (lane == 0 && (outs & kOutXC)) {
+                    const int64_t at = xc_at(A, inst);
+                    if (at >= 0 && (outs & kOutX)) O.x[at + 7 * M] = hmax;
+                    if (at >= 0 && (outs & kOutC)) O.c[at + 7 * M] = kc;
+                }
+            }
+            wave_sync();  // tables / st0 are rewritten by the next k
+        }
+        if (improved) {
+            best = obj;
+            best_k = k;
+        }
+        if ((outs & kOutXZ) && st != HALDA_STATUS_OPTIMAL) {  // x / c of a non-optimal instance are zero
+            const int N = 7 * M + 1;
+            const int64_t at = xc_at(A, inst);
+            if (at >= 0)
+                for (int cc = lane; cc < N; cc += 64) {
+                    if (outs & kOutX) O.x[at + cc] = 0.0;
+                    if (outs & kOutC) O.c[at + cc] = 0.0;
+                }
+        }
+        if (lane == 0) {
+            if (outs & kOutObk) O.obj_by_k[inst] = st == HALDA_STATUS_OPTIMAL ? obj : kInf;
+            if (outs & kOutSt) O.status[inst] = st;
+        }
+    }
+    if (lane == 0) {
+        O.best_k[f] = best_k;
+        O.obj_value[f] = best;
+    }
+    if (best_k == 0 && act) {
+        O.w[d0 + lane] = 0;
+        O.n[d0 + lane] = 0;
+    }
+}
+
+// halda_sweep_bounds_tables_kernel: one wave per fleet in 64-thread workgroups on a persistent grid, each
+// with the table kernel's dynamic LDS slice (make_slice of the launch's shape), the fleets dealt out as
+// sweep_body deals them (workgroup b takes fleets b, b + grid, ...). No spin-wait and nothing shared between
+// waves: the only synchronisation is wave_sync within the one wave.
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bounds_tables_kernel(SweepArgs A,
+                                                                                                  BoundArgs Bd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const Slice sl = make_slice(A.mmax, A.r1max, A.tab, A.tab_kc);
+    WaveCtx w = {};
+    w.rows = reinterpret_cast<int2 *>(smem + sl.rows);
+    w.cyc = reinterpret_cast<double *>(smem + sl.cyc);
+    w.cost = reinterpret_cast<double *>(smem + sl.cost);
+    w.cnt = reinterpret_cast<int *>(smem + sl.cnt);
+    w.st0 = reinterpret_cast<int *>(smem + sl.st0);
+    w.st1 = reinterpret_cast<int *>(smem + sl.st1);
+    w.rng = reinterpret_cast<int2 *>(smem + sl.rng);
+    w.inc = reinterpret_cast<double *>(smem + sl.inc);
+    w.G = reinterpret_cast<double *>(smem + sl.G);
+    w.H = reinterpret_cast<double *>(smem + sl.H);
+    w.work = reinterpret_cast<double *>(smem + sl.work);
+    w.split = reinterpret_cast<uint16_t *>(smem + sl.split);
+    const int nf = A.F.n_fleets;
+    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) sweep_fleet_bounds_tables(A, Bd, int(f), w, Wave(lane));
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the

@@ -31,23 +31,42 @@ INT32_MAX = 2**31 - 1
 Bounds = Optional[Tuple[Optional[Sequence[int]], Optional[Sequence[int]]]]
 
 
-def set_bounds_path(ctx, path: int) -> None:
-    """halda_set_bounds_path on a HaldaContext: 0 automatic, 1 always the general route, 2 the fused launch
-    where it applies."""
-    lib = _bind_bounds(ctx.lib)
+BOUNDS_ROUTES = ("none", "fused", "general", "tables")  # halda_last_bounds_route's values 0 .. 3
+_ROUTE_PATH = {"auto": None, "general": 1, "tables": 3}  # the `route` keyword -> halda_set_bounds_path
+
+
+def _set_path(ctx, lib, path: int) -> None:
     rc = lib.halda_set_bounds_path(ctx.ctx, int(path))
     if rc != 0:
         raise RuntimeError(f"halda_set_bounds_path failed ({rc}): {last_error(lib)}")
+    ctx._bounds_path = int(path)  # the library has no getter: the per-call `route` restores this
+
+
+def set_bounds_path(ctx, path: int) -> None:
+    """halda_set_bounds_path on a HaldaContext: 0 automatic, 1 always the general route, 2 the fused launch
+    where it applies, 3 the fused launch where it applies, else the table launch
+    (halda_sweep_bounds_tables_kernel: fleets of 1 .. 64 devices, any k, one launch) where that applies."""
+    _set_path(ctx, _bind_bounds(ctx.lib), path)
+
+
+def check_route(route) -> Optional[int]:
+    """The bounds path a `route` keyword selects for one call: None for "auto" (the context's path stays as it
+    is), 1 for "general", 3 for "tables" (the fused launch, else the table launch, else general). ValueError
+    for anything else."""
+    if not isinstance(route, str) or route not in _ROUTE_PATH:
+        raise ValueError(f"route: {route!r} is not one of {sorted(_ROUTE_PATH)}")
+    return _ROUTE_PATH[route]
 
 
 def last_bounds_route(ctx) -> str:
-    """The route of the context's last halda_solve_fleets_bounded call: "fused", "general" or "none"."""
+    """The route of the context's last halda_solve_fleets_bounded call: "fused", "general", "tables" or
+    "none"."""
     lib = _bind_bounds(ctx.lib)
     r = ctypes.c_int(0)
     rc = lib.halda_last_bounds_route(ctx.ctx, ctypes.byref(r))
     if rc != 0:
         raise RuntimeError(f"halda_last_bounds_route failed ({rc}): {last_error(lib)}")
-    return ("none", "fused", "general")[r.value]
+    return BOUNDS_ROUTES[r.value]
 
 
 def _int_list(a, what: str, M: int) -> List[int]:
@@ -107,9 +126,12 @@ def bounds_arrays(table: FleetTable, bounds: Sequence[Bounds]) -> Tuple[np.ndarr
 
 
 def solve_bounded_table(table: FleetTable, model: ModelProfile, pos: List[int], w_min: Optional[np.ndarray],
-                        w_max: Optional[np.ndarray], kv_factor: float, device: int = 0) -> FleetSolve:
+                        w_max: Optional[np.ndarray], kv_factor: float, device: int = 0,
+                        route: str = "auto") -> FleetSolve:
     """One halda_solve_fleets_bounded_host call on a packed table: the bounded sweep's FleetSolve
-    (want_x="open")."""
+    (want_x="open"). `route`: "auto" follows the context's bounds path; "general" / "tables" set it for this
+    call alone (inside the context's lock) and put the previous one back."""
+    path = check_route(route)
     ctx = get_context(device)
     lib = _bind_bounds(ctx.lib)
     nf, nd, nk = table.n_fleets, table.n_devices, len(pos)
@@ -130,8 +152,15 @@ def solve_bounded_table(table: FleetTable, model: ModelProfile, pos: List[int], 
     karr = np.asarray(pos, np.int32)
     m = model_struct(model, kv_factor)
     with ctx._lock:
-        rc = lib.halda_solve_fleets_bounded_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
-                                                 ctypes.byref(bd), ctypes.byref(r))
+        prev = getattr(ctx, "_bounds_path", 0)
+        if path is not None:
+            _set_path(ctx, lib, path)
+        try:
+            rc = lib.halda_solve_fleets_bounded_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data,
+                                                     nk, ctypes.byref(bd), ctypes.byref(r))
+        finally:
+            if path is not None:
+                _set_path(ctx, lib, prev)
     del keep
     if rc != 0:
         raise RuntimeError(f"halda_solve_fleets_bounded_host failed ({rc}): {last_error(lib)}")
@@ -140,9 +169,13 @@ def solve_bounded_table(table: FleetTable, model: ModelProfile, pos: List[int], 
 
 def halda_solve_bounded_batch(fleets: Sequence[Sequence[DeviceProfile]], model: ModelProfile,
                               bounds: Sequence[Bounds], k_candidates: Optional[Iterable[int]] = None,
-                              kv_bits: str = "8bit", device: int = 0) -> List[Optional[HALDAResult]]:
+                              kv_bits: str = "8bit", device: int = 0,
+                              route: str = "auto") -> List[Optional[HALDAResult]]:
     """Many fleets, each within its own bounds (`bounds[f]` = (w_min, w_max), either None, or None for no
-    bounds), in ONE GPU call. One HALDAResult per fleet, None where no k is feasible within the bounds."""
+    bounds), in ONE GPU call. One HALDAResult per fleet, None where no k is feasible within the bounds.
+    `route`: "auto" (the context's bounds path), "general", or "tables" -- one table launch for small fleets
+    and k > 1 where the fused launch does not apply (at most 64 devices per fleet; general elsewhere)."""
+    check_route(route)
     kv_factor = kv_bits_to_factor(kv_bits)
     fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
     if len(bounds) != len(fleets):
@@ -162,18 +195,19 @@ def halda_solve_bounded_batch(fleets: Sequence[Sequence[DeviceProfile]], model: 
     if not pos:
         return [None] * len(fleets)
     lo, hi = bounds_arrays(table, bounds)
-    res = solve_bounded_table(table, model, pos, lo, hi, kv_factor, device)
+    res = solve_bounded_table(table, model, pos, lo, hi, kv_factor, device, route)
     return _batch_results(table, res, pos, model)
 
 
 def halda_solve_bounded(devs: Sequence[DeviceProfile], model: ModelProfile, w_min: Optional[Sequence[int]] = None,
                         w_max: Optional[Sequence[int]] = None, k_candidates: Optional[Iterable[int]] = None,
-                        kv_bits: str = "8bit", device: int = 0) -> HALDAResult:
+                        kv_bits: str = "8bit", device: int = 0, route: str = "auto") -> HALDAResult:
     """halda_solve with every device's layer count kept in [w_min_i, w_max_i]; RuntimeError, as halda_solve
-    raises it, when no k is feasible within the bounds."""
+    raises it, when no k is feasible within the bounds. `route`: as halda_solve_bounded_batch."""
+    check_route(route)
     devs = list(devs)
     b = None if w_min is None and w_max is None else (w_min, w_max)
-    r = halda_solve_bounded_batch([devs], model, [b], k_candidates, kv_bits, device)[0]
+    r = halda_solve_bounded_batch([devs], model, [b], k_candidates, kv_bits, device, route)[0]
     if r is None:
         raise RuntimeError("No feasible MILP found for any k this round.")
     return r
@@ -199,10 +233,13 @@ class ReplacementWithin:
 
 def halda_replace_within_batch(fleets: Sequence[Sequence[DeviceProfile]], model: ModelProfile,
                                incumbents: Sequence[Incumbent], max_move: Union[int, Sequence[int]],
-                               kv_bits: str = "8bit", rel_tol: float = 0.0, device: int = 0
-                               ) -> List[ReplacementWithin]:
+                               kv_bits: str = "8bit", rel_tol: float = 0.0, device: int = 0,
+                               route: str = "auto") -> List[ReplacementWithin]:
     """Per fleet: halda_replace_or_keep (the incumbent priced, the free optimum), then the best plan inside
-    the move box around the incumbent at the incumbent's k -- one bounded call per distinct incumbent k."""
+    the move box around the incumbent at the incumbent's k -- one bounded call per distinct incumbent k.
+    `route`: the bounded calls' route, as halda_solve_bounded_batch ("tables" is the one for an incumbent at
+    k > 1 or a small fleet)."""
+    check_route(route)
     fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
     base = halda_replace_or_keep_batch(fleets, model, incumbents, rel_tol, kv_bits, None, device)
     plans = [_as_plan(p) for p in incumbents]
@@ -213,7 +250,7 @@ def halda_replace_within_batch(fleets: Sequence[Sequence[DeviceProfile]], model:
             by_k.setdefault(int(p[0]), []).append(f)
     for k, fs in sorted(by_k.items()):
         boxes = [move_bounds(plans[f][1], max_move) for f in fs]
-        got = halda_solve_bounded_batch([fleets[f] for f in fs], model, boxes, [k], kv_bits, device)
+        got = halda_solve_bounded_batch([fleets[f] for f in fs], model, boxes, [k], kv_bits, device, route)
         for f, r in zip(fs, got):
             within[f] = r
     out = []
@@ -230,6 +267,8 @@ def halda_replace_within_batch(fleets: Sequence[Sequence[DeviceProfile]], model:
 
 def halda_replace_within(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent,
                          max_move: Union[int, Sequence[int]], kv_bits: str = "8bit", rel_tol: float = 0.0,
-                         device: int = 0) -> ReplacementWithin:
+                         device: int = 0, route: str = "auto") -> ReplacementWithin:
     """halda_replace_within_batch for one fleet."""
-    return halda_replace_within_batch([list(devs)], model, [incumbent], max_move, kv_bits, rel_tol, device)[0]
+    check_route(route)
+    return halda_replace_within_batch([list(devs)], model, [incumbent], max_move, kv_bits, rel_tol, device,
+                                      route)[0]

@@ -491,7 +491,11 @@ typedef struct halda_bounds {
  * (halda_lower_kernel), halda_bound_cols_kernel overwrites the w columns' bounds, and the CSR pipeline
  * solves it. Fused route: where the sweep is the register launch alone over fleets of one size <= 64
  * (the sub-fleet, variants and plans kernels' gate: no k > 1 has L / k >= M, and L - M + 1 <= 64 at
- * k = 1), ONE launch of halda_sweep_bounds_kernel, one wave per fleet. */
+ * k = 1), ONE launch of halda_sweep_bounds_kernel, one wave per fleet. Table route (path 3 only, where
+ * the fused route does not apply): any mix of fleets of 1 .. 64 devices, at most 64 k, whose unbounded
+ * table slice fits the LDS budget -- small fleets, k > 1 with room -- in ONE launch of
+ * halda_sweep_bounds_tables_kernel, one wave per fleet on that slice; nothing is handed back and no
+ * context scratch is used. Bounds that never bind give the table sweep's bits there. */
 int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
                                int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out, void *stream);
 
@@ -500,11 +504,12 @@ int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const h
                                     int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out);
 
 /* Which route the context's last halda_solve_fleets_bounded / _host call took: 1 fused (one launch),
- * 2 general (lowering, bounds, CSR pipeline), 0 when none ran yet. */
+ * 2 general (lowering, bounds, CSR pipeline), 3 the table route (one launch), 0 when none ran yet. */
 int halda_last_bounds_route(void *ctx, int *route);
 
 /* How halda_solve_fleets_bounded runs: 0 automatic, 1 always general, 2 the fused route where it
- * applies (general elsewhere). HALDA_E_ARG for any other path. */
+ * applies (general elsewhere), 3 the fused route where it applies, else the table route where it
+ * applies (path 3; general elsewhere). HALDA_E_ARG for any other path. */
 int halda_set_bounds_path(void *ctx, int path);
 
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
