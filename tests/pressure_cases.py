@@ -13,6 +13,7 @@ convexity. Its answers are computed once per session (lru_cache) and must not be
 
 M = 33 uses scale 1/32 (the issue's first choice; it clears the floors of test_pressure_cases_are_pressured)."""
 
+import sys
 from fractions import Fraction
 from functools import lru_cache
 
@@ -164,16 +165,18 @@ def close(a, b, rel=REL_OBJ):
     return abs(a - b) <= rel * max(1.0, abs(b))
 
 
-def check_x(x, case, k, what=""):
+def check_x(x, case, k, what="", cases=None):
     """Assert a solver's x of (case, k) is the oracle's optimum: c.x within 1e-9 relative and, where the
-    optimum is unique, the w, n, s1, s2, s3 and t columns equal to the oracle's."""
-    st, xo, b1, _ = exact(case, k)
+    optimum is unique, the w, n, s1, s2, s3 and t columns equal to the oracle's. `cases`: the case module whose
+    exact / problem / unique look the case up (this one; tests/irregular_cases.py passes itself)."""
+    cs = cases or sys.modules[__name__]
+    st, xo, b1, _ = cs.exact(case, k)
     assert st == 0, (what, case, k)
     M = case[0]
-    p = problem(case, k)
+    p = cs.problem(case, k)
     x = np.asarray(x[:7 * M + 1], np.float64)
     assert close(float(np.dot(p["c"], x)), b1), (what, case, k, float(np.dot(p["c"], x)), b1)
-    if unique(case, k):
+    if cs.unique(case, k):
         assert np.array_equal(x[:2 * M], xo[:2 * M]), (what, case, k, "w / n", x[:2 * M], xo[:2 * M])
         assert np.array_equal(x[2 * M:6 * M], np.rint(xo[2 * M:6 * M])), (
             what, case, k, "slack / t", x[2 * M:6 * M], xo[2 * M:6 * M])
@@ -207,7 +210,11 @@ def golden_mismatch(rec, solver):
     """oracle.milp_oracle's k-sweep by `solver` ("exact" / "highs") on a recorded fleet against the record:
     None when they agree (status per k, a losing k's objective within 1.5e-6, the result by the standing
     rule), else what differs."""
-    devs, model = golden_devices(rec), our_model()
+    return sweep_mismatch(golden_devices(rec), our_model(), rec, solver)
+
+
+def sweep_mismatch(devs, model, rec, solver):
+    """golden_mismatch on any fleet and model (kv 4bit, mip_gap 1e-4)."""
     best, exact_k = mo.halda_solve_oracle(devs, model, mip_gap=1e-4, kv_bits="4bit", solver="exact")
     per_k = exact_k
     if solver != "exact":
@@ -258,9 +265,10 @@ def neighbour_plans():
     return out
 
 
-def price_fixed(case, k, w, n):
-    """(success, obj_value or None) of HiGHS on (case, k) with the w and n columns fixed to the plan."""
-    p = dict(problem(case, k))
+def price_fixed(case, k, w, n, prob=None):
+    """(success, obj_value or None) of HiGHS on (case, k) with the w and n columns fixed to the plan. `prob`: the
+    dense problem, when the case is another module's."""
+    p = dict(problem(case, k) if prob is None else prob)
     M = p["M"]
     v = np.asarray(list(w) + list(n), float)
     lb, ub = p["lb"].copy(), p["ub"].copy()
