@@ -7,7 +7,7 @@ from distilp_amd.solver import halda_context_sweep, halda_solve_variants, model_
 from distilp_amd.solver import (PlanEvaluation, Replacement, evaluate_plan_np, halda_evaluate_plan,  # noqa: F401
                                 halda_evaluate_plans_batch, halda_replace_or_keep, halda_replace_or_keep_batch)
 from distilp_amd.solver import (ReplacementWithin, halda_replace_within, halda_replace_within_batch,  # noqa: F401
-                                halda_solve_bounded, halda_solve_bounded_batch, move_bounds)
+                                halda_solve_bounded, halda_solve_bounded_batch, move_bounds, move_box)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

@@ -18,7 +18,10 @@ the best k and objective of the fleet without it. --kv-sweep / --n-kv-sweep prin
 regret / moved layers against the solution above; a file that does not name exactly the current devices is an
 error (exit status 2). --max-move D (with --evaluate-solution) adds one line after those: the best plan at that
 plan's k at most D layers per device away from it, `within D: k=..., obj=..., moved_layers=...`, or
-`within D: infeasible`.
+`within D: infeasible`. --max-move-n Dn (with --max-move) also keeps every device's GPU share at most Dn layers
+away from that plan's: the line becomes `within D (n within Dn): k=..., obj=..., moved_layers=...,
+moved_gpu_layers=...`. --cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
+halda_solve_bounded) and prints the usual output for that solve. Without these flags the output is unchanged.
 """
 
 from __future__ import annotations
@@ -119,17 +122,44 @@ def incumbent_lines(devices: List[DeviceProfile], model: ModelProfile, plan, res
     return [first, f"regret={rep.regret:.6f}, moved_layers={rep.moved_layers}"]
 
 
-def within_line(devices: List[DeviceProfile], model: ModelProfile, plan, max_move: int) -> str:
+def within_line(devices: List[DeviceProfile], model: ModelProfile, plan, max_move: int,
+                max_move_n: Optional[int] = None) -> str:
     """--max-move D: the best plan at the incumbent's k at most D layers per device away from it
-    (halda_solve_bounded inside move_bounds' box), or "infeasible" when the box holds no plan."""
-    from ..solver.bounds import halda_solve_bounded_batch, move_bounds
+    (halda_solve_bounded inside move_bounds' box), or "infeasible" when the box holds no plan. With
+    --max-move-n Dn the box also keeps every n_i within Dn of the incumbent's (move_box)."""
+    from ..solver.bounds import halda_solve_bounded_batch, move_bounds, move_box
 
-    k, w, _ = plan
-    r = halda_solve_bounded_batch([devices], model, [move_bounds(w, max_move)], [k], kv_bits="4bit")[0]
+    k, w, n = plan
+    if max_move_n is None:
+        head = f"within {max_move}"
+        r = halda_solve_bounded_batch([devices], model, [move_bounds(w, max_move)], [k], kv_bits="4bit")[0]
+    else:
+        head = f"within {max_move} (n within {max_move_n})"
+        r = halda_solve_bounded_batch([devices], model, [move_box(w, n, max_move, max_move_n)], [k],
+                                      kv_bits="4bit")[0]
     if r is None:
-        return f"within {max_move}: infeasible"
+        return f"{head}: infeasible"
     moved = sum(abs(int(a) - int(b)) for a, b in zip(r.w, w))
-    return f"within {max_move}: k={r.k}, obj={r.obj_value:.6f}, moved_layers={moved}"
+    line = f"{head}: k={r.k}, obj={r.obj_value:.6f}, moved_layers={moved}"
+    if max_move_n is not None:
+        line += f", moved_gpu_layers={sum(abs(int(a) - int(b)) for a, b in zip(r.n, n))}"
+    return line
+
+
+def cpu_only_n_max(devices: List[DeviceProfile], picks: Sequence[str]) -> List[int]:
+    """--cpu-only NAME_OR_INDEX ...: the n_max list with 0 on the picked devices (a device's name, else its
+    0-based index in the fleet's order) and "no bound" elsewhere. ValueError for a pick that names no device."""
+    names = [d.name for d in devices]
+    n_max = [2**31 - 1] * len(devices)
+    for p in picks:
+        if p in names:
+            i = names.index(p)
+        elif p.lstrip("-").isdigit() and 0 <= int(p) < len(devices):
+            i = int(p)
+        else:
+            raise ValueError(f"{p!r} is neither a device name nor an index below {len(devices)}")
+        n_max[i] = 0
+    return n_max
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -162,6 +192,10 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--max-move", type=int, metavar="D",
                    help="With --evaluate-solution: also print the best plan at that plan's k that moves at most D "
                         "layers per device away from it")
+    o.add_argument("--max-move-n", type=int, metavar="D",
+                   help="With --max-move: also keep every device's GPU layers within D of that plan's")
+    g.add_argument("--cpu-only", nargs="+", metavar="NAME_OR_INDEX",
+                   help="Solve without using the GPU of these devices (their name or 0-based index)")
     return p
 
 
@@ -186,6 +220,17 @@ def main(argv=None) -> int:
         parser.error("--max-move requires --evaluate-solution")
     if args.max_move is not None and args.max_move < 0:
         parser.error("--max-move must be >= 0")
+    if args.max_move_n is not None and args.max_move is None:
+        parser.error("--max-move-n requires --max-move")
+    if args.max_move_n is not None and args.max_move_n < 0:
+        parser.error("--max-move-n must be >= 0")
+    n_max = None
+    if args.cpu_only:
+        try:
+            n_max = cpu_only_n_max(devices, args.cpu_only)
+        except ValueError as e:
+            print(f"error: --cpu-only: {e}", file=sys.stderr)
+            return 2
     incumbent = None
     if args.evaluate_solution:
         try:
@@ -205,7 +250,12 @@ def main(argv=None) -> int:
 
     if not args.quiet:
         print(f"\n{bar}\nRunning HALDA solver...\n{bar}")
-    result = halda_solve(devices, model, mip_gap=args.mip_gap, plot=not args.no_plot, kv_bits="4bit")
+    if n_max is None:
+        result = halda_solve(devices, model, mip_gap=args.mip_gap, plot=not args.no_plot, kv_bits="4bit")
+    else:
+        from ..solver.bounds import halda_solve_bounded
+
+        result = halda_solve_bounded(devices, model, n_max=n_max, kv_bits="4bit")
 
     if args.quiet:
         print(f"k={result.k}, obj={result.obj_value:.6f}")
@@ -235,7 +285,10 @@ def main(argv=None) -> int:
         for line in incumbent_lines(devices, model, incumbent, result):
             print(line)
         if args.max_move is not None:
-            print(within_line(devices, model, incumbent, args.max_move))
+            if args.max_move_n is None:
+                print(within_line(devices, model, incumbent, args.max_move))
+            else:
+                print(within_line(devices, model, incumbent, args.max_move, args.max_move_n))
     return 0
 
 

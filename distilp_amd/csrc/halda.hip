@@ -27,6 +27,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1407,7 +1408,7 @@ int replan(FleetsPlan *P) {
 extern "C" {
 
 static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, const int32_t *ks, int32_t n_k,
-                      halda_fleet_result *out, hipStream_t s, const halda_bounds *bounds);
+                      halda_fleet_result *out, hipStream_t s, const halda_box *bounds);
 
 int halda_solve_fleets(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
                        int32_t n_k, halda_fleet_result *out, void *stream) {
@@ -1429,10 +1430,11 @@ int halda_solve_fleets(void *ctx, const halda_model *model, const halda_fleets *
 }
 
 // The CSR pipeline of halda_solve_fleets (the arguments checked, the device set): the batch lowered on the
-// GPU, then screened, solved and picked. bounds != nullptr (halda_solve_fleets_bounded's general route):
-// the w columns' bounds of the lowered batch are overwritten before the solve.
+// GPU, then screened, solved and picked. bounds != nullptr (halda_solve_fleets_bounded's / _boxed's general
+// route): the w columns' bounds of the lowered batch (with n bounds: the n columns' too) are overwritten
+// before the solve.
 static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, const int32_t *ks, int32_t n_k,
-                      halda_fleet_result *out, hipStream_t s, const halda_bounds *bounds) {
+                      halda_fleet_result *out, hipStream_t s, const halda_box *bounds) {
     const int32_t *kh = ks;
     {
         const int rc = order_after_previous(c, s);  // fleet_scratch / last_lowered are per context
@@ -1487,7 +1489,13 @@ static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, c
     hipLaunchKernelGGL(halda_lower_kernel, dim3(unsigned(F.n_fleets)), dim3(64), 0, s, *model, F, ks_dev, int(n_k), D,
                        O);
     HIP_TRY(hipGetLastError());
-    if (bounds && (bounds->w_min || bounds->w_max)) {
+    if (bounds && (bounds->n_min || bounds->n_max)) {
+        // same stream, behind the lowering: one wave per instance rewrites its M w and M n bounds
+        const BoxArgs Bx{bounds->w_min, bounds->w_max, bounds->n_min, bounds->n_max};
+        hipLaunchKernelGGL(halda_box_cols_kernel, dim3(unsigned((n_inst + 3) / 4)), dim3(256), 0, s, F, Bx, ks_dev,
+                           int(n_k), int(model->L), int64_t(D.cols), O.col_lb, O.col_ub);
+        HIP_TRY(hipGetLastError());
+    } else if (bounds && (bounds->w_min || bounds->w_max)) {
         // same stream, behind the lowering: one wave per instance rewrites its M w bounds
         const BoundArgs Bd{bounds->w_min, bounds->w_max};
         hipLaunchKernelGGL(halda_bound_cols_kernel, dim3(unsigned((n_inst + 3) / 4)), dim3(256), 0, s, F, Bd, ks_dev,
@@ -1495,7 +1503,8 @@ static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, c
         HIP_TRY(hipGetLastError());
     }
     // the lowered batch and its shape summary (R = W - M with lb(w) = 1 on every device: bounds only
-    // raise sum lb, so the slices sized here hold every bounded instance too)
+    // raise sum lb -- an n lower bound folded into lb(w) too -- so the slices sized here hold every bounded
+    // instance too)
     halda_batch b = {};
     b.n_inst = int32_t(n_inst);
     b.max_cols = int32_t(D.cols);
@@ -2833,11 +2842,14 @@ int halda_last_bounds_route(void *ctx, int *route) {
     return HALDA_OK;
 }
 
-int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
-                               int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out, void *stream) {
+// halda_solve_fleets_bounded and halda_solve_fleets_boxed: one body on a halda_box (w bounds alone: its n
+// arrays NULL). Without n bounds every launch is the bounded call's own kernel; with them the box kernels
+// under the same gates.
+static int solve_boxed(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks, int32_t n_k,
+                       const halda_box &B, halda_fleet_result *out, void *stream, const char *who) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c || !model || !fleets || !ks || !out)
-        return fail(HALDA_E_ARG, "halda_solve_fleets_bounded: NULL ctx/model/fleets/ks/out");
+        return fail(HALDA_E_ARG, std::string(who) + ": NULL ctx/model/fleets/ks/out");
     const halda_fleets &F = *fleets;
     if (F.n_fleets <= 0) return HALDA_OK;
     {
@@ -2847,8 +2859,7 @@ int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_
     int cur_dev = -1;
     if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    const halda_bounds none = {nullptr, nullptr};
-    const halda_bounds &B = bounds ? *bounds : none;
+    const bool nbox = B.n_min || B.n_max;
     // automatic = fused where admissible: one launch against the general route's lowering, patch, screen,
     // solve and pick launches
     if (c->bounds_path != 1 && c->fleets_fused && n_k <= 64) {
@@ -2864,8 +2875,10 @@ int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_
             c->fleet_timed = false;
             c->have_lowered = false;
             const BoundArgs Bd{B.w_min, B.w_max};
+            const BoxArgs Bx{B.w_min, B.w_max, B.n_min, B.n_max};
             if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            hipLaunchKernelGGL(halda_sweep_bounds_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, Bd);
+            if (nbox) hipLaunchKernelGGL(halda_sweep_box_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, Bx);
+            else hipLaunchKernelGGL(halda_sweep_bounds_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, Bd);
             HIP_TRY(hipGetLastError());
             if (c->timing) {
                 HIP_TRY(hipEventRecord(c->evf1, s));
@@ -2887,14 +2900,19 @@ int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_
             A.want = 0;
             c->fleet_timed = false;
             c->have_lowered = false;
-            const void *fn = reinterpret_cast<const void *>(halda_sweep_bounds_tables_kernel);
+            const void *fn = nbox ? reinterpret_cast<const void *>(halda_sweep_box_tables_kernel)
+                                  : reinterpret_cast<const void *>(halda_sweep_bounds_tables_kernel);
             int per_cu = 0;
             HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
             const unsigned grid =
                 unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(p.nf))));
             const BoundArgs Bd{B.w_min, B.w_max};
+            const BoxArgs Bx{B.w_min, B.w_max, B.n_min, B.n_max};
             if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            hipLaunchKernelGGL(halda_sweep_bounds_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bd);
+            if (nbox)
+                hipLaunchKernelGGL(halda_sweep_box_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bx);
+            else
+                hipLaunchKernelGGL(halda_sweep_bounds_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bd);
             HIP_TRY(hipGetLastError());
             if (c->timing) {
                 HIP_TRY(hipEventRecord(c->evf1, s));
@@ -2913,13 +2931,25 @@ int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_
     return fleets_csr(c, model, F, ks, n_k, out, s, &B);
 }
 
+int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                               int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out, void *stream) {
+    const halda_box B = {bounds ? bounds->w_min : nullptr, bounds ? bounds->w_max : nullptr, nullptr, nullptr};
+    return solve_boxed(ctx, model, fleets, ks, n_k, B, out, stream, "halda_solve_fleets_bounded");
+}
+
+int halda_solve_fleets_boxed(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                             int32_t n_k, const halda_box *box, halda_fleet_result *out, void *stream) {
+    const halda_box none = {nullptr, nullptr, nullptr, nullptr};
+    return solve_boxed(ctx, model, fleets, ks, n_k, box ? *box : none, out, stream, "halda_solve_fleets_boxed");
+}
+
 // The host variant: the table, the bounds (and x_off) cross PCIe once on the way in, the results on the way
 // out, through the context's staging scratch.
-int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks,
-                                    int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out_h) {
+static int solve_boxed_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks,
+                            int32_t n_k, const halda_box &B, halda_fleet_result *out_h, const char *who) {
     Ctx *c = static_cast<Ctx *>(ctx);
     if (!c || !model || !fh || !ks || !out_h)
-        return fail(HALDA_E_ARG, "halda_solve_fleets_bounded_host: NULL ctx/model/fleets/ks/out");
+        return fail(HALDA_E_ARG, std::string(who) + "_host: NULL ctx/model/fleets/ks/out");
     const int64_t nf = fh->n_fleets;
     if (nf <= 0) return HALDA_OK;
     {
@@ -2933,11 +2963,12 @@ int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const h
                              fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int32_t *bmin = bounds ? bounds->w_min : nullptr, *bmax = bounds ? bounds->w_max : nullptr;
+    const int32_t *bsrc[4] = {B.w_min, B.w_max, B.n_min, B.n_max};
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
     const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16);
-    const size_t o_bmin = take(4 * nd), o_bmax = take(4 * nd);
+    size_t o_b[4];
+    for (int a = 0; a < 4; ++a) o_b[a] = bsrc[a] ? take(4 * nd) : 0;
     const size_t n_inst = size_t(nf) * n_k;
     const bool xsel = out_h->x_off && (out_h->x || out_h->c);
     const size_t o_xoff = xsel ? take(8 * n_inst) : 0;
@@ -2971,8 +3002,8 @@ int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const h
     HIP_TRY(up(o_cls, fh->os_class, nd));
     HIP_TRY(up(o_fl, fh->flags, nd));
     for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
-    if (bmin) HIP_TRY(up(o_bmin, bmin, 4 * nd));
-    if (bmax) HIP_TRY(up(o_bmax, bmax, 4 * nd));
+    for (int a = 0; a < 4; ++a)
+        if (bsrc[a]) HIP_TRY(up(o_b[a], bsrc[a], 4 * nd));
     if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * n_inst));
     auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
     halda_fleets d = *fh;
@@ -2983,9 +3014,8 @@ int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const h
     d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
     d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
     d.d_avail_metal = F64(14); d.swap = F64(15);
-    halda_bounds db;
-    db.w_min = bmin ? reinterpret_cast<const int32_t *>(base + o_bmin) : nullptr;
-    db.w_max = bmax ? reinterpret_cast<const int32_t *>(base + o_bmax) : nullptr;
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    const halda_box db = {bdev(0), bdev(1), bdev(2), bdev(3)};
     halda_fleet_result r;
     r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
     r.obj_value = reinterpret_cast<double *>(base + o_obj);
@@ -2997,7 +3027,7 @@ int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const h
     r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
     r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
     {
-        const int rc = halda_solve_fleets_bounded(ctx, model, &d, ks, n_k, &db, &r, s);
+        const int rc = solve_boxed(ctx, model, &d, ks, n_k, db, &r, s, who);
         if (rc != HALDA_OK) return rc;
     }
     auto dn = [&](void *dst, size_t o, size_t bytes) {
@@ -3013,6 +3043,18 @@ int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const h
     HIP_TRY(dn(out_h->c, o_c, 8 * xs));
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
+}
+
+int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks,
+                                    int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out_h) {
+    const halda_box B = {bounds ? bounds->w_min : nullptr, bounds ? bounds->w_max : nullptr, nullptr, nullptr};
+    return solve_boxed_host(ctx, model, fh, ks, n_k, B, out_h, "halda_solve_fleets_bounded");
+}
+
+int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks,
+                                  int32_t n_k, const halda_box *box, halda_fleet_result *out_h) {
+    const halda_box none = {nullptr, nullptr, nullptr, nullptr};
+    return solve_boxed_host(ctx, model, fh, ks, n_k, box ? *box : none, out_h, "halda_solve_fleets_boxed");
 }
 
 // ---------------------------------------------------------------- several GPUs, one process

@@ -1909,8 +1909,9 @@ __device__ inline void rec_slacks(const FieldRec &r, int w, int n, int s[4]) {
 // order. Every candidate is evaluated on every lane (no divergent branches); an absent kink re-tries
 // nL, which never changes (best, bn): after nL's own try either bn = nL or best < cost(nL), and no
 // candidate lies below nL.
-template <bool kUniform>
-__device__ inline bool split_full_impl(const FieldRec &r, int w, double &g, int &n, int s[4]) {
+// R: the record type whose rec_interval gives [nL, nU] (FieldRec; the k-sweep's box record narrows it)
+template <bool kUniform, class R = FieldRec>
+__device__ inline bool split_full_impl(const R &r, int w, double &g, int &n, int s[4]) {
     int nL, nU;
     const bool okI = rec_interval(r, w, nL, nU);
     const double pv = rec_pv(r), aw = r.alpha * double(w);
@@ -1931,12 +1932,13 @@ __device__ inline bool split_full_impl(const FieldRec &r, int w, double &g, int 
     return ok;
 }
 __device__ inline bool split_full(const FieldRec &r, int w, double &g, int &n, int s[4]) {
-    return split_full_impl<false>(r, w, g, n, s);
+    return split_full_impl<false, FieldRec>(r, w, g, n, s);
 }
 // split_full at w = 1 (the record's lower bound): 0 <= nL <= n <= nU <= w = 1, so every kink clamps
 // to nL or nU and re-trying either is a no-op (after nU's try best <= cost(nU), and on a tie bn <= nU):
 // the two end tries give split_full's result.
-__device__ inline bool split_first(const FieldRec &r, int w, double &g, int &n, int s[4]) {
+template <class R>
+__device__ inline bool split_first_impl(const R &r, int w, double &g, int &n, int s[4]) {
     if (w != 1) return split_full(r, w, g, n, s);
     int nL, nU;
     const bool okI = rec_interval(r, w, nL, nU);
@@ -1954,11 +1956,15 @@ __device__ inline bool split_first(const FieldRec &r, int w, double &g, int &n, 
     }
     return ok;
 }
+__device__ inline bool split_first(const FieldRec &r, int w, double &g, int &n, int s[4]) {
+    return split_first_impl(r, w, g, n, s);
+}
 // split_full at w = 2 (the greedy's first increment): 0 <= nL <= n <= nU <= 2, so the three tries
 // n = 0, 1, 2 (clamped to [nL, nU]) cover every candidate split_full tries (its kinks clamp into the
 // same range) with the same cost expression and tie rule: the same minimum and least minimiser, one
 // try fewer than split_full's four.
-__device__ inline bool split_second(const FieldRec &r, int w, double &g, int &n, int s[4]) {
+template <class R>
+__device__ inline bool split_second_impl(const R &r, int w, double &g, int &n, int s[4]) {
     if (w != 2) return split_full(r, w, g, n, s);
     int nL, nU;
     const bool okI = rec_interval(r, w, nL, nU);
@@ -1977,11 +1983,15 @@ __device__ inline bool split_second(const FieldRec &r, int w, double &g, int &n,
     }
     return ok;
 }
+__device__ inline bool split_second(const FieldRec &r, int w, double &g, int &n, int s[4]) {
+    return split_second_impl(r, w, g, n, s);
+}
 __device__ inline bool split_full(const UFieldRec &r, int w, double &g, int &n, int s[4]) {
-    return split_full_impl<true>(r, w, g, n, s);
+    return split_full_impl<true, FieldRec>(r, w, g, n, s);
 }
 
-__device__ inline bool split_step(const FieldRec &r, int w, int n_prev, double &g, int &n, int s[4]) {
+template <class R>
+__device__ inline bool split_step_impl(const R &r, int w, int n_prev, double &g, int &n, int s[4]) {
     int nL, nU;
     const bool okI = rec_interval(r, w, nL, nU);
     const double pv = rec_pv(r), aw = r.alpha * double(w);
@@ -1997,6 +2007,9 @@ __device__ inline bool split_step(const FieldRec &r, int w, int n_prev, double &
         rec_slacks(r, w, bn, s);
     }
     return ok;
+}
+__device__ inline bool split_step(const FieldRec &r, int w, int n_prev, double &g, int &n, int s[4]) {
+    return split_step_impl(r, w, n_prev, g, n, s);
 }
 
 // dev_cycle on dev(): rows (alpha, alpha + p_bp) w + b n + slack terms <= -cst.

@@ -1575,6 +1575,9 @@ __global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIM
 struct BoundArgs {
     const int32_t *w_min, *w_max;  // halda_bounds: [dev_off[n_fleets]] device layout
 };
+struct BoxArgs {
+    const int32_t *w_min, *w_max, *n_min, *n_max;  // halda_box: the same layout
+};
 
 // Capped bound sums: every open W is < 1e6 < kBoundCap, so sum min(b_i, kBoundCap) compares with W as the
 // uncapped sum does, and 4096 capped terms of a lane's share / 64 lane sums stay inside an int.
@@ -1600,6 +1603,35 @@ __global__ __launch_bounds__(256) void halda_bound_cols_kernel(halda_fleets F, B
         const int hi = Bd.w_max ? Bd.w_max[d0 + i] : 0x7fffffff;
         col_lb[co + i] = lo > W ? double(W) + 1.0 : double(lo);
         col_ub[co + i] = double(min(W, hi));
+    }
+}
+
+// The same patch for a boxed call (halda_solve_fleets_boxed with n bounds; launched INSTEAD of
+// halda_bound_cols_kernel): the w columns get the folded lo = max(1, w_min, nlo) (an implied bound through
+// the link row n <= w, so the screen's sum of lower bounds is the fused routes' sum lo), the n columns
+// nlo = max(0, n_min) and min(the lowering's own upper bound, n_max). A crossing n pair is written as it
+// is: n_interval then finds no n at any w, every table entry of the device is +inf, the leaf is empty and
+// the instance INFEASIBLE.
+__global__ __launch_bounds__(256) void halda_box_cols_kernel(halda_fleets F, BoxArgs Bx, const int32_t *ks, int n_k, int L,
+                                                             int64_t cols, double *col_lb, double *col_ub) {
+    const int64_t inst = int64_t(blockIdx.x) * 4 + int(threadIdx.x >> 6);
+    if (inst >= int64_t(F.n_fleets) * n_k) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t f = inst / n_k;
+    const int j = int(inst - f * n_k);
+    const int64_t d0 = F.dev_off[f];
+    const int M = int(F.dev_off[f + 1] - d0);
+    const int W = L / ks[j];
+    const int64_t co = inst * cols;
+    for (int i = lane; i < M; i += 64) {
+        const int nlo = max(0, Bx.n_min ? Bx.n_min[d0 + i] : 0);
+        const int nmx = Bx.n_max ? Bx.n_max[d0 + i] : 0x7fffffff;
+        const int lo = max(max(1, Bx.w_min ? Bx.w_min[d0 + i] : 0), nlo);
+        const int hi = Bx.w_max ? Bx.w_max[d0 + i] : 0x7fffffff;
+        col_lb[co + i] = lo > W ? double(W) + 1.0 : double(lo);
+        col_ub[co + i] = double(min(W, hi));
+        col_lb[co + M + i] = double(nlo);
+        col_ub[co + M + i] = fmin(col_ub[co + M + i], double(nmx));
     }
 }
 
@@ -1630,21 +1662,99 @@ __device__ inline int rec_whi(const BoundRec &r) { return r.whi; }
 __device__ inline int rec_wlo(const UBoundRec &r) { return r.wlo; }
 __device__ inline int rec_whi(const UBoundRec &r) { return r.whi; }
 
+// halda_solve_fleets_boxed: the bounded record with a box on n beside [wlo, whi] -- n in [nlo, nhi],
+// nlo = max(0, n_min_i), nhi = n_max_i as given (rec_interval's own nU is already <= the reference's
+// nhi_i, so the minimum with it is taken there). The upper bound of the VRAM slack t stays the reference's
+// nhi_i = (gpu ? W : 0): the box narrows n, not t, so rec_interval's nhi_i - Kvram term is the FieldRec's.
+// A box record is a BoundRec, so rec_wlo / rec_whi, rec_try, rec_slacks and dev_cycle are the bounded
+// record's; only the n-interval, and with it the four splits, are its own.
+struct UBoxRec : UBoundRec {
+    int nlo, nhi;
+    __device__ inline const UBoxRec &core() const { return *this; }
+};
+
+struct BoxRec : BoundRec {
+    int nlo, nhi;
+    template <class SG>
+    __device__ inline UBoxRec bcast(const SG &sg, int src) const {
+        UBoxRec o;
+        static_cast<UBoundRec &>(o) = BoundRec::bcast(sg, src);
+        o.nlo = sg.bcast(nlo, src);
+        o.nhi = sg.bcast(nhi, src);
+        return o;
+    }
+    __device__ inline const BoxRec &core() const { return *this; }
+};
+
+// The FieldRec's interval clamped into [nlo, nhi] after everything it does: the intersection of two
+// intervals, empty (false) when either is or when they do not meet.
+template <class R>
+__device__ inline bool box_interval(const R &r, int w, int &nL, int &nU) {
+    const bool ok = rec_interval(static_cast<const FieldRec &>(r), w, nL, nU);
+    nL = max(nL, r.nlo);
+    nU = min(nU, r.nhi);
+    return ok & (nL <= nU);
+}
+__device__ inline bool rec_interval(const BoxRec &r, int w, int &nL, int &nU) { return box_interval(r, w, nL, nU); }
+__device__ inline bool rec_interval(const UBoxRec &r, int w, int &nL, int &nU) { return box_interval(r, w, nL, nU); }
+
+// The splits on a box record: the FieldRec's bodies (the same candidates, tie rule and term order) on the
+// clamped interval. The cost is convex piecewise linear in n, so its minimum over the narrower interval is
+// still at an end or at a kink clamped into it -- split_full's candidates -- and the intersection of an
+// L-natural-convex domain with a box is L-natural convex, so split_step's "n* moves by 0 or +1" holds.
+// The two shortcuts hold on the narrowed interval because it is a sub-interval of the one they were argued
+// for: at w = 1, 0 <= nL <= nU <= 1 still, so every kink clamps to an end and the two end tries are
+// split_full's; at w = 2, [nL, nU] is inside [0, 2] still, so the tries 0, 1, 2 clamped into it visit
+// every integer of it, split_full's candidates among them. (With wlo = max(1, w_min, nlo) > 1 the
+// shortcuts are not taken: both fall back to split_full, as on a BoundRec.)
+__device__ inline bool split_full(const BoxRec &r, int w, double &g, int &n, int s[4]) {
+    return split_full_impl<false, BoxRec>(r, w, g, n, s);
+}
+__device__ inline bool split_full(const UBoxRec &r, int w, double &g, int &n, int s[4]) {
+    return split_full_impl<true, UBoxRec>(r, w, g, n, s);
+}
+__device__ inline bool split_first(const BoxRec &r, int w, double &g, int &n, int s[4]) {
+    return split_first_impl(r, w, g, n, s);
+}
+__device__ inline bool split_second(const BoxRec &r, int w, double &g, int &n, int s[4]) {
+    return split_second_impl(r, w, g, n, s);
+}
+__device__ inline bool split_step(const BoxRec &r, int w, int n_prev, double &g, int &n, int s[4]) {
+    return split_step_impl(r, w, n_prev, g, n, s);
+}
+
+// The lane's folded bounds of a boxed call: nlo = max(0, n_min_i); the link row n_i <= w_i makes
+// lo_i = max(lo_i, nlo_i) an implied bound of the same MILP, used in sum lo, R and as the first table
+// entry. nhi'_i = min(nhi_i, n_max_i) with nhi_i = W on a GPU device, else 0: nlo_i > W already gives
+// sum lo > W (lo_i >= nlo_i, every lo >= 1), so the crossing test nlo_i > nhi'_i needs n_max and the GPU
+// flag alone and is one ballot, formed once for every k.
+__device__ inline bool box_fold(const Wave &sg, bool act, int gpu, int nmn, int nmx, int &lo, int &nlo) {
+    nlo = min(max(0, nmn), kBoundCap);
+    lo = max(lo, nlo);
+    return sg.any(act && nlo > min(gpu ? 0x7fffffff : 0, nmx));
+}
+
 // One fleet of M = A.uM <= kK1MaxM devices (lane = device) under its bounds, its fields (mf), the lane's
 // k_j / W_j and the lane's w_min / w_max already loaded. The host sends only batches the register sweep
 // takes alone (plan_sweep's kRegAlone): every k > 1 has W < M <= sum lo, so an open instance is k = 1 with
 // R = W - sum lo < kDpLanes, solved by k1_alloc and, for what the greedy does not take, k1_dp -- both
 // exact. The settled verdicts, the objective's order of additions and every store follow sweep_fleet, so
 // bounds that never bind give the sweep's bits.
+// Rec = BoxRec (halda_sweep_box_kernel): the lane's n_min / n_max too; lo is folded with nlo and the n
+// crossing joins the w crossing. A leaf may then start above lo (k1_alloc hands it to k1_dp, which takes
+// any leaf shape) or be empty (k1_dp's row is all +inf: K1_INFEASIBLE).
+template <class Rec = BoundRec>
 __device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveCtx &w, const Wave &sg,
-                                          const DevFields &mf, int64_t d0, int kj, int Wj, int wmn, int wmx) {
+                                          const DevFields &mf, int64_t d0, int kj, int Wj, int wmn, int wmx,
+                                          int nmn = 0, int nmx = 0x7fffffff) {
+    constexpr bool kBox = !std::is_same<Rec, BoundRec>::value;
     const FleetOut &O = A.out;
     const int lane = sg.sl;
     const bool kl = lane < A.n_k;
     const int M = A.uM;
     const int outs = A.outs;
     const bool act = lane < M;
-    BoundRec me = {};
+    Rec me = {};
     int bad = 0;
     static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
     bad = act ? bad : 0;
@@ -1655,10 +1765,15 @@ __device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveC
     // bound-infeasible. A lo_i > W already gives sum lo > W (every lo >= 1), so the crossing test needs
     // w_max alone; and where no bound crosses (every w_max_i >= lo_i >= 1) sum min(W, w_max_i) < W exactly
     // when sum w_max_i < W: all three tests are formed once, for every k of the call.
-    const int lo = min(max(1, wmn), kBoundCap);
+    int lo = min(max(1, wmn), kBoundCap);
+    bool ncross = false;
+    if constexpr (kBox) {
+        ncross = box_fold(sg, act, me.gpu, nmn, nmx, lo, me.nlo);
+        me.nhi = nmx;
+    }
     const int sumlo = sg.sum_i(act ? lo : 0);
     const int sumhi = sg.sum_i(act ? min(max(wmx, 0), kBoundCap) : 0);
-    const bool cross = sg.any(act && lo > wmx);
+    const bool cross = sg.any(act && lo > wmx) || ncross;
     double best = kInf;
     int best_k = 0;
     constexpr int kOpen = 1000;
@@ -1811,6 +1926,31 @@ __global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIM
     sweep_fleet_bounds(A, f, w, Wave(lane), mf, d0, kj, Wj, wmn, wmx);
 }
 
+// halda_sweep_box_kernel: halda_sweep_bounds_kernel with the n box -- the lane's n_min / n_max are two
+// more coalesced 4-byte loads, issued with the 18 field loads and the two w bounds.
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_box_kernel(
+    SweepArgs A, BoxArgs Bx) {
+    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    if (f >= A.F.n_fleets) return;
+    const int lane = int(threadIdx.x & 63);
+    const int M = A.uM;
+    const int64_t base = sload_i64(A.F.dev_off);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    const bool kl = lane < A.n_k;
+    const int kj = A.ks[kl ? lane : 0];
+    const int Wj = kl ? A.Ws[lane] : 0;
+    const int64_t d0 = base + int64_t(f) * M;
+    const int64_t g = d0 + (lane < M ? lane : 0);
+    const DevFields mf = load_fields(A.F, g);
+    const int wmn = Bx.w_min ? Bx.w_min[g] : 0;
+    const int wmx = Bx.w_max ? Bx.w_max[g] : 0x7fffffff;
+    const int nmn = Bx.n_min ? Bx.n_min[g] : 0;
+    const int nmx = Bx.n_max ? Bx.n_max[g] : 0x7fffffff;
+    sweep_fleet_bounds<BoxRec>(A, f, w, Wave(lane), mf, d0, kj, Wj, wmn, wmx, nmn, nmx);
+}
+
 // The table route of the bounded sweep (route 3): fleets of any sizes 1 .. kK1MaxM under their bounds, every
 // k, in one launch with the table kernel's LDS slice. What the register route leaves to the general route --
 // k > 1 with room, R + 1 > kDpLanes, small fleets of a long model -- is solved here by the table machinery
@@ -1830,6 +1970,17 @@ struct BoundSrc {
         r.whi = __shfl(me->whi, i);
     }
 };
+struct BoxSrc {  // the same for box records: nlo / nhi travel with wlo / whi
+    using Rec = BoxRec;
+    const BoxRec *me;
+    __device__ inline void load(BoxRec &r, const WaveCtx &w, int i) const {
+        BoundSrc{me}.load(r, w, i);
+        r.nlo = __shfl(me->nlo, i);
+        r.nhi = __shfl(me->nhi, i);
+    }
+};
+__device__ inline BoundSrc bound_src(const BoundRec *me) { return BoundSrc{me}; }
+__device__ inline BoxSrc bound_src(const BoxRec *me) { return BoxSrc{me}; }
 
 // One fleet of M <= kK1MaxM devices (lane = device) under its bounds. The settled verdicts are
 // sweep_fleet_bounds' (formed once for every k); an open k follows the table branch of
@@ -1837,8 +1988,14 @@ struct BoundSrc {
 // R = 0 where every w_i = lo_i is forced), else the tables and the DP, the objective in that branch's order
 // of additions. Bounds that never bind therefore give halda_sweep_tables_kernel's bits. A.k1dp (the test
 // path) sends every instance to the tables.
-__device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const BoundArgs &Bd, int f, const WaveCtx &w,
+// Rec = BoxRec, Args = BoxArgs (halda_sweep_box_tables_kernel): the n box as in sweep_fleet_bounds. A leaf
+// that starts above lo has +inf first table entries (leaf_ranges' lo > 0, the DP's usual case of a masked
+// entry) and an empty leaf an all +inf row (LeafInfo.empty: dp_pass finds nothing, INFEASIBLE); where
+// k1_alloc is tried first it hands either case back (K1_FALLBACK) to the tables.
+template <class Rec = BoundRec, class Args = BoundArgs>
+__device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Args &Bd, int f, const WaveCtx &w,
                                                  const Wave &sg) {
+    constexpr bool kBox = !std::is_same<Rec, BoundRec>::value;
     const FleetOut &O = A.out;
     const int lane = sg.sl;
     const bool kl = lane < A.n_k;
@@ -1853,7 +2010,12 @@ __device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Bound
     const DevFields mf = load_fields(A.F, g0);
     const int wmn = Bd.w_min ? Bd.w_min[g0] : 0;
     const int wmx = Bd.w_max ? Bd.w_max[g0] : 0x7fffffff;
-    BoundRec me = {};
+    int nmn = 0, nmx = 0x7fffffff;
+    if constexpr (kBox) {
+        nmn = Bd.n_min ? Bd.n_min[g0] : 0;
+        nmx = Bd.n_max ? Bd.n_max[g0] : 0x7fffffff;
+    }
+    Rec me = {};
     int bad = 0;
     static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
     bad = act ? bad : 0;
@@ -1861,10 +2023,15 @@ __device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Bound
     fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
     bad = sg.any(bad != 0) ? 1 : 0;
     // the three bound tests from the capped integer sums and the ballot, once for every k (sweep_fleet_bounds)
-    const int lo = min(max(1, wmn), kBoundCap);
+    int lo = min(max(1, wmn), kBoundCap);
+    bool ncross = false;
+    if constexpr (kBox) {
+        ncross = box_fold(sg, act, me.gpu, nmn, nmx, lo, me.nlo);
+        me.nhi = nmx;
+    }
     const int sumlo = sg.sum_i(act ? lo : 0);
     const int sumhi = sg.sum_i(act ? min(max(wmx, 0), kBoundCap) : 0);
-    const bool cross = sg.any(act && lo > wmx);
+    const bool cross = sg.any(act && lo > wmx) || ncross;
     double best = kInf;
     int best_k = 0;
     constexpr int kOpen = 1000;
@@ -1966,7 +2133,7 @@ __device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Bound
             const bool too_large = M > A.mmax || I.R1 > A.r1max || int64_t(M) * I.RS > (kc > 0.0 ? A.tab_kc : A.tab);
             int feas = 1;
             if (!too_large) {
-                table_pass<64>(BoundSrc{&me}, w, I, lane);
+                table_pass<64>(bound_src(&me), w, I, lane);
                 wave_sync();
                 feas = dp_pass(w, I, lane, nodes) ? 1 : 0;
             }
@@ -2059,6 +2226,31 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bo
     w.split = reinterpret_cast<uint16_t *>(smem + sl.split);
     const int nf = A.F.n_fleets;
     for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) sweep_fleet_bounds_tables(A, Bd, int(f), w, Wave(lane));
+}
+
+// halda_sweep_box_tables_kernel: halda_sweep_bounds_tables_kernel with the n box (the same slice: folding
+// nlo into lo only raises sum lo).
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_box_tables_kernel(SweepArgs A,
+                                                                                               BoxArgs Bx) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const Slice sl = make_slice(A.mmax, A.r1max, A.tab, A.tab_kc);
+    WaveCtx w = {};
+    w.rows = reinterpret_cast<int2 *>(smem + sl.rows);
+    w.cyc = reinterpret_cast<double *>(smem + sl.cyc);
+    w.cost = reinterpret_cast<double *>(smem + sl.cost);
+    w.cnt = reinterpret_cast<int *>(smem + sl.cnt);
+    w.st0 = reinterpret_cast<int *>(smem + sl.st0);
+    w.st1 = reinterpret_cast<int *>(smem + sl.st1);
+    w.rng = reinterpret_cast<int2 *>(smem + sl.rng);
+    w.inc = reinterpret_cast<double *>(smem + sl.inc);
+    w.G = reinterpret_cast<double *>(smem + sl.G);
+    w.H = reinterpret_cast<double *>(smem + sl.H);
+    w.work = reinterpret_cast<double *>(smem + sl.work);
+    w.split = reinterpret_cast<uint16_t *>(smem + sl.split);
+    const int nf = A.F.n_fleets;
+    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x)
+        sweep_fleet_bounds_tables<BoxRec, BoxArgs>(A, Bx, int(f), w, Wave(lane));
 }
 
 // ---------------------------------------------------------------- resident single-fleet solver

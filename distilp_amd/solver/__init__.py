@@ -1,7 +1,7 @@
 """Public solver API (reference: src/distilp/solver/__init__.py:5-13)."""
 
 from .bounds import (ReplacementWithin, halda_replace_within, halda_replace_within_batch,  # noqa: F401
-                     halda_solve_bounded, halda_solve_bounded_batch, move_bounds)
+                     halda_solve_bounded, halda_solve_bounded_batch, move_bounds, move_box)
 from .coefficients import HALDAResult, ILPResult
 from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
@@ -14,7 +14,7 @@ from .variants import halda_context_sweep, halda_solve_variants, model_grid  # n
 __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solve_subfleets", "halda_leave_one_out",
            "halda_leave_one_out_batch", "halda_select_devices", "halda_solve_variants", "halda_context_sweep",
            "model_grid", "halda_evaluate_plan", "halda_evaluate_plans_batch", "halda_replace_or_keep",
-           "halda_replace_or_keep_batch", "halda_solve_bounded", "halda_solve_bounded_batch", "move_bounds",
+           "halda_replace_or_keep_batch", "halda_solve_bounded", "halda_solve_bounded_batch", "move_bounds", "move_box",
            "halda_replace_within", "halda_replace_within_batch", "ReplacementWithin", "evaluate_plan_np",
            "PlanEvaluation", "Replacement", "HALDAResult",
            "ILPResult"]

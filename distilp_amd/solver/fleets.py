@@ -106,6 +106,11 @@ class HaldaBoundsC(ctypes.Structure):
     _fields_ = [("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p)]
 
 
+class HaldaBoxC(ctypes.Structure):  # halda_box: halda_bounds and the n columns' two arrays
+    _fields_ = [("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p), ("n_min", ctypes.c_void_p),
+                ("n_max", ctypes.c_void_p)]
+
+
 def _bind_bounds(lib):
     """The bounded-sweep entries' prototypes (halda_solve_fleets_bounded .. halda_set_bounds_path)."""
     lib = _bind(lib)
@@ -118,6 +123,12 @@ def _bind_bounds(lib):
     lib.halda_solve_fleets_bounded_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
                                                     ctypes.c_int32, P(HaldaBoundsC), P(HaldaFleetResultC)]
     lib.halda_solve_fleets_bounded_host.restype = ctypes.c_int
+    lib.halda_solve_fleets_boxed.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
+                                             ctypes.c_int32, P(HaldaBoxC), P(HaldaFleetResultC), ctypes.c_void_p]
+    lib.halda_solve_fleets_boxed.restype = ctypes.c_int
+    lib.halda_solve_fleets_boxed_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
+                                                  ctypes.c_int32, P(HaldaBoxC), P(HaldaFleetResultC)]
+    lib.halda_solve_fleets_boxed_host.restype = ctypes.c_int
     lib.halda_last_bounds_route.argtypes = [ctypes.c_void_p, P(ctypes.c_int)]
     lib.halda_last_bounds_route.restype = ctypes.c_int
     lib.halda_set_bounds_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -953,10 +964,11 @@ class DeviceFleetTable:
         if rc != 0:
             raise RuntimeError(f"halda_solve_fleets_plans failed ({rc}): {last_error(lib)}")
 
-    def set_bounds(self, w_min=None, w_max=None) -> None:
+    def set_bounds(self, w_min=None, w_max=None, n_min=None, n_max=None) -> None:
         """Give the table its resident per-device layer bounds: device tensors bound_min / bound_max
         [n_devices] (int32; zeros / INT32_MAX, "no bound", where not given), buffers of their own. A streaming
-        caller rewrites them in place between launches."""
+        caller rewrites them in place between launches. With n_min or n_max given, bound_nmin / bound_nmax
+        too (the n columns' box), and launch_with_bounds calls halda_solve_fleets_boxed."""
         import torch
 
         dev = self.out["best_k"].device
@@ -972,13 +984,27 @@ class DeviceFleetTable:
 
         self.bound_min, self.bound_max = tensor(w_min, 0), tensor(w_max, 2**31 - 1)
         self._bounds_c = HaldaBoundsC(self.bound_min.data_ptr(), self.bound_max.data_ptr())
+        self.bound_nmin = self.bound_nmax = self._box_c = None
+        if n_min is not None or n_max is not None:
+            self.bound_nmin, self.bound_nmax = tensor(n_min, 0), tensor(n_max, 2**31 - 1)
+            self._box_c = HaldaBoxC(self.bound_min.data_ptr(), self.bound_max.data_ptr(),
+                                    self.bound_nmin.data_ptr(), self.bound_nmax.data_ptr())
 
     def launch_with_bounds(self, ctx, stream: int) -> None:
         """Enqueue the k-sweep of every fleet within the resident bounds on `stream`
-        (halda_solve_fleets_bounded): self.out as launch() leaves it."""
+        (halda_solve_fleets_bounded; halda_solve_fleets_boxed when set_bounds got an n array): self.out as
+        launch() leaves it."""
         if getattr(self, "_bounds_c", None) is None:
             self.set_bounds()
         lib = _bind_bounds(ctx.lib)
+        if self._box_c is not None:
+            with ctx._lock:
+                rc = lib.halda_solve_fleets_boxed(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
+                                                  self.ks.ctypes.data, len(self.ks), ctypes.byref(self._box_c),
+                                                  ctypes.byref(self.res), ctypes.c_void_p(stream))
+            if rc != 0:
+                raise RuntimeError(f"halda_solve_fleets_boxed failed ({rc}): {last_error(lib)}")
+            return
         with ctx._lock:
             rc = lib.halda_solve_fleets_bounded(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
                                                 self.ks.ctypes.data, len(self.ks), ctypes.byref(self._bounds_c),

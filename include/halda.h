@@ -479,7 +479,7 @@ int halda_set_plans_path(void *ctx, int path);
  * the same rule (ascending k, strict "<"). An instance is HALDA_STATUS_INFEASIBLE when sum lo > W
  * (without bounds: M > W), when some lo_i > hi_i, or when sum hi < W; W >= 1e6 and rejected records
  * stay HALDA_STATUS_UNSUPPORTED. With no bounds, or with bounds that never bind (w_min <= 1,
- * w_max >= W), every output equals halda_solve_fleets' bit for bit. Bounds on n are not offered.
+ * w_max >= W), every output equals halda_solve_fleets' bit for bit. Bounds on n: halda_box, below.
  * ------------------------------------------------------------------------ */
 typedef struct halda_bounds {
     const int32_t *w_min, *w_max; /* [dev_off[n_fleets]] device layout; either may be NULL */
@@ -503,7 +503,7 @@ int halda_solve_fleets_bounded(void *ctx, const halda_model *model, const halda_
 int halda_solve_fleets_bounded_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
                                     int32_t n_k, const halda_bounds *bounds, halda_fleet_result *out);
 
-/* Which route the context's last halda_solve_fleets_bounded / _host call took: 1 fused (one launch),
+/* Which route the context's last halda_solve_fleets_bounded / _boxed / _host call took: 1 fused (one launch),
  * 2 general (lowering, bounds, CSR pipeline), 3 the table route (one launch), 0 when none ran yet. */
 int halda_last_bounds_route(void *ctx, int *route);
 
@@ -511,6 +511,42 @@ int halda_last_bounds_route(void *ctx, int *route);
  * applies (general elsewhere), 3 the fused route where it applies, else the table route where it
  * applies (path 3; general elsewhere). HALDA_E_ARG for any other path. */
 int halda_set_bounds_path(void *ctx, int path);
+
+/* ------------------------------------------------------------------------
+ * Layer bounds on n too: cap, pin or disable a device's GPU share (halda_solve_fleets_boxed).
+ *
+ * halda_box is halda_bounds with two more optional int32 arrays in the same layout, for the n columns.
+ * Device i has the reference's own range n in [0, nhi_i], nhi_i = W on a GPU device, else 0:
+ *    nlo_i  = max(0, n_min_i)      (zero, a negative entry, or n_min == NULL: no lower bound)
+ *    nhi'_i = min(nhi_i, n_max_i)  (INT32_MAX, or n_max == NULL: no upper bound; 0: the GPU is not used)
+ * The link row n_i <= w_i stays, so the effective lower bound on w is lo_i = max(1, w_min_i, nlo_i) -- an
+ * implied bound of the same MILP, used in the sum lo > W verdict and in R = W - sum lo. The answer is
+ * that of the reference's fixed-k MILP with only the bounds of the w and n columns replaced: every row
+ * stays, and the slack, z and C columns keep their bounds -- the VRAM slack's upper bound stays nhi_i,
+ * n_max narrows n, not the slack. An instance is HALDA_STATUS_INFEASIBLE in halda_solve_fleets_bounded's
+ * three cases (with the folded lo_i) and when some nlo_i > nhi'_i (n_min_i >= 1 on a device without a GPU
+ * included), in the same order of precedence against HALDA_STATUS_UNSUPPORTED. A device with
+ * w_min = w_max and n_min = n_max is pinned in both columns: pinning every device prices that plan, with
+ * halda_eval_plans' status and objective.
+ *
+ * With n_min and n_max both NULL the call IS halda_solve_fleets_bounded: the same route, the same
+ * kernels, the same bits. With n arrays that never bind (n_min <= 0, n_max >= W) every output equals
+ * that call's bit for bit. The routes, halda_set_bounds_path and halda_last_bounds_route are shared:
+ * with n bounds the general route patches the lowered batch with halda_box_cols_kernel (w and n
+ * columns), the fused route launches halda_sweep_box_kernel and the table route
+ * halda_sweep_box_tables_kernel, each under the gate of its bounded twin.
+ * ------------------------------------------------------------------------ */
+typedef struct halda_box {
+    const int32_t *w_min, *w_max, *n_min, *n_max; /* [dev_off[n_fleets]] device layout; any may be NULL */
+} halda_box;
+
+/* Asynchronous on `stream`; arguments and outputs as halda_solve_fleets_bounded (box == NULL: no bounds). */
+int halda_solve_fleets_boxed(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                             int32_t n_k, const halda_box *box, halda_fleet_result *out, void *stream);
+
+/* Synchronous variant on HOST arrays, as halda_solve_fleets_bounded_host. */
+int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                                  int32_t n_k, const halda_box *box, halda_fleet_result *out);
 
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */

@@ -1,0 +1,410 @@
+"""Layer bounds on n on the GPU (libhalda halda_solve_fleets_boxed): n arrays that never bind give
+halda_solve_fleets_bounded's bits (and halda_solve_fleets' with no w bounds) on every route; binding boxes give the
+exact oracle's solutions on the fused (halda_sweep_box_kernel), table (halda_sweep_box_tables_kernel) and general
+(halda_box_cols_kernel, then the CSR pipeline) routes, which agree with each other; pins price the plan as
+halda_eval_plans does; crossing pairs and n_min on a device without a GPU are infeasible; the DP test path; and
+the Python entries. The route is asserted in every case with last_bounds_route, and the launch with
+last_fleet_ms (timing on): one launch in the sweep's or the table sweep's slot on the fused and table routes, the
+lowering on the general one."""
+
+import ctypes
+
+import numpy as np
+import pytest
+
+from distilp_amd.solver import _libhalda as lh
+from distilp_amd.solver import (halda_replace_within, halda_solve_batch, halda_solve_bounded,
+                                halda_solve_bounded_batch)
+from distilp_amd.solver import bounds as bd
+from distilp_amd.solver import plans as pl
+from distilp_amd.solver.fleets import DeviceFleetTable, HaldaBoxC, _bind_bounds, fleet_table
+
+from . import bounds_cases as bc
+from . import box_cases as xc
+from .test_gpu_bounds import IMAX, KS80, KV, Run, _torch, fleet, same
+
+pytestmark = pytest.mark.gpu
+
+ROUTE_PATH = {"fused": 0, "tables": 3, "general": 1}
+SLOT = {"fused": {"halda_sweep_kernel"}, "tables": {"halda_sweep_tables_kernel"}}
+
+
+@pytest.fixture
+def ctx():
+    c = lh.get_context(0)
+    yield c
+    c.set_fleets_path("fused")
+    c.set_timing(False)
+    bd.set_bounds_path(c, 0)
+
+
+class BoxRun(Run):
+    def boxed(self, ctx, box, null_struct=False):
+        """One halda_solve_fleets_boxed call; box: four host int arrays or None (a NULL pointer) each."""
+        lib = _bind_bounds(ctx.lib)
+        keep = [None if a is None else self.torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.dev)
+                for a in box]
+        b = HaldaBoxC(*[None if t is None else t.data_ptr() for t in keep])
+        rc = lib.halda_solve_fleets_boxed(ctx.ctx, ctypes.byref(self.m), ctypes.byref(self.fs), self.ks.ctypes.data,
+                                          len(self.ks), None if null_struct else ctypes.byref(b),
+                                          ctypes.byref(self.res), None)
+        assert rc == 0, lh.last_error(lib)
+        out = self.collect()
+        del keep
+        return out, bd.last_bounds_route(ctx)
+
+
+def on_route(ctx, route):
+    bd.set_bounds_path(ctx, ROUTE_PATH[route])
+    ctx.set_timing(True)
+
+
+def launched(ctx, route):
+    ran = set(ctx.last_fleet_ms())
+    if route in SLOT:
+        assert ran == SLOT[route], (route, ran)
+    else:
+        assert "halda_lower_kernel" in ran and not (ran & {"halda_sweep_kernel", "halda_sweep_tables_kernel"}), ran
+
+
+def close_outputs(a, b, what):
+    """Status, best k and plan equal; the objectives with the same finiteness and within the cross-path bound."""
+    for f in ("status", "best_k", "w", "n"):
+        assert np.array_equal(a[f], b[f]), (what, f)
+    for f in ("obj_value", "obj_by_k"):
+        x, y = a[f], b[f]
+        fin = np.isfinite(y)
+        assert np.array_equal(np.isfinite(x), fin), (what, f)
+        assert (np.abs(x[fin] - y[fin]) <= 1e-12 * np.maximum(1.0, np.abs(y[fin]))).all(), (what, f)
+
+
+# ------------------------------------------------------------------ 1. n arrays that never bind
+# (route, M, ks): the fused route's gate needs every k > 1 closed and L - M + 1 <= 64 at k = 1
+NOOP = {"fused-m64": ("fused", 64, KS80), "fused-m63": ("fused", 63, KS80), "fused-m24": ("fused", 24, [1]),
+        "tables-m16": ("tables", 16, [1, 2, 4, 5]), "tables-m2": ("tables", 2, [1, 40]), "tables-m1": ("tables", 1, [1]),
+        "general-m16": ("general", 16, [1, 2, 4, 5]), "general-m2": ("general", 2, [1, 40]),
+        "general-m1": ("general", 1, [1]), "general-m65": ("general", 65, [1, 2])}
+
+
+def noop_n_variants(nd, W):
+    return [(None, None), (np.zeros(nd, np.int32), np.full(nd, IMAX, np.int32)),
+            (np.zeros(nd, np.int32), np.full(nd, W, np.int32)), (np.full(nd, -5, np.int32), None),
+            (None, np.full(nd, W, np.int32))]
+
+
+@pytest.mark.parametrize("name", sorted(NOOP))
+def test_noop_n_bounds_equal_the_bounded_call(ctx, llama_online_model, name):
+    route, M, ks = NOOP[name]
+    model = llama_online_model
+    W = int(model.L) // min(ks)
+    table = fleet_table([fleet(M, 1100 + s) for s in range(4)], model)
+    nd = table.n_devices
+    run = BoxRun(table, model, ks)
+    on_route(ctx, route)
+    # binding w bounds around the k = 1 optimum: every third device may not grow, the others move by 2
+    free, r = run.bounded(ctx, None, None)
+    assert r == route and (free["best_k"] > 0).all()
+    lo = np.maximum(1, free["w"] - 2).astype(np.int32)
+    hi = np.minimum(W, free["w"] + 2).astype(np.int32)
+    hi[::3] = np.maximum(free["w"][::3], 1)
+    for wlo, whi in ((None, None), (lo, hi)):
+        want, r = run.bounded(ctx, wlo, whi)
+        assert r == route
+        if wlo is None and route != "general":  # no bounds at all: the sweep's own bits
+            if route == "tables":
+                ctx.set_fleets_path("wave")
+            same(want, run.plain(ctx))
+            ctx.set_fleets_path("fused")
+        for nlo, nhi in noop_n_variants(nd, W):
+            got, r = run.boxed(ctx, (wlo, whi, nlo, nhi))
+            assert r == route, name
+            launched(ctx, route)
+            same(got, want)
+    got, r = run.boxed(ctx, (None,) * 4, null_struct=True)
+    assert r == route
+    same(got, free)
+
+
+# ------------------------------------------------------------------ 2. binding boxes against the exact oracle
+def oracle_batch(model, M, k, seeds, kinds):
+    """The cases of (M, k) that exist, their fleets and boxes."""
+    cs, devs, boxes = [], [], []
+    for c in xc.cases([M], [k], seeds, kinds):
+        b = xc.box(model, M, k, c[2], c[3])
+        if b is not None:
+            cs.append(c)
+            devs.append(list(bc.devices(M, c[2])))
+            boxes.append(b)
+    return cs, devs, boxes
+
+
+def check_against_oracle(ctx, model, M, k, routes, seeds, kinds=xc.MOVE_KINDS + xc.CAP_KINDS):
+    """Every case of (M, k) in ONE call per route; the first route against the exact oracle -- status, the w, n,
+    slack and t columns of x, c.x and the objective -- and the other routes against the first."""
+    cs, devs, boxes = oracle_batch(model, M, k, seeds, kinds)
+    table = fleet_table(devs, model)
+    run = BoxRun(table, model, [k])
+    outs = {}
+    for route in routes:
+        on_route(ctx, route)
+        outs[route], r = run.boxed(ctx, xc.flat(boxes, table))
+        assert r == route, (M, k, route)
+        launched(ctx, route)
+    got = outs[routes[0]]
+    N, skipped, feasible = 7 * M + 1, 0, 0
+    for f, (c, dv, b) in enumerate(zip(cs, devs, boxes)):
+        st, x, cx, obj, unique = xc.exact_answer(model, dv, k, b)
+        if st != 0:
+            assert got["status"][f] == lh.STATUS_INFEASIBLE and got["best_k"][f] == 0, c
+            continue
+        feasible += 1
+        assert got["status"][f] == lh.STATUS_OPTIMAL and got["best_k"][f] == k, c
+        assert bc.rel(got["obj_value"][f], obj) <= 1e-9 and got["obj_by_k"][f] == got["obj_value"][f], c
+        if not unique:
+            skipped += 1
+            continue
+        a = f * M
+        gx, gc = got["x"][f * run.xs:f * run.xs + N], got["c"][f * run.xs:f * run.xs + N]
+        assert got["w"][a:a + M].tolist() == [int(round(v)) for v in x[:M]], c
+        assert got["n"][a:a + M].tolist() == [int(round(v)) for v in x[M:2 * M]], c
+        assert np.array_equal(gx[:6 * M], np.round(x[:6 * M])), c  # w, n, the three class slacks and t
+        assert bc.rel(float(gc.dot(gx)), cx) <= 1e-9, c
+        w, n = got["w"][a:a + M], got["n"][a:a + M]
+        assert (w >= b[0]).all() and (w <= b[1]).all() and (n >= b[2]).all() and (n <= b[3]).all(), c
+    assert skipped * 10 <= len(cs), (skipped, len(cs))
+    for route in routes[1:]:
+        close_outputs(outs[route], got, (M, k, route))
+    return feasible, len(cs)
+
+
+@pytest.mark.parametrize("M,seeds", [(64, range(3)), (24, range(6))])
+def test_binding_boxes_on_the_fused_route_equal_the_oracle_and_the_general_route(ctx, llama_online_model, M, seeds):
+    feasible, total = check_against_oracle(ctx, llama_online_model, M, 1, ("fused", "general"), seeds)
+    assert total == 4 * len(seeds) and feasible >= 3 * len(seeds)
+
+
+@pytest.mark.parametrize("M", [4, 16])
+@pytest.mark.parametrize("k", [1, 2, 4, 5])
+def test_binding_boxes_on_the_table_route_equal_the_oracle_and_the_general_route(ctx, llama_online_model, M, k):
+    feasible, total = check_against_oracle(ctx, llama_online_model, M, k, ("tables", "general"), range(12))
+    assert total >= 36 and feasible >= 24
+
+
+def test_every_k_of_one_call_on_the_table_route(ctx, llama_online_model):
+    """ks = [1, 2, 4, 5] in one call (the same box for every k): the table route equals the general one, and the
+    best k's plan obeys the box."""
+    model = llama_online_model
+    for M in (4, 16):
+        cs, devs, boxes = oracle_batch(model, M, 2, range(6), ("box2", "half"))
+        table = fleet_table(devs, model)
+        run = BoxRun(table, model, [1, 2, 4, 5])
+        flat = xc.flat(boxes, table)
+        on_route(ctx, "tables")
+        tab, r = run.boxed(ctx, flat)
+        assert r == "tables"
+        launched(ctx, "tables")
+        on_route(ctx, "general")
+        gen, r = run.boxed(ctx, flat)
+        assert r == "general"
+        close_outputs(tab, gen, M)
+        ok = tab["best_k"] > 0
+        assert ok.sum() >= len(cs) // 2
+        okd = np.repeat(ok, M)
+        assert ((tab["n"] >= flat[2]) & (tab["n"] <= flat[3]) & (tab["w"] >= flat[0]) & (tab["w"] <= flat[1]))[okd].all()
+
+
+# ------------------------------------------------------------------ 3. pins against halda_eval_plans
+@pytest.mark.parametrize("route,M,k", [("fused", 64, 1), ("fused", 24, 1), ("tables", 16, 1), ("tables", 16, 2),
+                                       ("tables", 4, 4), ("general", 16, 2), ("general", 4, 1)])
+def test_pinned_boxes_price_the_plan_as_eval_plans_does(ctx, llama_online_model, route, M, k):
+    model = llama_online_model
+    seeds = range(4) if M == 64 else range(12)
+    cs, devs, boxes = oracle_batch(model, M, k, seeds, ("pin",))
+    table = fleet_table(devs, model)
+    run = BoxRun(table, model, [k])
+    on_route(ctx, route)
+    got, r = run.boxed(ctx, xc.flat(boxes, table))
+    assert r == route
+    launched(ctx, route)
+    w1 = np.concatenate([b[0] for b in boxes]).astype(np.int32)
+    n1 = np.concatenate([b[2] for b in boxes]).astype(np.int32)
+    buf = pl.evaluate_table(table, model, np.full(len(cs), k, np.int32), w1, n1, KV)
+    feasible = 0
+    for f, c in enumerate(cs):
+        assert (got["status"][f] == lh.STATUS_OPTIMAL) == (buf.status[f] == lh.STATUS_OPTIMAL), c
+        if buf.status[f] != lh.STATUS_OPTIMAL:
+            assert got["status"][f] == lh.STATUS_INFEASIBLE and got["best_k"][f] == 0, c
+            continue
+        feasible += 1
+        a = f * M
+        assert np.array_equal(got["w"][a:a + M], w1[a:a + M]) and np.array_equal(got["n"][a:a + M], n1[a:a + M]), c
+        if route == "general":
+            assert bc.rel(got["obj_value"][f], buf.obj[f]) <= 1e-12, c
+        else:
+            assert got["obj_value"][f] == buf.obj[f], c
+    assert feasible >= len(cs) // 3
+
+
+# ------------------------------------------------------------------ 4. crossing pairs and GPU-less lower bounds
+@pytest.mark.parametrize("route,M,ks", [("fused", 64, KS80), ("fused", 24, [1]), ("tables", 16, [1, 2, 4, 5]),
+                                        ("tables", 2, [1, 2]), ("general", 16, [1, 2, 4, 5]), ("general", 65, [1])])
+def test_crossing_and_gpuless_n_bounds_are_infeasible(ctx, llama_online_model, route, M, ks):
+    model = llama_online_model
+    W = int(model.L)
+    devs = [fleet(M, 1300 + s) for s in range(5)]
+    table = fleet_table(devs, model)
+    own = [xc.mo.lower_dense(d, model, 1, KV)["ub"][M:2 * M] for d in devs]
+    nlo, nhi = np.zeros((5, M), np.int32), np.full((5, M), IMAX, np.int32)
+    nlo[0, M // 2], nhi[0, M // 2] = 3, 2            # fleet 0: a crossing pair
+    gpuless = [int(np.flatnonzero(o == 0)[0]) if (o == 0).any() else -1 for o in own]
+    if gpuless[1] >= 0:
+        nlo[1, gpuless[1]] = 1                        # fleet 1: n_min = 1 on a device without a GPU
+    else:
+        nhi[1, 0] = -1                                # (none in this fleet: a negative n_max crosses n_min = 0)
+    nlo[2, :] = W + 1                                 # fleet 2: n_min > W folds into sum lo > W
+    nhi[3, :] = W                                     # fleet 3: never binds
+    # fleet 4: no bounds
+    run = BoxRun(table, model, ks)
+    on_route(ctx, route)
+    free, _ = run.bounded(ctx, None, None)
+    got, r = run.boxed(ctx, (None, None, nlo.ravel(), nhi.ravel()))
+    assert r == route
+    launched(ctx, route)
+    st = got["status"].reshape(5, len(ks))
+    assert (st[:3] == lh.STATUS_INFEASIBLE).all() and (got["best_k"][:3] == 0).all()
+    assert (got["obj_value"][:3] == np.inf).all() and (got["w"].reshape(5, M)[:3] == 0).all()
+    assert (got["n"].reshape(5, M)[:3] == 0).all() and (got["obj_by_k"].reshape(5, len(ks))[:3] == np.inf).all()
+    nx = run.xs * len(ks)
+    assert (got["x"][:3 * nx] == 0).all() and (got["c"][:3 * nx] == 0).all()
+    for f in ("best_k", "obj_value"):
+        assert np.array_equal(got[f][3:], free[f][3:]), f
+    assert np.array_equal(got["w"][3 * M:], free["w"][3 * M:]) and (got["best_k"][3:] > 0).all()
+
+
+# ------------------------------------------------------------------ 5. the DP test path
+def test_dp_path_gives_the_same_answers_on_box_cases(ctx, llama_online_model):
+    model = llama_online_model
+    for route, M, k in (("fused", 24, 1), ("tables", 16, 1), ("tables", 16, 2)):
+        cs, devs, boxes = oracle_batch(model, M, k, range(6), xc.MOVE_KINDS + xc.CAP_KINDS + ("pin",))
+        table = fleet_table(devs, model)
+        run = BoxRun(table, model, [k])
+        flat = xc.flat(boxes, table)
+        on_route(ctx, route)
+        greedy, r = run.boxed(ctx, flat)
+        assert r == route
+        ctx.set_fleets_path("dp")
+        dp, r = run.boxed(ctx, flat)
+        ctx.set_fleets_path("fused")
+        assert r == route
+        if route == "fused":
+            same(dp, greedy)
+        else:
+            close_outputs(dp, greedy, (route, M, k))
+        assert (greedy["best_k"] == k).sum() >= len(cs) // 2
+
+
+# ------------------------------------------------------------------ 6. the Python entries
+def test_solve_bounded_with_n_max(llama_online_model):
+    model = llama_online_model
+    for M in (4, 24):
+        devs = fleet(M, 1600 + M)
+        free = halda_solve_bounded(devs, model, k_candidates=[1], kv_bits="4bit")
+        assert max(free.n) > 0
+        i = int(np.argmax(free.n))
+        n_max = [IMAX] * M
+        n_max[i] = 0
+        off = halda_solve_bounded(devs, model, n_max=n_max, k_candidates=[1], kv_bits="4bit")
+        assert off.n[i] == 0 and sum(off.w) == model.L and off.obj_value >= free.obj_value
+        b = ([1] * M, [int(model.L)] * M, [0] * M, n_max)
+        st, x, _, obj, unique = xc.exact_answer(model, devs, 1, b)
+        assert st == 0 and bc.rel(off.obj_value, obj) <= 1e-9
+        if unique:
+            assert off.w + off.n == [int(round(v)) for v in x[:2 * M]]
+        same_ = halda_solve_bounded(devs, model, n_min=[-1] * M, n_max=[IMAX] * M, k_candidates=[1], kv_bits="4bit")
+        assert (same_.w, same_.n, same_.obj_value) == (free.w, free.n, free.obj_value)
+        none = [j for j, h in enumerate(xc.mo.lower_dense(devs, model, 1, KV)["ub"][M:2 * M]) if h == 0]
+        if none:
+            n_min = [0] * M
+            n_min[none[0]] = 1
+            with pytest.raises(RuntimeError, match="No feasible MILP"):
+                halda_solve_bounded(devs, model, n_min=n_min, k_candidates=[1], kv_bits="4bit")
+
+
+def test_bounded_batch_mixes_pairs_boxes_and_free_fleets(llama_online_model):
+    model = llama_online_model
+    fleets = [fleet(M, 1600 + M) for M in (3, 8, 8, 20)]
+    free = halda_solve_batch(fleets, model, k_candidates=[1, 10], kv_bits="4bit")
+    free1 = halda_solve_batch(fleets, model, k_candidates=[1], kv_bits="4bit")
+    i = int(np.argmax(free1[1].n))
+    n_max = [IMAX] * 8
+    n_max[i] = max(0, free1[1].n[i] - 1)
+    boxes = [None, (None, None, None, n_max), ([1] * 8, [1] * 8), (None, None, [3] + [0] * 19, [2] + [IMAX] * 19)]
+    got = halda_solve_bounded_batch(fleets, model, boxes, k_candidates=[1, 10], kv_bits="4bit")
+    assert (got[0].w, got[0].n, got[0].obj_value) == (free[0].w, free[0].n, free[0].obj_value)
+    assert got[2].w == [1] * 8 and got[2].k == 10  # the pair of a 2-tuple: every device capped at one layer
+    assert got[3] is None  # a crossing n pair: no k is feasible
+    one = halda_solve_bounded_batch(fleets[1:2], model, boxes[1:2], k_candidates=[1], kv_bits="4bit")[0]
+    assert one.n[i] <= n_max[i] and one.obj_value >= free1[1].obj_value
+    if free1[1].n[i] > 0:
+        assert (one.w, one.n) != (free1[1].w, free1[1].n)
+    assert got[1] is not None and got[1].obj_value >= free[1].obj_value
+    with pytest.raises(ValueError, match="n_max of 7 entries"):
+        halda_solve_bounded_batch(fleets, model, [None, (None, None, None, [0] * 7), None, None], kv_bits="4bit")
+
+
+def test_replace_within_with_an_n_budget(llama_online_model):
+    model = llama_online_model
+    for M in (4, 16, 24):
+        devs = fleet(M, 1400 + M)
+        inc = halda_solve_batch([fleet(M, 1500 + M)], model, k_candidates=[1], kv_bits="4bit")[0]
+        r0 = halda_replace_within(devs, model, inc, 2, kv_bits="4bit", route="tables")
+        r = halda_replace_within(devs, model, inc, 2, kv_bits="4bit", route="tables", max_move_n=1)
+        assert r0.moved_gpu_layers_within == sum(abs(a - b) for a, b in zip(r0.within.n, inc.n))
+        if r.within is None:
+            continue
+        wlo, whi, nlo, nhi = bd.move_box(inc.w, inc.n, 2, 1)
+        assert r.within.k == inc.k and sum(r.within.w) == model.L
+        assert all(l <= v <= h for l, v, h in zip(wlo, r.within.w, whi))
+        assert all(l <= v <= h for l, v, h in zip(nlo, r.within.n, nhi))
+        assert r.moved_gpu_layers_within == sum(abs(a - b) for a, b in zip(r.within.n, inc.n)) <= M
+        assert r.moved_layers_within == sum(abs(a - b) for a, b in zip(r.within.w, inc.w))
+        assert r.within.obj_value >= r0.within.obj_value  # the n box only narrows the w box
+        st, x, _, obj, unique = xc.exact_answer(model, devs, 1, (wlo, whi, nlo, nhi))
+        assert st == 0 and bc.rel(r.within.obj_value, obj) <= 1e-9, M
+
+
+def test_resident_n_bounds_follow_their_contents(ctx, llama_online_model):
+    torch, dev = _torch()
+    model = llama_online_model
+    table = fleet_table([fleet(64, 1700 + s) for s in range(4)], model)
+    dt = DeviceFleetTable(table, model, KS80, KV, dev)
+    dt.set_bounds(n_max=np.full(table.n_devices, IMAX, np.int32))
+    assert dt.bound_nmin is not None and (dt.bound_nmin == 0).all()
+    s = torch.cuda.Stream(dev)
+    dt.launch_with_bounds(ctx, s.cuda_stream)
+    torch.cuda.synchronize(dev)
+    assert bd.last_bounds_route(ctx) == "fused"
+    w0, n0 = dt.out["w"].cpu().numpy().copy(), dt.out["n"].cpu().numpy().copy()
+    best = dt.out["obj_value"].cpu().numpy().copy()
+    dt.launch(ctx, s.cuda_stream)
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(dt.out["w"].cpu().numpy(), w0) and np.array_equal(dt.out["obj_value"].cpu().numpy(), best)
+    i = int(np.argmax(n0[64:128]))
+    assert n0[64 + i] > 0
+    with torch.cuda.stream(s):  # in place: fleet 0 pinned in both columns, fleet 1's largest GPU share switched off
+        for t in (dt.bound_min, dt.bound_max):
+            t[:64].copy_(dt.out["w"][:64])
+        for t in (dt.bound_nmin, dt.bound_nmax):
+            t[:64].copy_(dt.out["n"][:64])
+        dt.bound_nmax[64 + i] = 0
+    dt.launch_with_bounds(ctx, s.cuda_stream)
+    torch.cuda.synchronize(dev)
+    w1, n1, obj1 = dt.out["w"].cpu().numpy(), dt.out["n"].cpu().numpy(), dt.out["obj_value"].cpu().numpy()
+    assert np.array_equal(w1[:64], w0[:64]) and np.array_equal(n1[:64], n0[:64]) and obj1[0] == best[0]
+    assert n1[64 + i] == 0 and obj1[1] >= best[1] and w1[64:128].sum() == model.L
+    assert np.array_equal(w1[128:], w0[128:]) and np.array_equal(obj1[2:], best[2:])
+    dt.set_bounds()  # back to w bounds alone: the bounded entry
+    assert dt.bound_nmax is None
+    dt.launch_with_bounds(ctx, s.cuda_stream)
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(dt.out["w"].cpu().numpy(), w0) and np.array_equal(dt.out["obj_value"].cpu().numpy(), best)
