@@ -5,12 +5,13 @@
 // the whole halda_solve k-sweep of :369-436 (halda_solve_fleets); the C ABI is in
 // include/halda.h, the design (and why the solve is exact) in DESIGN.md.
 //
-// One translation unit in four files:
+// One translation unit in five files:
 //   halda_prims.hpp  constants, stamps, LDS slices, wave / segment reductions;
 //   halda_solve.hpp  the milp() replacement: records, splits, greedy, DP, CSR decode,
 //                    screen / k = 1 / general kernels;
 //   halda_sweep.hpp  the k-sweep: GPU lowering, fused sweep kernels, k-slot kernel, pick;
-//   halda.hip        host side: contexts, launch sequences, the C ABI, RCCL latency mode.
+//   halda.hip        host side: contexts, launch sequences, the C ABI, RCCL latency mode;
+//   halda_stage.hpp  the host entries' staging layout (no HIP: also built alone by a CPU test).
 // Floating point keeps the reference's operation order (-ffp-contract=off).
 
 #include <hip/hip_runtime.h>
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "halda.h"
+#include "halda_stage.hpp"
 
 namespace {
 // Page-locked host blocks handed out by halda_host_alloc: a call whose every host array lies in one of
@@ -286,8 +288,10 @@ int order_after_previous(Ctx *ctx, hipStream_t s) {
     return HALDA_OK;
 }
 
-// A stream's scratch slot (see Ctx::SweepSlot): grown to hold `need` bytes at *buf.
-int grow(uint8_t **buf, size_t *bytes, size_t need) {
+// A grow-only device buffer (a stream's scratch slot, see Ctx::SweepSlot; the context's staging scratch):
+// grown to hold `need` bytes at *buf.
+template <class T>
+int grow(T **buf, size_t *bytes, size_t need) {
     need = (need + 255) & ~size_t(255);
     if (need > *bytes) {
         if (*buf) HIP_TRY(hipFree(*buf));  // hipFree waits for the device
@@ -296,6 +300,32 @@ int grow(uint8_t **buf, size_t *bytes, size_t need) {
         HIP_TRY(hipMalloc(buf, need));
         *bytes = need;
     }
+    return HALDA_OK;
+}
+
+// The host entries' staging (layouts: halda_stage.hpp): the context's scratch grown to `bytes`, then one
+// copy per array straight between the caller's memory and the scratch (a DMA where the caller's is
+// page-locked, halda_host_alloc). An empty array is skipped, on the way back an absent one too.
+int ensure_scratch(Ctx *c, size_t bytes) { return grow(&c->scratch, &c->scratch_bytes, bytes); }
+
+int upload(char *base, size_t o, const void *src, size_t bytes, hipStream_t s) {
+    if (bytes) HIP_TRY(hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s));
+    return HALDA_OK;
+}
+
+int upload(char *base, const stage::TableLayout &t, const halda_fleets &F, hipStream_t s) {
+    int rc = upload(base, t.dev_off, F.dev_off, 8 * (t.nf + 1), s);
+    if (rc == HALDA_OK) rc = upload(base, t.os_class, F.os_class, t.nd, s);
+    if (rc == HALDA_OK) rc = upload(base, t.flags, F.flags, t.nd, s);
+    for (int a = 0; a < stage::kFields && rc == HALDA_OK; ++a)
+        rc = upload(base, t.field[a], F.*stage::kField[a], 8 * t.nd, s);
+    return rc;
+}
+
+template <size_t N>
+int download(const std::array<stage::Copy, N> &copies, const char *base, hipStream_t s) {
+    for (const stage::Copy &k : copies)
+        if (k.host && k.bytes) HIP_TRY(hipMemcpyAsync(k.host, base + k.off, k.bytes, hipMemcpyDeviceToHost, s));
     return HALDA_OK;
 }
 
@@ -1012,26 +1042,22 @@ int shard_steps(Ctx *c, const halda_model &model, const halda_fleets &F, const i
         if (rc != HALDA_OK) return rc;
     }
     // rank-local sub-sweep results in the context's shard scratch (one block per rank state)
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
+    stage::Bump lay;
     std::vector<size_t> o_bk, o_obj, o_w, o_n, o_obk, o_st;
     for (auto &r : R) {
         r.mine.clear();
         for (int j = r.rank; j < n_k; j += world) r.mine.push_back(ks[j]);  // as halda_solve_distributed deals them
         const size_t nsub = std::max<size_t>(r.mine.size(), 1);
-        o_bk.push_back(take(4 * nf));
-        o_obj.push_back(take(8 * nf));
-        o_w.push_back(take(4 * size_t(nd)));
-        o_n.push_back(take(4 * size_t(nd)));
-        o_obk.push_back(take(8 * nf * nsub));
-        o_st.push_back(take(4 * nf * nsub));
+        o_bk.push_back(lay.take(4 * nf));
+        o_obj.push_back(lay.take(8 * nf));
+        o_w.push_back(lay.take(4 * size_t(nd)));
+        o_n.push_back(lay.take(4 * size_t(nd)));
+        o_obk.push_back(lay.take(8 * nf * nsub));
+        o_st.push_back(lay.take(4 * nf * nsub));
     }
-    if (off > c->shard_bytes) {
-        if (c->shard) HIP_TRY(hipFree(c->shard));
-        c->shard = nullptr;
-        c->shard_bytes = 0;
-        HIP_TRY(hipMalloc(&c->shard, off));
-        c->shard_bytes = off;
+    {
+        const int rc = grow(&c->shard, &c->shard_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
     }
     char *base = static_cast<char *>(c->shard);
     for (size_t i = 0; i < R.size(); ++i) {
@@ -1371,10 +1397,7 @@ int check_fleets_args(const halda_model *model, const halda_fleets *fleets, cons
     if (n_k <= 0 || n_k > 1024) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
     if (F.min_devices < 1 || F.max_devices < F.min_devices || F.max_devices > 4096)
         return fail(HALDA_E_ARG, "halda_fleets: need 1 <= min_devices <= max_devices <= 4096");
-    if (!F.dev_off || !F.os_class || !F.flags || !F.scpu_b1 || !F.sgpu_b1 || !F.T_cpu || !F.T_gpu ||
-        !F.t_kvcpy_cpu || !F.t_kvcpy_gpu || !F.t_ram2vram || !F.t_vram2ram || !F.t_comm || !F.s_disk ||
-        !F.d_avail_ram || !F.c_cpu || !F.c_gpu || !F.d_avail_cuda || !F.d_avail_metal || !F.swap)
-        return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!stage::complete(F)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
     if (!out->best_k || !out->obj_value || !out->w || !out->n) return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
     if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
     // ks (host memory): ascending, unique, positive
@@ -1445,23 +1468,21 @@ static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, c
     if (n_inst > (int64_t(1) << 30) || int64_t(F.n_fleets) * D.nnz > (int64_t(1) << 31) - 1)
         return fail(HALDA_E_ARG, "batch too large for one call");
     // scratch layout
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_ncols = take(4 * n_inst), o_nrows = take(4 * n_inst), o_csr = take(8 * n_inst),
-                 o_col = take(8 * n_inst), o_row = take(8 * n_inst),
-                 o_rp = take(4 * size_t(F.n_fleets) * size_t(D.rows + 1)), o_ci = take(4 * size_t(F.n_fleets) * D.nnz),
-                 o_val = take(8 * size_t(F.n_fleets) * D.nnz), o_c = take(8 * n_inst * D.cols),
-                 o_clb = take(8 * n_inst * D.cols), o_cub = take(8 * n_inst * D.cols),
-                 o_rlb = take(8 * n_inst * D.rows), o_rub = take(8 * n_inst * D.rows), o_int = take(n_inst * D.cols),
-                 o_offs = take(24 * size_t(F.n_fleets)), o_st = take(4 * n_inst), o_x = take(8 * n_inst * D.cols),
-                 o_obj = take(8 * n_inst), o_db = take(8 * n_inst), o_gap = take(8 * n_inst), o_nodes = take(8 * n_inst),
-                 o_ks = take(4 * size_t(n_k));
-    if (off > c->fleet_scratch_bytes) {
-        if (c->fleet_scratch) HIP_TRY(hipFree(c->fleet_scratch));
-        c->fleet_scratch = nullptr;
-        c->fleet_scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->fleet_scratch, off));
-        c->fleet_scratch_bytes = off;
+    stage::Bump lay;
+    const size_t nfl = size_t(F.n_fleets);
+    const size_t o_ncols = lay.take(4 * n_inst), o_nrows = lay.take(4 * n_inst), o_csr = lay.take(8 * n_inst),
+                 o_col = lay.take(8 * n_inst), o_row = lay.take(8 * n_inst),
+                 o_rp = lay.take(4 * nfl * size_t(D.rows + 1)), o_ci = lay.take(4 * nfl * D.nnz),
+                 o_val = lay.take(8 * nfl * D.nnz), o_c = lay.take(8 * n_inst * D.cols),
+                 o_clb = lay.take(8 * n_inst * D.cols), o_cub = lay.take(8 * n_inst * D.cols),
+                 o_rlb = lay.take(8 * n_inst * D.rows), o_rub = lay.take(8 * n_inst * D.rows),
+                 o_int = lay.take(n_inst * D.cols), o_offs = lay.take(24 * nfl), o_st = lay.take(4 * n_inst),
+                 o_x = lay.take(8 * n_inst * D.cols), o_obj = lay.take(8 * n_inst), o_db = lay.take(8 * n_inst),
+                 o_gap = lay.take(8 * n_inst), o_nodes = lay.take(8 * n_inst),
+                 o_ks = lay.take(4 * size_t(n_k));
+    {
+        const int rc = grow(&c->fleet_scratch, &c->fleet_scratch_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
     }
     char *base = static_cast<char *>(c->fleet_scratch);
     // the k list travels with the stream (pageable source: the copy is staged before the call returns)
@@ -1821,36 +1842,21 @@ int halda_solve_fleets_host(void *ctx, const halda_model *model, const halda_fle
     if (!fh->dev_off) return fail(HALDA_E_ARG, "halda_fleets.dev_off is NULL");
     const int64_t nf = fh->n_fleets, nd = fh->dev_off[nf];
     if (nd < nf || n_k <= 0) return fail(HALDA_E_ARG, "bad device count / n_k");
+    if (!stage::complete(*fh)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 10),
-                 o_i64 = take(8 * nd * 6);
-    const bool xsel = out_h->x_off && (out_h->x || out_h->c);
-    const size_t o_xoff = xsel ? take(8 * size_t(nf) * n_k) : 0;
-    const size_t o_bk = take(4 * nf), o_obj = take(8 * nf), o_w = take(4 * nd),
-                 o_n = take(4 * nd), o_obk = take(8 * nf * n_k), o_st = take(4 * nf * n_k);
+    // the table's fields in two blocks (10 + 6 rows): the layout's total decides the transport below
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd, 10);
+    const bool xsel = stage::compact(*out_h);
     // x / c extent: the dense layout, or the caller's compact one (x_off, host memory)
-    size_t xs = size_t(nf) * n_k * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
-    if (xsel) {
-        int64_t ext = 0;
-        for (int64_t f = 0; f < nf; ++f) {
-            const int64_t N = 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1;
-            for (int j = 0; j < n_k; ++j) {
-                const int64_t a = out_h->x_off[f * n_k + j];
-                if (a >= 0) ext = std::max(ext, a + N);
-            }
-        }
-        xs = size_t(ext);
-    }
-    const size_t o_x = out_h->x ? take(8 * xs) : 0, o_c = out_h->c ? take(8 * xs) : 0;
-    if (off > c->scratch_bytes) {
-        if (c->scratch) HIP_TRY(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->scratch, off));
-        c->scratch_bytes = off;
+    const size_t n_inst = size_t(nf) * n_k;
+    const size_t xs = stage::xc_extent(fh->dev_off, nf, n_k, 1, fh->max_devices, xsel ? out_h->x_off : nullptr);
+    const stage::ResultSlots R = stage::lay_result(lay, *out_h, nf, nd, n_inst, xs);
+    const size_t off = lay.off;
+    {
+        const int rc = ensure_scratch(c, off);
+        if (rc != HALDA_OK) return rc;
     }
     char *base = static_cast<char *>(c->scratch);
     // inputs are packed into pinned host memory and cross PCIe in ONE copy (results likewise)
@@ -1866,70 +1872,36 @@ int halda_solve_fleets_host(void *ctx, const halda_model *model, const halda_fle
     }
     char *pin = static_cast<char *>(c->pinned);
     const bool zc = off <= kZeroCopyBytes && !c->host_copy;
+    const auto copies = stage::result_copies(R, *out_h);
     // every array in halda_host_alloc blocks (the batch API's workspaces): DMA straight from / to them
     bool direct = !zc;
     if (direct) {
-        const double *fa[16] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu, fh->t_kvcpy_gpu,
-                                fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk, fh->d_avail_ram, fh->c_cpu,
-                                fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
-        for (int a = 0; a < 16 && direct; ++a) direct = fa[a] && in_host_block(fa[a], 8 * nd);
-        direct = direct && in_host_block(fh->dev_off, 8 * (nf + 1)) && fh->os_class && fh->flags &&
-                 in_host_block(fh->os_class, nd) && in_host_block(fh->flags, nd) &&
-                 in_host_block(out_h->x_off, xsel ? 8 * size_t(nf) * n_k : 0) &&
-                 in_host_block(out_h->best_k, 4 * nf) && in_host_block(out_h->obj_value, 8 * nf) &&
-                 in_host_block(out_h->w, 4 * nd) && in_host_block(out_h->n, 4 * nd) &&
-                 in_host_block(out_h->obj_by_k, 8 * nf * n_k) && in_host_block(out_h->status, 4 * nf * n_k) &&
-                 in_host_block(out_h->x, 8 * xs) && in_host_block(out_h->c, 8 * xs);
+        for (int a = 0; a < stage::kFields && direct; ++a) direct = in_host_block(fh->*stage::kField[a], 8 * nd);
+        direct = direct && in_host_block(fh->dev_off, 8 * (nf + 1)) && in_host_block(fh->os_class, nd) &&
+                 in_host_block(fh->flags, nd) && in_host_block(out_h->x_off, xsel ? 8 * n_inst : 0);
+        for (const stage::Copy &k : copies) direct = direct && in_host_block(k.host, k.bytes);
     }
     auto up = [&](size_t o, const void *src, size_t bytes) {
         if (direct) return hipMemcpyAsync(static_cast<char *>(c->scratch) + o, src, bytes, hipMemcpyHostToDevice, s);
         std::memcpy(pin + o, src, bytes);
         return hipSuccess;
     };
-    halda_fleets d = *fh;
-    HIP_TRY(up(o_doff, fh->dev_off, 8 * (nf + 1)));
-    HIP_TRY(up(o_cls, fh->os_class, nd));
-    HIP_TRY(up(o_fl, fh->flags, nd));
-    const double *f64[10] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu,
-                             fh->t_kvcpy_gpu, fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk};
-    const double *b64[6] = {fh->d_avail_ram, fh->c_cpu, fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
-    for (int a = 0; a < 10; ++a) {
-        if (!f64[a] || !fh->os_class || !fh->flags) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-        HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
-    }
-    for (int a = 0; a < 6; ++a) {
-        if (!b64[a]) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-        HIP_TRY(up(o_i64 + 8 * nd * a, b64[a], 8 * nd));
-    }
+    HIP_TRY(up(T.dev_off, fh->dev_off, 8 * (nf + 1)));
+    HIP_TRY(up(T.os_class, fh->os_class, nd));
+    HIP_TRY(up(T.flags, fh->flags, nd));
+    for (int a = 0; a < stage::kFields; ++a) HIP_TRY(up(T.field[a], fh->*stage::kField[a], 8 * nd));
+    if (xsel) HIP_TRY(up(R.x_off, out_h->x_off, 8 * n_inst));
     // small calls (a single halda_solve: ~8 KB in, ~70 KB out) skip both copies: the kernels read the
     // table from and write the results to the pinned buffer itself, across PCIe, and the host polls
     // the completion event instead of sleeping in a stream synchronisation
-    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * size_t(nf) * n_k));
     if (zc) {
         if (!c->pinned_dev) HIP_TRY(hipHostGetDevicePointer(&c->pinned_dev, c->pinned, 0));
         base = static_cast<char *>(c->pinned_dev);
     } else if (!direct) {
-        HIP_TRY(hipMemcpyAsync(base, pin, o_bk, hipMemcpyHostToDevice, s));  // the table (and x_off)
+        HIP_TRY(hipMemcpyAsync(base, pin, R.best_k, hipMemcpyHostToDevice, s));  // the table (and x_off)
     }
-    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
-    auto I64 = [&](int a) { return reinterpret_cast<const double *>(base + o_i64 + 8 * nd * a); };
-    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
-    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
-    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
-    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
-    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
-    d.d_avail_ram = I64(0); d.c_cpu = I64(1); d.c_gpu = I64(2); d.d_avail_cuda = I64(3); d.d_avail_metal = I64(4);
-    d.swap = I64(5);
-    halda_fleet_result r;
-    r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
-    r.obj_value = reinterpret_cast<double *>(base + o_obj);
-    r.w = reinterpret_cast<int32_t *>(base + o_w);
-    r.n = reinterpret_cast<int32_t *>(base + o_n);
-    r.obj_by_k = reinterpret_cast<double *>(base + o_obk);
-    r.status = reinterpret_cast<int32_t *>(base + o_st);
-    r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
-    r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
-    r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
+    const halda_fleets d = stage::rebase(*fh, base, T);
+    halda_fleet_result r = stage::bind_result(base, R, *out_h, true);  // the statuses: read below (host_zero)
     // zero-copy through the fused sweep: the kernels skip the zero x / c of non-optimal instances
     // (stores across PCIe, most of a one-fleet k-sweep's time); the copy-out below zero-fills them
     const bool host_zero = zc && c->fleets_fused && (r.x || r.c) && !xsel;
@@ -1962,49 +1934,31 @@ int halda_solve_fleets_host(void *ctx, const halda_model *model, const halda_fle
         }
         HIP_TRY(q);
     } else if (direct) {
-        auto dn = [&](void *dst, size_t o, size_t bytes) {
-            return dst ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-        };
-        HIP_TRY(dn(out_h->best_k, o_bk, 4 * nf));
-        HIP_TRY(dn(out_h->obj_value, o_obj, 8 * nf));
-        HIP_TRY(dn(out_h->w, o_w, 4 * nd));
-        HIP_TRY(dn(out_h->n, o_n, 4 * nd));
-        HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * nf * n_k));
-        HIP_TRY(dn(out_h->status, o_st, 4 * nf * n_k));
-        HIP_TRY(dn(out_h->x, o_x, 8 * xs));
-        HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+        const int rcd = download(copies, base, s);
+        if (rcd != HALDA_OK) return rcd;
         HIP_TRY(hipStreamSynchronize(s));
         return HALDA_OK;
     } else {
-        HIP_TRY(hipMemcpyAsync(pin + o_bk, base + o_bk, off - o_bk, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(pin + R.best_k, base + R.best_k, off - R.best_k, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    auto down = [&](void *dst, size_t o, size_t bytes) {
-        if (dst) std::memcpy(dst, pin + o, bytes);
-        return hipSuccess;
-    };
-    HIP_TRY(down(out_h->best_k, o_bk, 4 * nf));
-    HIP_TRY(down(out_h->obj_value, o_obj, 8 * nf));
-    HIP_TRY(down(out_h->w, o_w, 4 * nd));
-    HIP_TRY(down(out_h->n, o_n, 4 * nd));
-    HIP_TRY(down(out_h->obj_by_k, o_obk, 8 * nf * n_k));
-    HIP_TRY(down(out_h->status, o_st, 4 * nf * n_k));
+    // the results are in the pinned buffer: one memcpy per array the caller passed (x / c, the last two
+    // of the list, below when the host zero-fills them)
+    for (size_t a = 0; a < copies.size() - (host_zero ? 2 : 0); ++a)
+        if (copies[a].host) std::memcpy(copies[a].host, pin + copies[a].off, copies[a].bytes);
     if (host_zero) {
         // per (fleet, k): the kernel's x / c where the instance is optimal, zeros elsewhere
-        const size_t per = xs / (size_t(nf) * n_k);
-        const int32_t *st = reinterpret_cast<const int32_t *>(pin + o_st);
-        for (size_t i = 0; i < size_t(nf) * n_k; ++i) {
+        const size_t per = xs / n_inst;
+        const int32_t *st = reinterpret_cast<const int32_t *>(pin + R.status);
+        for (size_t i = 0; i < n_inst; ++i) {
             const bool opt = st[i] == HALDA_STATUS_OPTIMAL;
             for (int a = 0; a < 2; ++a) {
                 double *dst = a == 0 ? out_h->x : out_h->c;
                 if (!dst) continue;
-                if (opt) std::memcpy(dst + i * per, pin + (a == 0 ? o_x : o_c) + 8 * i * per, 8 * per);
+                if (opt) std::memcpy(dst + i * per, pin + (a == 0 ? R.x : R.c) + 8 * i * per, 8 * per);
                 else std::memset(dst + i * per, 0, 8 * per);
             }
         }
-    } else {
-        HIP_TRY(down(out_h->x, o_x, 8 * xs));
-        HIP_TRY(down(out_h->c, o_c, 8 * xs));
     }
     return HALDA_OK;
 }
@@ -2112,10 +2066,7 @@ static int solve_subfleets(void *ctx, const halda_model *model, const halda_flee
     X.dev_off = I.sub_off;
     X.os_class = E.os_class;
     X.flags = E.flags;
-    X.scpu_b1 = E.f[0]; X.sgpu_b1 = E.f[1]; X.T_cpu = E.f[2]; X.T_gpu = E.f[3]; X.t_kvcpy_cpu = E.f[4];
-    X.t_kvcpy_gpu = E.f[5]; X.t_ram2vram = E.f[6]; X.t_vram2ram = E.f[7]; X.t_comm = E.f[8]; X.s_disk = E.f[9];
-    X.d_avail_ram = E.f[10]; X.c_cpu = E.f[11]; X.c_gpu = E.f[12]; X.d_avail_cuda = E.f[13];
-    X.d_avail_metal = E.f[14]; X.swap = E.f[15];
+    for (int a = 0; a < stage::kFields; ++a) X.*stage::kField[a] = E.f[a];
     c->sub_route = 2;
     return halda_solve_fleets(ctx, model, &X, ks, n_k, out, s);
 }
@@ -2163,97 +2114,36 @@ int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_
         return fail(HALDA_E_ARG, "halda_subfleets: min_devices / max_devices are not the lists' shortest and longest "
                                  "length (" + std::to_string(lmin) + ", " + std::to_string(lmax) + ")");
     const int64_t tot = ih->sub_off[n];
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    // layout: the parent table, the item arrays, the results over the items
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const size_t o_par = lay.take(4 * n), o_soff = lay.take(8 * (n + 1)), o_sidx = lay.take(4 * tot);
+    const bool xsel = stage::compact(*out_h);
+    const size_t xs = stage::xc_extent(ih->sub_off, n, n_k, 1, lmax, xsel ? out_h->x_off : nullptr);
+    const stage::ResultSlots R = stage::lay_result(lay, *out_h, n, tot, size_t(n) * n_k, xs);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16),
-                 o_par = take(4 * n), o_soff = take(8 * (n + 1)), o_sidx = take(4 * tot);
-    const bool xsel = out_h->x_off && (out_h->x || out_h->c);
-    const size_t o_xoff = xsel ? take(8 * size_t(n) * n_k) : 0;
-    const size_t o_bk = take(4 * n), o_obj = take(8 * n), o_w = take(4 * tot), o_n = take(4 * tot),
-                 o_obk = take(8 * n * n_k), o_st = take(4 * n * n_k);
-    // x / c extent: the dense layout, or the caller's compact one (x_off, host memory)
-    size_t xs = size_t(n) * n_k * (7 * size_t(lmax) + 1);
-    if (xsel) {
-        int64_t ext = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t N = 7 * (ih->sub_off[i + 1] - ih->sub_off[i]) + 1;
-            for (int j = 0; j < n_k; ++j) {
-                const int64_t a = out_h->x_off[i * n_k + j];
-                if (a >= 0) ext = std::max(ext, a + N);
-            }
-        }
-        xs = size_t(ext);
-    }
-    const size_t o_x = out_h->x ? take(8 * xs) : 0, o_c = out_h->c ? take(8 * xs) : 0;
-    if (off > c->scratch_bytes) {
-        if (c->scratch) HIP_TRY(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->scratch, off));
-        c->scratch_bytes = off;
-    }
+    int rc = ensure_scratch(c, lay.off);
     char *base = static_cast<char *>(c->scratch);
-    // in: the parent table and the item arrays, one copy per array straight from the caller's memory (a
-    // DMA where it is page-locked, halda_host_alloc)
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    const double *f64[16] = {th->scpu_b1, th->sgpu_b1, th->T_cpu, th->T_gpu, th->t_kvcpy_cpu, th->t_kvcpy_gpu,
-                             th->t_ram2vram, th->t_vram2ram, th->t_comm, th->s_disk, th->d_avail_ram, th->c_cpu,
-                             th->c_gpu, th->d_avail_cuda, th->d_avail_metal, th->swap};
-    if (!th->os_class || !th->flags) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-    for (int a = 0; a < 16; ++a)
-        if (!f64[a]) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-    HIP_TRY(up(o_doff, th->dev_off, 8 * (nf + 1)));
-    HIP_TRY(up(o_cls, th->os_class, nd));
-    HIP_TRY(up(o_fl, th->flags, nd));
-    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
-    HIP_TRY(up(o_par, ih->parent, 4 * n));
-    HIP_TRY(up(o_soff, ih->sub_off, 8 * (n + 1)));
-    HIP_TRY(up(o_sidx, ih->sub_idx, 4 * tot));
-    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * size_t(n) * n_k));
-    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
-    halda_fleets d = *th;
-    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
-    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
-    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
-    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
-    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
-    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
-    d.d_avail_metal = F64(14); d.swap = F64(15);
+    // in: one copy per array; the call (it knows the total: no read-back); out and wait
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    if (rc == HALDA_OK) rc = upload(base, o_par, ih->parent, 4 * n, s);
+    if (rc == HALDA_OK) rc = upload(base, o_soff, ih->sub_off, 8 * (n + 1), s);
+    if (rc == HALDA_OK) rc = upload(base, o_sidx, ih->sub_idx, 4 * tot, s);
+    if (rc == HALDA_OK && xsel) rc = upload(base, R.x_off, out_h->x_off, 8 * R.n_inst, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
     halda_subfleets di = *ih;
     di.min_devices = int32_t(lmin);
     di.max_devices = int32_t(lmax);
     di.parent = reinterpret_cast<const int32_t *>(base + o_par);
     di.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
     di.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
-    halda_fleet_result r;
-    r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
-    r.obj_value = reinterpret_cast<double *>(base + o_obj);
-    r.w = reinterpret_cast<int32_t *>(base + o_w);
-    r.n = reinterpret_cast<int32_t *>(base + o_n);
-    r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
-    r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
-    r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
-    r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
-    r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
-    {
-        const int rc = solve_subfleets(ctx, model, &d, &di, ks, n_k, &r, s, tot);  // no read-back of the total
-        if (rc != HALDA_OK) return rc;
-    }
-    auto dn = [&](void *dst, size_t o, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    HIP_TRY(dn(out_h->best_k, o_bk, 4 * n));
-    HIP_TRY(dn(out_h->obj_value, o_obj, 8 * n));
-    HIP_TRY(dn(out_h->w, o_w, 4 * tot));
-    HIP_TRY(dn(out_h->n, o_n, 4 * tot));
-    HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n * n_k));
-    HIP_TRY(dn(out_h->status, o_st, 4 * n * n_k));
-    HIP_TRY(dn(out_h->x, o_x, 8 * xs));
-    HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+    halda_fleet_result r = stage::bind_result(base, R, *out_h);
+    rc = solve_subfleets(ctx, model, &d, &di, ks, n_k, &r, s, tot);
+    if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
 }
@@ -2422,90 +2312,26 @@ int halda_solve_variants_host(void *ctx, const halda_model *models, int32_t n_va
         return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
     const int64_t nf = fh->n_fleets, nd = fh->dev_off[nf], nv = n_var;
     if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
-    const double *f64[16] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu, fh->t_kvcpy_gpu,
-                             fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk, fh->d_avail_ram, fh->c_cpu,
-                             fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
-    if (!fh->os_class || !fh->flags) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-    for (int a = 0; a < 16; ++a)
-        if (!f64[a]) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!stage::complete(*fh)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    // layout: the table, once; the results variant-major over (variant, fleet, k)
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const bool xsel = stage::compact(*out_h);
+    const size_t xs = stage::xc_extent(fh->dev_off, nf, n_k, nv, fh->max_devices, xsel ? out_h->x_off : nullptr);
+    const stage::ResultSlots R = stage::lay_result(lay, *out_h, nv * nf, nv * nd, size_t(nv) * nf * n_k, xs);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16);
-    const bool xsel = out_h->x_off && (out_h->x || out_h->c);
-    const size_t n_inst = size_t(nv) * nf * n_k;
-    const size_t o_xoff = xsel ? take(8 * n_inst) : 0;
-    const size_t o_bk = take(4 * nv * nf), o_obj = take(8 * nv * nf), o_w = take(4 * nv * nd), o_n = take(4 * nv * nd),
-                 o_obk = take(8 * n_inst), o_st = take(4 * n_inst);
-    // x / c extent: the dense layout over (variant, fleet, k), or the caller's compact one (x_off, host memory)
-    size_t xs = n_inst * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
-    if (xsel) {
-        int64_t ext = 0;
-        for (int64_t v = 0; v < nv; ++v)
-            for (int64_t f = 0; f < nf; ++f) {
-                const int64_t N = 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1;
-                for (int j = 0; j < n_k; ++j) {
-                    const int64_t a = out_h->x_off[(v * nf + f) * n_k + j];
-                    if (a >= 0) ext = std::max(ext, a + N);
-                }
-            }
-        xs = size_t(ext);
-    }
-    const size_t o_x = out_h->x ? take(8 * xs) : 0, o_c = out_h->c ? take(8 * xs) : 0;
-    if (off > c->scratch_bytes) {
-        if (c->scratch) HIP_TRY(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->scratch, off));
-        c->scratch_bytes = off;
-    }
+    int rc = ensure_scratch(c, lay.off);
     char *base = static_cast<char *>(c->scratch);
-    // in: the table, once, one copy per array straight from the caller's memory (a DMA where it is
-    // page-locked, halda_host_alloc)
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIP_TRY(up(o_doff, fh->dev_off, 8 * (nf + 1)));
-    HIP_TRY(up(o_cls, fh->os_class, nd));
-    HIP_TRY(up(o_fl, fh->flags, nd));
-    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
-    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * n_inst));
-    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
-    halda_fleets d = *fh;
-    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
-    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
-    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
-    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
-    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
-    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
-    d.d_avail_metal = F64(14); d.swap = F64(15);
-    halda_fleet_result r;
-    r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
-    r.obj_value = reinterpret_cast<double *>(base + o_obj);
-    r.w = reinterpret_cast<int32_t *>(base + o_w);
-    r.n = reinterpret_cast<int32_t *>(base + o_n);
-    r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
-    r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
-    r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
-    r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
-    r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
-    {
-        const int rc = solve_variants(ctx, models, n_var, &d, ks, n_k, &r, s, nd);  // no read-back of the total
-        if (rc != HALDA_OK) return rc;
-    }
-    // out: only the variants' slices
-    auto dn = [&](void *dst, size_t o, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    HIP_TRY(dn(out_h->best_k, o_bk, 4 * nv * nf));
-    HIP_TRY(dn(out_h->obj_value, o_obj, 8 * nv * nf));
-    HIP_TRY(dn(out_h->w, o_w, 4 * nv * nd));
-    HIP_TRY(dn(out_h->n, o_n, 4 * nv * nd));
-    HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n_inst));
-    HIP_TRY(dn(out_h->status, o_st, 4 * n_inst));
-    HIP_TRY(dn(out_h->x, o_x, 8 * xs));
-    HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+    // in: one copy per array; the call (it knows the total: no read-back); out, only the variants' slices
+    if (rc == HALDA_OK) rc = upload(base, T, *fh, s);
+    if (rc == HALDA_OK && xsel) rc = upload(base, R.x_off, out_h->x_off, 8 * R.n_inst, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*fh, base, T);
+    halda_fleet_result r = stage::bind_result(base, R, *out_h);
+    rc = solve_variants(ctx, models, n_var, &d, ks, n_k, &r, s, nd);
+    if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
 }
@@ -2549,10 +2375,7 @@ static int check_plans_args(const void *ctx, const halda_model *model, const hal
 static int check_plans_table(const halda_fleets &F) {
     if (F.min_devices < 1 || F.max_devices < F.min_devices || F.max_devices > 4096)
         return fail(HALDA_E_ARG, "halda_fleets: need 1 <= min_devices <= max_devices <= 4096");
-    if (!F.dev_off || !F.os_class || !F.flags || !F.scpu_b1 || !F.sgpu_b1 || !F.T_cpu || !F.T_gpu ||
-        !F.t_kvcpy_cpu || !F.t_kvcpy_gpu || !F.t_ram2vram || !F.t_vram2ram || !F.t_comm || !F.s_disk ||
-        !F.d_avail_ram || !F.c_cpu || !F.c_gpu || !F.d_avail_cuda || !F.d_avail_metal || !F.swap)
-        return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!stage::complete(F)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
     return HALDA_OK;
 }
 
@@ -2673,78 +2496,34 @@ static int plans_host(void *ctx, const halda_model *model, const halda_fleets *f
     }
     const int64_t nd = fh->dev_off[nf];
     if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
-    const double *f64[16] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu, fh->t_kvcpy_gpu,
-                             fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk, fh->d_avail_ram, fh->c_cpu,
-                             fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
+    // layout: the table; the plans and the evaluation's outputs; the sweep's outputs (none: the same slots, empty)
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const size_t o_pk = lay.take(4 * nf), o_pw = lay.take(4 * nd), o_pn = lay.take(4 * nd);
+    const size_t o_est = lay.take(4 * nf), o_eobj = lay.take(8 * nf), o_ecyc = lay.take(8 * nf),
+                 o_ebot = lay.take(4 * nf), o_erea = lay.take(4 * nf);
+    const bool exsel = eh->x_off && (eh->x || eh->c);
+    const size_t o_exoff = exsel ? lay.take(8 * nf) : 0;
+    const size_t exs = stage::xc_extent(fh->dev_off, nf, 1, 1, fh->max_devices, exsel ? eh->x_off : nullptr);
+    const size_t o_ex = eh->x ? lay.take(8 * exs) : 0, o_ec = eh->c ? lay.take(8 * exs) : 0;
+    const halda_fleet_result none = {};
+    const halda_fleet_result &oh = out_h ? *out_h : none;
+    const bool xsel = stage::compact(oh);
+    const int64_t nk = out_h ? n_k : 0;
+    const size_t xs = stage::xc_extent(fh->dev_off, nf, nk, 1, fh->max_devices, xsel ? oh.x_off : nullptr);
+    const stage::ResultSlots R = stage::lay_result(lay, oh, nf, nd, size_t(nf) * nk, xs);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16);
-    // the plans and the evaluation's outputs
-    const size_t o_pk = take(4 * nf), o_pw = take(4 * nd), o_pn = take(4 * nd);
-    const size_t o_est = take(4 * nf), o_eobj = take(8 * nf), o_ecyc = take(8 * nf), o_ebot = take(4 * nf),
-                 o_erea = take(4 * nf);
-    const bool exsel = eh->x_off && (eh->x || eh->c);
-    const size_t o_exoff = exsel ? take(8 * nf) : 0;
-    size_t exs = size_t(nf) * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
-    if (exsel) {
-        int64_t ext = 0;
-        for (int64_t f = 0; f < nf; ++f) {
-            const int64_t a = eh->x_off[f];
-            if (a >= 0) ext = std::max(ext, a + 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1);
-        }
-        exs = size_t(ext);
-    }
-    const size_t o_ex = eh->x ? take(8 * exs) : 0, o_ec = eh->c ? take(8 * exs) : 0;
-    // the sweep's outputs
-    const size_t n_inst = out_h ? size_t(nf) * n_k : 0;
-    const bool xsel = out_h && out_h->x_off && (out_h->x || out_h->c);
-    const size_t o_xoff = xsel ? take(8 * n_inst) : 0;
-    const size_t o_bk = take(4 * nf), o_obj = take(8 * nf), o_w = take(4 * nd), o_n = take(4 * nd),
-                 o_obk = take(8 * n_inst), o_st = take(4 * n_inst);
-    size_t xs = n_inst * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
-    if (xsel) {
-        int64_t ext = 0;
-        for (int64_t f = 0; f < nf; ++f) {
-            const int64_t N = 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1;
-            for (int j = 0; j < n_k; ++j) {
-                const int64_t a = out_h->x_off[f * n_k + j];
-                if (a >= 0) ext = std::max(ext, a + N);
-            }
-        }
-        xs = size_t(ext);
-    }
-    const size_t o_x = out_h && out_h->x ? take(8 * xs) : 0, o_c = out_h && out_h->c ? take(8 * xs) : 0;
-    if (off > c->scratch_bytes) {
-        if (c->scratch) HIP_TRY(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->scratch, off));
-        c->scratch_bytes = off;
-    }
+    int rc = ensure_scratch(c, lay.off);
     char *base = static_cast<char *>(c->scratch);
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIP_TRY(up(o_doff, fh->dev_off, 8 * (nf + 1)));
-    HIP_TRY(up(o_cls, fh->os_class, nd));
-    HIP_TRY(up(o_fl, fh->flags, nd));
-    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
-    HIP_TRY(up(o_pk, ph->k, 4 * nf));
-    HIP_TRY(up(o_pw, ph->w, 4 * nd));
-    HIP_TRY(up(o_pn, ph->n, 4 * nd));
-    if (exsel) HIP_TRY(up(o_exoff, eh->x_off, 8 * nf));
-    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * n_inst));
-    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
-    halda_fleets d = *fh;
-    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
-    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
-    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
-    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
-    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
-    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
-    d.d_avail_metal = F64(14); d.swap = F64(15);
+    if (rc == HALDA_OK) rc = upload(base, T, *fh, s);
+    if (rc == HALDA_OK) rc = upload(base, o_pk, ph->k, 4 * nf, s);
+    if (rc == HALDA_OK) rc = upload(base, o_pw, ph->w, 4 * nd, s);
+    if (rc == HALDA_OK) rc = upload(base, o_pn, ph->n, 4 * nd, s);
+    if (rc == HALDA_OK && exsel) rc = upload(base, o_exoff, eh->x_off, 8 * nf, s);
+    if (rc == HALDA_OK && xsel) rc = upload(base, R.x_off, oh.x_off, 8 * R.n_inst, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*fh, base, T);
     halda_plans dp;
     dp.k = reinterpret_cast<const int32_t *>(base + o_pk);
     dp.w = reinterpret_cast<const int32_t *>(base + o_pw);
@@ -2758,43 +2537,19 @@ static int plans_host(void *ctx, const halda_model *model, const halda_fleets *f
     de.x = eh->x ? reinterpret_cast<double *>(base + o_ex) : nullptr;
     de.c = eh->c ? reinterpret_cast<double *>(base + o_ec) : nullptr;
     de.x_off = exsel ? reinterpret_cast<const int64_t *>(base + o_exoff) : nullptr;
-    if (out_h) {
-        halda_fleet_result r;
-        r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
-        r.obj_value = reinterpret_cast<double *>(base + o_obj);
-        r.w = reinterpret_cast<int32_t *>(base + o_w);
-        r.n = reinterpret_cast<int32_t *>(base + o_n);
-        r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
-        r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
-        r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
-        r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
-        r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
-        const int rc = halda_solve_fleets_plans(ctx, model, &d, ks, n_k, &dp, &de, &r, s);
-        if (rc != HALDA_OK) return rc;
-    } else {
-        const int rc = halda_eval_plans(ctx, model, &d, &dp, &de, s);
-        if (rc != HALDA_OK) return rc;
-    }
-    auto dn = [&](void *dst, size_t o, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    HIP_TRY(dn(eh->status, o_est, 4 * nf));
-    HIP_TRY(dn(eh->obj_value, o_eobj, 8 * nf));
-    HIP_TRY(dn(eh->cycle, o_ecyc, 8 * nf));
-    HIP_TRY(dn(eh->bottleneck, o_ebot, 4 * nf));
-    HIP_TRY(dn(eh->reason, o_erea, 4 * nf));
-    HIP_TRY(dn(eh->x, o_ex, 8 * exs));
-    HIP_TRY(dn(eh->c, o_ec, 8 * exs));
-    if (out_h) {
-        HIP_TRY(dn(out_h->best_k, o_bk, 4 * nf));
-        HIP_TRY(dn(out_h->obj_value, o_obj, 8 * nf));
-        HIP_TRY(dn(out_h->w, o_w, 4 * nd));
-        HIP_TRY(dn(out_h->n, o_n, 4 * nd));
-        HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n_inst));
-        HIP_TRY(dn(out_h->status, o_st, 4 * n_inst));
-        HIP_TRY(dn(out_h->x, o_x, 8 * xs));
-        HIP_TRY(dn(out_h->c, o_c, 8 * xs));
-    }
+    halda_fleet_result r = stage::bind_result(base, R, oh);
+    rc = out_h ? halda_solve_fleets_plans(ctx, model, &d, ks, n_k, &dp, &de, &r, s)
+               : halda_eval_plans(ctx, model, &d, &dp, &de, s);
+    const std::array<stage::Copy, 7> eval_copies = {{{eh->status, o_est, size_t(4 * nf)},
+                                                     {eh->obj_value, o_eobj, size_t(8 * nf)},
+                                                     {eh->cycle, o_ecyc, size_t(8 * nf)},
+                                                     {eh->bottleneck, o_ebot, size_t(4 * nf)},
+                                                     {eh->reason, o_erea, size_t(4 * nf)},
+                                                     {eh->x, o_ex, 8 * exs},
+                                                     {eh->c, o_ec, 8 * exs}}};
+    if (rc == HALDA_OK) rc = download(eval_copies, base, s);
+    if (rc == HALDA_OK) rc = download(stage::result_copies(R, oh), base, s);  // no sweep: every host pointer NULL
+    if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
 }
@@ -2958,89 +2713,31 @@ static int solve_boxed_host(void *ctx, const halda_model *model, const halda_fle
     }
     const int64_t nd = fh->dev_off[nf];
     if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
-    const double *f64[16] = {fh->scpu_b1, fh->sgpu_b1, fh->T_cpu, fh->T_gpu, fh->t_kvcpy_cpu, fh->t_kvcpy_gpu,
-                             fh->t_ram2vram, fh->t_vram2ram, fh->t_comm, fh->s_disk, fh->d_avail_ram, fh->c_cpu,
-                             fh->c_gpu, fh->d_avail_cuda, fh->d_avail_metal, fh->swap};
+    // layout: the table, the bounds that were passed, the results
+    const int32_t *bsrc[4] = {B.w_min, B.w_max, B.n_min, B.n_max};
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    size_t o_b[4];
+    for (int a = 0; a < 4; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nd) : 0;
+    const bool xsel = stage::compact(*out_h);
+    const size_t xs = stage::xc_extent(fh->dev_off, nf, n_k, 1, fh->max_devices, xsel ? out_h->x_off : nullptr);
+    const stage::ResultSlots R = stage::lay_result(lay, *out_h, nf, nd, size_t(nf) * n_k, xs);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int32_t *bsrc[4] = {B.w_min, B.w_max, B.n_min, B.n_max};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_doff = take(8 * (nf + 1)), o_cls = take(nd), o_fl = take(nd), o_f64 = take(8 * nd * 16);
-    size_t o_b[4];
-    for (int a = 0; a < 4; ++a) o_b[a] = bsrc[a] ? take(4 * nd) : 0;
-    const size_t n_inst = size_t(nf) * n_k;
-    const bool xsel = out_h->x_off && (out_h->x || out_h->c);
-    const size_t o_xoff = xsel ? take(8 * n_inst) : 0;
-    const size_t o_bk = take(4 * nf), o_obj = take(8 * nf), o_w = take(4 * nd), o_n = take(4 * nd),
-                 o_obk = take(8 * n_inst), o_st = take(4 * n_inst);
-    size_t xs = n_inst * (7 * size_t(std::max(fh->max_devices, 1)) + 1);
-    if (xsel) {
-        int64_t ext = 0;
-        for (int64_t f = 0; f < nf; ++f) {
-            const int64_t N = 7 * (fh->dev_off[f + 1] - fh->dev_off[f]) + 1;
-            for (int j = 0; j < n_k; ++j) {
-                const int64_t a = out_h->x_off[f * n_k + j];
-                if (a >= 0) ext = std::max(ext, a + N);
-            }
-        }
-        xs = size_t(ext);
-    }
-    const size_t o_x = out_h->x ? take(8 * xs) : 0, o_c = out_h->c ? take(8 * xs) : 0;
-    if (off > c->scratch_bytes) {
-        if (c->scratch) HIP_TRY(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->scratch, off));
-        c->scratch_bytes = off;
-    }
+    int rc = ensure_scratch(c, lay.off);
     char *base = static_cast<char *>(c->scratch);
-    auto up = [&](size_t o, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIP_TRY(up(o_doff, fh->dev_off, 8 * (nf + 1)));
-    HIP_TRY(up(o_cls, fh->os_class, nd));
-    HIP_TRY(up(o_fl, fh->flags, nd));
-    for (int a = 0; a < 16; ++a) HIP_TRY(up(o_f64 + 8 * nd * a, f64[a], 8 * nd));
-    for (int a = 0; a < 4; ++a)
-        if (bsrc[a]) HIP_TRY(up(o_b[a], bsrc[a], 4 * nd));
-    if (xsel) HIP_TRY(up(o_xoff, out_h->x_off, 8 * n_inst));
-    auto F64 = [&](int a) { return reinterpret_cast<const double *>(base + o_f64 + 8 * nd * a); };
-    halda_fleets d = *fh;
-    d.dev_off = reinterpret_cast<const int64_t *>(base + o_doff);
-    d.os_class = reinterpret_cast<const uint8_t *>(base + o_cls);
-    d.flags = reinterpret_cast<const uint8_t *>(base + o_fl);
-    d.scpu_b1 = F64(0); d.sgpu_b1 = F64(1); d.T_cpu = F64(2); d.T_gpu = F64(3); d.t_kvcpy_cpu = F64(4);
-    d.t_kvcpy_gpu = F64(5); d.t_ram2vram = F64(6); d.t_vram2ram = F64(7); d.t_comm = F64(8); d.s_disk = F64(9);
-    d.d_avail_ram = F64(10); d.c_cpu = F64(11); d.c_gpu = F64(12); d.d_avail_cuda = F64(13);
-    d.d_avail_metal = F64(14); d.swap = F64(15);
+    if (rc == HALDA_OK) rc = upload(base, T, *fh, s);
+    for (int a = 0; a < 4 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nd, s);
+    if (rc == HALDA_OK && xsel) rc = upload(base, R.x_off, out_h->x_off, 8 * R.n_inst, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*fh, base, T);
     auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
     const halda_box db = {bdev(0), bdev(1), bdev(2), bdev(3)};
-    halda_fleet_result r;
-    r.best_k = reinterpret_cast<int32_t *>(base + o_bk);
-    r.obj_value = reinterpret_cast<double *>(base + o_obj);
-    r.w = reinterpret_cast<int32_t *>(base + o_w);
-    r.n = reinterpret_cast<int32_t *>(base + o_n);
-    r.obj_by_k = out_h->obj_by_k ? reinterpret_cast<double *>(base + o_obk) : nullptr;
-    r.status = out_h->status ? reinterpret_cast<int32_t *>(base + o_st) : nullptr;
-    r.x = out_h->x ? reinterpret_cast<double *>(base + o_x) : nullptr;
-    r.c = out_h->c ? reinterpret_cast<double *>(base + o_c) : nullptr;
-    r.x_off = xsel ? reinterpret_cast<const int64_t *>(base + o_xoff) : nullptr;
-    {
-        const int rc = solve_boxed(ctx, model, &d, ks, n_k, db, &r, s, who);
-        if (rc != HALDA_OK) return rc;
-    }
-    auto dn = [&](void *dst, size_t o, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, base + o, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    HIP_TRY(dn(out_h->best_k, o_bk, 4 * nf));
-    HIP_TRY(dn(out_h->obj_value, o_obj, 8 * nf));
-    HIP_TRY(dn(out_h->w, o_w, 4 * nd));
-    HIP_TRY(dn(out_h->n, o_n, 4 * nd));
-    HIP_TRY(dn(out_h->obj_by_k, o_obk, 8 * n_inst));
-    HIP_TRY(dn(out_h->status, o_st, 4 * n_inst));
-    HIP_TRY(dn(out_h->x, o_x, 8 * xs));
-    HIP_TRY(dn(out_h->c, o_c, 8 * xs));
+    halda_fleet_result r = stage::bind_result(base, R, *out_h);
+    rc = solve_boxed(ctx, model, &d, ks, n_k, db, &r, s, who);
+    if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
 }
@@ -3110,17 +2807,9 @@ int halda_solve_fleets_multi(void *mctx, const halda_model *model, const halda_f
         offs[r].resize(size_t(hi - lo + 1));
         for (int f = lo; f <= hi; ++f) offs[r][size_t(f - lo)] = fh->dev_off[f] - d0;
         th.emplace_back([&, r, lo, hi, d0]() {
-            halda_fleets sub = *fh;  // min / max devices stay the call's (valid bounds for the block)
+            halda_fleets sub = stage::shifted(*fh, d0);  // min / max devices stay the call's (valid for the block)
             sub.n_fleets = hi - lo;
             sub.dev_off = offs[r].data();
-            sub.os_class = fh->os_class + d0;
-            sub.flags = fh->flags + d0;
-            sub.scpu_b1 = fh->scpu_b1 + d0; sub.sgpu_b1 = fh->sgpu_b1 + d0; sub.T_cpu = fh->T_cpu + d0;
-            sub.T_gpu = fh->T_gpu + d0; sub.t_kvcpy_cpu = fh->t_kvcpy_cpu + d0; sub.t_kvcpy_gpu = fh->t_kvcpy_gpu + d0;
-            sub.t_ram2vram = fh->t_ram2vram + d0; sub.t_vram2ram = fh->t_vram2ram + d0; sub.t_comm = fh->t_comm + d0;
-            sub.s_disk = fh->s_disk + d0; sub.d_avail_ram = fh->d_avail_ram + d0; sub.c_cpu = fh->c_cpu + d0;
-            sub.c_gpu = fh->c_gpu + d0; sub.d_avail_cuda = fh->d_avail_cuda + d0;
-            sub.d_avail_metal = fh->d_avail_metal + d0; sub.swap = fh->swap + d0;
             halda_fleet_result o = *out_h;
             o.best_k = out_h->best_k + lo;
             o.obj_value = out_h->obj_value + lo;
@@ -3230,23 +2919,12 @@ int halda_solve_fleets_sharded_emulated(void *ctx, int32_t world, int32_t report
         if (rc != HALDA_OK) return rc;
     }
     // every virtual rank but report_rank gets its own result arrays (the caller's are report_rank's)
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    std::vector<size_t> o_bk(world), o_obj(world), o_w(world), o_n(world), o_obk(world), o_st(world);
-    for (int r = 0; r < world; ++r) {
-        o_bk[r] = take(4 * nf);
-        o_obj[r] = take(8 * nf);
-        o_w[r] = take(4 * size_t(nd));
-        o_n[r] = take(4 * size_t(nd));
-        o_obk[r] = take(8 * size_t(nf) * n_k);
-        o_st[r] = take(4 * size_t(nf) * n_k);
-    }
-    if (off > c->emu_bytes) {
-        if (c->emu) HIP_TRY(hipFree(c->emu));
-        c->emu = nullptr;
-        c->emu_bytes = 0;
-        HIP_TRY(hipMalloc(&c->emu, off));
-        c->emu_bytes = off;
+    stage::Bump lay;
+    std::vector<stage::ResultSlots> slots;
+    for (int r = 0; r < world; ++r) slots.push_back(stage::lay_result(lay, *out, nf, nd, size_t(nf) * n_k, 0));
+    {
+        const int rc = grow(&c->emu, &c->emu_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
     }
     char *base = static_cast<char *>(c->emu);
     std::vector<ShardRank> R(static_cast<size_t>(world));
@@ -3257,13 +2935,7 @@ int halda_solve_fleets_sharded_emulated(void *ctx, int32_t world, int32_t report
             o = *out;
             continue;
         }
-        o = {};
-        o.best_k = reinterpret_cast<int32_t *>(base + o_bk[r]);
-        o.obj_value = reinterpret_cast<double *>(base + o_obj[r]);
-        o.w = reinterpret_cast<int32_t *>(base + o_w[r]);
-        o.n = reinterpret_cast<int32_t *>(base + o_n[r]);
-        o.obj_by_k = out->obj_by_k ? reinterpret_cast<double *>(base + o_obk[r]) : nullptr;
-        o.status = out->status ? reinterpret_cast<int32_t *>(base + o_st[r]) : nullptr;
+        o = stage::bind_result(base, slots[size_t(r)], *out);  // x / c are NULL (checked above)
     }
     // each all-reduce as one device kernel over the virtual ranks' buffers (in place, every rank's copy
     // gets the reduced value), in the step order of shard_steps
@@ -3340,20 +3012,16 @@ int halda_solve_batch(void *ctx, const halda_batch *in_h, halda_result *out_h) {
         }
     }
     HIP_TRY(hipSetDevice(c->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_ncols = take(4 * n), o_nrows = take(4 * n), o_csr = take(8 * n), o_col = take(8 * n),
-                 o_row = take(8 * n), o_rp = take(4 * n_rp), o_ci = take(4 * nnz), o_val = take(8 * nnz),
-                 o_c = take(8 * n_colsum), o_clb = take(8 * n_colsum), o_cub = take(8 * n_colsum),
-                 o_rlb = take(8 * n_rowsum), o_rub = take(8 * n_rowsum), o_int = take(n_colsum),
-                 o_st = take(4 * n), o_x = take(8 * n_colsum), o_obj = take(8 * n), o_db = take(8 * n),
-                 o_gap = take(8 * n), o_nodes = take(8 * n);
-    if (off > c->scratch_bytes) {
-        if (c->scratch) HIP_TRY(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->scratch, off));
-        c->scratch_bytes = off;
+    stage::Bump lay;
+    const size_t o_ncols = lay.take(4 * n), o_nrows = lay.take(4 * n), o_csr = lay.take(8 * n),
+                 o_col = lay.take(8 * n), o_row = lay.take(8 * n), o_rp = lay.take(4 * n_rp),
+                 o_ci = lay.take(4 * nnz), o_val = lay.take(8 * nnz), o_c = lay.take(8 * n_colsum), o_clb = lay.take(8 * n_colsum), o_cub = lay.take(8 * n_colsum),
+                 o_rlb = lay.take(8 * n_rowsum), o_rub = lay.take(8 * n_rowsum), o_int = lay.take(n_colsum),
+                 o_st = lay.take(4 * n), o_x = lay.take(8 * n_colsum), o_obj = lay.take(8 * n), o_db = lay.take(8 * n),
+                 o_gap = lay.take(8 * n), o_nodes = lay.take(8 * n);
+    {
+        const int rc = ensure_scratch(c, lay.off);
+        if (rc != HALDA_OK) return rc;
     }
     char *base = static_cast<char *>(c->scratch);
     hipStream_t s = c->stream;

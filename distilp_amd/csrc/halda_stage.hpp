@@ -1,0 +1,155 @@
+// The host entry points' staging layer: where a call's table, inputs and results lie in the context's
+// staging buffer, and the device-side structs that point there. Pure layout arithmetic on include/halda.h
+// and the standard library -- no HIP call, so a host compiler builds it alone (tests/stage_layout.cpp);
+// the copies themselves (ensure_scratch, upload, download) are in halda.hip next to grow().
+#pragma once
+
+#include <algorithm>
+#include <array>
+#include <cstddef>
+#include <cstdint>
+
+#include "halda.h"
+
+namespace stage {
+
+// Offsets handed out front to back, each region 256-byte aligned; `off` ends as the buffer's size.
+struct Bump {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~size_t(255);
+        return o;
+    }
+};
+
+// The double arrays of a halda_fleets, in the order every layout and kernel argument uses.
+constexpr int kFields = 16;
+using Field = const double *halda_fleets::*;
+constexpr Field kField[kFields] = {
+    &halda_fleets::scpu_b1,     &halda_fleets::sgpu_b1,     &halda_fleets::T_cpu,         &halda_fleets::T_gpu,
+    &halda_fleets::t_kvcpy_cpu, &halda_fleets::t_kvcpy_gpu, &halda_fleets::t_ram2vram,    &halda_fleets::t_vram2ram,
+    &halda_fleets::t_comm,      &halda_fleets::s_disk,      &halda_fleets::d_avail_ram,   &halda_fleets::c_cpu,
+    &halda_fleets::c_gpu,       &halda_fleets::d_avail_cuda, &halda_fleets::d_avail_metal, &halda_fleets::swap};
+
+// No NULL array in the table.
+inline bool complete(const halda_fleets &F) {
+    bool ok = F.dev_off && F.os_class && F.flags;
+    for (Field f : kField) ok = ok && F.*f;
+    return ok;
+}
+
+// A table of nf fleets / nd devices in a staging buffer: dev_off, os_class, flags, then the fields as rows of
+// one block of kFields x nd doubles (`split` < kFields: two blocks, the first of `split` rows --
+// halda_solve_fleets_host's, whose total decides its transport).
+struct TableLayout {
+    int64_t nf, nd;
+    size_t dev_off, os_class, flags, field[kFields];
+};
+
+inline TableLayout lay_table(Bump &b, int64_t nf, int64_t nd, int split = kFields) {
+    TableLayout t{nf, nd, b.take(8 * (nf + 1)), b.take(nd), b.take(nd), {}};
+    const size_t b0 = b.take(8 * nd * split), b1 = split < kFields ? b.take(8 * nd * (kFields - split)) : 0;
+    for (int a = 0; a < kFields; ++a) t.field[a] = a < split ? b0 + 8 * nd * a : b1 + 8 * nd * (a - split);
+    return t;
+}
+
+// F with its arrays at `base` + the layout's offsets (the scalar members copied).
+inline halda_fleets rebase(const halda_fleets &F, const char *base, const TableLayout &t) {
+    halda_fleets d = F;
+    d.dev_off = reinterpret_cast<const int64_t *>(base + t.dev_off);
+    d.os_class = reinterpret_cast<const uint8_t *>(base + t.os_class);
+    d.flags = reinterpret_cast<const uint8_t *>(base + t.flags);
+    for (int a = 0; a < kFields; ++a) d.*kField[a] = reinterpret_cast<const double *>(base + t.field[a]);
+    return d;
+}
+
+// F with every per-device array moved on by d0 devices (dev_off is the caller's to set).
+inline halda_fleets shifted(const halda_fleets &F, int64_t d0) {
+    halda_fleets s = F;
+    s.os_class += d0;
+    s.flags += d0;
+    for (Field f : kField) s.*f += d0;
+    return s;
+}
+
+// Doubles that x (and c) hold. Row r has off[r + 1] - off[r] devices (dev_off, or the items' sub_off), and
+// the slot of (repeat v, row r, k index j) is (v * n_rows + r) * n_k + j: n_repeat the variants (else 1),
+// n_k = 1 for the plan evaluation's one slot per fleet. Without x_off the dense layout, stride
+// 7 max_devices + 1 per slot; with it max(x_off + 7 M_r + 1) over the slots with x_off >= 0 (none: 0).
+inline size_t xc_extent(const int64_t *off, int64_t n_rows, int64_t n_k, int64_t n_repeat, int64_t max_devices,
+                        const int64_t *x_off) {
+    if (!x_off) return size_t(n_repeat * n_rows * n_k) * (7 * size_t(std::max<int64_t>(max_devices, 1)) + 1);
+    int64_t ext = 0;
+    for (int64_t v = 0; v < n_repeat; ++v)
+        for (int64_t r = 0; r < n_rows; ++r) {
+            const int64_t N = 7 * (off[r + 1] - off[r]) + 1;
+            for (int64_t j = 0; j < n_k; ++j) {
+                const int64_t a = x_off[(v * n_rows + r) * n_k + j];
+                if (a >= 0) ext = std::max(ext, a + N);
+            }
+        }
+    return size_t(ext);
+}
+
+// The compact x / c layout is in use: the caller passed x_off and wants x or c.
+inline bool compact(const halda_fleet_result &h) { return h.x_off && (h.x || h.c); }
+
+// A halda_fleet_result in a staging buffer, for the host's `h`: x_off (compact layout only), then best_k,
+// obj_value, w, n, obj_by_k, status (always reserved), then x and c where the host passed them. rows: the
+// fleets, items or variants x fleets; devs: their devices; n_inst: rows x n_k; ext: xc_extent.
+struct ResultSlots {
+    size_t rows, devs, n_inst, ext;
+    size_t x_off, best_k, obj_value, w, n, obj_by_k, status, x, c;
+};
+
+inline ResultSlots lay_result(Bump &b, const halda_fleet_result &h, size_t rows, size_t devs, size_t n_inst,
+                              size_t ext) {
+    ResultSlots s{rows, devs, n_inst, ext, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    s.x_off = compact(h) ? b.take(8 * n_inst) : 0;
+    s.best_k = b.take(4 * rows);
+    s.obj_value = b.take(8 * rows);
+    s.w = b.take(4 * devs);
+    s.n = b.take(4 * devs);
+    s.obj_by_k = b.take(8 * n_inst);
+    s.status = b.take(4 * n_inst);
+    s.x = h.x ? b.take(8 * ext) : 0;
+    s.c = h.c ? b.take(8 * ext) : 0;
+    return s;
+}
+
+// The device-side result at `base`: the optional arrays bound where the host passed them (per_k: obj_by_k and
+// status whether or not it did -- halda_solve_fleets_host reads the statuses itself).
+inline halda_fleet_result bind_result(char *base, const ResultSlots &s, const halda_fleet_result &h,
+                                      bool per_k = false) {
+    halda_fleet_result r;
+    r.best_k = reinterpret_cast<int32_t *>(base + s.best_k);
+    r.obj_value = reinterpret_cast<double *>(base + s.obj_value);
+    r.w = reinterpret_cast<int32_t *>(base + s.w);
+    r.n = reinterpret_cast<int32_t *>(base + s.n);
+    r.obj_by_k = per_k || h.obj_by_k ? reinterpret_cast<double *>(base + s.obj_by_k) : nullptr;
+    r.status = per_k || h.status ? reinterpret_cast<int32_t *>(base + s.status) : nullptr;
+    r.x = h.x ? reinterpret_cast<double *>(base + s.x) : nullptr;
+    r.c = h.c ? reinterpret_cast<double *>(base + s.c) : nullptr;
+    r.x_off = compact(h) ? reinterpret_cast<const int64_t *>(base + s.x_off) : nullptr;
+    return r;
+}
+
+// What comes back: (host pointer, offset, bytes); an entry with a NULL host pointer or no bytes is skipped.
+struct Copy {
+    void *host;
+    size_t off, bytes;
+};
+
+inline std::array<Copy, 8> result_copies(const ResultSlots &s, const halda_fleet_result &h) {
+    return {{{h.best_k, s.best_k, 4 * s.rows},
+             {h.obj_value, s.obj_value, 8 * s.rows},
+             {h.w, s.w, 4 * s.devs},
+             {h.n, s.n, 4 * s.devs},
+             {h.obj_by_k, s.obj_by_k, 8 * s.n_inst},
+             {h.status, s.status, 4 * s.n_inst},
+             {h.x, s.x, 8 * s.ext},
+             {h.c, s.c, 8 * s.ext}}};
+}
+
+}  // namespace stage
