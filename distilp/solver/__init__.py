@@ -8,6 +8,8 @@ from distilp_amd.solver import (PlanEvaluation, Replacement, evaluate_plan_np, h
                                 halda_evaluate_plans_batch, halda_replace_or_keep, halda_replace_or_keep_batch)
 from distilp_amd.solver import (ReplacementWithin, halda_replace_within, halda_replace_within_batch,  # noqa: F401
                                 halda_solve_bounded, halda_solve_bounded_batch, move_bounds, move_box)
+from distilp_amd.solver import (FrontierPoint, halda_move_frontier, halda_move_frontier_batch,  # noqa: F401
+                                halda_solve_budget)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

@@ -20,7 +20,10 @@ error (exit status 2). --max-move D (with --evaluate-solution) adds one line aft
 plan's k at most D layers per device away from it, `within D: k=..., obj=..., moved_layers=...`, or
 `within D: infeasible`. --max-move-n Dn (with --max-move) also keeps every device's GPU share at most Dn layers
 away from that plan's: the line becomes `within D (n within Dn): k=..., obj=..., moved_layers=...,
-moved_gpu_layers=...`. --cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
+moved_gpu_layers=...`. --move-frontier B (with --evaluate-solution) prints, after those, one line per point
+p = 0 .. B // 2 of the total-move-budget frontier at that plan's k (halda_move_frontier: at most p layers change
+device, moved_layers <= 2 p): `frontier p: moved_layers=..., obj=..., regret=...`, or `frontier p: infeasible`.
+--cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
 halda_solve_bounded) and prints the usual output for that solve. Without these flags the output is unchanged.
 """
 
@@ -146,6 +149,21 @@ def within_line(devices: List[DeviceProfile], model: ModelProfile, plan, max_mov
     return line
 
 
+def frontier_lines(devices: List[DeviceProfile], model: ModelProfile, plan, budget: int) -> List[str]:
+    """--move-frontier B: one line per point of halda_move_frontier around the incumbent (kv_bits "4bit" like
+    the solve above)."""
+    from ..solver.budget import halda_move_frontier
+
+    out = []
+    for p, pt in enumerate(halda_move_frontier(devices, model, plan, budget, kv_bits="4bit")):
+        if pt.plan is None:
+            out.append(f"frontier {p}: infeasible")
+        else:
+            out.append(f"frontier {p}: moved_layers={pt.moved_layers}, obj={pt.obj_value:.6f}, "
+                       f"regret={pt.regret:.6f}")
+    return out
+
+
 def cpu_only_n_max(devices: List[DeviceProfile], picks: Sequence[str]) -> List[int]:
     """--cpu-only NAME_OR_INDEX ...: the n_max list with 0 on the picked devices (a device's name, else its
     0-based index in the fleet's order) and "no bound" elsewhere. ValueError for a pick that names no device."""
@@ -194,6 +212,9 @@ def _parser() -> argparse.ArgumentParser:
                         "layers per device away from it")
     o.add_argument("--max-move-n", type=int, metavar="D",
                    help="With --max-move: also keep every device's GPU layers within D of that plan's")
+    o.add_argument("--move-frontier", type=int, metavar="B",
+                   help="With --evaluate-solution: also print, for every total budget up to B moved layers, the best "
+                        "plan at that plan's k within it")
     g.add_argument("--cpu-only", nargs="+", metavar="NAME_OR_INDEX",
                    help="Solve without using the GPU of these devices (their name or 0-based index)")
     return p
@@ -224,6 +245,10 @@ def main(argv=None) -> int:
         parser.error("--max-move-n requires --max-move")
     if args.max_move_n is not None and args.max_move_n < 0:
         parser.error("--max-move-n must be >= 0")
+    if args.move_frontier is not None and not args.evaluate_solution:
+        parser.error("--move-frontier requires --evaluate-solution")
+    if args.move_frontier is not None and args.move_frontier < 0:
+        parser.error("--move-frontier must be >= 0")
     n_max = None
     if args.cpu_only:
         try:
@@ -289,6 +314,14 @@ def main(argv=None) -> int:
                 print(within_line(devices, model, incumbent, args.max_move))
             else:
                 print(within_line(devices, model, incumbent, args.max_move, args.max_move_n))
+        if args.move_frontier is not None:
+            try:
+                lines = frontier_lines(devices, model, incumbent, args.move_frontier)
+            except ValueError as e:
+                print(f"error: --move-frontier: {e}", file=sys.stderr)
+                return 2
+            for line in lines:
+                print(line)
     return 0
 
 

@@ -2754,6 +2754,116 @@ int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const hal
     return solve_boxed_host(ctx, model, fh, ks, n_k, box ? *box : none, out_h, "halda_solve_fleets_boxed");
 }
 
+// ---------------------------------------------------------------- a total move budget and its frontier
+// halda_solve_fleets_budget: ONE launch of halda_sweep_budget_kernel under a gate formed from the shapes
+// alone (fleets of 1 .. kK1MaxM devices, one k, max_p <= 63, the slice within the LDS budget). No context
+// scratch, no flags, nothing handed back; outside the gate an error and no launch.
+constexpr int kBudgetMaxP = 63;
+
+int64_t halda_budget_lds_bytes(int32_t max_devices, int32_t max_p, int32_t k) {
+    if (max_devices < 1 || max_p < 0 || k < 1) return -1;
+    if (max_devices > 4096 || max_p > 4096) return INT64_MAX;  // far outside the gate; no overflow below
+    return budget_slice(max_devices, max_p, k > 1).total;
+}
+
+static int check_budget_args(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                             const halda_budget *budget, const halda_frontier *fr, const char *who) {
+    if (!ctx || !model || !fleets || !budget || !fr)
+        return fail(HALDA_E_ARG, std::string(who) + ": NULL ctx/model/fleets/budget/frontier");
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(F)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    if (k < 1) return fail(HALDA_E_ARG, std::string(who) + ": k must be >= 1");
+    if (!budget->w0) return fail(HALDA_E_ARG, std::string(who) + ": halda_budget.w0 is NULL");
+    if (!fr->status || !fr->obj || !fr->moved || !fr->w || !fr->n)
+        return fail(HALDA_E_ARG, std::string(who) + ": halda_frontier has a NULL array");
+    if (F.min_devices < 1 || F.max_devices < F.min_devices || F.max_devices > kK1MaxM)
+        return fail(HALDA_E_ARG, std::string(who) + ": every fleet must have 1 .. 64 devices");
+    if (budget->max_p < 0 || budget->max_p > kBudgetMaxP)
+        return fail(HALDA_E_ARG, std::string(who) + ": max_p must be in 0 .. 63");
+    const int64_t lds = halda_budget_lds_bytes(F.max_devices, budget->max_p, k);
+    if (lds > kLdsBudget)
+        return fail(HALDA_E_ARG, std::string(who) + ": the slice of " + std::to_string(lds) +
+                                     " B exceeds the LDS budget of " + std::to_string(kLdsBudget) + " B");
+    return HALDA_OK;
+}
+
+int halda_solve_fleets_budget(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                              const halda_budget *budget, halda_frontier *frontier, void *stream) {
+    const int rc = check_budget_args(ctx, model, fleets, k, budget, frontier, "halda_solve_fleets_budget");
+    if (rc != HALDA_OK) return rc;
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    if (frontier->n_devices < F.n_fleets)
+        return fail(HALDA_E_ARG, "halda_solve_fleets_budget: halda_frontier.n_devices is not dev_off[n_fleets]");
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    SweepArgs A = {};
+    static_cast<halda_model &>(A.Mo) = *model;
+    A.Mo.bvo = model_bvo(*model);
+    A.F = F;
+    A.ks[0] = k;
+    A.Ws[0] = model->L / k;
+    A.n_k = 1;
+    A.mmax = F.max_devices;
+    A.uM = F.min_devices == F.max_devices ? F.max_devices : 0;
+    A.xstride = 7 * int64_t(F.max_devices) + 1;
+    const BudgetArgs Bg{budget->w0,       budget->w_min,   budget->w_max,   budget->max_p, frontier->n_devices,
+                        frontier->status, frontier->obj,   frontier->moved, frontier->w,   frontier->n};
+    const int64_t slice = budget_slice(F.max_devices, budget->max_p, k > 1).total;
+    int per_cu = 0;
+    const void *fn = reinterpret_cast<const void *>(halda_sweep_budget_kernel);
+    HIP_TRY(c->occupancy(fn, slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
+    const unsigned grid =
+        unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(F.n_fleets))));
+    hipLaunchKernelGGL(halda_sweep_budget_kernel, dim3(grid), dim3(64), size_t(slice), s, A, Bg);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const halda_fleets *fh, int32_t k,
+                                   const halda_budget *budget, halda_frontier *fr_h) {
+    int rc = check_budget_args(ctx, model, fh, k, budget, fr_h, "halda_solve_fleets_budget_host");
+    if (rc != HALDA_OK) return rc;
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int64_t nf = fh->n_fleets;
+    if (nf <= 0) return HALDA_OK;
+    const int64_t nd = fh->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    {
+        const int64_t f = stage::bad_incumbent(fh->dev_off, nf, budget->w0, model->L / k);
+        if (f >= 0)
+            return fail(HALDA_E_ARG, "halda_solve_fleets_budget_host: fleet " + std::to_string(f) +
+                                         ": the incumbent needs every w0_i >= 1 and sum w0 = L / k");
+    }
+    const int32_t *bsrc[3] = {budget->w0, budget->w_min, budget->w_max};
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    size_t o_b[3];
+    for (int a = 0; a < 3; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nd) : 0;
+    const stage::FrontierSlots R = stage::lay_frontier(lay, nf, nd, budget->max_p);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *fh, s);
+    for (int a = 0; a < 3 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nd, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*fh, base, T);
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    const halda_budget db = {bdev(0), bdev(1), bdev(2), budget->max_p};
+    halda_frontier r = stage::bind_frontier(base, R, nd);
+    rc = halda_solve_fleets_budget(ctx, model, &d, k, &db, &r, s);
+    if (rc == HALDA_OK) rc = download(stage::frontier_copies(R, *fr_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
 // ---------------------------------------------------------------- several GPUs, one process
 // The fleets of one call are independent: a multi-device context deals them out in contiguous
 // blocks, one host thread per device runs halda_solve_fleets_host on its block, and the results

@@ -152,4 +152,54 @@ inline std::array<Copy, 8> result_copies(const ResultSlots &s, const halda_fleet
              {h.c, s.c, 8 * s.ext}}};
 }
 
+// A halda_frontier in a staging buffer: status, obj and moved per (fleet, point), then the w and n planes.
+struct FrontierSlots {
+    size_t pts, plane;  // n_fleets x (max_p + 1) points; (max_p + 1) x n_devices plane entries
+    size_t status, obj, moved, w, n;
+};
+
+inline FrontierSlots lay_frontier(Bump &b, int64_t nf, int64_t nd, int64_t max_p) {
+    FrontierSlots s{size_t(nf * (max_p + 1)), size_t(nd * (max_p + 1)), 0, 0, 0, 0, 0};
+    s.status = b.take(4 * s.pts);
+    s.obj = b.take(8 * s.pts);
+    s.moved = b.take(4 * s.pts);
+    s.w = b.take(4 * s.plane);
+    s.n = b.take(4 * s.plane);
+    return s;
+}
+
+inline halda_frontier bind_frontier(char *base, const FrontierSlots &s, int64_t nd) {
+    halda_frontier r;
+    r.n_devices = nd;
+    r.status = reinterpret_cast<int32_t *>(base + s.status);
+    r.obj = reinterpret_cast<double *>(base + s.obj);
+    r.moved = reinterpret_cast<int32_t *>(base + s.moved);
+    r.w = reinterpret_cast<int32_t *>(base + s.w);
+    r.n = reinterpret_cast<int32_t *>(base + s.n);
+    return r;
+}
+
+inline std::array<Copy, 5> frontier_copies(const FrontierSlots &s, const halda_frontier &h) {
+    return {{{h.status, s.status, 4 * s.pts},
+             {h.obj, s.obj, 8 * s.pts},
+             {h.moved, s.moved, 4 * s.pts},
+             {h.w, s.w, 4 * s.plane},
+             {h.n, s.n, 4 * s.plane}}};
+}
+
+// The incumbents of a budget call: every w0_i >= 1 and every fleet's sum equal to W. -1, or the first fleet
+// that breaks either.
+inline int64_t bad_incumbent(const int64_t *dev_off, int64_t nf, const int32_t *w0, int64_t W) {
+    for (int64_t f = 0; f < nf; ++f) {
+        int64_t sum = 0;
+        bool ok = true;
+        for (int64_t i = dev_off[f]; i < dev_off[f + 1]; ++i) {
+            ok = ok && w0[i] >= 1;
+            sum += w0[i];
+        }
+        if (!ok || sum != W) return f;
+    }
+    return -1;
+}
+
 }  // namespace stage

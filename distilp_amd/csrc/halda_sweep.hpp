@@ -2253,6 +2253,310 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bo
         sweep_fleet_bounds_tables<BoxRec, BoxArgs>(A, Bx, int(f), w, Wave(lane));
 }
 
+// ---------------------------------------------------------------- total move budget (halda_solve_fleets_budget)
+// The fixed-k problem at the incumbent's k with sum_i |w_i - w0_i| <= B added: the constraint couples the
+// devices, so it is not a narrowing of column bounds. Both plans sum to W, hence sum |delta| = 2 sum delta+;
+// the solver works in p = sum_i max(0, w_i - w0_i) with P = B / 2 and answers every budget p = 0 .. P at once.
+// Only w_i in [w0_i - P, w0_i + P] can matter: the tables G / H are built on that window by table_pass
+// (rows of at most 2 P + 1 entries), and a DP over the devices carries the state (d, p): d the net deviation
+// of the devices so far, p the sum of their positive deviations, valid while the sum of the negative ones,
+// p - d, is in [0, P]. k > 1 scans the cycle-time thresholds T pass by pass (DESIGN.md section 2's exact scan
+// in its pass-per-candidate form: nothing is assumed of the rows' shape).
+struct BudgetArgs {
+    const int32_t *w0, *w_min, *w_max;  // device layout; w_min / w_max may be NULL
+    int P;                              // halda_budget.max_p
+    int64_t nd;                         // devices of the table: the stride of the w / n planes
+    int32_t *status;                    // [fleet][P + 1]
+    double *obj;                        // [fleet][P + 1]
+    int32_t *moved;                     // [fleet][P + 1]
+    int32_t *w, *n;                     // [P + 1][nd]
+};
+
+// The wave's LDS slice (bytes): G and, for k > 1, H as mmax rows of 2 P + 1 doubles (an odd stride); two
+// value planes of S = (2 P + 1)(P + 1) doubles; one arg-min byte plane of S per device; per device wlo - w0;
+// per point the plan's table indices (bytes) and its n (ints).
+struct BudgetSlice {
+    int64_t G, H, V, arg, off, plan, nplan, total;
+    int S, RS;
+};
+
+__host__ __device__ inline BudgetSlice budget_slice(int mmax, int P, bool kc) {
+    BudgetSlice s;
+    s.RS = 2 * P + 1;
+    s.S = (2 * P + 1) * (P + 1);
+    int64_t o = 0;
+    s.G = o;     o = align16(o + int64_t(mmax) * s.RS * 8);
+    s.H = o;     o = align16(o + (kc ? int64_t(mmax) * s.RS * 8 : 0));
+    s.V = o;     o = align16(o + 2 * int64_t(s.S) * 8);
+    s.arg = o;   o = align16(o + int64_t(mmax) * s.S);
+    s.off = o;   o = align16(o + int64_t(mmax) * 4);
+    s.plan = o;  o = align16(o + int64_t(P + 1) * mmax);
+    s.nplan = o; o = align16(o + int64_t(P + 1) * mmax * 4);
+    s.total = o;
+    return s;
+}
+
+struct BudgetCtx {
+    double *V;       // two planes of S
+    uint8_t *arg;    // [device][S]
+    int *off;        // [device] wlo - w0
+    uint8_t *plan;   // [point][mmax]
+    int *nplan;      // [point][mmax]
+    int S, RS, P, mmax;
+};
+
+constexpr uint8_t kBudgetNone = 255;  // arg-min of a state no transition reaches (2 P <= 126 < 255)
+
+// One budget DP over the M devices with the entries H > T masked (kc == 0: no mask). Lanes own states; a
+// transition tries the device's R1 entries in ascending order and keeps the first least value (strict "<":
+// the least w_i). Returns the plane that holds F_M; arg holds every device's arg-min plane.
+__device__ inline const double *budget_dp(const WaveCtx &w, const BudgetCtx &b, int M, int R1, double kc, double T,
+                                          int lane) {
+    const int P = b.P, P1 = b.P + 1, S = b.S;
+    double *cur = b.V, *nxt = b.V + S;
+    for (int s = lane; s < S; s += 64) cur[s] = s == P * P1 ? 0.0 : kInf;
+    wave_sync();
+    for (int i = 0; i < M; ++i) {
+        const int oi = b.off[i];
+        const double *Gi = w.G + i * b.RS, *Hi = w.H + i * b.RS;
+        uint8_t *ai = b.arg + int64_t(i) * S;
+        for (int s = lane; s < S; s += 64) {
+            const int dq = s / P1, p = s - dq * P1, d = dq - P, q = p - d;
+            double best = kInf;
+            int be = kBudgetNone;
+            if (q >= 0 && q <= P) {
+                for (int e = 0; e < R1; ++e) {
+                    const int delta = oi + e;
+                    const int pp = p - max(0, delta), qp = q - max(0, -delta);
+                    if (pp < 0 || qp < 0) continue;
+                    if (kc > 0.0 && !(Hi[e] <= T)) continue;
+                    const double v = cur[(pp - qp + P) * P1 + pp] + Gi[e];
+                    if (v < best) {
+                        best = v;
+                        be = e;
+                    }
+                }
+            }
+            nxt[s] = best;
+            ai[s] = uint8_t(be);
+        }
+        wave_sync();
+        double *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    return cur;
+}
+
+// The plan of point p (lane p) with a finite F_M[0][p]: from state (d = 0, p) after the last device back to
+// (0, 0). Every state on that path has a finite value, so its arg-min is an entry of the row and the
+// predecessor it names is a valid state.
+__device__ inline void budget_backtrack(const BudgetCtx &b, int M, int p) {
+    const int P = b.P, P1 = b.P + 1;
+    int d = 0, pc = p;
+    for (int i = M - 1; i >= 0; --i) {
+        const int e = b.arg[int64_t(i) * b.S + (d + P) * P1 + pc];
+        b.plan[p * b.mmax + i] = uint8_t(e);
+        const int delta = b.off[i] + e;
+        d -= delta;
+        pc -= max(0, delta);
+    }
+}
+
+__device__ inline void sweep_fleet_budget(const SweepArgs &A, const BudgetArgs &Bg, int f, const WaveCtx &w,
+                                          const BudgetCtx &b, const Wave &sg) {
+    const int lane = sg.sl;
+    const int P = Bg.P, P1 = P + 1;
+    const int k = A.ks[0], W = A.Ws[0];
+    const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
+    const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
+    const bool act = lane < M;
+    const bool pt = lane < P1;
+    const int64_t g0 = d0 + (act ? lane : 0);
+    const DevFields mf = load_fields(A.F, g0);
+    const int wmn = Bg.w_min ? Bg.w_min[g0] : 0;
+    const int wmx = Bg.w_max ? Bg.w_max[g0] : 0x7fffffff;
+    const int w0 = min(max(Bg.w0[g0], -kBoundCap), kBoundCap);
+    BoundRec me = {};
+    int bad = 0;
+    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
+    bad = act ? bad : 0;
+    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
+    fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
+    bad = sg.any(bad != 0) ? 1 : 0;
+    const int lo = min(max(1, wmn), kBoundCap);
+    const int sumlo = sg.sum_i(act ? lo : 0);
+    const int sumw0 = sg.sum_i(act ? w0 : 0);
+    const bool w0bad = sg.any(act && w0 < 1) || sumw0 != W;  // the host entries reject it before the launch
+    // the window: only w_i within P of w0_i can matter
+    const int wlo = max(lo, w0 - P), whi = min(min(W, wmx), w0 + P);
+    const int sumwlo = sg.sum_i(act ? min(wlo, kBoundCap) : 0);
+    constexpr int kOpen = 1000;
+    int st = kOpen;
+    if (!(W < 1000000)) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumlo > W) st = HALDA_STATUS_INFEASIBLE;
+    else if (bad || w0bad) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumwlo > W) st = HALDA_STATUS_INFEASIBLE;  // the budget cannot reach the box
+    const int64_t fo = int64_t(f) * P1;
+    if (st != kOpen) {
+        if (pt) {
+            Bg.status[fo + lane] = st;
+            Bg.obj[fo + lane] = kInf;
+            Bg.moved[fo + lane] = 0;
+        }
+        if (act)
+            for (int p = 0; p < P1; ++p) {
+                Bg.w[int64_t(p) * Bg.nd + d0 + lane] = 0;
+                Bg.n[int64_t(p) * Bg.nd + d0 + lane] = 0;
+            }
+        return;
+    }
+    opaque_rec(me);
+    const double kc = double(k - 1);
+    me.W = W;
+    me.wlo = wlo;
+    me.whi = whi;
+    if (act) b.off[lane] = wlo - w0;
+    Inst I = {};
+    I.inst = f;
+    I.M = M;
+    I.W = W;
+    I.Wd = double(W);
+    I.kc = kc;
+    I.iC = 7 * M;
+    I.R1 = min(W - sumwlo, 2 * P) + 1;
+    I.RS = b.RS;
+    const int R1 = I.R1;
+    table_pass<64>(bound_src(&me), w, I, lane);
+    wave_sync();
+    // best[p] (lane p): the least (k - 1) T + F^T_M[0][p] and the T that gave it
+    double best = kInf, bT = kInf;
+    if (kc == 0.0) {
+        const double *F = budget_dp(w, b, M, R1, 0.0, kInf, lane);
+        if (pt) best = F[P * P1 + lane];
+        wave_sync();
+        if (pt && best < kInf) budget_backtrack(b, M, lane);
+    } else {
+        const double *F = budget_dp(w, b, M, R1, 0.0, kInf, lane);
+        const double sinf = pt ? F[P * P1 + lane] : kInf;
+        // the first threshold that leaves every device an entry: max_i min_e H_i[e]
+        double hmin = kInf;
+        if (act)
+            for (int e = 0; e < R1; ++e) hmin = fmin(hmin, w.H[lane * b.RS + e]);
+        double T = sg.max_f64(act ? hmin : 0.0);
+        while (T < kInf) {
+            // point p is closed once (k - 1) T + S_inf[p] >= best[p]; the scan stops when every point is
+            if (!sg.any(pt && !(kc * T + sinf >= best))) break;
+            wave_sync();
+            F = budget_dp(w, b, M, R1, kc, T, lane);
+            if (pt) {
+                const double c = kc * T + F[P * P1 + lane];
+                if (c < best) {  // strict: the earliest T wins
+                    best = c;
+                    bT = T;
+                }
+            }
+            double nx = kInf;  // the next distinct finite H above T
+            for (int t = lane; t < M * R1; t += 64) {
+                const int i = t / R1, e = t - i * R1;
+                const double h = w.H[i * b.RS + e];
+                if (h > T) nx = fmin(nx, h);
+            }
+            T = sg.min_f64(nx);
+        }
+        // the arg-min planes of each distinct winning T, once, for the points it won
+        bool left = pt && best < kInf;
+        while (sg.any(left)) {
+            const double Tw = sg.min_f64(left ? bT : kInf);
+            wave_sync();
+            budget_dp(w, b, M, R1, kc, Tw, lane);
+            if (left && bT == Tw) {
+                budget_backtrack(b, M, lane);
+                left = false;
+            }
+        }
+    }
+    wave_sync();
+    // price every exact-p plan lane-per-device, the constants added in sweep_fleet's order
+    double objv = kInf;
+    int movedv = 0;
+    for (int p = 0; p < P1; ++p) {
+        if (!(sg.bcast(best, p) < kInf)) continue;
+        double gd = 0.0, H = 0.0;
+        int wl = 0, n = 0;
+        if (act) {
+            wl = wlo + b.plan[p * b.mmax + lane];
+            double Pc, Qc;
+            int sl[4] = {0, 0, 0, 0};
+            split_full(me, wl, gd, n, sl);
+            dev_cycle(me, wl, n, sl, Pc, Qc);
+            H = fmax(0.0, Qc >= Pc ? 0.5 * (Pc + Qc) : Pc);
+            b.nplan[p * b.mmax + lane] = n;
+        }
+        const double hmax = sg.max_f64(act ? H : 0.0);
+        double obj = sg.sum_f64(act ? gd : 0.0) + kc * hmax;
+        obj = obj + tsum;
+        obj = obj + xsum;
+        obj = obj + kappa;
+        const int mv = sg.sum_i(act ? abs(wl - w0) : 0);
+        if (lane == p) {
+            objv = obj;
+            movedv = mv;
+        }
+    }
+    wave_sync();
+    // point p: the best exact point p' <= p, the fewest moves among equal objectives (strict "<", ascending)
+    double run = kInf;
+    int src = -1, runmv = 0;
+    for (int p = 0; p < P1; ++p) {
+        const double o = sg.bcast(objv, p);
+        const int mv = sg.bcast(movedv, p);
+        if (lane >= p && o < run) {
+            run = o;
+            src = p;
+            runmv = mv;
+        }
+    }
+    if (pt) {
+        Bg.status[fo + lane] = src >= 0 ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+        Bg.obj[fo + lane] = run;
+        Bg.moved[fo + lane] = runmv;
+    }
+    for (int p = 0; p < P1; ++p) {
+        const int sp = sg.bcast(src, p);
+        if (act) {
+            Bg.w[int64_t(p) * Bg.nd + d0 + lane] = sp >= 0 ? wlo + b.plan[sp * b.mmax + lane] : 0;
+            Bg.n[int64_t(p) * Bg.nd + d0 + lane] = sp >= 0 ? b.nplan[sp * b.mmax + lane] : 0;
+        }
+    }
+    wave_sync();  // the slice is rewritten by the wave's next fleet
+}
+
+// halda_sweep_budget_kernel: one wave per fleet in 64-thread workgroups on a persistent grid, each with its
+// dynamic LDS slice (budget_slice of the launch's shape); workgroup b takes fleets b, b + grid, .... No
+// spin-wait and nothing shared between waves: the only synchronisation is wave_sync within the one wave.
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_budget_kernel(SweepArgs A,
+                                                                                           BudgetArgs Bg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const BudgetSlice sl = budget_slice(A.mmax, Bg.P, A.ks[0] > 1);
+    WaveCtx w = {};
+    w.G = reinterpret_cast<double *>(smem + sl.G);
+    w.H = reinterpret_cast<double *>(smem + sl.H);
+    BudgetCtx b;
+    b.V = reinterpret_cast<double *>(smem + sl.V);
+    b.arg = smem + sl.arg;
+    b.off = reinterpret_cast<int *>(smem + sl.off);
+    b.plan = smem + sl.plan;
+    b.nplan = reinterpret_cast<int *>(smem + sl.nplan);
+    b.S = sl.S;
+    b.RS = sl.RS;
+    b.P = Bg.P;
+    b.mmax = A.mmax;
+    const int nf = A.F.n_fleets;
+    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) sweep_fleet_budget(A, Bg, int(f), w, b, Wave(lane));
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the

@@ -2,6 +2,8 @@
 
 from .bounds import (ReplacementWithin, halda_replace_within, halda_replace_within_batch,  # noqa: F401
                      halda_solve_bounded, halda_solve_bounded_batch, move_bounds, move_box)
+from .budget import (FrontierPoint, halda_move_frontier, halda_move_frontier_batch,  # noqa: F401
+                     halda_solve_budget)
 from .coefficients import HALDAResult, ILPResult
 from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
@@ -15,7 +17,8 @@ __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solv
            "halda_leave_one_out_batch", "halda_select_devices", "halda_solve_variants", "halda_context_sweep",
            "model_grid", "halda_evaluate_plan", "halda_evaluate_plans_batch", "halda_replace_or_keep",
            "halda_replace_or_keep_batch", "halda_solve_bounded", "halda_solve_bounded_batch", "move_bounds", "move_box",
-           "halda_replace_within", "halda_replace_within_batch", "ReplacementWithin", "evaluate_plan_np",
+           "halda_replace_within", "halda_replace_within_batch", "ReplacementWithin", "halda_move_frontier",
+           "halda_move_frontier_batch", "halda_solve_budget", "FrontierPoint", "evaluate_plan_np",
            "PlanEvaluation", "Replacement", "HALDAResult",
            "ILPResult"]
 

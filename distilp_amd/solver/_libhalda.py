@@ -91,7 +91,8 @@ EXPORTS = ("halda_version", "halda_init", "halda_solve_batch", "halda_solve_batc
            "halda_last_variants_route", "halda_eval_plans", "halda_eval_plans_host", "halda_solve_fleets_plans",
            "halda_solve_fleets_plans_host", "halda_last_plans_route", "halda_set_plans_path",
            "halda_solve_fleets_bounded", "halda_solve_fleets_bounded_host", "halda_last_bounds_route",
-           "halda_set_bounds_path", "halda_solve_fleets_boxed", "halda_solve_fleets_boxed_host")
+           "halda_set_bounds_path", "halda_solve_fleets_boxed", "halda_solve_fleets_boxed_host",
+           "halda_solve_fleets_budget", "halda_solve_fleets_budget_host", "halda_budget_lds_bytes")
 
 _lib = None
 _lib_lock = threading.Lock()

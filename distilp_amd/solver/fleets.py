@@ -137,6 +137,34 @@ def _bind_bounds(lib):
     return lib
 
 
+class HaldaBudgetC(ctypes.Structure):
+    _fields_ = [("w0", ctypes.c_void_p), ("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p),
+                ("max_p", ctypes.c_int32)]
+
+
+class HaldaFrontierC(ctypes.Structure):
+    _fields_ = [("n_devices", ctypes.c_int64), ("status", ctypes.c_void_p), ("obj", ctypes.c_void_p),
+                ("moved", ctypes.c_void_p), ("w", ctypes.c_void_p), ("n", ctypes.c_void_p)]
+
+
+def _bind_budget(lib):
+    """The budget entries' prototypes (halda_solve_fleets_budget, its host form, halda_budget_lds_bytes)."""
+    lib = _bind(lib)
+    if getattr(lib, "_budget_bound", False):
+        return lib
+    P = ctypes.POINTER
+    lib.halda_solve_fleets_budget.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_int32,
+                                              P(HaldaBudgetC), P(HaldaFrontierC), ctypes.c_void_p]
+    lib.halda_solve_fleets_budget.restype = ctypes.c_int
+    lib.halda_solve_fleets_budget_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_int32,
+                                                   P(HaldaBudgetC), P(HaldaFrontierC)]
+    lib.halda_solve_fleets_budget_host.restype = ctypes.c_int
+    lib.halda_budget_lds_bytes.argtypes = [ctypes.c_int32] * 3
+    lib.halda_budget_lds_bytes.restype = ctypes.c_int64
+    lib._budget_bound = True
+    return lib
+
+
 def _bind(lib):
     if getattr(lib, "_fleets_bound", False):
         return lib
@@ -1011,6 +1039,62 @@ class DeviceFleetTable:
                                                 ctypes.byref(self.res), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"halda_solve_fleets_bounded failed ({rc}): {last_error(lib)}")
+
+    def set_budget(self, k, w0, max_p: int, w_min=None, w_max=None) -> None:
+        """Give the table its resident incumbents for halda_solve_fleets_budget: device tensors budget_w0
+        [n_devices] (int32; the caller checks every w0_i >= 1 and every fleet's sum = L // k) and, where given,
+        budget_min / budget_max, next to the frontier's result buffers budget_out: status / obj / moved
+        [n_fleets, max_p + 1], w / n [max_p + 1, n_devices]. A streaming caller rewrites budget_w0 in place
+        between launches (e.g. copies out["w"] into it). ValueError, as the other Python entries raise it, for
+        a shape outside the launch's gate (budget.check_gate)."""
+        import torch
+
+        from .budget import check_gate
+
+        sizes = self.table.sizes()
+        if isinstance(max_p, bool) or int(max_p) != max_p or max_p < 0:
+            raise ValueError(f"max_p: {max_p!r} is not a non-negative integer")
+        if int(k) < 1:
+            raise ValueError(f"k = {k} must be positive")
+        check_gate(int(sizes.max()), int(sizes.min()), int(max_p), int(k))
+        dev = self.out["best_k"].device
+        nf, nd, P1 = self.table.n_fleets, self.table.n_devices, int(max_p) + 1
+
+        def tensor(a):
+            if a is None:
+                return None
+            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))
+            if t.numel() != nd:
+                raise ValueError(f"budget array of {t.numel()} entries, expected {nd}")
+            return t.to(device=dev, dtype=torch.int32).contiguous().clone()
+
+        if w0 is None:
+            raise ValueError("set_budget needs the incumbents' w0")
+        self.budget_k = int(k)
+        self.budget_w0, self.budget_min, self.budget_max = tensor(w0), tensor(w_min), tensor(w_max)
+        self.budget_out = {"status": torch.empty((nf, P1), dtype=torch.int32, device=dev),
+                           "obj": torch.empty((nf, P1), dtype=torch.float64, device=dev),
+                           "moved": torch.empty((nf, P1), dtype=torch.int32, device=dev),
+                           "w": torch.empty((P1, nd), dtype=torch.int32, device=dev),
+                           "n": torch.empty((P1, nd), dtype=torch.int32, device=dev)}
+        o = self.budget_out
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._budget_c = HaldaBudgetC(ptr(self.budget_w0), ptr(self.budget_min), ptr(self.budget_max), int(max_p))
+        self._frontier_c = HaldaFrontierC(nd, o["status"].data_ptr(), o["obj"].data_ptr(), o["moved"].data_ptr(),
+                                          o["w"].data_ptr(), o["n"].data_ptr())
+
+    def launch_with_budget(self, ctx, stream: int) -> None:
+        """Enqueue the move frontier of every fleet around the resident incumbents on `stream`
+        (halda_solve_fleets_budget): self.budget_out. set_budget has checked the gate."""
+        if getattr(self, "_budget_c", None) is None:
+            raise RuntimeError("launch_with_budget: call set_budget first")
+        lib = _bind_budget(ctx.lib)
+        with ctx._lock:
+            rc = lib.halda_solve_fleets_budget(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
+                                               self.budget_k, ctypes.byref(self._budget_c),
+                                               ctypes.byref(self._frontier_c), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"halda_solve_fleets_budget failed ({rc}): {last_error(lib)}")
 
 
 class RcclComm:

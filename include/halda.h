@@ -548,6 +548,53 @@ int halda_solve_fleets_boxed(void *ctx, const halda_model *model, const halda_fl
 int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
                                   int32_t n_k, const halda_box *box, halda_fleet_result *out);
 
+/* A total move budget around a deployed plan: the best plan within B moved layers, and its frontier.
+ *
+ * The problem is the fixed-k MILP at the incumbent's k (one k per call, W = L / k) with the optional w_min /
+ * w_max of halda_bounds on the w columns and ONE added constraint that couples the devices:
+ * sum_i |w_i - w0_i| <= B. n, the slacks, z and C are re-optimised freely. Both plans sum to W, so
+ * sum |delta| is even; the call works in p = sum_i max(0, w_i - w0_i), the layers that change device, and
+ * answers every p = 0 .. max_p (B = 2 p) at once: point p is the optimum over the plans with
+ * sum max(0, delta) <= p, and among equal objectives the plan with the fewest moves. The frontier is
+ * non-increasing in p; point 0 is "w pinned, n re-optimised".
+ *
+ * Per point: status HALDA_STATUS_OPTIMAL, _INFEASIBLE (no plan within the budget and the bounds) or
+ * _UNSUPPORTED (W >= 1e6, a rejected record, or -- device entry only -- an incumbent with w0_i < 1 or
+ * sum w0 != W, which the host entry rejects with HALDA_E_ARG before any GPU work); obj the reference's
+ * c.x + sum t_comm + sum xi + kappa (+inf where not optimal), the bits halda_eval_plans gives the returned
+ * plan; moved = sum |w - w0| of the returned plan (<= 2 p); w and n as max_p + 1 planes in the table's device
+ * layout (zeros where not optimal).
+ *
+ * Gate, from the shapes alone: every fleet has 1 .. 64 devices, 0 <= max_p <= 63, and
+ * halda_budget_lds_bytes(max_devices, max_p, k) is at most 160 KiB. Outside it the call returns HALDA_E_ARG
+ * and launches nothing: there is no fallback. One launch of halda_sweep_budget_kernel (one wave per fleet;
+ * no context scratch, nothing shared between waves, so launches on different streams need no ordering). */
+typedef struct halda_budget {
+    const int32_t *w0;            /* [dev_off[n_fleets]] the incumbents' layer counts, device layout */
+    const int32_t *w_min, *w_max; /* as halda_bounds; either may be NULL */
+    int32_t max_p;                /* P = B / 2 */
+} halda_budget;
+
+typedef struct halda_frontier {
+    int64_t n_devices; /* dev_off[n_fleets]: the stride of the w / n planes */
+    int32_t *status;   /* [n_fleets * (max_p + 1)] */
+    double *obj;       /* [n_fleets * (max_p + 1)] */
+    int32_t *moved;    /* [n_fleets * (max_p + 1)] */
+    int32_t *w, *n;    /* [(max_p + 1) * n_devices]: plane p holds point p's plan of every fleet */
+} halda_frontier;
+
+/* Asynchronous on `stream`; fleets, budget and frontier hold device arrays. */
+int halda_solve_fleets_budget(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                              const halda_budget *budget, halda_frontier *frontier, void *stream);
+
+/* Synchronous variant on HOST arrays (frontier->n_devices is taken from dev_off). */
+int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                                   const halda_budget *budget, halda_frontier *frontier);
+
+/* Bytes of dynamic LDS per wave of halda_sweep_budget_kernel for this shape (the gate's figure); -1 for
+ * max_devices < 1, max_p < 0 or k < 1. No context needed. */
+int64_t halda_budget_lds_bytes(int32_t max_devices, int32_t max_p, int32_t k);
+
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */
 int halda_resident_release(void *ctx);
