@@ -2615,6 +2615,10 @@ static int solve_boxed(void *ctx, const halda_model *model, const halda_fleets *
     if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
     const bool nbox = B.n_min || B.n_max;
+    // the fused kernels' second argument: the box kernels take all four arrays, the others the w pair
+    BoundArgs Bd{B.w_min, B.w_max};
+    BoxArgs Bx{B.w_min, B.w_max, B.n_min, B.n_max};
+    void *bargs = nbox ? static_cast<void *>(&Bx) : static_cast<void *>(&Bd);
     // automatic = fused where admissible: one launch against the general route's lowering, patch, screen,
     // solve and pick launches
     if (c->bounds_path != 1 && c->fleets_fused && n_k <= 64) {
@@ -2629,12 +2633,11 @@ static int solve_boxed(void *ctx, const halda_model *model, const halda_fleets *
             A.want = 0;
             c->fleet_timed = false;
             c->have_lowered = false;
-            const BoundArgs Bd{B.w_min, B.w_max};
-            const BoxArgs Bx{B.w_min, B.w_max, B.n_min, B.n_max};
+            const void *fn = nbox ? reinterpret_cast<const void *>(halda_sweep_box_kernel)
+                                  : reinterpret_cast<const void *>(halda_sweep_bounds_kernel);
+            void *args[] = {&A, bargs};
             if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            if (nbox) hipLaunchKernelGGL(halda_sweep_box_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, Bx);
-            else hipLaunchKernelGGL(halda_sweep_bounds_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, Bd);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipLaunchKernel(fn, dim3(p.grid1), dim3(p.block1), args, 0, s));
             if (c->timing) {
                 HIP_TRY(hipEventRecord(c->evf1, s));
                 c->fleet_timed = true;
@@ -2661,14 +2664,9 @@ static int solve_boxed(void *ctx, const halda_model *model, const halda_fleets *
             HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
             const unsigned grid =
                 unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(p.nf))));
-            const BoundArgs Bd{B.w_min, B.w_max};
-            const BoxArgs Bx{B.w_min, B.w_max, B.n_min, B.n_max};
+            void *args[] = {&A, bargs};
             if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            if (nbox)
-                hipLaunchKernelGGL(halda_sweep_box_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bx);
-            else
-                hipLaunchKernelGGL(halda_sweep_bounds_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bd);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(64), args, size_t(p.slice), s));
             if (c->timing) {
                 HIP_TRY(hipEventRecord(c->evf1, s));
                 c->fleet_timed = true;

@@ -375,6 +375,24 @@ struct WaveCtx {
     uint8_t *dparg;  // register sweep: the wave's arg-min strip of the k = 1 DP fallback (k1_dp)
 };
 
+// The wave's arrays in its slice at base (LDS, or a global-table launch's scratch).
+__device__ inline WaveCtx wave_ctx(unsigned char *base, const Slice &sl) {
+    WaveCtx w = {};
+    w.rows = reinterpret_cast<int2 *>(base + sl.rows);
+    w.cyc = reinterpret_cast<double *>(base + sl.cyc);
+    w.cost = reinterpret_cast<double *>(base + sl.cost);
+    w.cnt = reinterpret_cast<int *>(base + sl.cnt);
+    w.st0 = reinterpret_cast<int *>(base + sl.st0);
+    w.st1 = reinterpret_cast<int *>(base + sl.st1);
+    w.rng = reinterpret_cast<int2 *>(base + sl.rng);
+    w.inc = reinterpret_cast<double *>(base + sl.inc);
+    w.G = reinterpret_cast<double *>(base + sl.G);
+    w.H = reinterpret_cast<double *>(base + sl.H);
+    w.work = reinterpret_cast<double *>(base + sl.work);
+    w.split = reinterpret_cast<uint16_t *>(base + sl.split);
+    return w;
+}
+
 // Device record: costs / decoded rows from LDS, integer bounds from the batch.
 __device__ inline void load_dev(Dev &d, const halda_batch &B, const WaveCtx &w, int64_t co, int M, int i,
                                 double Wd) {
@@ -1636,21 +1654,7 @@ __device__ inline void solve_general(halda_batch B, halda_result Rz, uint8_t *cl
     // gated: only flagged work can be here -- k = 1 hand-backs (no k > 1 or wide instance in the batch), or
     // the k > 1 instances the screen flagged (the k > 1 launch of launch())
     if (gated && __hip_atomic_load(hb_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != launch_id) return;
-    const Slice sl = make_slice(mmax, r1max, tab, tab_kc);
-    unsigned char *base = slice_base;
-    WaveCtx w;
-    w.rows = reinterpret_cast<int2 *>(base + sl.rows);
-    w.cyc = reinterpret_cast<double *>(base + sl.cyc);
-    w.cost = reinterpret_cast<double *>(base + sl.cost);
-    w.cnt = reinterpret_cast<int *>(base + sl.cnt);
-    w.st0 = reinterpret_cast<int *>(base + sl.st0);
-    w.st1 = reinterpret_cast<int *>(base + sl.st1);
-    w.rng = reinterpret_cast<int2 *>(base + sl.rng);
-    w.inc = reinterpret_cast<double *>(base + sl.inc);
-    w.G = reinterpret_cast<double *>(base + sl.G);
-    w.H = reinterpret_cast<double *>(base + sl.H);
-    w.work = reinterpret_cast<double *>(base + sl.work);
-    w.split = reinterpret_cast<uint16_t *>(base + sl.split);
+    const WaveCtx w = wave_ctx(slice_base, make_slice(mmax, r1max, tab, tab_kc));
 
     // this wave owns instances blockIdx.x + j * gridDim.x; a 64-wide window of
     // them is screened by one ballot over the verdict bytes
@@ -1771,7 +1775,15 @@ __host__ __device__ inline K1Slice make_k1_slice(int mmax) {
     return s;
 }
 
-
+// The k = 1 fast path's arrays in its slice: the rows, their count and the cyc / cost records.
+__device__ inline WaveCtx wave_ctx(unsigned char *base, const K1Slice &sl) {
+    WaveCtx w = {};
+    w.rows = reinterpret_cast<int2 *>(base + sl.rows);
+    w.cyc = reinterpret_cast<double *>(base + sl.cyc);
+    w.cost = reinterpret_cast<double *>(base + sl.cost);
+    w.cnt = reinterpret_cast<int *>(base + sl.cnt);
+    return w;
+}
 
 enum { K1_OK = 0, K1_INFEASIBLE = 1, K1_FALLBACK = 2 };
 
@@ -2721,11 +2733,7 @@ __global__ __launch_bounds__(64, HALDA_K1_WAVES_PER_SIMD) void halda_solve_k1_se
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const K1Slice sl = make_k1_slice(min(mmax, kK1MaxM));
-    WaveCtx w = {};
-    w.rows = reinterpret_cast<int2 *>(smem + sl.rows);
-    w.cyc = reinterpret_cast<double *>(smem + sl.cyc);
-    w.cost = reinterpret_cast<double *>(smem + sl.cost);
-    w.cnt = reinterpret_cast<int *>(smem + sl.cnt);
+    const WaveCtx w = wave_ctx(smem, sl);
     unsigned char *scol = smem + sl.stage;
     unsigned char *sval = smem + sl.stage + kStageColBytes;
     K1Screen sc{mmax, r1max, tab, tab_kc, gen_flag, launch_id, cls, &Rz, false};
@@ -2790,11 +2798,7 @@ __global__ __launch_bounds__(64, HALDA_K1_WAVES_PER_SIMD) void halda_solve_k1_ke
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const K1Slice sl = make_k1_slice(min(mmax, kK1MaxM));
-    WaveCtx w = {};
-    w.rows = reinterpret_cast<int2 *>(smem + sl.rows);
-    w.cyc = reinterpret_cast<double *>(smem + sl.cyc);
-    w.cost = reinterpret_cast<double *>(smem + sl.cost);
-    w.cnt = reinterpret_cast<int *>(smem + sl.cnt);
+    const WaveCtx w = wave_ctx(smem, sl);
     unsigned char *scol = smem + sl.stage;
     unsigned char *sval = smem + sl.stage + kStageColBytes;
     const int S = gridDim.x;

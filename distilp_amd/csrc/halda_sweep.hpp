@@ -658,6 +658,25 @@ __device__ inline void put_xc(const SweepArgs &A, const FleetOut &O, int64_t ins
     }
 }
 
+// The C column of the same solution, x = the largest cycle time and c = k - 1: one lane's pair of stores.
+__device__ inline void put_xc_cycle(const SweepArgs &A, const FleetOut &O, int64_t inst, int M, double hmax,
+                                    double kc) {
+    const int64_t at = xc_at(A, inst);
+    if (at >= 0 && (A.outs & kOutX)) O.x[at + 7 * M] = hmax;
+    if (at >= 0 && (A.outs & kOutC)) O.c[at + 7 * M] = kc;
+}
+
+// x / c of an instance without a solution: its 7 M + 1 entries zeroed by the whole wave.
+__device__ inline void zero_xc(const SweepArgs &A, const FleetOut &O, int64_t inst, int M, int lane) {
+    const int N = 7 * M + 1;
+    const int64_t at = xc_at(A, inst);
+    if (at >= 0)
+        for (int cc = lane; cc < N; cc += 64) {
+            if (A.outs & kOutX) O.x[at + cc] = 0.0;
+            if (A.outs & kOutC) O.c[at + cc] = 0.0;
+        }
+}
+
 #ifndef HALDA_SWEEP_TABLE_K1
 #define HALDA_SWEEP_TABLE_K1 1  // table launches also run the k = 1 register greedy (else k = 1 via tables)
 #endif
@@ -1039,22 +1058,7 @@ __device__ inline void sweep_body(const SweepArgs &A, const SweepBatch &B, unsig
     if (A.want == 1 && __hip_atomic_load(A.hb_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.launch_id)
         return;
     WaveCtx w = {};
-    if constexpr (kTables) {
-        const Slice sl = make_slice(A.mmax, A.r1max, A.tab, A.tab_kc);
-        unsigned char *base = slice_base;
-        w.rows = reinterpret_cast<int2 *>(base + sl.rows);
-        w.cyc = reinterpret_cast<double *>(base + sl.cyc);
-        w.cost = reinterpret_cast<double *>(base + sl.cost);
-        w.cnt = reinterpret_cast<int *>(base + sl.cnt);
-        w.st0 = reinterpret_cast<int *>(base + sl.st0);
-        w.st1 = reinterpret_cast<int *>(base + sl.st1);
-        w.rng = reinterpret_cast<int2 *>(base + sl.rng);
-        w.inc = reinterpret_cast<double *>(base + sl.inc);
-        w.G = reinterpret_cast<double *>(base + sl.G);
-        w.H = reinterpret_cast<double *>(base + sl.H);
-        w.work = reinterpret_cast<double *>(base + sl.work);
-        w.split = reinterpret_cast<uint16_t *>(base + sl.split);
-    }
+    if constexpr (kTables) w = wave_ctx(slice_base, make_slice(A.mmax, A.r1max, A.tab, A.tab_kc));
     const int S = gridDim.x;
     const int nf = B.F.n_fleets;
     for (int64_t b = blockIdx.x; b < nf; b += int64_t(64) * S) {
@@ -1587,33 +1591,16 @@ constexpr int kBoundCap = 1 << 24;
 // columns at (f n_k + j) cols, the w columns first): one wave per instance, lane = column, col_lb / col_ub
 // of the M w columns overwritten with lo / hi. lo is capped at W + 1 (any lo > W is infeasible by itself,
 // the screen's rule), so the screen's integer sum of the lower bounds stays small.
-__global__ __launch_bounds__(256) void halda_bound_cols_kernel(halda_fleets F, BoundArgs Bd, const int32_t *ks, int n_k,
-                                                               int L, int64_t cols, double *col_lb, double *col_ub) {
-    const int64_t inst = int64_t(blockIdx.x) * 4 + int(threadIdx.x >> 6);
-    if (inst >= int64_t(F.n_fleets) * n_k) return;
-    const int lane = int(threadIdx.x & 63);
-    const int64_t f = inst / n_k;
-    const int j = int(inst - f * n_k);
-    const int64_t d0 = F.dev_off[f];
-    const int M = int(F.dev_off[f + 1] - d0);
-    const int W = L / ks[j];
-    const int64_t co = inst * cols;
-    for (int i = lane; i < M; i += 64) {
-        const int lo = max(1, Bd.w_min ? Bd.w_min[d0 + i] : 0);
-        const int hi = Bd.w_max ? Bd.w_max[d0 + i] : 0x7fffffff;
-        col_lb[co + i] = lo > W ? double(W) + 1.0 : double(lo);
-        col_ub[co + i] = double(min(W, hi));
-    }
-}
-
-// The same patch for a boxed call (halda_solve_fleets_boxed with n bounds; launched INSTEAD of
+// Args = BoxArgs (halda_solve_fleets_boxed with n bounds; halda_box_cols_kernel is launched INSTEAD of
 // halda_bound_cols_kernel): the w columns get the folded lo = max(1, w_min, nlo) (an implied bound through
 // the link row n <= w, so the screen's sum of lower bounds is the fused routes' sum lo), the n columns
 // nlo = max(0, n_min) and min(the lowering's own upper bound, n_max). A crossing n pair is written as it
 // is: n_interval then finds no n at any w, every table entry of the device is +inf, the leaf is empty and
 // the instance INFEASIBLE.
-__global__ __launch_bounds__(256) void halda_box_cols_kernel(halda_fleets F, BoxArgs Bx, const int32_t *ks, int n_k, int L,
-                                                             int64_t cols, double *col_lb, double *col_ub) {
+template <class Args>
+__device__ inline void bound_cols(const halda_fleets &F, const Args &Bd, const int32_t *ks, int n_k, int L,
+                                  int64_t cols, double *col_lb, double *col_ub) {
+    constexpr bool kBox = std::is_same<Args, BoxArgs>::value;
     const int64_t inst = int64_t(blockIdx.x) * 4 + int(threadIdx.x >> 6);
     if (inst >= int64_t(F.n_fleets) * n_k) return;
     const int lane = int(threadIdx.x & 63);
@@ -1624,15 +1611,30 @@ __global__ __launch_bounds__(256) void halda_box_cols_kernel(halda_fleets F, Box
     const int W = L / ks[j];
     const int64_t co = inst * cols;
     for (int i = lane; i < M; i += 64) {
-        const int nlo = max(0, Bx.n_min ? Bx.n_min[d0 + i] : 0);
-        const int nmx = Bx.n_max ? Bx.n_max[d0 + i] : 0x7fffffff;
-        const int lo = max(max(1, Bx.w_min ? Bx.w_min[d0 + i] : 0), nlo);
-        const int hi = Bx.w_max ? Bx.w_max[d0 + i] : 0x7fffffff;
+        int nlo = 0, nmx = 0x7fffffff;
+        if constexpr (kBox) {
+            nlo = max(0, Bd.n_min ? Bd.n_min[d0 + i] : 0);
+            nmx = Bd.n_max ? Bd.n_max[d0 + i] : 0x7fffffff;
+        }
+        const int lo = max(max(1, Bd.w_min ? Bd.w_min[d0 + i] : 0), nlo);
+        const int hi = Bd.w_max ? Bd.w_max[d0 + i] : 0x7fffffff;
         col_lb[co + i] = lo > W ? double(W) + 1.0 : double(lo);
         col_ub[co + i] = double(min(W, hi));
-        col_lb[co + M + i] = double(nlo);
-        col_ub[co + M + i] = fmin(col_ub[co + M + i], double(nmx));
+        if constexpr (kBox) {
+            col_lb[co + M + i] = double(nlo);
+            col_ub[co + M + i] = fmin(col_ub[co + M + i], double(nmx));
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void halda_bound_cols_kernel(halda_fleets F, BoundArgs Bd, const int32_t *ks, int n_k,
+                                                               int L, int64_t cols, double *col_lb, double *col_ub) {
+    bound_cols(F, Bd, ks, n_k, L, cols, col_lb, col_ub);
+}
+
+__global__ __launch_bounds__(256) void halda_box_cols_kernel(halda_fleets F, BoxArgs Bx, const int32_t *ks, int n_k, int L,
+                                                             int64_t cols, double *col_lb, double *col_ub) {
+    bound_cols(F, Bx, ks, n_k, L, cols, col_lb, col_ub);
 }
 
 // The compact record with its w bounds: k1_alloc, k1_dp and the splits read a record's bounds through
@@ -1734,26 +1736,99 @@ __device__ inline bool box_fold(const Wave &sg, bool act, int gpu, int nmn, int 
     return sg.any(act && nlo > min(gpu ? 0x7fffffff : 0, nmx));
 }
 
-// One fleet of M = A.uM <= kK1MaxM devices (lane = device) under its bounds, its fields (mf), the lane's
-// k_j / W_j and the lane's w_min / w_max already loaded. The host sends only batches the register sweep
-// takes alone (plan_sweep's kRegAlone): every k > 1 has W < M <= sum lo, so an open instance is k = 1 with
-// R = W - sum lo < kDpLanes, solved by k1_alloc and, for what the greedy does not take, k1_dp -- both
-// exact. The settled verdicts, the objective's order of additions and every store follow sweep_fleet, so
-// bounds that never bind give the sweep's bits.
-// Rec = BoxRec (halda_sweep_box_kernel): the lane's n_min / n_max too; lo is folded with nlo and the n
-// crossing joins the w crossing. A leaf may then start above lo (k1_alloc hands it to k1_dp, which takes
-// any leaf shape) or be empty (k1_dp's row is all +inf: K1_INFEASIBLE).
-template <class Rec = BoundRec>
-__device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveCtx &w, const Wave &sg,
-                                          const DevFields &mf, int64_t d0, int kj, int Wj, int wmn, int wmx,
-                                          int nmn = 0, int nmx = 0x7fffffff) {
+// The table route of the bounded sweep (route 3): fleets of any sizes 1 .. kK1MaxM under their bounds, every
+// k, in one launch with the table kernel's LDS slice. What the register route leaves to the general route --
+// k > 1 with room, R + 1 > kDpLanes, small fleets of a long model -- is solved here by the table machinery
+// on bounded records: table_entry builds w = wlo + e and masks w > whi, the DP sees only R1 = W - sum lo + 1
+// and the tables. The slice is the one plan_sweep sizes for the unbounded batch: sum lo >= M, so every
+// bounded R1 fits it. No fleet is handed back (A.want = 0: no flag bytes, no hand-back flag, no scratch), and
+// the waves share nothing, so launches on different streams need no ordering between them.
+
+// Device records for table_pass: lane i holds device i's record with its bounds (M <= 64), other lanes
+// fetch it by shuffle, wlo / whi with the record.
+struct BoundSrc {
+    using Rec = BoundRec;
+    const BoundRec *me;
+    __device__ inline void load(BoundRec &r, const WaveCtx &, int i) const {
+        static_cast<FieldRec &>(r) = me->shfl(i);
+        r.wlo = __shfl(me->wlo, i);
+        r.whi = __shfl(me->whi, i);
+    }
+};
+struct BoxSrc {  // the same for box records: nlo / nhi travel with wlo / whi
+    using Rec = BoxRec;
+    const BoxRec *me;
+    __device__ inline void load(BoxRec &r, const WaveCtx &w, int i) const {
+        BoundSrc{me}.load(r, w, i);
+        r.nlo = __shfl(me->nlo, i);
+        r.nhi = __shfl(me->nhi, i);
+    }
+};
+__device__ inline BoundSrc bound_src(const BoundRec *me) { return BoundSrc{me}; }
+__device__ inline BoxSrc bound_src(const BoxRec *me) { return BoxSrc{me}; }
+
+// What a lane brings to bounded_fleet, every load issued together before the body: the fleet's extent, the
+// lane's k_j / W_j, its device's fields and its bounds (no bound where an array is absent; n_min / n_max
+// only with Args = BoxArgs: two more coalesced 4-byte loads beside the two w bounds and the 18 fields).
+struct BoundedLane {
+    int64_t d0;
+    int M, kj, Wj;
+    DevFields mf;
+    int wmn, wmx, nmn, nmx;
+};
+
+template <class Args>
+__device__ inline BoundedLane bounded_lane(const SweepArgs &A, const Args &Bd, int lane, int64_t d0, int M) {
+    BoundedLane in;
+    const bool kl = lane < A.n_k;
+    in.kj = A.ks[kl ? lane : 0];
+    in.Wj = kl ? A.Ws[lane] : 0;
+    in.d0 = d0;
+    in.M = M;
+    const int64_t g = d0 + (lane < M ? lane : 0);
+    in.mf = load_fields(A.F, g);
+    in.wmn = Bd.w_min ? Bd.w_min[g] : 0;
+    in.wmx = Bd.w_max ? Bd.w_max[g] : 0x7fffffff;
+    in.nmn = 0;
+    in.nmx = 0x7fffffff;
+    if constexpr (std::is_same<Args, BoxArgs>::value) {
+        in.nmn = Bd.n_min ? Bd.n_min[g] : 0;
+        in.nmx = Bd.n_max ? Bd.n_max[g] : 0x7fffffff;
+    }
+    return in;
+}
+
+// One fleet of M <= kK1MaxM devices (lane = device) under its bounds, on either fused route. The settled
+// verdicts, the objective's order of additions and every store follow sweep_fleet, so bounds that never bind
+// give the sweep's bits: halda_sweep_kernel's on the register route, halda_sweep_tables_kernel's on the
+// table route.
+// kTables = false, the register route (M = A.uM): the host sends only batches the register sweep takes
+// alone (plan_sweep's kRegAlone): every k > 1 has W < M <= sum lo, so an open instance is k = 1 with
+// R = W - sum lo < kDpLanes, solved by k1_alloc and, for what the greedy does not take, k1_dp -- both exact.
+// kTables = true, the table route: an open k follows the table branch of sweep_fleet<true, false> on a
+// BoundRec with R = W - sum lo: k1_alloc where that branch takes it (k = 1, or R = 0 where every w_i = lo_i
+// is forced), else the tables and the DP, the objective in that branch's order of additions. A.k1dp (the
+// test path) sends every instance to the tables.
+// Rec = BoxRec (the two box kernels): the lane's n_min / n_max too; lo is folded with nlo and the n crossing
+// joins the w crossing. A leaf may then start above lo or be empty. On the register route k1_alloc hands it
+// to k1_dp, which takes any leaf shape (an empty leaf: its row is all +inf, K1_INFEASIBLE). On the table
+// route a leaf that starts above lo has +inf first table entries (leaf_ranges' lo > 0, the DP's usual case of
+// a masked entry) and an empty leaf an all +inf row (LeafInfo.empty: dp_pass finds nothing, INFEASIBLE);
+// where k1_alloc is tried first it hands either case back (K1_FALLBACK) to the tables.
+template <class Rec, bool kTables>
+__device__ inline void bounded_fleet(const SweepArgs &A, int f, const WaveCtx &w, const Wave &sg,
+                                     const BoundedLane &in) {
     constexpr bool kBox = !std::is_same<Rec, BoundRec>::value;
     const FleetOut &O = A.out;
     const int lane = sg.sl;
     const bool kl = lane < A.n_k;
-    const int M = A.uM;
+    const int kj = in.kj, Wj = in.Wj;
+    const int64_t d0 = in.d0;
+    const int M = in.M;
     const int outs = A.outs;
     const bool act = lane < M;
+    const DevFields &mf = in.mf;
+    const int wmn = in.wmn, wmx = in.wmx;
     Rec me = {};
     int bad = 0;
     static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
@@ -1764,12 +1839,13 @@ __device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveC
     // lo_i = max(1, w_min_i); hi_i = min(W, w_max_i). sum lo > W, some lo_i > hi_i and sum hi < W are
     // bound-infeasible. A lo_i > W already gives sum lo > W (every lo >= 1), so the crossing test needs
     // w_max alone; and where no bound crosses (every w_max_i >= lo_i >= 1) sum min(W, w_max_i) < W exactly
-    // when sum w_max_i < W: all three tests are formed once, for every k of the call.
+    // when sum w_max_i < W: all three tests are formed once, from the capped integer sums and the ballot,
+    // for every k of the call.
     int lo = min(max(1, wmn), kBoundCap);
     bool ncross = false;
     if constexpr (kBox) {
-        ncross = box_fold(sg, act, me.gpu, nmn, nmx, lo, me.nlo);
-        me.nhi = nmx;
+        ncross = box_fold(sg, act, me.gpu, in.nmn, in.nmx, lo, me.nlo);
+        me.nhi = in.nmx;
     }
     const int sumlo = sg.sum_i(act ? lo : 0);
     const int sumhi = sg.sum_i(act ? min(max(wmx, 0), kBoundCap) : 0);
@@ -1789,16 +1865,10 @@ __device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveC
     }
     if ((outs & kOutXZ) && (outs & kOutXC)) {  // x / c of a settled instance are zero
         uint64_t settled = sg.bits(kl && stj != kOpen);
-        const int N = 7 * M + 1;
         while (settled) {
             const int j = __builtin_ctzll(settled);
             settled &= settled - 1;
-            const int64_t at = xc_at(A, int64_t(f) * A.n_k + j);
-            if (at >= 0)
-                for (int cc = lane; cc < N; cc += 64) {
-                    if (outs & kOutX) O.x[at + cc] = 0.0;
-                    if (outs & kOutC) O.c[at + cc] = 0.0;
-                }
+            zero_xc(A, O, int64_t(f) * A.n_k + j, M, lane);
         }
     }
     uint64_t todo = sg.bits(kl && stj == kOpen);
@@ -1816,16 +1886,22 @@ __device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveC
         bool improved = false;
         int rc = K1_FALLBACK, e = 0, rounds = 0, nE = 0;
         double gE = 0.0;
-        bool haveE = true;  // gE / nE hold the split at w = lo + e (k1_alloc), else split here
+        bool haveE = true;  // gE / nE hold the split at w = lo + e (k1_alloc), else split here (after k1_dp)
         me.W = W;
         me.wlo = lo;
         me.whi = min(W, wmx);
-        // k = 1, or R = 0 (every w_i = lo_i is forced): the allocation that minimises sum g is the answer
-        if (k == 1 || R == 0) {
-            if (!A.k1dp) rc = k1_alloc(me, M, R, sg, e, rounds, gE, nE);
-            if (rc == K1_FALLBACK && R < kDpLanes) {
-                rc = k1_dp(me, M, R, sg, e, w.dparg);
-                haveE = false;
+        // k = 1: the register greedy; R = 0: every w_i = lo_i is forced, so the allocation that minimises
+        // sum g is the answer for any k (the output adds (k - 1) max_i H_i)
+        if constexpr (kTables) {
+            if ((k == 1 || R == 0) && (HALDA_SWEEP_TABLE_K1 || R == 0) && !A.k1dp)
+                rc = k1_alloc(me, M, R, sg, e, rounds, gE, nE);
+        } else {
+            if (k == 1 || R == 0) {
+                if (!A.k1dp) rc = k1_alloc(me, M, R, sg, e, rounds, gE, nE);
+                if (rc == K1_FALLBACK && R < kDpLanes) {
+                    rc = k1_dp(me, M, R, sg, e, w.dparg);
+                    haveE = false;
+                }
             }
         }
         if (rc == K1_INFEASIBLE) {
@@ -1864,260 +1940,10 @@ __device__ inline void sweep_fleet_bounds(const SweepArgs &A, int f, const WaveC
                     O.n[d0 + lane] = n;
                 }
             }
-            if (lane == 0 && (outs & kOutXC)) {
-                const int64_t at = xc_at(A, inst);
-                if (at >= 0 && (outs & kOutX)) O.x[at + 7 * M] = hmax;
-                if (at >= 0 && (outs & kOutC)) O.c[at + 7 * M] = kc;
-            }
-        } else {
+            if (lane == 0 && (outs & kOutXC)) put_xc_cycle(A, O, inst, M, hmax, kc);
+        } else if constexpr (!kTables) {
             // k > 1 with room, or R + 1 > kDpLanes: not a batch the host sends here (the general route's)
             st = HALDA_STATUS_UNSUPPORTED;
-        }
-        if (improved) {
-            best = obj;
-            best_k = k;
-        }
-        if ((outs & kOutXZ) && st != HALDA_STATUS_OPTIMAL) {  // x / c of a non-optimal instance are zero
-            const int N = 7 * M + 1;
-            const int64_t at = xc_at(A, inst);
-            if (at >= 0)
-                for (int cc = lane; cc < N; cc += 64) {
-                    if (outs & kOutX) O.x[at + cc] = 0.0;
-                    if (outs & kOutC) O.c[at + cc] = 0.0;
-                }
-        }
-        if (lane == 0) {
-            if (outs & kOutObk) O.obj_by_k[inst] = st == HALDA_STATUS_OPTIMAL ? obj : kInf;
-            if (outs & kOutSt) O.status[inst] = st;
-        }
-    }
-    if (lane == 0) {
-        O.best_k[f] = best_k;
-        O.obj_value[f] = best;
-    }
-    if (best_k == 0 && act) {
-        O.w[d0 + lane] = 0;
-        O.n[d0 + lane] = 0;
-    }
-}
-
-// halda_sweep_bounds_kernel: the fused route -- the register sweep of a batch of fleets of one size
-// A.uM <= kK1MaxM that needs no table launch (the host checks both: the sub-fleet, variants and plans
-// kernels' gate), under per-device bounds. One wave per fleet, kSweepWavesPerBlock per workgroup, lane =
-// device; the lane's w_min / w_max are two 4-byte loads issued with the 18 field loads.
-__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_bounds_kernel(
-    SweepArgs A, BoundArgs Bd) {
-    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
-    if (f >= A.F.n_fleets) return;
-    const int lane = int(threadIdx.x & 63);
-    const int M = A.uM;
-    const int64_t base = sload_i64(A.F.dev_off);
-    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
-    WaveCtx w = {};
-    w.dparg = dparg[threadIdx.x >> 6];
-    const bool kl = lane < A.n_k;
-    const int kj = A.ks[kl ? lane : 0];
-    const int Wj = kl ? A.Ws[lane] : 0;
-    const int64_t d0 = base + int64_t(f) * M;
-    const int64_t g = d0 + (lane < M ? lane : 0);
-    const DevFields mf = load_fields(A.F, g);
-    const int wmn = Bd.w_min ? Bd.w_min[g] : 0;
-    const int wmx = Bd.w_max ? Bd.w_max[g] : 0x7fffffff;
-    sweep_fleet_bounds(A, f, w, Wave(lane), mf, d0, kj, Wj, wmn, wmx);
-}
-
-// halda_sweep_box_kernel: halda_sweep_bounds_kernel with the n box -- the lane's n_min / n_max are two
-// more coalesced 4-byte loads, issued with the 18 field loads and the two w bounds.
-__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_box_kernel(
-    SweepArgs A, BoxArgs Bx) {
-    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
-    if (f >= A.F.n_fleets) return;
-    const int lane = int(threadIdx.x & 63);
-    const int M = A.uM;
-    const int64_t base = sload_i64(A.F.dev_off);
-    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
-    WaveCtx w = {};
-    w.dparg = dparg[threadIdx.x >> 6];
-    const bool kl = lane < A.n_k;
-    const int kj = A.ks[kl ? lane : 0];
-    const int Wj = kl ? A.Ws[lane] : 0;
-    const int64_t d0 = base + int64_t(f) * M;
-    const int64_t g = d0 + (lane < M ? lane : 0);
-    const DevFields mf = load_fields(A.F, g);
-    const int wmn = Bx.w_min ? Bx.w_min[g] : 0;
-    const int wmx = Bx.w_max ? Bx.w_max[g] : 0x7fffffff;
-    const int nmn = Bx.n_min ? Bx.n_min[g] : 0;
-    const int nmx = Bx.n_max ? Bx.n_max[g] : 0x7fffffff;
-    sweep_fleet_bounds<BoxRec>(A, f, w, Wave(lane), mf, d0, kj, Wj, wmn, wmx, nmn, nmx);
-}
-
-// The table route of the bounded sweep (route 3): fleets of any sizes 1 .. kK1MaxM under their bounds, every
-// k, in one launch with the table kernel's LDS slice. What the register route leaves to the general route --
-// k > 1 with room, R + 1 > kDpLanes, small fleets of a long model -- is solved here by the table machinery
-// on bounded records: table_entry builds w = wlo + e and masks w > whi, the DP sees only R1 = W - sum lo + 1
-// and the tables. The slice is the one plan_sweep sizes for the unbounded batch: sum lo >= M, so every
-// bounded R1 fits it. No fleet is handed back (A.want = 0: no flag bytes, no hand-back flag, no scratch), and
-// the waves share nothing, so launches on different streams need no ordering between them.
-
-// Device records for table_pass: lane i holds device i's record with its bounds (M <= 64), other lanes
-// fetch it by shuffle, wlo / whi with the record.
-struct BoundSrc {
-    using Rec = BoundRec;
-    const BoundRec *me;
-    __device__ inline void load(BoundRec &r, const WaveCtx &, int i) const {
-        static_cast<FieldRec &>(r) = me->shfl(i);
-        r.wlo = __shfl(me->wlo, i);
-        r.whi = __shfl(me->whi, i);
-    }
-};
-struct BoxSrc {  // the same for box records: nlo / nhi travel with wlo / whi
-    using Rec = BoxRec;
-    const BoxRec *me;
-    __device__ inline void load(BoxRec &r, const WaveCtx &w, int i) const {
-        BoundSrc{me}.load(r, w, i);
-        r.nlo = __shfl(me->nlo, i);
-        r.nhi = __shfl(me->nhi, i);
-    }
-};
-__device__ inline BoundSrc bound_src(const BoundRec *me) { return BoundSrc{me}; }
-__device__ inline BoxSrc bound_src(const BoxRec *me) { return BoxSrc{me}; }
-
-// One fleet of M <= kK1MaxM devices (lane = device) under its bounds. The settled verdicts are
-// sweep_fleet_bounds' (formed once for every k); an open k follows the table branch of
-// sweep_fleet<true, false> on a BoundRec with R = W - sum lo: k1_alloc where that branch takes it (k = 1, or
-// R = 0 where every w_i = lo_i is forced), else the tables and the DP, the objective in that branch's order
-// of additions. Bounds that never bind therefore give halda_sweep_tables_kernel's bits. A.k1dp (the test
-// path) sends every instance to the tables.
-// Rec = BoxRec, Args = BoxArgs (halda_sweep_box_tables_kernel): the n box as in sweep_fleet_bounds. A leaf
-// that starts above lo has +inf first table entries (leaf_ranges' lo > 0, the DP's usual case of a masked
-// entry) and an empty leaf an all +inf row (LeafInfo.empty: dp_pass finds nothing, INFEASIBLE); where
-// k1_alloc is tried first it hands either case back (K1_FALLBACK) to the tables.
-template <class Rec = BoundRec, class Args = BoundArgs>
-__device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Args &Bd, int f, const WaveCtx &w,
-                                                 const Wave &sg) {
-    constexpr bool kBox = !std::is_same<Rec, BoundRec>::value;
-    const FleetOut &O = A.out;
-    const int lane = sg.sl;
-    const bool kl = lane < A.n_k;
-    const int kj = A.ks[kl ? lane : 0];
-    const int Wj = kl ? A.Ws[lane] : 0;
-    // the fleet's extent through the scalar cache (dev_off is read-only to the kernel)
-    const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
-    const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
-    const int outs = A.outs;
-    const bool act = lane < M;
-    const int64_t g0 = d0 + (act ? lane : 0);
-    const DevFields mf = load_fields(A.F, g0);
-    const int wmn = Bd.w_min ? Bd.w_min[g0] : 0;
-    const int wmx = Bd.w_max ? Bd.w_max[g0] : 0x7fffffff;
-    int nmn = 0, nmx = 0x7fffffff;
-    if constexpr (kBox) {
-        nmn = Bd.n_min ? Bd.n_min[g0] : 0;
-        nmx = Bd.n_max ? Bd.n_max[g0] : 0x7fffffff;
-    }
-    Rec me = {};
-    int bad = 0;
-    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
-    bad = act ? bad : 0;
-    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
-    fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
-    bad = sg.any(bad != 0) ? 1 : 0;
-    // the three bound tests from the capped integer sums and the ballot, once for every k (sweep_fleet_bounds)
-    int lo = min(max(1, wmn), kBoundCap);
-    bool ncross = false;
-    if constexpr (kBox) {
-        ncross = box_fold(sg, act, me.gpu, nmn, nmx, lo, me.nlo);
-        me.nhi = nmx;
-    }
-    const int sumlo = sg.sum_i(act ? lo : 0);
-    const int sumhi = sg.sum_i(act ? min(max(wmx, 0), kBoundCap) : 0);
-    const bool cross = sg.any(act && lo > wmx) || ncross;
-    double best = kInf;
-    int best_k = 0;
-    constexpr int kOpen = 1000;
-    int stj = kOpen;
-    if (!(Wj < 1000000)) stj = HALDA_STATUS_UNSUPPORTED;
-    else if (sumlo > Wj) stj = HALDA_STATUS_INFEASIBLE;  // sum lb(w) > W (without bounds: M > W)
-    else if (bad) stj = HALDA_STATUS_UNSUPPORTED;
-    else if (cross || sumhi < Wj) stj = HALDA_STATUS_INFEASIBLE;
-    if (kl && stj != kOpen) {
-        const int64_t inst = int64_t(f) * A.n_k + lane;
-        if (outs & kOutObk) O.obj_by_k[inst] = kInf;
-        if (outs & kOutSt) O.status[inst] = stj;
-    }
-    if ((outs & kOutXZ) && (outs & kOutXC)) {  // x / c of a settled instance are zero
-        uint64_t settled = sg.bits(kl && stj != kOpen);
-        const int N = 7 * M + 1;
-        while (settled) {
-            const int j = __builtin_ctzll(settled);
-            settled &= settled - 1;
-            const int64_t at = xc_at(A, int64_t(f) * A.n_k + j);
-            if (at >= 0)
-                for (int cc = lane; cc < N; cc += 64) {
-                    if (outs & kOutX) O.x[at + cc] = 0.0;
-                    if (outs & kOutC) O.c[at + cc] = 0.0;
-                }
-        }
-    }
-    uint64_t todo = sg.bits(kl && stj == kOpen);
-    while (todo) {
-        const int j = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        opaque_rec(me);
-        const int k = sg.bcast(kj, j);
-        const int W = sg.bcast(Wj, j);
-        const int64_t inst = int64_t(f) * A.n_k + j;
-        const double kc = double(k - 1);
-        const int R = W - sumlo;
-        int st;
-        double obj = kInf;
-        bool improved = false;
-        int rc = K1_FALLBACK, e = 0, rounds = 0, nE = 0;
-        double gE = 0.0;
-        me.W = W;
-        me.wlo = lo;
-        me.whi = min(W, wmx);
-        // k = 1: the register greedy; R = 0: every w_i = lo_i is forced, so the same code gives the solution
-        // for any k (the output adds (k - 1) max_i H_i)
-        if ((k == 1 || R == 0) && (HALDA_SWEEP_TABLE_K1 || R == 0) && !A.k1dp)
-            rc = k1_alloc(me, M, R, sg, e, rounds, gE, nE);
-        if (rc == K1_INFEASIBLE) {
-            st = HALDA_STATUS_INFEASIBLE;
-        } else if (rc == K1_OK) {
-            double g = 0.0, H = 0.0, z = 0.0;
-            int n = 0, sl[4] = {0, 0, 0, 0};
-            const int wl = lo + e;
-            const bool need_h = kc != 0.0 || (outs & kOutX);
-            if (act) {
-                g = gE;
-                n = nE;
-                rec_slacks(me, wl, n, sl);
-                if (need_h) {
-                    double P, Q;
-                    dev_cycle(me, wl, n, sl, P, Q);
-                    z = Q > P ? 0.5 * (Q - P) : 0.0;
-                    H = Q >= P ? 0.5 * (P + Q) : P;
-                }
-            }
-            const double hmax = need_h ? fmax(0.0, sg.max_f64(act ? H : 0.0)) : 0.0;
-            obj = sg.sum_f64(act ? g : 0.0) + kc * hmax;
-            obj = obj + tsum;
-            obj = obj + xsum;
-            obj = obj + kappa;
-            st = HALDA_STATUS_OPTIMAL;
-            improved = obj < best;
-            if (act) {
-                if (outs & kOutXC) put_xc(A, O, inst, M, lane, wl, n, sl, z, me);
-                if (improved) {
-                    O.w[d0 + lane] = wl;
-                    O.n[d0 + lane] = n;
-                }
-            }
-            if (lane == 0 && (outs & kOutXC)) {
-                const int64_t at = xc_at(A, inst);
-                if (at >= 0 && (outs & kOutX)) O.x[at + 7 * M] = hmax;
-                if (at >= 0 && (outs & kOutC)) O.c[at + 7 * M] = kc;
-            }
         } else {
             Inst I = {};
             I.inst = int(inst);
@@ -2166,11 +1992,7 @@ __device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Args 
                     O.w[d0 + lane] = wl;
                     O.n[d0 + lane] = n;
                 }
-                if (lane == 0 && (outs & kOutXC)) {
-                    const int64_t at = xc_at(A, inst);
-                    if (at >= 0 && (outs & kOutX)) O.x[at + 7 * M] = hmax;
-                    if (at >= 0 && (outs & kOutC)) O.c[at + 7 * M] = kc;
-                }
+                if (lane == 0 && (outs & kOutXC)) put_xc_cycle(A, O, inst, M, hmax, kc);
             }
             wave_sync();  // tables / st0 are rewritten by the next k
         }
@@ -2178,15 +2000,8 @@ __device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Args 
             best = obj;
             best_k = k;
         }
-        if ((outs & kOutXZ) && st != HALDA_STATUS_OPTIMAL) {  // x / c of a non-optimal instance are zero
-            const int N = 7 * M + 1;
-            const int64_t at = xc_at(A, inst);
-            if (at >= 0)
-                for (int cc = lane; cc < N; cc += 64) {
-                    if (outs & kOutX) O.x[at + cc] = 0.0;
-                    if (outs & kOutC) O.c[at + cc] = 0.0;
-                }
-        }
+        // x / c of a non-optimal instance are zero
+        if ((outs & kOutXZ) && st != HALDA_STATUS_OPTIMAL) zero_xc(A, O, inst, M, lane);
         if (lane == 0) {
             if (outs & kOutObk) O.obj_by_k[inst] = st == HALDA_STATUS_OPTIMAL ? obj : kInf;
             if (outs & kOutSt) O.status[inst] = st;
@@ -2202,55 +2017,61 @@ __device__ inline void sweep_fleet_bounds_tables(const SweepArgs &A, const Args 
     }
 }
 
-// halda_sweep_bounds_tables_kernel: one wave per fleet in 64-thread workgroups on a persistent grid, each
-// with the table kernel's dynamic LDS slice (make_slice of the launch's shape), the fleets dealt out as
-// sweep_body deals them (workgroup b takes fleets b, b + grid, ...). No spin-wait and nothing shared between
-// waves: the only synchronisation is wave_sync within the one wave.
-__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bounds_tables_kernel(SweepArgs A,
-                                                                                                  BoundArgs Bd) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x;
-    const Slice sl = make_slice(A.mmax, A.r1max, A.tab, A.tab_kc);
+// The fused route's kernels -- the register sweep of a batch of fleets of one size A.uM <= kK1MaxM that needs
+// no table launch (the host checks both: the sub-fleet, variants and plans kernels' gate), under per-device
+// bounds. One wave per fleet, kSweepWavesPerBlock per workgroup, lane = device; the lane's bounds are 4-byte
+// loads issued with the 18 field loads.
+template <class Rec, class Args>
+__device__ inline void bounded_regs(const SweepArgs &A, const Args &Bd) {
+    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    if (f >= A.F.n_fleets) return;
+    const int lane = int(threadIdx.x & 63);
+    const int M = A.uM;
+    const int64_t base = sload_i64(A.F.dev_off);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
     WaveCtx w = {};
-    w.rows = reinterpret_cast<int2 *>(smem + sl.rows);
-    w.cyc = reinterpret_cast<double *>(smem + sl.cyc);
-    w.cost = reinterpret_cast<double *>(smem + sl.cost);
-    w.cnt = reinterpret_cast<int *>(smem + sl.cnt);
-    w.st0 = reinterpret_cast<int *>(smem + sl.st0);
-    w.st1 = reinterpret_cast<int *>(smem + sl.st1);
-    w.rng = reinterpret_cast<int2 *>(smem + sl.rng);
-    w.inc = reinterpret_cast<double *>(smem + sl.inc);
-    w.G = reinterpret_cast<double *>(smem + sl.G);
-    w.H = reinterpret_cast<double *>(smem + sl.H);
-    w.work = reinterpret_cast<double *>(smem + sl.work);
-    w.split = reinterpret_cast<uint16_t *>(smem + sl.split);
-    const int nf = A.F.n_fleets;
-    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) sweep_fleet_bounds_tables(A, Bd, int(f), w, Wave(lane));
+    w.dparg = dparg[threadIdx.x >> 6];
+    bounded_fleet<Rec, false>(A, f, w, Wave(lane), bounded_lane(A, Bd, lane, base + int64_t(f) * M, M));
 }
 
-// halda_sweep_box_tables_kernel: halda_sweep_bounds_tables_kernel with the n box (the same slice: folding
-// nlo into lo only raises sum lo).
-__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_box_tables_kernel(SweepArgs A,
-                                                                                               BoxArgs Bx) {
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_bounds_kernel(
+    SweepArgs A, BoundArgs Bd) {
+    bounded_regs<BoundRec>(A, Bd);
+}
+
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_box_kernel(
+    SweepArgs A, BoxArgs Bx) {
+    bounded_regs<BoxRec>(A, Bx);
+}
+
+// The table route's kernels: one wave per fleet in 64-thread workgroups on a persistent grid, each with the
+// table kernel's dynamic LDS slice (make_slice of the launch's shape; the same slice with the n box: folding
+// nlo into lo only raises sum lo), the fleets dealt out as sweep_body deals them (workgroup b takes fleets b,
+// b + grid, ...). No spin-wait and nothing shared between waves: the only synchronisation is wave_sync within
+// the one wave.
+template <class Rec, class Args>
+__device__ inline void bounded_tables(const SweepArgs &A, const Args &Bd) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
-    const Slice sl = make_slice(A.mmax, A.r1max, A.tab, A.tab_kc);
-    WaveCtx w = {};
-    w.rows = reinterpret_cast<int2 *>(smem + sl.rows);
-    w.cyc = reinterpret_cast<double *>(smem + sl.cyc);
-    w.cost = reinterpret_cast<double *>(smem + sl.cost);
-    w.cnt = reinterpret_cast<int *>(smem + sl.cnt);
-    w.st0 = reinterpret_cast<int *>(smem + sl.st0);
-    w.st1 = reinterpret_cast<int *>(smem + sl.st1);
-    w.rng = reinterpret_cast<int2 *>(smem + sl.rng);
-    w.inc = reinterpret_cast<double *>(smem + sl.inc);
-    w.G = reinterpret_cast<double *>(smem + sl.G);
-    w.H = reinterpret_cast<double *>(smem + sl.H);
-    w.work = reinterpret_cast<double *>(smem + sl.work);
-    w.split = reinterpret_cast<uint16_t *>(smem + sl.split);
+    const WaveCtx w = wave_ctx(smem, make_slice(A.mmax, A.r1max, A.tab, A.tab_kc));
     const int nf = A.F.n_fleets;
-    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x)
-        sweep_fleet_bounds_tables<BoxRec, BoxArgs>(A, Bx, int(f), w, Wave(lane));
+    for (int64_t b = blockIdx.x; b < nf; b += gridDim.x) {
+        const int f = int(b);
+        // the fleet's extent through the scalar cache (dev_off is read-only to the kernel)
+        const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
+        const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
+        bounded_fleet<Rec, true>(A, f, w, Wave(lane), bounded_lane(A, Bd, lane, d0, M));
+    }
+}
+
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bounds_tables_kernel(SweepArgs A,
+                                                                                                  BoundArgs Bd) {
+    bounded_tables<BoundRec>(A, Bd);
+}
+
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_box_tables_kernel(SweepArgs A,
+                                                                                               BoxArgs Bx) {
+    bounded_tables<BoxRec>(A, Bx);
 }
 
 // ---------------------------------------------------------------- total move budget (halda_solve_fleets_budget)
