@@ -10,6 +10,8 @@ from distilp_amd.solver import (ReplacementWithin, halda_replace_within, halda_r
                                 halda_solve_bounded, halda_solve_bounded_batch, move_bounds, move_box)
 from distilp_amd.solver import (FrontierPoint, halda_move_frontier, halda_move_frontier_batch,  # noqa: F401
                                 halda_solve_budget)
+from distilp_amd.solver import (SubsetPoint, halda_select_devices_exact, halda_subset_frontier,  # noqa: F401
+                                halda_subset_frontier_batch)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

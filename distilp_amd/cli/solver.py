@@ -164,6 +164,41 @@ def frontier_lines(devices: List[DeviceProfile], model: ModelProfile, plan, budg
     return out
 
 
+def pick_indices(devices: List[DeviceProfile], picks: Sequence[str]) -> List[int]:
+    """NAME_OR_INDEX ...: each pick as a device index (a device's name, else its 0-based index). ValueError
+    for a pick that names no device."""
+    names = [d.name for d in devices]
+    out = []
+    for p in picks:
+        if p in names:
+            out.append(names.index(p))
+        elif p.isdigit() and int(p) < len(devices):
+            out.append(int(p))
+        else:
+            raise ValueError(f"{p!r} is neither a device name nor an index below {len(devices)}")
+    return out
+
+
+def select_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: float, max_drop: Optional[int],
+                 keep: Sequence[int]) -> List[str]:
+    """--select-devices [D] [--keep ...]: one line per point of halda_subset_frontier, then the selection (the
+    strict prefix-minimum over d), device names in the fleet's order (kv_bits "4bit" like the solve above)."""
+    from ..solver.subsets import halda_subset_frontier, select_point
+
+    pts = halda_subset_frontier(devices, model, max_drop, keep or None, mip_gap=mip_gap, kv_bits="4bit")
+    out = []
+    for d, pt in enumerate(pts):
+        if pt.result is None:
+            out.append(f"drop {d}: infeasible")
+        else:
+            out.append(f"drop {d}: dropped=[{', '.join(devices[i].name for i in pt.dropped)}], k={pt.result.k}, "
+                       f"obj={pt.obj_value:.6f}")
+    best = select_point(pts)
+    out.append("selected: infeasible" if best is None
+               else f"selected: kept=[{', '.join(devices[i].name for i in best.kept)}]")
+    return out
+
+
 def cpu_only_n_max(devices: List[DeviceProfile], picks: Sequence[str]) -> List[int]:
     """--cpu-only NAME_OR_INDEX ...: the n_max list with 0 on the picked devices (a device's name, else its
     0-based index in the fleet's order) and "no bound" elsewhere. ValueError for a pick that names no device."""
@@ -215,6 +250,11 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--move-frontier", type=int, metavar="B",
                    help="With --evaluate-solution: also print, for every total budget up to B moved layers, the best "
                         "plan at that plan's k within it")
+    o.add_argument("--select-devices", nargs="?", type=int, const=-1, default=None, metavar="D",
+                   help="After the solution, print the best sub-fleet with exactly d devices left out for every "
+                        "d up to D (default: every subset), and the selection over them")
+    o.add_argument("--keep", nargs="+", metavar="NAME_OR_INDEX", default=[],
+                   help="With --select-devices: devices (name or 0-based index) that may not be left out")
     g.add_argument("--cpu-only", nargs="+", metavar="NAME_OR_INDEX",
                    help="Solve without using the GPU of these devices (their name or 0-based index)")
     return p
@@ -249,6 +289,8 @@ def main(argv=None) -> int:
         parser.error("--move-frontier requires --evaluate-solution")
     if args.move_frontier is not None and args.move_frontier < 0:
         parser.error("--move-frontier must be >= 0")
+    if args.keep and args.select_devices is None:
+        parser.error("--keep requires --select-devices")
     n_max = None
     if args.cpu_only:
         try:
@@ -305,6 +347,16 @@ def main(argv=None) -> int:
             print(line)
     if args.kv_sweep or args.n_kv_sweep:
         for line in variant_sweep_lines(devices, model, args.mip_gap, args.kv_sweep, args.n_kv_sweep):
+            print(line)
+    if args.select_devices is not None:
+        try:
+            lines = select_lines(devices, model, args.mip_gap,
+                                 None if args.select_devices == -1 else args.select_devices,
+                                 pick_indices(devices, args.keep))
+        except (ValueError, IndexError) as e:
+            print(f"error: --select-devices: {e}", file=sys.stderr)
+            return 2
+        for line in lines:
             print(line)
     if incumbent is not None:
         for line in incumbent_lines(devices, model, incumbent, result):

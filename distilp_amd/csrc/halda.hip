@@ -163,6 +163,10 @@ struct Ctx {
     size_t sub_tab_bytes = 0;
     int sub_path = 0;               // halda_set_subfleets_path: 0 automatic, 1 always expand
     int sub_route = 0;              // the last halda_solve_subfleets call: 1 fused, 2 expansion (0: none yet)
+    uint8_t *sel_buf = nullptr;     // halda_solve_subsets: combo lists, per-(d, fleet) records, per-candidate results
+    size_t sel_bytes = 0;
+    int sel_path = 0;               // halda_set_subsets_path: 0 automatic, 1 always expand
+    int sel_route = 0;              // the last halda_solve_subsets call: 1 fused, 2 expansion, 3 mixed (0: none yet)
     uint8_t *var_desc = nullptr;    // halda_solve_variants: the fused route's per-variant models (SweepModel)
     size_t var_desc_bytes = 0;
     int var_path = 0;               // halda_set_variants_path: 0 automatic, 1 always loop
@@ -1228,6 +1232,7 @@ void halda_free(void *ctx) {
     if (c->fleet_scratch) (void)hipFree(c->fleet_scratch);
     if (c->gtab) (void)hipFree(c->gtab);
     if (c->sub_tab) (void)hipFree(c->sub_tab);
+    if (c->sel_buf) (void)hipFree(c->sel_buf);
     if (c->var_desc) (void)hipFree(c->var_desc);
     for (auto &x : c->sws) {
         if (x.fflag) (void)hipFree(x.fflag);
@@ -2143,6 +2148,349 @@ int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_
     halda_fleet_result r = stage::bind_result(base, R, *out_h);
     rc = solve_subfleets(ctx, model, &d, &di, ks, n_k, &r, s, tot);
     if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- exact device selection: all subsets
+// halda_solve_subsets: per fleet and d = 0 .. max_drop, the best candidate (the fleet without d of its
+// droppable devices) by halda_solve_subfleets' value, the earliest in enumeration order among equals.
+// The host lays out one SubsetFleet per (d, fleet) and one combo list per (q, d) in use, uploads both once,
+// and works d by d in launches of at most kSubsetsFusedChunk items (fused route) or kSubsetsChunkDevices
+// listed devices (expansion route, cut at candidate boundaries); every launch is followed by
+// halda_subsets_pick_kernel, which folds its items into the frontier. Everything lives in the context's
+// grow-only sel_buf, so the call runs after the previous user of the context's shared scratch on another
+// stream (order_after_previous).
+constexpr int64_t kSubsetsChunkDevices = int64_t(1) << 21;
+constexpr int64_t kSubsetsFusedChunk = int64_t(1) << 22;
+constexpr int kSubsetsRing = 8192;  // 64-entry w / n strips of the fused route (written, never read)
+
+int halda_set_subsets_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "subsets path must be 0 (automatic) or 1 (always expand)");
+    c->sel_path = path;
+    return HALDA_OK;
+}
+
+int halda_last_subsets_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->sel_route;
+    return HALDA_OK;
+}
+
+static int64_t binom_sat(int q, int d) {
+    if (d < 0 || d > q) return 0;
+    d = std::min(d, q - d);
+    unsigned __int128 v = 1;
+    for (int i = 1; i <= d; ++i) v = v * unsigned(q - d + i) / unsigned(i);  // exact: a product of i consecutive
+    return v > (unsigned __int128)INT64_MAX ? INT64_MAX : int64_t(v);
+}
+
+int64_t halda_subsets_count(int32_t q, int32_t max_drop) {
+    if (q < 0 || q > 64 || max_drop < 0) return -1;
+    int64_t tot = 0;
+    for (int d = 0; d <= std::min(max_drop, q); ++d) {
+        const int64_t b = binom_sat(q, d);
+        if (b > INT64_MAX - tot) return INT64_MAX;
+        tot += b;
+    }
+    return tot;
+}
+
+// The combos of d of q slots in enumeration order: ascending index lists, lexicographic.
+static void subset_combos(int q, int d, std::vector<uint64_t> &out) {
+    int idx[64];
+    for (int j = 0; j < d; ++j) idx[j] = j;
+    while (true) {
+        uint64_t m = 0;
+        for (int j = 0; j < d; ++j) m |= uint64_t(1) << idx[j];
+        out.push_back(m);
+        int j = d - 1;
+        while (j >= 0 && idx[j] == q - d + j) --j;
+        if (j < 0) return;
+        ++idx[j];
+        for (int t = j + 1; t < d; ++t) idx[t] = idx[t - 1] + 1;
+    }
+}
+
+struct SubsetLaunch {
+    int d;
+    bool fused;
+    int64_t i0, n, l0, nd;  // first item, items, listed devices in front of it, its listed devices
+    int lmin, lmax;         // expansion: the shortest and longest list of the launch
+};
+
+// sizes: every fleet's device count (host); keep: host masks or NULL
+static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets *table, const int32_t *sizes,
+                         const halda_subsets *subsets, const int32_t *ks, int32_t n_k,
+                         halda_subset_frontier *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int nf = table->n_fleets, D = subsets->max_drop;
+    const uint64_t *keep = subsets->keep_mask;
+    if (!frontier->status || !frontier->obj || !frontier->dropped_mask || !frontier->best_k)
+        return fail(HALDA_E_ARG, "halda_subset_frontier: NULL");
+    if (D < 0 || D > 63) return fail(HALDA_E_ARG, "halda_subsets: max_drop must be in 0..63");
+    if (n_k <= 0 || n_k > 1024) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    for (int j = 0; j < n_k; ++j)
+        if (ks[j] < 1 || (j && ks[j] <= ks[j - 1])) return fail(HALDA_E_ARG, "ks must be ascending, unique, > 0");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    // the gate, from the shapes alone
+    std::vector<uint64_t> drop(nf);
+    std::vector<int> qs(nf), Df(nf);
+    int Dmax = -1;
+    bool uniform = true;
+    for (int f = 0; f < nf; ++f) {
+        const int M = sizes[f];
+        if (M < 1 || M > 64)
+            return fail(HALDA_E_ARG, "halda_solve_subsets: fleet " + std::to_string(f) + " has " + std::to_string(M) +
+                                         " devices (1..64)");
+        const uint64_t all = M == 64 ? ~uint64_t(0) : (uint64_t(1) << M) - 1, k = keep ? keep[f] : 0;
+        if (k & ~all)
+            return fail(HALDA_E_ARG, "halda_subsets: keep_mask of fleet " + std::to_string(f) + " names a device past " +
+                                         std::to_string(M));
+        drop[f] = all & ~k;
+        qs[f] = __builtin_popcountll(drop[f]);
+        Df[f] = std::min({D, qs[f], M - 1});
+        Dmax = std::max(Dmax, Df[f]);
+        uniform = uniform && M == sizes[0];
+        const int64_t cnt = halda_subsets_count(qs[f], Df[f]);
+        if (cnt > HALDA_SUBSETS_MAX)
+            return fail(HALDA_E_ARG, "halda_solve_subsets: fleet " + std::to_string(f) + " has " + std::to_string(cnt) +
+                                         " candidates, the limit is " + std::to_string(HALDA_SUBSETS_MAX));
+    }
+    if (D > Dmax)
+        return fail(HALDA_E_ARG, "halda_subsets: max_drop " + std::to_string(D) + " is beyond min(q, M - 1) = " +
+                                     std::to_string(Dmax) + " of every fleet");
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    // the combo lists of every (q, d) in use, and the records per (d, fleet)
+    std::vector<uint64_t> combos;
+    std::vector<int64_t> coff(65 * 64, -1);
+    std::vector<SubsetFleet> recs(size_t(D + 1) * nf);
+    std::vector<SubsetLaunch> launches;
+    int64_t max_items = 0, max_dev = 0;
+    bool any_fused = false, any_expand = false;
+    for (int d = 0; d <= D; ++d) {
+        SubsetFleet *R = recs.data() + size_t(d) * nf;
+        int64_t cmax = 0;
+        for (int f = 0; f < nf; ++f) {
+            SubsetFleet &r = R[f];
+            r = SubsetFleet{};
+            r.drop_mask = drop[f];
+            r.M = sizes[f];
+            r.cnt = d <= Df[f] ? int32_t(binom_sat(qs[f], d)) : 0;
+            if (r.cnt > 0) {
+                int64_t &o = coff[size_t(qs[f]) * 64 + d];
+                if (o < 0) {
+                    o = int64_t(combos.size());
+                    subset_combos(qs[f], d, combos);
+                }
+                r.combo_off = o;
+            }
+            cmax = std::max<int64_t>(cmax, r.cnt);
+        }
+        // the route of this d: the sub-fleet kernel's gate on a batch of the d's items
+        bool fused = false;
+        SweepPlan p;
+        const int64_t padded = cmax * nf;
+        if (c->sel_path == 0 && c->fleets_fused && n_k <= 64 && uniform && padded < (int64_t(1) << 31)) {
+            halda_fleets V = *table;
+            V.n_fleets = int32_t(std::min(padded, kSubsetsFusedChunk));
+            V.min_devices = V.max_devices = sizes[0] - d;
+            halda_fleet_result o = {};
+            const int rc = plan_sweep(c, *model, V, ks, n_k, o, &p);
+            if (rc != HALDA_OK) return rc;
+            fused = p.kind == kRegAlone && !p.A.k1dp;
+        }
+        if (fused) {
+            for (int f = 0; f < nf; ++f) R[f].item_off = int64_t(f) * cmax;
+            for (int64_t a = 0; a < padded; a += kSubsetsFusedChunk)
+                launches.push_back(SubsetLaunch{d, true, a, std::min(kSubsetsFusedChunk, padded - a), cmax, 0, 0, 0});
+            max_items = std::max(max_items, std::min(kSubsetsFusedChunk, padded));
+            any_fused = true;
+        } else {
+            int64_t items = 0, devs = 0;
+            for (int f = 0; f < nf; ++f) {
+                R[f].item_off = items;
+                R[f].list_off = devs;
+                items += R[f].cnt;
+                devs += int64_t(R[f].cnt) * (sizes[f] - d);
+            }
+            // chunks of at most kSubsetsChunkDevices listed devices, cut at candidate boundaries
+            int f = 0;
+            int64_t a = 0;
+            while (a < items) {
+                SubsetLaunch L{d, false, a, 0, 0, 0, 64, 0};
+                while (R[f].cnt == 0 || R[f].item_off + R[f].cnt <= a) ++f;
+                L.l0 = R[f].list_off + (a - R[f].item_off) * (sizes[f] - d);
+                int64_t b = a;
+                for (int g = f; g < nf && b < items; ++g) {
+                    if (R[g].cnt == 0) continue;
+                    const int len = sizes[g] - d;
+                    const int64_t left = R[g].item_off + R[g].cnt - b;
+                    int64_t take = std::min<int64_t>(left, (kSubsetsChunkDevices - L.nd) / len);
+                    if (take <= 0) break;
+                    take = std::min<int64_t>(take, INT32_MAX / 2 - L.n);
+                    L.n += take;
+                    L.nd += take * len;
+                    L.lmin = std::min(L.lmin, len);
+                    L.lmax = std::max(L.lmax, len);
+                    b += take;
+                    if (take < left) break;
+                }
+                launches.push_back(L);
+                max_items = std::max(max_items, L.n);
+                max_dev = std::max(max_dev, L.nd);
+                a = b;
+            }
+            any_expand = true;
+        }
+        // (fused launches carry cmax in l0: the expansion fields are unused there)
+    }
+    // scratch: combos, records, per-item results, then the fused ring or the expansion's item arrays and w / n
+    stage::Bump lay;
+    const size_t o_combo = lay.take(8 * combos.size()), o_rec = lay.take(sizeof(SubsetFleet) * recs.size()),
+                 o_obj = lay.take(8 * size_t(max_items)), o_bk = lay.take(4 * size_t(max_items)),
+                 o_par = lay.take(4 * size_t(max_items)), o_soff = lay.take(8 * size_t(max_items + 1));
+    const size_t wn = std::max<size_t>(size_t(max_dev), any_fused ? size_t(kSubsetsRing) * 64 : 0);
+    const size_t o_sidx = lay.take(4 * size_t(max_dev)), o_w = lay.take(4 * wn), o_n = lay.take(4 * wn);
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sel_buf, &c->sel_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
+    }
+    char *base = reinterpret_cast<char *>(c->sel_buf);
+    // (pageable sources: the copies are staged before the calls return)
+    HIP_TRY(hipMemcpyAsync(base + o_combo, combos.data(), 8 * combos.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_rec, recs.data(), sizeof(SubsetFleet) * recs.size(), hipMemcpyHostToDevice, s));
+    halda_fleet_result out = {};
+    out.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+    out.obj_value = reinterpret_cast<double *>(base + o_obj);
+    out.w = reinterpret_cast<int32_t *>(base + o_w);
+    out.n = reinterpret_cast<int32_t *>(base + o_n);
+    const SubsetFrontier FR{frontier->status, frontier->obj, frontier->dropped_mask, frontier->best_k};
+    c->fleet_timed = false;
+    for (const SubsetLaunch &L : launches) {
+        SubsetArgs U = {};
+        U.fl = reinterpret_cast<const SubsetFleet *>(base + o_rec) + size_t(L.d) * nf;
+        U.combos = reinterpret_cast<const uint64_t *>(base + o_combo);
+        U.i0 = L.i0;
+        U.n = int32_t(L.n);
+        U.n_fleets = nf;
+        U.d = L.d;
+        if (L.fused) {
+            U.cmax = int32_t(L.l0);
+            halda_fleets V = *table;
+            V.n_fleets = int32_t(L.n);
+            V.min_devices = V.max_devices = sizes[0] - L.d;
+            SweepPlan p;
+            const int rc = plan_sweep(c, *model, V, ks, n_k, out, &p);
+            if (rc != HALDA_OK) return rc;
+            SweepArgs &A = p.A;
+            A.fflag = nullptr;  // the register sweep alone never flags
+            A.hb_flag = c->hb_flag;
+            A.launch_id = ++c->launch_id;
+            A.want = 0;
+            c->have_lowered = false;
+            hipLaunchKernelGGL(halda_sweep_subsets_kernel,
+                               dim3(unsigned((L.n + kSweepWavesPerBlock - 1) / kSweepWavesPerBlock)),
+                               dim3(64 * kSweepWavesPerBlock), 0, s, A, U, kSubsetsRing - 1);
+            HIP_TRY(hipGetLastError());
+        } else {
+            U.l0 = L.l0;
+            halda_subfleets I;
+            I.n_items = int32_t(L.n);
+            I.min_devices = L.lmin;
+            I.max_devices = L.lmax;
+            I.parent = reinterpret_cast<const int32_t *>(base + o_par);
+            I.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
+            I.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
+            hipLaunchKernelGGL(halda_subsets_index_kernel, dim3(unsigned((L.n + 3) / 4)), dim3(256), 0, s, U,
+                               reinterpret_cast<int32_t *>(base + o_par), reinterpret_cast<int64_t *>(base + o_soff),
+                               reinterpret_cast<int32_t *>(base + o_sidx));
+            HIP_TRY(hipGetLastError());
+            // the sub-fleet entry's expansion route, unedited, on the items just written
+            const int path = c->sub_path, route = c->sub_route;
+            c->sub_path = 1;
+            const int rc = solve_subfleets(ctx, model, table, &I, ks, n_k, &out, s, L.nd);
+            c->sub_path = path;
+            c->sub_route = route;
+            if (rc != HALDA_OK) return rc;
+        }
+        hipLaunchKernelGGL(halda_subsets_pick_kernel, dim3(unsigned(nf)), dim3(256), 0, s, U,
+                           static_cast<const double *>(out.obj_value), static_cast<const int32_t *>(out.best_k), FR,
+                           D + 1);
+        HIP_TRY(hipGetLastError());
+    }
+    c->sel_route = any_fused && any_expand ? 3 : any_fused ? 1 : 2;
+    return HALDA_OK;
+}
+
+int halda_solve_subsets(void *ctx, const halda_model *model, const halda_fleets *fleets, const halda_subsets *subsets,
+                        const int32_t *ks, int32_t n_k, halda_subset_frontier *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fleets || !subsets || !ks || !frontier)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/ks/frontier");
+    const int64_t nf = fleets->n_fleets;
+    if (nf <= 0) return HALDA_OK;
+    if (!fleets->dev_off) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    std::vector<int32_t> sizes(size_t(nf), fleets->max_devices);
+    if (fleets->min_devices != fleets->max_devices) {
+        HIP_TRY(hipSetDevice(c->device));
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+        std::vector<int64_t> off(size_t(nf) + 1);
+        HIP_TRY(hipMemcpyAsync(off.data(), fleets->dev_off, 8 * (nf + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int64_t f = 0; f < nf; ++f)
+            sizes[f] = int32_t(std::max<int64_t>(-1, std::min<int64_t>(off[f + 1] - off[f], 65)));
+    }
+    return solve_subsets(ctx, model, fleets, sizes.data(), subsets, ks, n_k, frontier, stream);
+}
+
+int halda_solve_subsets_host(void *ctx, const halda_model *model, const halda_fleets *th, const halda_subsets *subsets,
+                             const int32_t *ks, int32_t n_k, halda_subset_frontier *fh) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !subsets || !ks || !fh)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/ks/frontier");
+    if (th->n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!fh->status || !fh->obj || !fh->dropped_mask || !fh->best_k)
+        return fail(HALDA_E_ARG, "halda_subset_frontier: NULL");
+    if (subsets->max_drop < 0 || subsets->max_drop > 63)
+        return fail(HALDA_E_ARG, "halda_subsets: max_drop must be in 0..63");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    std::vector<int32_t> sizes(size_t(nf), 0);
+    for (int64_t f = 0; f < nf; ++f)
+        sizes[f] = int32_t(std::max<int64_t>(-1, std::min<int64_t>(th->dev_off[f + 1] - th->dev_off[f], 65)));
+    const size_t pts = size_t(nf) * size_t(subsets->max_drop + 1);
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const size_t o_st = lay.take(4 * pts), o_obj = lay.take(8 * pts), o_mask = lay.take(8 * pts), o_bk = lay.take(4 * pts);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    halda_subset_frontier fd;
+    fd.status = reinterpret_cast<int32_t *>(base + o_st);
+    fd.obj = reinterpret_cast<double *>(base + o_obj);
+    fd.dropped_mask = reinterpret_cast<uint64_t *>(base + o_mask);
+    fd.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+    rc = solve_subsets(ctx, model, &d, sizes.data(), subsets, ks, n_k, &fd, s);
+    if (rc != HALDA_OK) return rc;
+    const std::array<stage::Copy, 4> back = {{{fh->status, o_st, 4 * pts},
+                                              {fh->obj, o_obj, 8 * pts},
+                                              {fh->dropped_mask, o_mask, 8 * pts},
+                                              {fh->best_k, o_bk, 4 * pts}}};
+    rc = download(back, base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;

@@ -1267,6 +1267,196 @@ __global__ __launch_bounds__(256) void halda_expand_subfleets_kernel(halda_fleet
     }
 }
 
+// ---------------------------------------------------------------- exact device selection: all subsets
+// halda_solve_subsets: the candidates of a fleet are the fleet without d of its droppable devices, kept
+// devices in their order; a candidate is a 64-bit combo over droppable SLOTS (bit r: drop the r-th
+// droppable device). The host lays out, per d, one SubsetFleet per fleet and one combo list per (q, d) in
+// enumeration order (ascending index lists, lexicographic); every launch below works on one d and on the
+// items [i0, i0 + n) of that d's item numbering.
+struct SubsetFleet {
+    int64_t item_off;    // the fleet's first item of this d (fused: f * cmax, expansion: compact prefix)
+    int64_t combo_off;   // its (q, d) combo list in SubsetArgs::combos
+    int64_t list_off;    // expansion: listed devices of every item in front of the fleet's first
+    uint64_t drop_mask;  // its droppable devices
+    int32_t cnt;         // its candidates of this d (0: d is beyond what the fleet may drop)
+    int32_t M;           // its devices
+};
+
+struct SubsetArgs {
+    const SubsetFleet *fl;   // [n_fleets] of this d
+    const uint64_t *combos;  // every (q, d) list of the call
+    int64_t i0;              // the launch's first item
+    int64_t l0;              // expansion: listed devices in front of item i0
+    int32_t n;               // its items
+    int32_t cmax;            // fused: item slots per fleet (slots past cnt run nothing)
+    int32_t n_fleets, d;
+};
+
+__device__ inline uint64_t sload_u64(const uint64_t *p) {
+    return uint64_t(sload_i64(reinterpret_cast<const int64_t *>(p)));
+}
+
+__device__ inline SubsetFleet subset_fleet(const SubsetArgs &U, int f) {
+    const int64_t *p = reinterpret_cast<const int64_t *>(U.fl + f);
+    SubsetFleet s;
+    s.item_off = sload_i64(p);
+    s.combo_off = sload_i64(p + 1);
+    s.list_off = sload_i64(p + 2);
+    s.drop_mask = uint64_t(sload_i64(p + 3));
+    const int64_t cm = sload_i64(p + 4);
+    s.cnt = int32_t(uint32_t(uint64_t(cm)));
+    s.M = int32_t(uint64_t(cm) >> 32);
+    return s;
+}
+
+// Lane j < M - d: the parent index of the j-th kept device of the candidate (lanes past it: that of lane
+// 0). Lane = parent device; its slot is the number of droppable devices below it; it is kept unless it is
+// droppable and its combo bit is set. Kept lanes push their index forward to their rank among the kept,
+// the others (dropped, or past M) to the lanes behind the kept ones: a permutation, every lane active.
+__device__ inline int subset_kept_index(uint64_t drop_mask, uint64_t combo, int M, int lane, int *n_kept) {
+    const uint64_t below = (uint64_t(1) << lane) - 1;
+    const int slot = __popcll(drop_mask & below);
+    const bool kept = lane < M && !(((drop_mask >> lane) & 1) && ((combo >> slot) & 1));
+    const uint64_t km = __ballot(kept);
+    const int nk = __popcll(km);
+    const int dest = kept ? __popcll(km & below) : nk + __popcll(~km & below);
+    const int got = __builtin_amdgcn_ds_permute(dest << 2, lane);
+    *n_kept = nk;
+    return lane < nk ? got : __builtin_amdgcn_readfirstlane(got);
+}
+
+// halda_sweep_subsets_kernel: the fused route -- one wave per (fleet, candidate) of one d, every fleet of
+// M = A.uM + d devices (A.uM = M - d is the candidates' length; the host sends only shapes whose register
+// sweep needs no table launch, the sub-fleet kernel's gate). Item g = i0 + wave is (fleet g / cmax,
+// candidate g % cmax); the fleet's record and the combo are wave-uniform reads through the scalar cache.
+// The kept devices' fields are loaded by the compacted lanes and handed to sweep_fleet (kPre) as
+// halda_sweep_subfleets_kernel hands its gathered fields: the same code on the same fields, so the same
+// bits as halda_solve_subfleets of the candidate's list. Only best_k / obj_value per item are kept
+// (A.out over the launch's items); w / n go to a ring of 64-entry strips nobody reads (ring_mask).
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_subsets_kernel(
+    SweepArgs A, SubsetArgs U, int ring_mask) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    if (i >= U.n) return;
+    const int lane = int(threadIdx.x & 63);
+    const uint32_t g = uint32_t(U.i0) + uint32_t(i);  // the host sends n_fleets * cmax < 2^31 (a 32-bit division)
+    const int f = int(g / uint32_t(U.cmax));
+    const int cand = int(g - uint32_t(f) * uint32_t(U.cmax));
+    const SubsetFleet sf = subset_fleet(U, f);
+    if (cand >= sf.cnt) return;
+    const uint64_t combo = sload_u64(U.combos + sf.combo_off + cand);
+    const int64_t base = sload_i64(A.F.dev_off + f);
+    int nk;
+    const int idx = subset_kept_index(sf.drop_mask, combo, sf.M, lane, &nk);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    SweepPre pre;
+    const bool kl = lane < A.n_k;
+    pre.kj = A.ks[kl ? lane : 0];
+    pre.Wj = kl ? A.Ws[lane] : 0;
+    pre.d0 = int64_t(i & ring_mask) * 64;
+    pre.mf = load_fields(A.F, base + idx);
+    sweep_fleet<false, false, Wave, true, false>(A, A.F, A.out, i, w, Wave(lane), &pre);
+}
+
+// halda_subsets_index_kernel: the expansion route -- one wave per item writes the candidate as an item of
+// halda_solve_subfleets (parent, sub_off, the kept devices' indices) over the launch's items; the fleet of
+// item g is the last one whose item_off is <= g (a binary search over uniform reads).
+__global__ __launch_bounds__(256) void halda_subsets_index_kernel(SubsetArgs U, int32_t *parent, int64_t *sub_off,
+                                                                  int32_t *sub_idx) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * 4 + int(threadIdx.x >> 6));
+    if (i >= U.n) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t g = U.i0 + i;
+    int lo = 0, hi = U.n_fleets - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (sload_i64(&U.fl[mid].item_off) <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    const SubsetFleet sf = subset_fleet(U, lo);
+    const int64_t cand = g - sf.item_off;
+    const uint64_t combo = sload_u64(U.combos + sf.combo_off + cand);
+    int nk;
+    const int idx = subset_kept_index(sf.drop_mask, combo, sf.M, lane, &nk);
+    const int64_t so = sf.list_off + cand * int64_t(sf.M - U.d) - U.l0;
+    if (lane < nk) sub_idx[so + lane] = idx;
+    if (lane == 0) {
+        parent[i] = lo;
+        sub_off[i] = so;
+        if (i == U.n - 1) sub_off[i + 1] = so + nk;
+    }
+}
+
+// halda_subsets_pick_kernel: one workgroup per fleet -- the arg-min of the launch's items of the fleet's
+// group (this d) on (obj_value, candidate index), lexicographic with strict <, so the earliest candidate
+// among equal objectives: per thread over its candidates in ascending order, a wave reduction, then one
+// over the workgroup's waves through LDS. Folded into the frontier entry where the group began in an
+// earlier launch (strict <: the earlier launch's candidates come first). A group without candidates, or
+// whose candidates are all infeasible, gets INFEASIBLE, +inf and mask 0.
+struct SubsetFrontier {
+    int32_t *status;
+    double *obj;
+    uint64_t *dropped_mask;
+    int32_t *best_k;
+};
+
+__device__ inline void subset_min(double &o, int64_t &c, double o2, int64_t c2) {
+    if (c2 >= 0 && (c < 0 || o2 < o || (o2 == o && c2 < c))) {
+        o = o2;
+        c = c2;
+    }
+}
+
+__global__ __launch_bounds__(256) void halda_subsets_pick_kernel(SubsetArgs U, const double *obj, const int32_t *best_k,
+                                                                 SubsetFrontier R, int stride) {
+    const int f = int(blockIdx.x);
+    const SubsetFleet sf = subset_fleet(U, f);
+    const int64_t a = sf.item_off > U.i0 ? sf.item_off : U.i0;
+    const int64_t e = sf.item_off + sf.cnt, lim = U.i0 + U.n;
+    const int64_t b = e < lim ? e : lim;
+    const int64_t at = int64_t(f) * stride + U.d;
+    if (sf.cnt == 0) {
+        if (threadIdx.x == 0 && U.i0 == 0) {
+            R.status[at] = HALDA_STATUS_INFEASIBLE;
+            R.obj[at] = kInf;
+            R.dropped_mask[at] = 0;
+            R.best_k[at] = 0;
+        }
+        return;
+    }
+    if (a >= b) return;
+    double o = kInf;
+    int64_t c = -1;
+    for (int64_t g = a + threadIdx.x; g < b; g += 256) subset_min(o, c, obj[g - U.i0], g - sf.item_off);
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double o2 = __shfl_xor(o, s);
+        const int64_t c2 = (int64_t(__shfl_xor(int(uint64_t(c) >> 32), s)) << 32) | uint32_t(__shfl_xor(int(c), s));
+        subset_min(o, c, o2, c2);
+    }
+    __shared__ double so[4];
+    __shared__ int64_t sc[4];
+    if ((threadIdx.x & 63) == 0) {
+        so[threadIdx.x >> 6] = o;
+        sc[threadIdx.x >> 6] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int wv = 1; wv < 4; ++wv) subset_min(o, c, so[wv], sc[wv]);
+    if (a > sf.item_off && !(o < R.obj[at])) return;  // the group began earlier: only a strictly lower value moves it
+    uint64_t mask = 0;
+    if (o < kInf) {
+        const uint64_t combo = U.combos[sf.combo_off + c];
+        int r = 0;
+        for (uint64_t m = sf.drop_mask; m; m &= m - 1, ++r)
+            if ((combo >> r) & 1) mask |= m & (~m + 1);
+    }
+    R.status[at] = o < kInf ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+    R.obj[at] = o;
+    R.dropped_mask[at] = mask;
+    R.best_k[at] = best_k[sf.item_off + c - U.i0];
+}
+
 // ---------------------------------------------------------------- model variants of one table
 // halda_solve_variants: one fleet table solved for n_var models in one launch, blockIdx.y the variant.
 // The variants share the table, the k list, L (so every W = L / k and the plan's shapes) and has_f_q /

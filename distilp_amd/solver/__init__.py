@@ -11,6 +11,8 @@ from .plans import (PlanEvaluation, Replacement, evaluate_plan_np, halda_evaluat
                     halda_evaluate_plans_batch, halda_replace_or_keep, halda_replace_or_keep_batch)
 from .subfleets import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
                         halda_solve_subfleets)
+from .subsets import (SubsetPoint, halda_select_devices_exact, halda_subset_frontier,  # noqa: F401
+                      halda_subset_frontier_batch)
 from .variants import halda_context_sweep, halda_solve_variants, model_grid  # noqa: F401
 
 __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solve_subfleets", "halda_leave_one_out",
@@ -19,7 +21,8 @@ __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solv
            "halda_replace_or_keep_batch", "halda_solve_bounded", "halda_solve_bounded_batch", "move_bounds", "move_box",
            "halda_replace_within", "halda_replace_within_batch", "ReplacementWithin", "halda_move_frontier",
            "halda_move_frontier_batch", "halda_solve_budget", "FrontierPoint", "evaluate_plan_np",
-           "PlanEvaluation", "Replacement", "HALDAResult",
+           "PlanEvaluation", "Replacement", "HALDAResult", "halda_subset_frontier", "halda_subset_frontier_batch",
+           "halda_select_devices_exact", "SubsetPoint",
            "ILPResult"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

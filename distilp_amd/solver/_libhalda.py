@@ -92,7 +92,9 @@ EXPORTS = ("halda_version", "halda_init", "halda_solve_batch", "halda_solve_batc
            "halda_solve_fleets_plans_host", "halda_last_plans_route", "halda_set_plans_path",
            "halda_solve_fleets_bounded", "halda_solve_fleets_bounded_host", "halda_last_bounds_route",
            "halda_set_bounds_path", "halda_solve_fleets_boxed", "halda_solve_fleets_boxed_host",
-           "halda_solve_fleets_budget", "halda_solve_fleets_budget_host", "halda_budget_lds_bytes")
+           "halda_solve_fleets_budget", "halda_solve_fleets_budget_host", "halda_budget_lds_bytes",
+           "halda_solve_subsets", "halda_solve_subsets_host", "halda_subsets_count", "halda_last_subsets_route",
+           "halda_set_subsets_path")
 
 _lib = None
 _lib_lock = threading.Lock()

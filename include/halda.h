@@ -595,6 +595,73 @@ int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const ha
  * max_devices < 1, max_p < 0 or k < 1. No context needed. */
 int64_t halda_budget_lds_bytes(int32_t max_devices, int32_t max_p, int32_t k);
 
+/* ------------------------------------------------------------------------
+ * Exact device selection: the best sub-fleet over all subsets of the droppable devices.
+ *
+ * Per fleet of M <= 64 devices: keep_mask names the devices that may not be dropped (bit i: device i;
+ * NULL: none), q = M - |keep| are droppable, and a candidate is the fleet without d of them, the kept
+ * devices in their order (kappa's head by halda_solve_subfleets' rule). A candidate's value is what
+ * halda_solve_subfleets writes for that list, bit for bit (+inf where no k is feasible). Candidates are
+ * enumerated by d ascending and, within one d, by their ascending dropped-index lists in lexicographic
+ * order; among equal objectives the earliest wins (strict <).
+ *
+ * The frontier has max_drop + 1 points per fleet, laid out [fleet][max_drop + 1]: point d is the best
+ * candidate with exactly d devices dropped -- status HALDA_STATUS_OPTIMAL or _INFEASIBLE, obj, the dropped
+ * devices as a mask, and the candidate's best_k. A point whose candidates are all infeasible has +inf and
+ * mask 0. A fleet may drop at most min(q, M - 1) devices: its points beyond that have no candidate and read
+ * INFEASIBLE, +inf, mask 0, best_k 0 (so fleets of several sizes share one max_drop).
+ *
+ * Gate, from the shapes alone, before any GPU work (HALDA_E_ARG): every fleet has 1 .. 64 devices;
+ * 0 <= max_drop <= 63 and max_drop <= min(q, M - 1) of at least one fleet; no keep bit at or above M; and
+ * halda_subsets_count(q, min(max_drop, q, M - 1)) <= HALDA_SUBSETS_MAX candidates per fleet.
+ *
+ * Routes, per d (halda_last_subsets_route): fused -- every fleet of one size M and a batch of all the d's
+ * candidates, fleets of M - d devices, planned as the register sweep alone (halda_solve_subfleets' gate):
+ * one wave per (fleet, candidate) forms the candidate from a per-(q, d) combo list and gathers its
+ * devices' fields from the table (halda_sweep_subsets_kernel); expansion -- every other shape:
+ * halda_subsets_index_kernel writes the candidates as halda_solve_subfleets items in context scratch and
+ * that entry's expansion route runs on them, in chunks of at most 2^21 listed devices. Either way
+ * halda_subsets_pick_kernel reduces each (fleet, d) group on the device: the per-candidate values never
+ * leave it. The scratch is per context, so the call runs after the previous user of the context's shared
+ * scratch on another stream.
+ * ------------------------------------------------------------------------ */
+#define HALDA_SUBSETS_MAX (1 << 20)
+
+typedef struct halda_subsets {
+    int32_t max_drop;
+    const uint64_t *keep_mask; /* HOST memory, [n_fleets], or NULL */
+} halda_subsets;
+
+typedef struct halda_subset_frontier {
+    int32_t *status;        /* [n_fleets * (max_drop + 1)] */
+    double *obj;            /* [n_fleets * (max_drop + 1)] */
+    uint64_t *dropped_mask; /* [n_fleets * (max_drop + 1)] */
+    int32_t *best_k;        /* [n_fleets * (max_drop + 1)] */
+} halda_subset_frontier;
+
+/* Asynchronous on `stream` (NULL = the context's stream); fleets and frontier hold device arrays, ks and
+ * keep_mask are host memory. With mixed fleet sizes the call reads dev_off back (it waits for `stream`
+ * once). */
+int halda_solve_subsets(void *ctx, const halda_model *model, const halda_fleets *fleets, const halda_subsets *subsets,
+                        const int32_t *ks, int32_t n_k, halda_subset_frontier *frontier, void *stream);
+
+/* Synchronous variant on HOST arrays: the table crosses PCIe on the way in, the frontier on the way back. */
+int halda_solve_subsets_host(void *ctx, const halda_model *model, const halda_fleets *fleets,
+                             const halda_subsets *subsets, const int32_t *ks, int32_t n_k,
+                             halda_subset_frontier *frontier);
+
+/* sum over d <= max_drop of C(q, d), saturated at INT64_MAX; -1 for q < 0, q > 64 or max_drop < 0. No
+ * context needed. */
+int64_t halda_subsets_count(int32_t q, int32_t max_drop);
+
+/* Which routes the context's last halda_solve_subsets / _host call took: 1 fused for every d, 2 expansion
+ * for every d, 3 mixed (they differ by d), 0 when none ran yet. */
+int halda_last_subsets_route(void *ctx, int *route);
+
+/* How halda_solve_subsets runs: 0 automatic (default: the fused route where it applies), 1 always expand
+ * (test path: the fused route is compared against it). HALDA_E_ARG for any other path. */
+int halda_set_subsets_path(void *ctx, int path);
+
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */
 int halda_resident_release(void *ctx);
