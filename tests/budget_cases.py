@@ -30,6 +30,62 @@ PS_A = (0, 1, 2, 3)
 LIST_B = [(M, k, s) for M, ks in ((8, (1, 2)), (16, (1, 2, 4))) for k in ks for s in range(6)]
 PS_B = (0, 1, 2, 4, 8)
 
+# list P, memory-pressured fleets (tests/pressure_cases.py, kv 4bit): (M, scale, k, seed s); the incumbent is the
+# pressured optimum of seed s + 100 of the same class at the same k. M = 5: oracle (a) against (b) on PS_A;
+# M = 16: oracle (b) re-priced by Pinned on PS_B; one 64-device fleet at P = 2, oracle (b).
+PS_P64 = (0, 1, 2)
+
+
+def _list_p():
+    from . import pressure_cases as pc
+
+    out = [(5, pc.S16, k, s) for k in (1, 2, 4) for s in range(3)]
+    out += [(16, pc.S16, k, s) for k in (1, 2, 4) for s in range(3)]
+    out += [(16, pc.S64, k, s) for k in (1, 2) for s in range(3)]
+    return out + [(64, pc.S64, 1, 0)]
+
+
+LIST_P = _list_p()
+
+
+def ps_of_p(M):
+    return PS_A if M == 5 else PS_B if M == 16 else PS_P64
+
+
+def key_p(M, scale, k, s):
+    return f"{M},1/{scale.denominator},{k},{s}"
+
+
+def list_p_case(M, scale, k, s):
+    """(devs, w0) of a list P case."""
+    from . import pressure_cases as pc
+
+    st, x, _, _ = pc.exact((M, scale, s + 100, "4bit"), k)
+    assert st == 0, (M, scale, k, s)
+    return pc.devices(s, M, scale), [int(v) for v in np.rint(x[:M])]
+
+
+def list_p_answer(model, M, scale, k, s):
+    """(w0, {p: obj_value}, free_p) of a list P case by its oracle; for M = 5 oracle (a), asserted equal to (b)."""
+    devs, w0 = list_p_case(M, scale, k, s)
+    prob = problem(model, devs, k)
+    pin, objs = Pinned(prob), {}
+    a = enumerate_frontier(prob, w0, PS_A) if M == 5 else None
+    for p in ps_of_p(M):
+        b, w = highs_budget(prob, w0, p)
+        assert b is not None, (M, scale, k, s, p)
+        e = pin(w)
+        assert e is not None and bc.rel(b, e) <= 1e-9, (M, scale, k, s, p, b, e)
+        assert sum(w) == prob["W"] and sum(max(0, x - y) for x, y in zip(w, w0)) <= p
+        if a is not None:
+            assert a[p] is not None and bc.rel(a[p], e) <= 1e-9, (M, scale, k, s, p, a[p], e)
+            e = a[p]
+        objs[p] = e
+    st, x, b1, b2, _ = mo.exact_solve(prob)
+    assert st == 0
+    free_p = sum(max(0, int(round(v)) - c) for v, c in zip(x[:M], w0))
+    return w0, objs, free_p, bool(mo.uniqueness_margin_ok(b1, b2))
+
 
 def key(M, k, s):
     return f"{M},{k},{s}"
@@ -163,6 +219,16 @@ def edge_cases(model):
     out["tied_k2"] = dict(devs=tied, k=2, w0=[L // 2 - 6, 2, 2, 2], w_min=None, w_max=None, P=3, oracle="a")
     pr = pc.devices(0, 3, pc.S16)
     out["pressured"] = dict(devs=pr, k=2, w0=_spread(L // 2, 3), w_min=None, w_max=None, P=3, oracle="a")
+    # a pressured 5-device fleet around the pressured optimum of seed + 100: a cap that excludes w0, and a floor
+    devs5, w5 = list_p_case(5, pc.S16, 2, 1)
+    j = int(np.argmax(w5))
+    cap = [L] * 5
+    cap[j] = w5[j] - 2
+    out["pressured_cap_excludes_w0"] = dict(devs=devs5, k=2, w0=w5, w_min=None, w_max=cap, P=3, oracle="a")
+    i = int(np.argmin(w5))
+    lo = [1] * 5
+    lo[i] = w5[i] + 1
+    out["pressured_w_min"] = dict(devs=devs5, k=2, w0=w5, w_min=lo, w_max=None, P=3, oracle="a")
     return out
 
 

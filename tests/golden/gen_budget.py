@@ -10,6 +10,8 @@ the pinned exact solver. The file holds recorded results only:
         optimum w* at that k}}                                     list A, oracle (a), checked against (b)
   "B": {"M,k,s": {"w0": [...], "obj": {p: ...}, "free_p": ...}}  list B, oracle (b), checked against pinned-exact
   "edge": {name: {"obj": {p: ...}}}                              the edge shapes, by the oracle each names
+  "P": {"M,scale,k,s": {"w0", "obj", "free_p", "free_unique"}}   list P (memory-pressured fleets), oracle (a) for
+                                                                 M = 5 checked against (b), oracle (b) elsewhere
 
 A disagreement between the two oracles beyond 1e-9 relative STOPS the generator.
 """
@@ -34,7 +36,7 @@ def main():
     from oracle import milp_oracle as mo
 
     model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
-    out = {"A": {}, "B": {}, "edge": {}}
+    out = {"A": {}, "B": {}, "edge": {}, "P": {}}
 
     def free_p(prob, w0):
         st, x, b1, b2, _ = mo.exact_solve(prob)
@@ -67,6 +69,15 @@ def main():
             better += objs[q] < objs[p]
         out["B"][bu.key(M, k, s)] = {"w0": w0, "obj": {str(p): objs[p] for p in bu.PS_B}, "free_p": free_p(prob, w0)}
     print(f"list B: {better} of {steps} steps between consecutive budgets strictly improve")
+    steps = better = 0
+    for M, sc, k, s in bu.LIST_P:
+        w0, objs, fp, uniq = bu.list_p_answer(model, M, sc, k, s)
+        ps = bu.ps_of_p(M)
+        steps += len(ps) - 1
+        better += sum(objs[q] < objs[p] for p, q in zip(ps, ps[1:]))
+        out["P"][bu.key_p(M, sc, k, s)] = {"w0": w0, "obj": {str(p): objs[p] for p in ps}, "free_p": fp,
+                                          "free_unique": uniq}
+    print(f"list P: {better} of {steps} steps between consecutive budgets strictly improve")
     for name, e in bu.edge_cases(model).items():
         ans = bu.edge_answer(model, e)
         out["edge"][name] = {"obj": {str(p): ans[p] for p in sorted(ans)}}

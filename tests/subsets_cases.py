@@ -46,13 +46,40 @@ def starved_keep():
     return dead[0]
 
 
+# A fleet key names a device list: ("synth", seed, M) -- subfleets_cases.our_devices, kv 8bit, the default k list --
+# ("p", M, scale, seed) a pressured fleet and ("i", irregular case) an edited one, both kv 4bit on the k of PRESSURE_KS.
+PRESSURE_KS = {5: None, 16: (1, 2, 4, 5), 64: (1,)}  # None: the default k list
+
+
+def fleet_of(key):
+    """(devs, model, kv_bits, k_candidates or None) of a fleet key."""
+    if key[0] == "synth":
+        return our_devices(key[1], key[2]), our_model(), "8bit", None
+    from . import irregular_cases as ic
+    from . import pressure_cases as pc
+
+    if key[0] == "p":
+        _, M, scale, seed = key
+        return pc.devices(seed, M, scale), pc.our_model(), "4bit", PRESSURE_KS[M]
+    case = key[1]
+    assert ic.model_of(case) is pc.our_model()
+    return ic.devices(case), pc.our_model(), "4bit", PRESSURE_KS[case[0]]
+
+
 @lru_cache(maxsize=None)
-def oracle_list(seed, M, kept, kv_bits="8bit"):
-    """The exact oracle's result dict (None: infeasible) of the sub-fleet `kept` (a tuple of indices)."""
-    devs = our_devices(seed, M)
-    best, _ = mo.halda_solve_oracle([devs[i] for i in kept], our_model(), mip_gap=1e-4, kv_bits=kv_bits,
+def oracle_of(key, kept):
+    """The exact oracle's result dict (None: infeasible) of the sub-fleet `kept` (a tuple of indices) of a fleet
+    key; kappa's head is the kept list's first is_head device, else its first device."""
+    devs, model, kv, ks = fleet_of(key)
+    best, _ = mo.halda_solve_oracle([devs[i] for i in kept], model, k_candidates=ks, mip_gap=1e-4, kv_bits=kv,
                                     solver="exact")
     return best
+
+
+def oracle_list(seed, M, kept, kv_bits="8bit"):
+    """oracle_of on the synthetic fleet (seed, M)."""
+    assert kv_bits == "8bit"
+    return oracle_of(("synth", seed, M), tuple(kept))
 
 
 def slots_of(M, keep):
@@ -70,17 +97,43 @@ def candidates(M, keep, d):
 
 
 def brute_force(seed, M, max_drop, keep):
+    """brute_force_of on the synthetic fleet (seed, M)."""
+    return brute_force_of(("synth", seed, M), max_drop, keep)
+
+
+def brute_force_of(key, max_drop, keep):
     """Per d: (best obj or inf, dropped of the earliest minimum or None, runner-up obj or inf) by the oracle."""
     out = []
+    M = len(fleet_of(key)[0])
     for d in range(limit_of(M, keep, max_drop) + 1):
         objs = []
         for gone, kept in candidates(M, keep, d):
-            r = oracle_list(seed, M, kept)
+            r = oracle_of(key, kept)
             objs.append((math.inf if r is None else r["obj_value"], gone))
         best = min(objs, key=lambda t: t[0])  # min keeps the earliest among equals
         others = sorted(o for o, g in objs if g != best[1])
         out.append((best[0], best[1] if best[0] < math.inf else None, others[0] if others else math.inf))
     return out
+
+
+def _pressure_cases():
+    """(key, max_drop or None, keep) under memory pressure and with moved heads: three pressured 5-device fleets,
+    every subset; a pressured 16-device fleet at D = 2; 16-device fleets with two heads, the head last and no head,
+    D = 2, without `keep` and with `keep` naming the head (device 0 where there is none); and a pressured and a
+    head-last 64-device fleet at D = 1 (the fused route)."""
+    from . import irregular_cases as ic
+    from . import pressure_cases as pc
+
+    out = [(("p", 5, pc.S16, s), None, ()) for s in range(3)] + [(("p", 16, pc.S16, 0), 2, ())]
+    for edit in ("two_heads", "head_at:last", "no_head"):
+        case = (16, pc.S16, 1, "4bit", (edit,))
+        head = ic.head_of(ic.edited_fleet(1, 16, pc.S16, (edit,))[0])
+        out += [(("i", case), 2, ()), (("i", case), 2, (head,))]
+    out += [(("p", 64, pc.S16, 0), 1, ()), (("i", (64, pc.S16, 0, "4bit", ("head_at:last",))), 1, ())]
+    return out
+
+
+PRESSURE_CASES = _pressure_cases()
 
 
 def oracle_solver(seed, M):

@@ -195,7 +195,7 @@ def test_kernel_objective_is_the_plan_evaluation_bit_for_bit(llama_online_model,
 
 
 @pytest.mark.parametrize("name", ["one_device", "wide_64", "cap_excludes_w0", "crossing_box", "clipped_window",
-                                  "tied_k2", "pressured"])
+                                  "tied_k2", "pressured", "pressured_cap_excludes_w0", "pressured_w_min"])
 def test_kernel_outputs_on_the_edge_shapes(llama_online_model, name):
     model = llama_online_model
     e, g = bu.edge_cases(model)[name], bu.golden()["edge"][name]["obj"]
@@ -208,9 +208,114 @@ def test_kernel_outputs_on_the_edge_shapes(llama_online_model, name):
             assert res.status[0, p] == lh.STATUS_OPTIMAL and bc.rel(res.obj[0, p], g[str(p)]) <= 1e-9, (name, p)
 
 
+# ------------------------------------------------------------------ 1c. list P: memory-pressured fleets
+def p_groups():
+    """List P by launch: {(M, scale): cases}; one budget (the largest recorded p) per group."""
+    out = {}
+    for c in bu.LIST_P:
+        out.setdefault(c[:2], []).append(c)
+    return out
+
+
+@pytest.fixture(scope="module")
+def solved_p(llama_online_model):
+    """List P solved once: {case: frontier}; one Python call per (M, scale), one GPU call per k inside it."""
+    from . import pressure_cases as pc
+
+    model, gold, out = llama_online_model, bu.golden()["P"], {}
+    for (M, sc), cases in p_groups().items():
+        fleets = [pc.devices(s, M, sc) for _, _, _, s in cases]
+        incs = [(k, gold[bu.key_p(*c)]["w0"], [0] * M) for c in cases for k in [c[2]]]
+        got = bg.halda_move_frontier_batch(fleets, model, incs, 2 * max(bu.ps_of_p(M)), KVB)
+        out.update(zip(cases, got))
+    return out
+
+
+def test_list_p_equals_the_oracle(llama_online_model, solved_p):
+    """Every recorded point of the pressured list within 1e-9 of the golden, every point under its own
+    constraints, the frontier non-increasing and every plan priced by halda_evaluate_plan bit for bit."""
+    from . import pressure_cases as pc
+
+    model, gold = llama_online_model, bu.golden()["P"]
+    for c in bu.LIST_P:
+        M, sc, k, s = c
+        g, fr = gold[bu.key_p(*c)], solved_p[c]
+        assert len(fr) == max(bu.ps_of_p(M)) + 1
+        for p in bu.ps_of_p(M):
+            check_point(model, None, k, g["w0"], p, fr[p], g["obj"][str(p)], tag=c)
+        for p, pt in enumerate(fr):
+            check_point(model, None, k, g["w0"], p, pt, pt.obj_value if pt.plan else None, tag=c)
+    check_frontier_prices(model, [pc.devices(s, M, sc) for M, sc, _, s in bu.LIST_P], [solved_p[c] for c in bu.LIST_P],
+                          "P")
+
+
+def test_list_p_kernel_objective_is_the_plan_evaluation_bit_for_bit(llama_online_model, solved_p):
+    """One raw call per (M, scale, k): the kernel's obj against halda_eval_plans on its own plan (check_raw), the
+    device-formed frontier non-increasing, the recorded points within 1e-9, the Python frontier's plans the
+    kernel's."""
+    from . import pressure_cases as pc
+
+    model, gold = llama_online_model, bu.golden()["P"]
+    for (M, sc), cases in p_groups().items():
+        for k in sorted({c[2] for c in cases}):
+            sub = [c for c in cases if c[2] == k]
+            res = check_raw(model, [pc.devices(c[3], M, sc) for c in sub], k, [gold[bu.key_p(*c)]["w0"] for c in sub],
+                            max(bu.ps_of_p(M)), tag=("P", M, sc, k))
+            assert (res.status == lh.STATUS_OPTIMAL).all()
+            assert (np.diff(res.obj, axis=1) <= 0).all()
+            for f, c in enumerate(sub):
+                for p in bu.ps_of_p(M):
+                    assert bc.rel(res.obj[f, p], gold[bu.key_p(*c)]["obj"][str(p)]) <= 1e-9, (c, p)
+                    assert solved_p[c][p].plan.w == res.w[p, f * M:(f + 1) * M].tolist(), (c, p)
+
+
+# list P's cases beyond the gate (gate_p: 60 / 59 on 5 devices, 47 / 45 on 16), by the exact oracle's free_p
+def _beyond_p():
+    from . import pressure_cases as pc
+
+    return {(5, pc.S16, 1, 1): 64, (16, pc.S16, 1, 0): 49, (16, pc.S64, 1, 0): 64, (16, pc.S64, 1, 1): 61}
+
+
+def test_list_p_ends_of_the_frontier_equal_the_bounded_solves(llama_online_model, solved_p):
+    """Point 0 equals halda_solve_bounded with w pinned (1e-12); the point at the free optimum's own move count,
+    and every later one, equals the free optimum at that k wherever the gate reaches it; elsewhere no point
+    beats it."""
+    from . import pressure_cases as pc
+
+    model, gold = llama_online_model, bu.golden()["P"]
+    beyond, reached = {}, 0
+    for (M, sc), cases in p_groups().items():
+        for k in sorted({c[2] for c in cases}):
+            sub = [c for c in cases if c[2] == k]
+            P = min(gate_p(M, k), max(gold[bu.key_p(*c)]["free_p"] for c in sub))
+            fleets = [pc.devices(c[3], M, sc) for c in sub]
+            w0s = [gold[bu.key_p(*c)]["w0"] for c in sub]
+            pinned = bd.halda_solve_bounded_batch(fleets, model, [(w0, w0) for w0 in w0s], [k], KVB)
+            free = bd.halda_solve_bounded_batch(fleets, model, [None] * len(sub), [k], KVB)
+            wide = bg.halda_move_frontier_batch(fleets, model, [(k, w0, [0] * M) for w0 in w0s], 2 * P, KVB)
+            for c, w0, a, b, fw in zip(sub, w0s, pinned, free, wide):
+                fr = solved_p[c]
+                assert a is not None and bc.rel(fr[0].obj_value, a.obj_value) <= 1e-12, (c, fr[0].obj_value, a.obj_value)
+                assert fr[0].plan.w == list(w0) and fr[0].moved_layers == 0
+                n = min(len(fr), len(fw))
+                assert [pt.obj_value for pt in fw[:n]] == [pt.obj_value for pt in fr[:n]], c
+                ps = sum(max(0, x - y) for x, y in zip(b.w, w0))
+                assert ps == gold[bu.key_p(*c)]["free_p"], (c, ps)
+                assert all(pt.obj_value >= b.obj_value - 1e-12 * max(1.0, abs(b.obj_value)) for pt in fw), c
+                if ps > P:
+                    beyond[c] = ps
+                    continue
+                reached += 1
+                assert bc.rel(fw[ps].obj_value, b.obj_value) <= 1e-12, (c, ps, fw[ps].obj_value, b.obj_value)
+                assert all(pt.obj_value == fw[ps].obj_value for pt in fw[ps:]), c
+                if ps:
+                    assert fw[ps - 1].obj_value > fw[ps].obj_value, c
+    assert beyond == _beyond_p() and reached == len(bu.LIST_P) - len(beyond)
+
+
 # ------------------------------------------------------------------ 2. the edge shapes
 @pytest.mark.parametrize("name", ["one_device", "wide_64", "cap_excludes_w0", "crossing_box", "clipped_window",
-                                  "tied_k2", "pressured"])
+                                  "tied_k2", "pressured", "pressured_cap_excludes_w0", "pressured_w_min"])
 def test_edge_shape(llama_online_model, name):
     model = llama_online_model
     e, g = bu.edge_cases(model)[name], bu.golden()["edge"][name]["obj"]
@@ -222,6 +327,12 @@ def test_edge_shape(llama_online_model, name):
     check_frontier_prices(model, [e["devs"]], [fr], name)
     if name == "clipped_window":  # the window really is clipped at w = 1 and at w = W
         assert e["w0"][0] - e["P"] < 1 and e["w0"][2] + e["P"] > int(model.L) // e["k"]
+    if name == "pressured_cap_excludes_w0":
+        assert [pt.plan is None for pt in fr] == [True, True, False, False]
+        assert all(a <= b for pt in fr[2:] for a, b in zip(pt.plan.w, e["w_max"]))
+    if name == "pressured_w_min":
+        assert [pt.plan is None for pt in fr] == [True, False, False, False]
+        assert all(a >= b for pt in fr[1:] for a, b in zip(pt.plan.w, e["w_min"]))
     if name == "cap_excludes_w0":
         assert [pt.plan is None for pt in fr] == [True, True, False, False]
         with pytest.raises(RuntimeError):

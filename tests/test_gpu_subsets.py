@@ -177,6 +177,66 @@ def test_python_entries_against_the_brute_force(case):
     assert kept == winners[0].kept  # among equal objectives the fewest drops
 
 
+# ------------------------------------------------------------------ memory pressure and moved heads
+def case_id(case):
+    key, D, keep = case
+    name = f"p{key[1]}s{key[3]}" if key[0] == "p" else f"i{key[1][0]}{key[1][4][0]}"
+    return f"{name}-D{D}-keep{''.join(map(str, keep))}"
+
+
+@pytest.mark.parametrize("case", sc.PRESSURE_CASES, ids=case_id)
+def test_frontier_under_pressure_and_with_moved_heads(case):
+    """Both routes on a pressured or head-edited fleet: the raw frontier equals the arg-min over every candidate's
+    halda_solve_subfleets value bit for bit (check_frontier), the routes agree bit for bit, the 64-device fleets
+    take the fused route; and the raw objective equals the brute force over the exact oracle within 1e-9, the
+    dropped set too wherever the runner-up is no near tie."""
+    key, D, keep = case
+    devs, model, kv, ks = sc.fleet_of(key)
+    M = len(devs)
+    D = sc.limit_of(M, keep, D)
+    ks = list(KS80 if ks is None else ks)
+    st, obj, dm, bk = check_frontier([devs], model, D, [keep], ks=ks, route0="fused" if M == 64 else None)
+    bf = sc.brute_force_of(*case)
+    assert len(bf) == D + 1
+    for d, (best, gone, runner) in enumerate(bf):
+        if gone is None:
+            assert st[0, d] == INFEASIBLE and obj[0, d] == math.inf
+            continue
+        assert st[0, d] == lh.STATUS_OPTIMAL, (case, d)
+        assert abs(obj[0, d] - best) <= sc.REL_OBJ * max(1.0, abs(best)), (case, d, obj[0, d], best)
+        assert not int(dm[0, d]) & mask_of(keep)
+        if not sc.near_tie(best, runner):
+            assert int(dm[0, d]) == mask_of(gone), (case, d, int(dm[0, d]), gone)
+
+
+@pytest.mark.parametrize("edit", ["two_heads", "head_at:last", "no_head"])
+def test_a_candidate_that_drops_the_head_gets_the_documented_head(edit):
+    """The head of a kept list is its first is_head device, else its first device: the lists that drop device 0,
+    the head, and both, through halda_solve_subfleets (what a candidate's value is) and through the frontier with
+    those devices the only droppable ones, each against the exact oracle on that kept list."""
+    key = next(k for k, _, keep in sc.PRESSURE_CASES if k[0] == "i" and k[1][4] == (edit,) and k[1][0] == 16)
+    devs, model, kv, ks = sc.fleet_of(key)
+    M = len(devs)
+    head = next((i for i, d in enumerate(devs) if d.is_head), 0)
+    last = max(i for i, d in enumerate(devs) if d.is_head) if any(d.is_head for d in devs) else M - 1
+    drops = sorted({(0,), (head,), (last,), tuple(sorted({0, last}))})
+    lists = [[i for i in range(M) if i not in g] for g in drops]
+    got = halda_solve_subfleets([devs], model, [(0, kept) for kept in lists], k_candidates=list(ks), kv_bits=kv)
+    for g, kept, r in zip(drops, lists, got):
+        want = sc.oracle_of(key, tuple(kept))
+        assert r is not None and want is not None, (edit, g)
+        assert abs(r.obj_value - want["obj_value"]) <= sc.REL_OBJ * max(1.0, abs(want["obj_value"])), (edit, g, r, want)
+        assert r.sets == want["sets"], (edit, g)
+    keep = [i for i in range(M) if i not in (0, last)]
+    pts = halda_subset_frontier(devs, model, None, keep, k_candidates=list(ks), kv_bits=kv)
+    bf = sc.brute_force_of(key, None, tuple(keep))
+    assert len(pts) == len(bf) >= 2
+    for p, (best, gone, runner) in zip(pts, bf):
+        assert abs(p.obj_value - best) <= sc.REL_OBJ * max(1.0, abs(best)), (edit, p.dropped, p.obj_value, best)
+        if not sc.near_tie(best, runner):
+            assert tuple(p.dropped) == tuple(gone), (edit, p.dropped, gone)
+
+
 def test_an_infeasible_group_has_no_plan():
     seed, M, scale = sc.STARVED
     devs, model = pc.devices(seed, M, scale), pc.our_model()

@@ -187,6 +187,30 @@ def test_near_ties_stay_inside_the_cap():
     assert near <= sc.NEAR_TIE_CAP * len(pts)
 
 
+def test_near_ties_of_the_pressured_and_moved_head_cases_stay_inside_the_cap():
+    """The same cap over sc.PRESSURE_CASES (pressured fleets, fleets with two heads, the head last or none), by
+    the oracle alone; and the cases are what they are meant to be: dropping devices pushes the rest of a
+    pressured fleet into slacks, and some candidate drops the head."""
+    from oracle import milp_oracle as mo
+
+    pts = [(b, r) for case in sc.PRESSURE_CASES for b, g, r in sc.brute_force_of(*case) if g is not None]
+    near = sum(sc.near_tie(b, r) for b, r in pts)
+    print(f"near-tie points: {near} of {len(pts)}")
+    assert len(pts) >= 40 and near <= sc.NEAR_TIE_CAP * len(pts)
+    key = sc.PRESSURE_CASES[0][0]
+    devs, model, kv, _ = sc.fleet_of(key)
+    used = 0
+    for kept in itertools.combinations(range(5), 2):
+        r = sc.oracle_of(key, kept)
+        prob = mo.lower_dense([devs[i] for i in kept], model, r["k"], mo._kv_factor(kv))
+        st, x, *_ = mo.exact_solve(prob)
+        used += st == 0 and bool((x[4:12] > 0.5).any())  # a slack or a t column is in use at the best k
+    print(f"two-device sub-fleets whose optimum uses a slack: {used} of 10")
+    assert used >= 1  # the full fleet uses none at its best k: dropping devices is what brings the slacks in
+    heads = {k[1][4][0] for k, _, keep in sc.PRESSURE_CASES if k[0] == "i" and keep}
+    assert heads == {"two_heads", "head_at:last", "no_head"}
+
+
 def test_new_kernels_use_no_scratch(tmp_path):
     """halda_sweep_subsets_kernel keeps the register sweep's occupancy (four waves per SIMD: at most 128
     VGPRs, no scratch, no spills)."""
