@@ -12,6 +12,8 @@ from distilp_amd.solver import (FrontierPoint, halda_move_frontier, halda_move_f
                                 halda_solve_budget)
 from distilp_amd.solver import (SubsetPoint, halda_select_devices_exact, halda_subset_frontier,  # noqa: F401
                                 halda_subset_frontier_batch)
+from distilp_amd.solver import (ChangePoint, halda_change_frontier, halda_change_frontiers,  # noqa: F401
+                                halda_failover_frontiers, halda_failover_plan, halda_join_frontiers)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

@@ -23,6 +23,9 @@ away from that plan's: the line becomes `within D (n within Dn): k=..., obj=...,
 moved_gpu_layers=...`. --move-frontier B (with --evaluate-solution) prints, after those, one line per point
 p = 0 .. B // 2 of the total-move-budget frontier at that plan's k (halda_move_frontier: at most p layers change
 device, moved_layers <= 2 p): `frontier p: moved_layers=..., obj=..., regret=...`, or `frontier p: infeasible`.
+--failover P (with --evaluate-solution) prints, after those, one line per device: the best plan of the fleet
+without it at that plan's k that takes at most P layers off the survivors (halda_failover_frontiers' last
+point), `lose NAME: p=..., loaded=..., released=..., obj=..., regret=...`, or `lose NAME: infeasible`.
 --cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
 halda_solve_bounded) and prints the usual output for that solve. Without these flags the output is unchanged.
 """
@@ -164,6 +167,22 @@ def frontier_lines(devices: List[DeviceProfile], model: ModelProfile, plan, budg
     return out
 
 
+def failover_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_released: int) -> List[str]:
+    """--failover P: per device, the last point of its halda_failover_frontiers entry -- the best plan of the
+    fleet without it that takes at most P layers off the survivors (kv_bits "4bit" like the solve above)."""
+    from ..solver.change import halda_failover_frontiers
+
+    out = []
+    for dev, fr in zip(devices, halda_failover_frontiers(devices, model, plan, max_released, kv_bits="4bit")):
+        pt = fr[-1]
+        if pt.plan is None:
+            out.append(f"lose {dev.name}: infeasible")
+        else:
+            out.append(f"lose {dev.name}: p={pt.released_budget}, loaded={pt.loaded}, released={pt.released}, "
+                       f"obj={pt.obj_value:.6f}, regret={pt.regret:.6f}")
+    return out
+
+
 def pick_indices(devices: List[DeviceProfile], picks: Sequence[str]) -> List[int]:
     """NAME_OR_INDEX ...: each pick as a device index (a device's name, else its 0-based index). ValueError
     for a pick that names no device."""
@@ -250,6 +269,9 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--move-frontier", type=int, metavar="B",
                    help="With --evaluate-solution: also print, for every total budget up to B moved layers, the best "
                         "plan at that plan's k within it")
+    o.add_argument("--failover", type=int, metavar="P",
+                   help="With --evaluate-solution: also print, for the loss of each device, the best plan of the "
+                        "survivors at that plan's k that takes at most P layers off them")
     o.add_argument("--select-devices", nargs="?", type=int, const=-1, default=None, metavar="D",
                    help="After the solution, print the best sub-fleet with exactly d devices left out for every "
                         "d up to D (default: every subset), and the selection over them")
@@ -289,6 +311,10 @@ def main(argv=None) -> int:
         parser.error("--move-frontier requires --evaluate-solution")
     if args.move_frontier is not None and args.move_frontier < 0:
         parser.error("--move-frontier must be >= 0")
+    if args.failover is not None and not args.evaluate_solution:
+        parser.error("--failover requires --evaluate-solution")
+    if args.failover is not None and args.failover < 0:
+        parser.error("--failover must be >= 0")
     if args.keep and args.select_devices is None:
         parser.error("--keep requires --select-devices")
     n_max = None
@@ -371,6 +397,14 @@ def main(argv=None) -> int:
                 lines = frontier_lines(devices, model, incumbent, args.move_frontier)
             except ValueError as e:
                 print(f"error: --move-frontier: {e}", file=sys.stderr)
+                return 2
+            for line in lines:
+                print(line)
+        if args.failover is not None:
+            try:
+                lines = failover_lines(devices, model, incumbent, args.failover)
+            except ValueError as e:
+                print(f"error: --failover: {e}", file=sys.stderr)
                 return 2
             for line in lines:
                 print(line)

@@ -2082,18 +2082,13 @@ int halda_solve_subfleets(void *ctx, const halda_model *model, const halda_fleet
     return solve_subfleets(ctx, model, table, items, ks, n_k, out, stream, -1);
 }
 
-int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_fleets *th,
-                               const halda_subfleets *ih, const int32_t *ks, int32_t n_k, halda_fleet_result *out_h) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c || !model || !th || !ih || !ks || !out_h) return fail(HALDA_E_ARG, "NULL ctx/model/table/items/ks/out");
-    if (ih->n_items <= 0) return HALDA_OK;
-    if (!ih->parent || !ih->sub_off || !ih->sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
-    if (th->n_fleets <= 0 || !th->dev_off) return fail(HALDA_E_ARG, "halda_solve_subfleets_host: empty table");
-    if (n_k <= 0) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
-    if (!out_h->best_k || !out_h->obj_value || !out_h->w || !out_h->n)
-        return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
-    const int64_t nf = th->n_fleets, nd = th->dev_off[nf], n = ih->n_items;
-    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+// The items of a host call: sub_off from 0, parents and device indices in range, no empty list; the lists'
+// shortest and longest length in *lmin / *lmax. HALDA_E_ARG with the first offender otherwise.
+static int check_items_host(const halda_fleets &table, const halda_subfleets &items, int64_t *lmin_,
+                            int64_t *lmax_) {
+    const halda_fleets *th = &table;
+    const halda_subfleets *ih = &items;
+    const int64_t nf = th->n_fleets, n = ih->n_items;
     // the items: parents and device indices in range, no empty list, the length summary
     if (ih->sub_off[0] != 0) return fail(HALDA_E_ARG, "halda_subfleets: sub_off[0] must be 0");
     int64_t lmin = INT64_MAX, lmax = 0;
@@ -2112,6 +2107,28 @@ int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_
         }
         lmin = std::min(lmin, len);
         lmax = std::max(lmax, len);
+    }
+    *lmin_ = lmin;
+    *lmax_ = lmax;
+    return HALDA_OK;
+}
+
+int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                               const halda_subfleets *ih, const int32_t *ks, int32_t n_k, halda_fleet_result *out_h) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !ih || !ks || !out_h) return fail(HALDA_E_ARG, "NULL ctx/model/table/items/ks/out");
+    if (ih->n_items <= 0) return HALDA_OK;
+    if (!ih->parent || !ih->sub_off || !ih->sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (th->n_fleets <= 0 || !th->dev_off) return fail(HALDA_E_ARG, "halda_solve_subfleets_host: empty table");
+    if (n_k <= 0) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (!out_h->best_k || !out_h->obj_value || !out_h->w || !out_h->n)
+        return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf], n = ih->n_items;
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    int64_t lmin = 0, lmax = 0;
+    {
+        const int rc = check_items_host(*th, *ih, &lmin, &lmax);
+        if (rc != HALDA_OK) return rc;
     }
     if (lmax > 4096) return fail(HALDA_E_ARG, "halda_subfleets: a list of more than 4096 devices");
     // a summary that is given must be tight: the dense x / c layout strides by max_devices
@@ -3205,6 +3222,171 @@ int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const ha
     halda_frontier r = stage::bind_frontier(base, R, nd);
     rc = halda_solve_fleets_budget(ctx, model, &d, k, &db, &r, s);
     if (rc == HALDA_OK) rc = download(stage::frontier_copies(R, *fr_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- a changed fleet and its frontier
+// halda_solve_change: ONE launch of halda_sweep_change_kernel under a gate formed from the shapes alone (lists
+// of 1 .. kK1MaxM devices, one k, max_p <= 63, 2 max_p + max_deficit <= 254, the slice within the LDS
+// budget). No context scratch, no flags, nothing handed back; outside the gate an error and no launch.
+constexpr int kChangeMaxE = 254;  // the arg-min byte: table entries 0 .. 2 P + D, 255 marks "unreached"
+
+int64_t halda_change_lds_bytes(int32_t max_devices, int32_t max_p, int32_t max_deficit, int32_t k) {
+    if (max_devices < 1 || max_p < 0 || max_deficit < 0 || k < 1) return -1;
+    if (max_devices > 4096 || max_p > 4096 || max_deficit > 65536) return INT64_MAX;  // far outside the gate
+    return change_slice(max_devices, max_p, max_deficit, k > 1).total;
+}
+
+static int check_change_args(void *ctx, const halda_model *model, const halda_fleets *table,
+                             const halda_subfleets *items, int32_t k, const halda_change *change,
+                             const halda_change_frontier *fr, bool host, const char *who) {
+    if (!ctx || !model || !table || !items || !change || !fr)
+        return fail(HALDA_E_ARG, std::string(who) + ": NULL ctx/model/table/items/change/frontier");
+    const halda_subfleets &I = *items;
+    if (I.n_items <= 0) return HALDA_OK;
+    if (!I.parent || !I.sub_off || !I.sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (table->n_fleets <= 0) return fail(HALDA_E_ARG, std::string(who) + ": the table has no fleets");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    if (k < 1) return fail(HALDA_E_ARG, std::string(who) + ": k must be >= 1");
+    if (!change->w0) return fail(HALDA_E_ARG, std::string(who) + ": halda_change.w0 is NULL");
+    if (!fr->status || !fr->obj || !fr->loaded || !fr->released || !fr->w || !fr->n)
+        return fail(HALDA_E_ARG, std::string(who) + ": halda_change_frontier has a NULL array");
+    if (I.min_devices < 1 || I.max_devices < I.min_devices || I.max_devices > kK1MaxM)
+        return fail(HALDA_E_ARG, std::string(who) + ": every list must have 1 .. 64 devices");
+    if (change->max_p < 0 || change->max_p > kBudgetMaxP)
+        return fail(HALDA_E_ARG, std::string(who) + ": max_p must be in 0 .. 63");
+    if (change->max_deficit < (host ? -1 : 0))
+        return fail(HALDA_E_ARG, std::string(who) + ": max_deficit must be >= 0");
+    const int dmax = std::max(change->max_deficit, 0);
+    if (2 * int64_t(change->max_p) + dmax > kChangeMaxE)
+        return fail(HALDA_E_ARG, std::string(who) + ": 2 max_p + max_deficit must be at most 254");
+    const int64_t lds = halda_change_lds_bytes(I.max_devices, change->max_p, dmax, k);
+    if (lds > kLdsBudget)
+        return fail(HALDA_E_ARG, std::string(who) + ": the slice of " + std::to_string(lds) +
+                                     " B exceeds the LDS budget of " + std::to_string(kLdsBudget) + " B");
+    return HALDA_OK;
+}
+
+int halda_solve_change(void *ctx, const halda_model *model, const halda_fleets *table, const halda_subfleets *items,
+                       int32_t k, const halda_change *change, halda_change_frontier *frontier, void *stream) {
+    const int rc = check_change_args(ctx, model, table, items, k, change, frontier, false, "halda_solve_change");
+    if (rc != HALDA_OK) return rc;
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const halda_subfleets &I = *items;
+    if (I.n_items <= 0) return HALDA_OK;
+    if (frontier->n_devices < I.n_items)
+        return fail(HALDA_E_ARG, "halda_solve_change: halda_change_frontier.n_devices is not sub_off[n_items]");
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    SweepArgs A = {};
+    static_cast<halda_model &>(A.Mo) = *model;
+    A.Mo.bvo = model_bvo(*model);
+    A.F = *table;  // the parent table under the items' count and length summary
+    A.F.n_fleets = I.n_items;
+    A.F.min_devices = I.min_devices;
+    A.F.max_devices = I.max_devices;
+    A.ks[0] = k;
+    A.Ws[0] = model->L / k;
+    A.n_k = 1;
+    A.mmax = I.max_devices;
+    A.uM = I.min_devices == I.max_devices ? I.max_devices : 0;
+    A.xstride = 7 * int64_t(I.max_devices) + 1;
+    const ChangeArgs Cg{SubArgs{I.parent, I.sub_off, I.sub_idx},
+                        change->w0,
+                        change->w_min,
+                        change->w_max,
+                        change->max_p,
+                        change->max_deficit,
+                        frontier->n_devices,
+                        frontier->status,
+                        frontier->obj,
+                        frontier->loaded,
+                        frontier->released,
+                        frontier->w,
+                        frontier->n};
+    const int64_t slice = change_slice(I.max_devices, change->max_p, change->max_deficit, k > 1).total;
+    int per_cu = 0;
+    const void *fn = reinterpret_cast<const void *>(halda_sweep_change_kernel);
+    HIP_TRY(c->occupancy(fn, slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
+    const unsigned grid =
+        unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(I.n_items))));
+    hipLaunchKernelGGL(halda_sweep_change_kernel, dim3(grid), dim3(64), size_t(slice), s, A, Cg);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fleets *th, const halda_subfleets *ih,
+                            int32_t k, const halda_change *change, halda_change_frontier *fr_h) {
+    const char *who = "halda_solve_change_host";
+    if (!ctx || !model || !th || !ih || !change || !fr_h)
+        return fail(HALDA_E_ARG, std::string(who) + ": NULL ctx/model/table/items/change/frontier");
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int64_t n = ih->n_items;
+    if (n <= 0) return HALDA_OK;
+    if (!ih->parent || !ih->sub_off || !ih->sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (th->n_fleets <= 0 || !th->dev_off) return fail(HALDA_E_ARG, std::string(who) + ": empty table");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    int64_t lmin = 0, lmax = 0;
+    int rc = check_items_host(*th, *ih, &lmin, &lmax);
+    if (rc != HALDA_OK) return rc;
+    if ((ih->min_devices || ih->max_devices) && (lmin != ih->min_devices || lmax != ih->max_devices))
+        return fail(HALDA_E_ARG, "halda_subfleets: min_devices / max_devices are not the lists' shortest and longest "
+                                 "length (" + std::to_string(lmin) + ", " + std::to_string(lmax) + ")");
+    halda_subfleets di = *ih;
+    di.min_devices = int32_t(std::min<int64_t>(lmin, INT32_MAX));
+    di.max_devices = int32_t(std::min<int64_t>(lmax, INT32_MAX));
+    rc = check_change_args(ctx, model, th, &di, k, change, fr_h, true, who);
+    if (rc != HALDA_OK) return rc;
+    // the incumbents: every w0_i >= 0 and 0 <= D <= max_deficit (-1: the items' largest D is taken)
+    int64_t dtop = 0;
+    {
+        const int64_t i = stage::bad_change(ih->sub_off, n, change->w0, model->L / k, change->max_deficit, &dtop);
+        if (i >= 0)
+            return fail(HALDA_E_ARG, std::string(who) + ": item " + std::to_string(i) +
+                                         ": needs every w0_i >= 0 and a deficit L / k - sum w0 in 0 .. max_deficit");
+    }
+    halda_change dc = *change;
+    if (dc.max_deficit < 0) {
+        if (dtop > kChangeMaxE) return fail(HALDA_E_ARG, std::string(who) + ": 2 max_p + max_deficit must be at most 254");
+        dc.max_deficit = int32_t(dtop);
+        rc = check_change_args(ctx, model, th, &di, k, &dc, fr_h, true, who);
+        if (rc != HALDA_OK) return rc;
+    }
+    const int64_t tot = ih->sub_off[n];
+    const int32_t *bsrc[3] = {change->w0, change->w_min, change->w_max};
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const size_t o_par = lay.take(4 * n), o_soff = lay.take(8 * (n + 1)), o_sidx = lay.take(4 * tot);
+    size_t o_b[3];
+    for (int a = 0; a < 3; ++a) o_b[a] = bsrc[a] ? lay.take(4 * tot) : 0;
+    const stage::ChangeSlots R = stage::lay_change(lay, n, tot, dc.max_p);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    if (rc == HALDA_OK) rc = upload(base, o_par, ih->parent, 4 * n, s);
+    if (rc == HALDA_OK) rc = upload(base, o_soff, ih->sub_off, 8 * (n + 1), s);
+    if (rc == HALDA_OK) rc = upload(base, o_sidx, ih->sub_idx, 4 * tot, s);
+    for (int a = 0; a < 3 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * tot, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    di.parent = reinterpret_cast<const int32_t *>(base + o_par);
+    di.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
+    di.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    dc.w0 = bdev(0);
+    dc.w_min = bdev(1);
+    dc.w_max = bdev(2);
+    halda_change_frontier r = stage::bind_change(base, R, tot);
+    rc = halda_solve_change(ctx, model, &d, &di, k, &dc, &r, s);
+    if (rc == HALDA_OK) rc = download(stage::change_copies(R, *fr_h), base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;

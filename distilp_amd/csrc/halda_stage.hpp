@@ -202,4 +202,64 @@ inline int64_t bad_incumbent(const int64_t *dev_off, int64_t nf, const int32_t *
     return -1;
 }
 
+// A halda_change_frontier in a staging buffer: status, obj, loaded and released per (item, point), then the
+// w and n planes over the listed devices.
+struct ChangeSlots {
+    size_t pts, plane;  // n_items x (max_p + 1) points; (max_p + 1) x sub_off[n_items] plane entries
+    size_t status, obj, loaded, released, w, n;
+};
+
+inline ChangeSlots lay_change(Bump &b, int64_t n_items, int64_t tot, int64_t max_p) {
+    ChangeSlots s{size_t(n_items * (max_p + 1)), size_t(tot * (max_p + 1)), 0, 0, 0, 0, 0, 0};
+    s.status = b.take(4 * s.pts);
+    s.obj = b.take(8 * s.pts);
+    s.loaded = b.take(4 * s.pts);
+    s.released = b.take(4 * s.pts);
+    s.w = b.take(4 * s.plane);
+    s.n = b.take(4 * s.plane);
+    return s;
+}
+
+inline halda_change_frontier bind_change(char *base, const ChangeSlots &s, int64_t tot) {
+    halda_change_frontier r;
+    r.n_devices = tot;
+    r.status = reinterpret_cast<int32_t *>(base + s.status);
+    r.obj = reinterpret_cast<double *>(base + s.obj);
+    r.loaded = reinterpret_cast<int32_t *>(base + s.loaded);
+    r.released = reinterpret_cast<int32_t *>(base + s.released);
+    r.w = reinterpret_cast<int32_t *>(base + s.w);
+    r.n = reinterpret_cast<int32_t *>(base + s.n);
+    return r;
+}
+
+inline std::array<Copy, 6> change_copies(const ChangeSlots &s, const halda_change_frontier &h) {
+    return {{{h.status, s.status, 4 * s.pts},
+             {h.obj, s.obj, 8 * s.pts},
+             {h.loaded, s.loaded, 4 * s.pts},
+             {h.released, s.released, 4 * s.pts},
+             {h.w, s.w, 4 * s.plane},
+             {h.n, s.n, 4 * s.plane}}};
+}
+
+// The incumbents of a change call, laid out by sub_off: every w0_i >= 0 and every item's deficit
+// D = W - sum w0 in [0, max_deficit] (max_deficit < 0: no upper limit). Returns -1 and the largest deficit in
+// *dmax, or the first item that breaks a rule.
+inline int64_t bad_change(const int64_t *sub_off, int64_t n_items, const int32_t *w0, int64_t W, int64_t max_deficit,
+                          int64_t *dmax) {
+    int64_t top = 0;
+    for (int64_t i = 0; i < n_items; ++i) {
+        int64_t sum = 0;
+        bool ok = true;
+        for (int64_t j = sub_off[i]; j < sub_off[i + 1]; ++j) {
+            ok = ok && w0[j] >= 0;
+            sum += w0[j];
+        }
+        const int64_t D = W - sum;
+        if (!ok || D < 0 || (max_deficit >= 0 && D > max_deficit)) return i;
+        top = std::max(top, D);
+    }
+    *dmax = top;
+    return -1;
+}
+
 }  // namespace stage

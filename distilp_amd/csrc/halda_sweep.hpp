@@ -2568,6 +2568,320 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bu
     for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) sweep_fleet_budget(A, Bg, int(f), w, b, Wave(lane));
 }
 
+// ---------------------------------------------------------------- a changed fleet (halda_solve_change)
+// Re-placement after a device is lost or joins. An item is a sub-fleet of a parent fleet (SubArgs: the listed
+// devices in list order) with the layers each listed device holds now, w0_i >= 0 (0: a joiner). The deficit
+// D = W - sum w0 >= 0 is what the lost devices held. With delta_i = w_i - w0_i, loaded = sum max(0, delta)
+// and released = sum max(0, -delta), every plan has loaded = D + released; point p of the frontier is the
+// optimum of the list's fixed-k problem over the plans with released <= p. Only w_i in
+// [w0_i - P, w0_i + D + P] can matter: G / H are built on that window by table_pass (rows of at most
+// 2 P + D + 1 entries), and the DP over the devices carries the state (r, l): r the layers released so far,
+// in [0, P], l the layers loaded so far, in [0, D + P]. The exact-p answers are the final states (p, D + p).
+// With D = 0 and every w0_i >= 1 states, transitions and their order are the budget kernel's, hence its bits.
+struct ChangeArgs {
+    SubArgs S;                          // the items; A.F is the parent table with n_fleets = the item count
+    const int32_t *w0, *w_min, *w_max;  // laid out by sub_off; w_min / w_max may be NULL
+    int P, Dmax;                        // halda_change.max_p / max_deficit
+    int64_t nd;                         // sub_off[n_items]: the stride of the w / n planes
+    int32_t *status;                    // [item][P + 1]
+    double *obj;                        // [item][P + 1]
+    int32_t *loaded, *released;         // [item][P + 1]
+    int32_t *w, *n;                     // [P + 1][nd]
+};
+
+// The wave's LDS slice (bytes): G and, for k > 1, H as mmax rows of RS doubles, RS the odd number
+// (2 P + Dmax + 1) | 1; two value planes of S = (P + 1)(Dmax + P + 1) doubles; one arg-min byte plane of S
+// per device; per device wlo - w0; per point the plan's table indices (bytes) and its n (ints).
+struct ChangeSlice {
+    int64_t G, H, V, arg, off, plan, nplan, total;
+    int S, RS;
+};
+
+__host__ __device__ inline ChangeSlice change_slice(int mmax, int P, int Dmax, bool kc) {
+    ChangeSlice s;
+    s.RS = (2 * P + Dmax + 1) | 1;
+    s.S = (P + 1) * (Dmax + P + 1);
+    int64_t o = 0;
+    s.G = o;     o = align16(o + int64_t(mmax) * s.RS * 8);
+    s.H = o;     o = align16(o + (kc ? int64_t(mmax) * s.RS * 8 : 0));
+    s.V = o;     o = align16(o + 2 * int64_t(s.S) * 8);
+    s.arg = o;   o = align16(o + int64_t(mmax) * s.S);
+    s.off = o;   o = align16(o + int64_t(mmax) * 4);
+    s.plan = o;  o = align16(o + int64_t(P + 1) * mmax);
+    s.nplan = o; o = align16(o + int64_t(P + 1) * mmax * 4);
+    s.total = o;
+    return s;
+}
+
+struct ChangeCtx {
+    double *V;       // two planes of S
+    uint8_t *arg;    // [device][S]
+    int *off;        // [device] wlo - w0
+    uint8_t *plan;   // [point][mmax]
+    int *nplan;      // [point][mmax]
+    int S, RS, P, mmax;
+};
+
+constexpr uint8_t kChangeNone = 255;  // arg-min of a state no transition reaches (2 P + Dmax <= 254 < 255)
+
+// One DP over the item's M devices with the entries H > T masked (kc == 0: no mask). The item's states are
+// s = r * LQ + l, LQ = D + P + 1 (the item's own D: LQ (P + 1) <= S). Lanes own states; a transition tries
+// the device's R1 entries in ascending order and keeps the first least value (strict "<": the least w_i).
+// Returns the plane that holds the values after the last device; arg holds every device's arg-min plane.
+__device__ inline const double *change_dp(const WaveCtx &w, const ChangeCtx &c, int M, int R1, int LQ, double kc,
+                                          double T, int lane) {
+    const int Sn = (c.P + 1) * LQ;
+    double *cur = c.V, *nxt = c.V + c.S;
+    for (int s = lane; s < Sn; s += 64) cur[s] = s == 0 ? 0.0 : kInf;
+    wave_sync();
+    for (int i = 0; i < M; ++i) {
+        const int oi = c.off[i];
+        const double *Gi = w.G + i * c.RS, *Hi = w.H + i * c.RS;
+        uint8_t *ai = c.arg + int64_t(i) * c.S;
+        for (int s = lane; s < Sn; s += 64) {
+            const int r = s / LQ, l = s - r * LQ;
+            double best = kInf;
+            int be = kChangeNone;
+            for (int e = 0; e < R1; ++e) {
+                const int delta = oi + e;
+                const int lp = l - max(0, delta), rp = r - max(0, -delta);
+                if (lp < 0 || rp < 0) continue;
+                if (kc > 0.0 && !(Hi[e] <= T)) continue;
+                const double v = cur[rp * LQ + lp] + Gi[e];
+                if (v < best) {
+                    best = v;
+                    be = e;
+                }
+            }
+            nxt[s] = best;
+            ai[s] = uint8_t(be);
+        }
+        wave_sync();
+        double *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    return cur;
+}
+
+// The plan of point p (lane p) with a finite final value: from state (p, D + p) after the last device back
+// to (0, 0). Every state on that path has a finite value, so its arg-min is an entry of the row and the
+// predecessor it names is a valid state.
+__device__ inline void change_backtrack(const ChangeCtx &c, int M, int LQ, int D, int p) {
+    int r = p, l = D + p;
+    for (int i = M - 1; i >= 0; --i) {
+        const int e = c.arg[int64_t(i) * c.S + r * LQ + l];
+        c.plan[p * c.mmax + i] = uint8_t(e);
+        const int delta = c.off[i] + e;
+        l -= max(0, delta);
+        r -= max(0, -delta);
+    }
+}
+
+__device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &Cg, int it, const WaveCtx &w,
+                                         const ChangeCtx &c, const Wave &sg) {
+    const int lane = sg.sl;
+    const int P = Cg.P, P1 = P + 1;
+    const int k = A.ks[0], W = A.Ws[0];
+    // the item's extent, parent and the parent's first device: wave-uniform reads through the scalar cache
+    const int64_t so = sload_i64(Cg.S.sub_off + it);
+    const int M = A.uM > 0 ? A.uM : int(sload_i64(Cg.S.sub_off + it + 1) - so);
+    const int64_t base = sload_i64(A.F.dev_off + sload_i32(Cg.S.parent + it));
+    const bool act = lane < M;
+    const bool pt = lane < P1;
+    const int64_t o0 = so + (act ? lane : 0);
+    const int idx = Cg.S.sub_idx[o0];
+    const int wmn = Cg.w_min ? Cg.w_min[o0] : 0;
+    const int wmx = Cg.w_max ? Cg.w_max[o0] : 0x7fffffff;
+    const int w0 = min(max(Cg.w0[o0], -kBoundCap), kBoundCap);
+    const DevFields mf = load_fields(A.F, base + idx);
+    BoundRec me = {};
+    int bad = 0;
+    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
+    bad = act ? bad : 0;
+    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
+    fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
+    bad = sg.any(bad != 0) ? 1 : 0;
+    const int lo = min(max(1, wmn), kBoundCap);
+    const int sumlo = sg.sum_i(act ? lo : 0);
+    const int sumw0 = sg.sum_i(act ? w0 : 0);
+    // the deficit; 0 where the incumbent is rejected, so that nothing below is formed from it
+    const bool w0bad = sg.any(act && w0 < 0) || sumw0 > W || W - sumw0 > Cg.Dmax;  // the host entries reject it
+    const int D = w0bad ? 0 : W - sumw0;
+    // the window: a device gives up at most P layers and takes at most D + P
+    const int wlo = max(lo, w0 - P), whi = min(min(W, wmx), w0 + D + P);
+    const int sumwlo = sg.sum_i(act ? min(wlo, kBoundCap) : 0);
+    constexpr int kOpen = 1000;
+    int st = kOpen;
+    if (!(W < 1000000)) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumlo > W) st = HALDA_STATUS_INFEASIBLE;
+    else if (bad || w0bad) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumwlo > W) st = HALDA_STATUS_INFEASIBLE;  // the window cannot reach the box
+    const int64_t fo = int64_t(it) * P1;
+    if (st != kOpen) {
+        if (pt) {
+            Cg.status[fo + lane] = st;
+            Cg.obj[fo + lane] = kInf;
+            Cg.loaded[fo + lane] = 0;
+            Cg.released[fo + lane] = 0;
+        }
+        if (act)
+            for (int p = 0; p < P1; ++p) {
+                Cg.w[int64_t(p) * Cg.nd + so + lane] = 0;
+                Cg.n[int64_t(p) * Cg.nd + so + lane] = 0;
+            }
+        return;
+    }
+    opaque_rec(me);
+    const double kc = double(k - 1);
+    me.W = W;
+    me.wlo = wlo;
+    me.whi = whi;
+    if (act) c.off[lane] = wlo - w0;
+    Inst I = {};
+    I.inst = it;
+    I.M = M;
+    I.W = W;
+    I.Wd = double(W);
+    I.kc = kc;
+    I.iC = 7 * M;
+    I.R1 = min(W - sumwlo, 2 * P + D) + 1;
+    I.RS = c.RS;
+    const int R1 = I.R1, LQ = D + P + 1;
+    table_pass<64>(bound_src(&me), w, I, lane);
+    wave_sync();
+    // best[p] (lane p): the least (k - 1) T + F^T_M[p][D + p] and the T that gave it
+    double best = kInf, bT = kInf;
+    if (kc == 0.0) {
+        const double *F = change_dp(w, c, M, R1, LQ, 0.0, kInf, lane);
+        if (pt) best = F[lane * LQ + D + lane];
+        wave_sync();
+        if (pt && best < kInf) change_backtrack(c, M, LQ, D, lane);
+    } else {
+        const double *F = change_dp(w, c, M, R1, LQ, 0.0, kInf, lane);
+        const double sinf = pt ? F[lane * LQ + D + lane] : kInf;
+        // the first threshold that leaves every device an entry: max_i min_e H_i[e]
+        double hmin = kInf;
+        if (act)
+            for (int e = 0; e < R1; ++e) hmin = fmin(hmin, w.H[lane * c.RS + e]);
+        double T = sg.max_f64(act ? hmin : 0.0);
+        while (T < kInf) {
+            // point p is closed once (k - 1) T + S_inf[p] >= best[p]; the scan stops when every point is
+            if (!sg.any(pt && !(kc * T + sinf >= best))) break;
+            wave_sync();
+            F = change_dp(w, c, M, R1, LQ, kc, T, lane);
+            if (pt) {
+                const double v = kc * T + F[lane * LQ + D + lane];
+                if (v < best) {  // strict: the earliest T wins
+                    best = v;
+                    bT = T;
+                }
+            }
+            double nx = kInf;  // the next distinct finite H above T
+            for (int t = lane; t < M * R1; t += 64) {
+                const int i = t / R1, e = t - i * R1;
+                const double h = w.H[i * c.RS + e];
+                if (h > T) nx = fmin(nx, h);
+            }
+            T = sg.min_f64(nx);
+        }
+        // the arg-min planes of each distinct winning T, once, for the points it won
+        bool left = pt && best < kInf;
+        while (sg.any(left)) {
+            const double Tw = sg.min_f64(left ? bT : kInf);
+            wave_sync();
+            change_dp(w, c, M, R1, LQ, kc, Tw, lane);
+            if (left && bT == Tw) {
+                change_backtrack(c, M, LQ, D, lane);
+                left = false;
+            }
+        }
+    }
+    wave_sync();
+    // price every exact-p plan lane-per-device, the constants added in sweep_fleet's order
+    double objv = kInf;
+    int relv = 0;
+    for (int p = 0; p < P1; ++p) {
+        if (!(sg.bcast(best, p) < kInf)) continue;
+        double gd = 0.0, H = 0.0;
+        int wl = 0, n = 0;
+        if (act) {
+            wl = wlo + c.plan[p * c.mmax + lane];
+            double Pc, Qc;
+            int sl[4] = {0, 0, 0, 0};
+            split_full(me, wl, gd, n, sl);
+            dev_cycle(me, wl, n, sl, Pc, Qc);
+            H = fmax(0.0, Qc >= Pc ? 0.5 * (Pc + Qc) : Pc);
+            c.nplan[p * c.mmax + lane] = n;
+        }
+        const double hmax = sg.max_f64(act ? H : 0.0);
+        double obj = sg.sum_f64(act ? gd : 0.0) + kc * hmax;
+        obj = obj + tsum;
+        obj = obj + xsum;
+        obj = obj + kappa;
+        const int rl = sg.sum_i(act ? max(0, w0 - wl) : 0);
+        if (lane == p) {
+            objv = obj;
+            relv = rl;
+        }
+    }
+    wave_sync();
+    // point p: the best exact point p' <= p, the fewest released layers among equal objectives (strict "<",
+    // ascending)
+    double run = kInf;
+    int src = -1, runrl = 0;
+    for (int p = 0; p < P1; ++p) {
+        const double o = sg.bcast(objv, p);
+        const int rl = sg.bcast(relv, p);
+        if (lane >= p && o < run) {
+            run = o;
+            src = p;
+            runrl = rl;
+        }
+    }
+    if (pt) {
+        Cg.status[fo + lane] = src >= 0 ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+        Cg.obj[fo + lane] = run;
+        Cg.loaded[fo + lane] = src >= 0 ? D + runrl : 0;
+        Cg.released[fo + lane] = runrl;
+    }
+    for (int p = 0; p < P1; ++p) {
+        const int sp = sg.bcast(src, p);
+        if (act) {
+            Cg.w[int64_t(p) * Cg.nd + so + lane] = sp >= 0 ? wlo + c.plan[sp * c.mmax + lane] : 0;
+            Cg.n[int64_t(p) * Cg.nd + so + lane] = sp >= 0 ? c.nplan[sp * c.mmax + lane] : 0;
+        }
+    }
+    wave_sync();  // the slice is rewritten by the wave's next item
+}
+
+// halda_sweep_change_kernel: the budget kernel's launch shape -- one wave per item in 64-thread workgroups on
+// a persistent grid, each with its dynamic LDS slice (change_slice of the launch's shape); workgroup b takes
+// items b, b + grid, .... Lane j gathers the item's j-th listed device from the parent table
+// (halda_sweep_subfleets_kernel's index read). No spin-wait, no atomics and nothing shared between waves:
+// the only synchronisation is wave_sync within the one wave.
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_change_kernel(SweepArgs A,
+                                                                                           ChangeArgs Cg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const ChangeSlice sl = change_slice(A.mmax, Cg.P, Cg.Dmax, A.ks[0] > 1);
+    WaveCtx w = {};
+    w.G = reinterpret_cast<double *>(smem + sl.G);
+    w.H = reinterpret_cast<double *>(smem + sl.H);
+    ChangeCtx c;
+    c.V = reinterpret_cast<double *>(smem + sl.V);
+    c.arg = smem + sl.arg;
+    c.off = reinterpret_cast<int *>(smem + sl.off);
+    c.plan = smem + sl.plan;
+    c.nplan = reinterpret_cast<int *>(smem + sl.nplan);
+    c.S = sl.S;
+    c.RS = sl.RS;
+    c.P = Cg.P;
+    c.mmax = A.mmax;
+    const int n = A.F.n_fleets;
+    for (int64_t it = blockIdx.x; it < n; it += gridDim.x) sweep_item_change(A, Cg, int(it), w, c, Wave(lane));
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the

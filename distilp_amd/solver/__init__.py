@@ -4,6 +4,8 @@ from .bounds import (ReplacementWithin, halda_replace_within, halda_replace_with
                      halda_solve_bounded, halda_solve_bounded_batch, move_bounds, move_box)
 from .budget import (FrontierPoint, halda_move_frontier, halda_move_frontier_batch,  # noqa: F401
                      halda_solve_budget)
+from .change import (ChangePoint, halda_change_frontier, halda_change_frontiers,  # noqa: F401
+                     halda_failover_frontiers, halda_failover_plan, halda_join_frontiers)
 from .coefficients import HALDAResult, ILPResult
 from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
@@ -22,7 +24,8 @@ __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solv
            "halda_replace_within", "halda_replace_within_batch", "ReplacementWithin", "halda_move_frontier",
            "halda_move_frontier_batch", "halda_solve_budget", "FrontierPoint", "evaluate_plan_np",
            "PlanEvaluation", "Replacement", "HALDAResult", "halda_subset_frontier", "halda_subset_frontier_batch",
-           "halda_select_devices_exact", "SubsetPoint",
+           "halda_select_devices_exact", "SubsetPoint", "halda_change_frontier", "halda_change_frontiers",
+           "halda_failover_frontiers", "halda_join_frontiers", "halda_failover_plan", "ChangePoint",
            "ILPResult"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

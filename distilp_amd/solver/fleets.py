@@ -165,6 +165,17 @@ def _bind_budget(lib):
     return lib
 
 
+class HaldaChangeC(ctypes.Structure):
+    _fields_ = [("w0", ctypes.c_void_p), ("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p),
+                ("max_p", ctypes.c_int32), ("max_deficit", ctypes.c_int32)]
+
+
+class HaldaChangeFrontierC(ctypes.Structure):
+    _fields_ = [("n_devices", ctypes.c_int64), ("status", ctypes.c_void_p), ("obj", ctypes.c_void_p),
+                ("loaded", ctypes.c_void_p), ("released", ctypes.c_void_p), ("w", ctypes.c_void_p),
+                ("n", ctypes.c_void_p)]
+
+
 def _bind(lib):
     if getattr(lib, "_fleets_bound", False):
         return lib
@@ -1095,6 +1106,79 @@ class DeviceFleetTable:
                                                ctypes.byref(self._frontier_c), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"halda_solve_fleets_budget failed ({rc}): {last_error(lib)}")
+
+    def set_change(self, k, items, w0, max_p: int, max_deficit: int, w_min=None, w_max=None) -> None:
+        """Give the table its resident items and incumbents for halda_solve_change. `items` is (parent, sub_off,
+        sub_idx) as subfleets.pack_items returns them (validated here against the table); w0 / w_min / w_max are
+        laid out by sub_off (int32; the caller keeps every w0_i >= 0 and every item's deficit L // k - sum w0 in
+        0 .. max_deficit -- the arrays given here are checked, later in-place rewrites are the caller's). Device
+        tensors change_w0 / change_min / change_max and the result buffers change_out: status / obj / loaded /
+        released [n_items, max_p + 1], w / n [max_p + 1, sub_off[-1]]. A streaming caller rewrites change_w0 in
+        place between launches. ValueError for a shape outside the launch's gate (change.check_gate)."""
+        import torch
+
+        from .change import check_gate, check_w0
+        from .subfleets import HaldaSubfleetsC, check_items
+
+        if isinstance(max_p, bool) or int(max_p) != max_p or max_p < 0:
+            raise ValueError(f"max_p: {max_p!r} is not a non-negative integer")
+        if isinstance(max_deficit, bool) or int(max_deficit) != max_deficit or max_deficit < 0:
+            raise ValueError(f"max_deficit: {max_deficit!r} is not a non-negative integer")
+        if int(k) < 1:
+            raise ValueError(f"k = {k} must be positive")
+        parent, sub_off, sub_idx = (np.ascontiguousarray(a, t) for a, t in zip(items, (np.int32, np.int64, np.int32)))
+        check_items(self.table.sizes(), parent.astype(np.int64), sub_off, sub_idx.astype(np.int64))
+        lens = np.diff(sub_off)
+        if len(lens) == 0:
+            raise ValueError("set_change needs at least one item")
+        check_gate(int(lens.max()), int(lens.min()), int(max_p), int(max_deficit), int(k))
+        if w0 is None:
+            raise ValueError("set_change needs the items' w0")
+        dev = self.out["best_k"].device
+        n, tot, P1 = len(parent), int(sub_off[-1]), int(max_p) + 1
+        if not torch.is_tensor(w0):
+            check_w0(sub_off, np.asarray(w0), int(self.model.L) // int(k), int(max_deficit))
+
+        def tensor(a, dtype=torch.int32, count=tot):
+            if a is None:
+                return None
+            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+            if t.numel() != count:
+                raise ValueError(f"change array of {t.numel()} entries, expected {count}")
+            return t.to(device=dev, dtype=dtype).contiguous().clone()
+
+        self.change_k = int(k)
+        self.change_items = (tensor(parent, count=n), tensor(sub_off, torch.int64, n + 1), tensor(sub_idx))
+        self.change_w0, self.change_min, self.change_max = tensor(w0), tensor(w_min), tensor(w_max)
+        self.change_out = {"status": torch.empty((n, P1), dtype=torch.int32, device=dev),
+                           "obj": torch.empty((n, P1), dtype=torch.float64, device=dev),
+                           "loaded": torch.empty((n, P1), dtype=torch.int32, device=dev),
+                           "released": torch.empty((n, P1), dtype=torch.int32, device=dev),
+                           "w": torch.empty((P1, tot), dtype=torch.int32, device=dev),
+                           "n": torch.empty((P1, tot), dtype=torch.int32, device=dev)}
+        o = self.change_out
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        it = self.change_items
+        self._items_c = HaldaSubfleetsC(n, int(lens.min()), int(lens.max()), ptr(it[0]), ptr(it[1]), ptr(it[2]))
+        self._change_c = HaldaChangeC(ptr(self.change_w0), ptr(self.change_min), ptr(self.change_max), int(max_p),
+                                      int(max_deficit))
+        self._change_frontier_c = HaldaChangeFrontierC(tot, *(o[f].data_ptr() for f in
+                                                              ("status", "obj", "loaded", "released", "w", "n")))
+
+    def launch_with_change(self, ctx, stream: int) -> None:
+        """Enqueue the change frontier of every resident item on `stream` (halda_solve_change): self.change_out.
+        set_change has checked the gate."""
+        if getattr(self, "_change_c", None) is None:
+            raise RuntimeError("launch_with_change: call set_change first")
+        from .change import _bind_change
+
+        lib = _bind_change(ctx.lib)
+        with ctx._lock:
+            rc = lib.halda_solve_change(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
+                                        ctypes.byref(self._items_c), self.change_k, ctypes.byref(self._change_c),
+                                        ctypes.byref(self._change_frontier_c), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"halda_solve_change failed ({rc}): {last_error(lib)}")
 
 
 class RcclComm:

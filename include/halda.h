@@ -596,6 +596,65 @@ int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const ha
 int64_t halda_budget_lds_bytes(int32_t max_devices, int32_t max_p, int32_t k);
 
 /* ------------------------------------------------------------------------
+ * Re-placement of a live fleet after a device is lost or joins: the exact frontier.
+ *
+ * An item is a sub-fleet of a parent fleet in halda_subfleets' format (the listed devices in list order,
+ * kappa's head by halda_solve_subfleets' rule) with the layers each listed device holds now: w0_i >= 0,
+ * 0 for a device that holds nothing (a joiner). One k per call, W = L / k. The deficit D = W - sum w0 >= 0
+ * is the number of layers the lost devices held. With delta_i = w_i - w0_i, loaded = sum max(0, delta) is
+ * what some device must newly load and released = sum max(0, -delta) what is taken off a listed device;
+ * loaded = D + released for every plan. Point p = 0 .. max_p is the optimum of the list's fixed-k problem
+ * (what halda_solve_subfleets solves for it at that one k, inside the optional w_min / w_max) over the plans
+ * with released <= p, among equal objectives the plan with the fewest released layers; n, the slacks, z and C
+ * are re-optimised. The frontier is non-increasing; point 0 deals the orphans out and disturbs no survivor.
+ * With D = 0 and every w0_i >= 1 the outputs are halda_solve_fleets_budget's of the materialised list, bit
+ * for bit (moved = loaded + released).
+ *
+ * Per point: status HALDA_STATUS_OPTIMAL, _INFEASIBLE (no plan: with D = 0 and a joiner point 0 has none,
+ * since every listed device needs w >= 1) or _UNSUPPORTED (W >= 1e6, a rejected record, or -- device entry
+ * only -- some w0_i < 0, D < 0 or D > max_deficit, which the host entry rejects with HALDA_E_ARG before any
+ * GPU work); obj as halda_frontier's (the bits halda_eval_plans gives the returned plan on the materialised
+ * list; +inf where not optimal); loaded / released of the returned plan (zero where not optimal); w and n as
+ * max_p + 1 planes laid out by sub_off (zeros where not optimal).
+ *
+ * Gate, from the shapes alone: lists of 1 .. 64 devices, 0 <= max_p <= 63, max_deficit >= 0,
+ * 2 max_p + max_deficit <= 254, and halda_change_lds_bytes(max_devices, max_p, max_deficit, k) at most
+ * 160 KiB. Outside it the call returns HALDA_E_ARG and launches nothing: there is no fallback. One launch of
+ * halda_sweep_change_kernel (one wave per item; no context scratch, nothing shared between waves). */
+typedef struct halda_change {
+    const int32_t *w0;            /* [sub_off[n_items]] the layers each listed device holds, laid out by sub_off */
+    const int32_t *w_min, *w_max; /* as halda_bounds, laid out by sub_off; either may be NULL */
+    int32_t max_p;                /* P: the most released layers asked for */
+    int32_t max_deficit;          /* an upper bound of every item's D (host entry: -1 = compute it) */
+} halda_change;
+
+typedef struct halda_change_frontier {
+    int64_t n_devices; /* sub_off[n_items]: the stride of the w / n planes */
+    int32_t *status;   /* [n_items * (max_p + 1)] */
+    double *obj;       /* [n_items * (max_p + 1)] */
+    int32_t *loaded;   /* [n_items * (max_p + 1)] */
+    int32_t *released; /* [n_items * (max_p + 1)] */
+    int32_t *w, *n;    /* [(max_p + 1) * n_devices]: plane p holds point p's plan of every item */
+} halda_change_frontier;
+
+/* Asynchronous on `stream`; table, items, change and frontier hold device arrays. The items are the
+ * caller's to get right, as for halda_solve_subfleets (min_devices / max_devices must be the lists' shortest
+ * and longest length). */
+int halda_solve_change(void *ctx, const halda_model *model, const halda_fleets *table, const halda_subfleets *items,
+                       int32_t k, const halda_change *change, halda_change_frontier *frontier, void *stream);
+
+/* Synchronous variant on HOST arrays (frontier->n_devices is taken from sub_off). Validates the items as
+ * halda_solve_subfleets_host does, every w0_i >= 0 and 0 <= D <= max_deficit per item; max_deficit = -1 lets
+ * it take the items' largest D. */
+int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fleets *table,
+                            const halda_subfleets *items, int32_t k, const halda_change *change,
+                            halda_change_frontier *frontier);
+
+/* Bytes of dynamic LDS per wave of halda_sweep_change_kernel for this shape (the gate's figure); -1 for
+ * max_devices < 1, max_p < 0, max_deficit < 0 or k < 1. No context needed. */
+int64_t halda_change_lds_bytes(int32_t max_devices, int32_t max_p, int32_t max_deficit, int32_t k);
+
+/* ------------------------------------------------------------------------
  * Exact device selection: the best sub-fleet over all subsets of the droppable devices.
  *
  * Per fleet of M <= 64 devices: keep_mask names the devices that may not be dropped (bit i: device i;
