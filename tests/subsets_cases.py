@@ -47,7 +47,8 @@ def starved_keep():
 
 
 # A fleet key names a device list: ("synth", seed, M) -- subfleets_cases.our_devices, kv 8bit, the default k list --
-# ("p", M, scale, seed) a pressured fleet and ("i", irregular case) an edited one, both kv 4bit on the k of PRESSURE_KS.
+# ("p", M, scale, seed) a pressured fleet and ("i", irregular case) an edited one, both kv 4bit on the k of PRESSURE_KS;
+# ("deep", M, seed, L, ks) bounds_cases.devices(M, seed) on the model with L layers, kv 4bit, on the k list ks.
 PRESSURE_KS = {5: None, 16: (1, 2, 4, 5), 64: (1,)}  # None: the default k list
 
 
@@ -58,6 +59,11 @@ def fleet_of(key):
     from . import irregular_cases as ic
     from . import pressure_cases as pc
 
+    if key[0] == "deep":  # ("deep", M, seed, L, k list or None): bounds_cases.devices(M, seed) on the model at L
+        from . import bounds_cases as bc
+
+        _, M, seed, L, ks = key
+        return list(bc.devices(M, seed)), pc.our_model().model_copy(update={"L": L}), "4bit", ks
     if key[0] == "p":
         _, M, scale, seed = key
         return pc.devices(seed, M, scale), pc.our_model(), "4bit", PRESSURE_KS[M]
