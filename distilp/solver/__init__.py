@@ -14,6 +14,8 @@ from distilp_amd.solver import (SubsetPoint, halda_select_devices_exact, halda_s
                                 halda_subset_frontier_batch)
 from distilp_amd.solver import (ChangePoint, halda_change_frontier, halda_change_frontiers,  # noqa: F401
                                 halda_failover_frontiers, halda_failover_plan, halda_join_frontiers)
+from distilp_amd.solver import (ScalePoint, halda_scale_in, halda_scale_in_frontier,  # noqa: F401
+                                halda_scale_in_frontier_batch, halda_scale_out_frontier)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

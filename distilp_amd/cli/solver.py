@@ -23,6 +23,9 @@ away from that plan's: the line becomes `within D (n within Dn): k=..., obj=...,
 moved_gpu_layers=...`. --move-frontier B (with --evaluate-solution) prints, after those, one line per point
 p = 0 .. B // 2 of the total-move-budget frontier at that plan's k (halda_move_frontier: at most p layers change
 device, moved_layers <= 2 p): `frontier p: moved_layers=..., obj=..., regret=...`, or `frontier p: infeasible`.
+--scale-in D (with --evaluate-solution and --failover P; --keep names devices that may not be dropped) prints, last,
+one line per (d, p): `scale-in d, p: dropped=[names], loaded=..., released=..., obj=..., regret=...` or
+`scale-in d, p: infeasible` (halda_scale_in_frontier's cells).
 --failover P (with --evaluate-solution) prints, after those, one line per device: the best plan of the fleet
 without it at that plan's k that takes at most P layers off the survivors (halda_failover_frontiers' last
 point), `lose NAME: p=..., loaded=..., released=..., obj=..., regret=...`, or `lose NAME: infeasible`.
@@ -234,6 +237,26 @@ def cpu_only_n_max(devices: List[DeviceProfile], picks: Sequence[str]) -> List[i
     return n_max
 
 
+def scale_in_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_drop: int, max_released: int,
+                   keep: List[int]) -> List[str]:
+    """--scale-in D --failover P: one line per (d, p), d = 0 .. D devices handed back and at most p layers taken
+    off the others -- the cells of halda_scale_in_frontier (kv_bits "4bit" like the solve above)."""
+    from ..solver.scale import halda_scale_in_frontier
+
+    out = []
+    for d, row in enumerate(halda_scale_in_frontier(devices, model, plan, max_drop, max_released, keep=keep or None,
+                                                    kv_bits="4bit")):
+        for p, cell in enumerate(row):
+            pt = cell.point
+            if pt.plan is None:
+                out.append(f"scale-in {d}, {p}: infeasible")
+            else:
+                names = ", ".join(devices[i].name for i in cell.dropped)
+                out.append(f"scale-in {d}, {p}: dropped=[{names}], loaded={pt.loaded}, released={pt.released}, "
+                           f"obj={pt.obj_value:.6f}, regret={pt.regret:.6f}")
+    return out
+
+
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Run HALDA solver for distributed LLM inference optimization",
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -272,11 +295,15 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--failover", type=int, metavar="P",
                    help="With --evaluate-solution: also print, for the loss of each device, the best plan of the "
                         "survivors at that plan's k that takes at most P layers off them")
+    o.add_argument("--scale-in", type=int, metavar="D",
+                   help="With --evaluate-solution and --failover P: also print, for every d up to D devices handed "
+                        "back and every budget p up to P, which devices to drop and the best plan of the others")
     o.add_argument("--select-devices", nargs="?", type=int, const=-1, default=None, metavar="D",
                    help="After the solution, print the best sub-fleet with exactly d devices left out for every "
                         "d up to D (default: every subset), and the selection over them")
     o.add_argument("--keep", nargs="+", metavar="NAME_OR_INDEX", default=[],
-                   help="With --select-devices: devices (name or 0-based index) that may not be left out")
+                   help="With --select-devices or --scale-in: devices (name or 0-based index) that may not be left "
+                        "out")
     g.add_argument("--cpu-only", nargs="+", metavar="NAME_OR_INDEX",
                    help="Solve without using the GPU of these devices (their name or 0-based index)")
     return p
@@ -315,8 +342,12 @@ def main(argv=None) -> int:
         parser.error("--failover requires --evaluate-solution")
     if args.failover is not None and args.failover < 0:
         parser.error("--failover must be >= 0")
-    if args.keep and args.select_devices is None:
-        parser.error("--keep requires --select-devices")
+    if args.scale_in is not None and (not args.evaluate_solution or args.failover is None):
+        parser.error("--scale-in requires --evaluate-solution and --failover")
+    if args.scale_in is not None and args.scale_in < 0:
+        parser.error("--scale-in must be >= 0")
+    if args.keep and args.select_devices is None and args.scale_in is None:
+        parser.error("--keep requires --select-devices or --scale-in")
     n_max = None
     if args.cpu_only:
         try:
@@ -405,6 +436,15 @@ def main(argv=None) -> int:
                 lines = failover_lines(devices, model, incumbent, args.failover)
             except ValueError as e:
                 print(f"error: --failover: {e}", file=sys.stderr)
+                return 2
+            for line in lines:
+                print(line)
+        if args.scale_in is not None:
+            try:
+                lines = scale_in_lines(devices, model, incumbent, args.scale_in, args.failover,
+                                       pick_indices(devices, args.keep))
+            except (ValueError, IndexError) as e:
+                print(f"error: --scale-in: {e}", file=sys.stderr)
                 return 2
             for line in lines:
                 print(line)

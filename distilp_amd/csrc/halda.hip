@@ -167,6 +167,7 @@ struct Ctx {
     size_t sel_bytes = 0;
     int sel_path = 0;               // halda_set_subsets_path: 0 automatic, 1 always expand
     int sel_route = 0;              // the last halda_solve_subsets call: 1 fused, 2 expansion, 3 mixed (0: none yet)
+    int64_t scale_chunk = 0;        // halda_set_change_subsets_chunk: a launch's scratch cap (0: the default)
     uint8_t *var_desc = nullptr;    // halda_solve_variants: the fused route's per-variant models (SweepModel)
     size_t var_desc_bytes = 0;
     int var_path = 0;               // halda_set_variants_path: 0 automatic, 1 always loop
@@ -3387,6 +3388,367 @@ int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fle
     halda_change_frontier r = stage::bind_change(base, R, tot);
     rc = halda_solve_change(ctx, model, &d, &di, k, &dc, &r, s);
     if (rc == HALDA_OK) rc = download(stage::change_copies(R, *fr_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- scale-in / scale-out
+// halda_solve_change_subsets: halda_solve_subsets' candidates (the same combo lists and per-(d, fleet)
+// records) under halda_solve_change's value. Per d one or more launches, each of its d's list lengths and
+// max_deficit = that d's largest deficit: index kernel, halda_solve_change on the items just written, pick
+// kernel. A launch's scratch (halda_change_subsets_launch_bytes) stays within the context's cap; everything
+// lives in the context's grow-only sel_buf, so the call runs after the previous user of the context's shared
+// scratch on another stream (order_after_previous).
+constexpr int64_t kChangeSubsetsChunkBytes = int64_t(256) << 20;
+constexpr int64_t kChangeSubsetsFixedBytes = 4096;  // the launch's 12 regions, each 256-byte aligned, and sub_off's end
+
+static int64_t change_subsets_item_bytes(int len, int P1) {
+    // parent, sub_off, the four per-point arrays; per listed device sub_idx, w0 / w_min / w_max and the two planes
+    return 12 + 20 * int64_t(P1) + int64_t(len) * (16 + 8 * int64_t(P1));
+}
+
+int64_t halda_change_subsets_launch_bytes(int32_t len, int32_t max_p, int64_t n_items) {
+    if (len < 1 || max_p < 0 || n_items < 0) return -1;
+    return kChangeSubsetsFixedBytes + n_items * change_subsets_item_bytes(len, max_p + 1);
+}
+
+int halda_set_change_subsets_chunk(void *ctx, int64_t bytes) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (bytes < 0) return fail(HALDA_E_ARG, "the chunk cap must be >= 0 (0: the default)");
+    c->scale_chunk = bytes;
+    return HALDA_OK;
+}
+
+int64_t halda_change_subsets_max_deficit(const int32_t *w0, int32_t M, uint64_t keep_mask, int32_t d, int32_t W) {
+    if (!w0 || M < 1 || M > 64 || d < 0) return -1;
+    const uint64_t all = M == 64 ? ~uint64_t(0) : (uint64_t(1) << M) - 1;
+    if (keep_mask & ~all) return -1;
+    int64_t sum = 0;
+    std::vector<int64_t> can;
+    for (int i = 0; i < M; ++i) {
+        sum += w0[i];
+        if (!((keep_mask >> i) & 1)) can.push_back(w0[i]);
+    }
+    if (d > int(can.size())) return -1;
+    std::sort(can.begin(), can.end(), std::greater<int64_t>());
+    int64_t D = int64_t(W) - sum;
+    for (int j = 0; j < d; ++j) D += can[j];
+    return D;
+}
+
+// The gate's findings: per fleet its droppable devices, their count, the most it may drop within the range and
+// its size; per d of the range the largest deficit and the longest list of the fleets that admit it (-1 / 0: none).
+struct ChangeSubsetsGate {
+    std::vector<uint64_t> drop;
+    std::vector<int> qs, Df, sizes;
+    std::vector<int64_t> dtop;
+    std::vector<int> ltop;
+};
+
+// The gate, from the shapes and w0 alone: no GPU work. off / w0_h: the table's dev_off and the call's w0 in HOST
+// memory.
+static int change_subsets_gate(const halda_model *model, const halda_fleets *table, const int64_t *off,
+                               const int32_t *w0_h, int32_t k, const halda_change_subsets *cs,
+                               const halda_change_subset_frontier *fr, ChangeSubsetsGate &Q) {
+    const char *who = "halda_solve_change_subsets";
+    const int nf = table->n_fleets, d0 = cs->min_drop, d1 = cs->max_drop, P = cs->max_p;
+    const uint64_t *keep = cs->keep_mask;
+    if (!fr->status || !fr->obj || !fr->dropped_mask || !fr->loaded || !fr->released || !fr->w || !fr->n)
+        return fail(HALDA_E_ARG, "halda_change_subset_frontier has a NULL array");
+    if (!cs->w0) return fail(HALDA_E_ARG, "halda_change_subsets.w0 is NULL");
+    if (d0 < 0 || d1 < d0 || d1 > 63)
+        return fail(HALDA_E_ARG, std::string(who) + ": needs 0 <= min_drop <= max_drop <= 63");
+    if (P < 0 || P > kBudgetMaxP) return fail(HALDA_E_ARG, std::string(who) + ": max_p must be in 0 .. 63");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    if (k < 1) return fail(HALDA_E_ARG, std::string(who) + ": k must be >= 1");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    // the gate, from the shapes and w0 alone
+    const int64_t W = model->L / k;
+    const int D1 = d1 - d0 + 1;
+    std::vector<uint64_t> &drop = Q.drop;
+    std::vector<int> &qs = Q.qs, &Df = Q.Df, &sizes = Q.sizes, &ltop = Q.ltop;
+    std::vector<int64_t> &dtop = Q.dtop;
+    drop.assign(nf, 0);
+    qs.assign(nf, 0);
+    Df.assign(nf, 0);
+    sizes.assign(nf, 0);
+    dtop.assign(size_t(D1), -1);
+    ltop.assign(size_t(D1), 0);
+    bool any = false;
+    for (int f = 0; f < nf; ++f) {
+        const int64_t M64 = off[f + 1] - off[f];
+        if (M64 < 1 || M64 > 64)
+            return fail(HALDA_E_ARG, std::string(who) + ": fleet " + std::to_string(f) + " has " + std::to_string(M64) +
+                                         " devices (1..64)");
+        const int M = sizes[f] = int(M64);
+        const uint64_t all = M == 64 ? ~uint64_t(0) : (uint64_t(1) << M) - 1, km = keep ? keep[f] : 0;
+        if (km & ~all)
+            return fail(HALDA_E_ARG, "halda_change_subsets: keep_mask of fleet " + std::to_string(f) +
+                                         " names a device past " + std::to_string(M));
+        drop[f] = all & ~km;
+        qs[f] = __builtin_popcountll(drop[f]);
+        Df[f] = std::min({d1, qs[f], M - 1});
+        int64_t sum = 0, cnt = 0;
+        std::vector<int64_t> can;
+        for (int i = 0; i < M; ++i) {
+            const int64_t v = w0_h[off[f] + i];
+            if (v < 0)
+                return fail(HALDA_E_ARG, std::string(who) + ": fleet " + std::to_string(f) + ": every w0_i must be >= 0");
+            sum += v;
+            if ((drop[f] >> i) & 1) can.push_back(v);
+        }
+        if (sum > W)
+            return fail(HALDA_E_ARG, std::string(who) + ": fleet " + std::to_string(f) + ": w0 sums to " +
+                                         std::to_string(sum) + ", above L / k = " + std::to_string(W));
+        std::sort(can.begin(), can.end(), std::greater<int64_t>());
+        int64_t D = W - sum;
+        for (int d = 0; d <= Df[f]; ++d) {
+            if (d) D += can[d - 1];
+            if (d < d0) continue;
+            any = true;
+            cnt += binom_sat(qs[f], d);
+            if (cnt > HALDA_SUBSETS_MAX)
+                return fail(HALDA_E_ARG, std::string(who) + ": fleet " + std::to_string(f) + " has more than " +
+                                             std::to_string(HALDA_SUBSETS_MAX) + " candidates");
+            dtop[d - d0] = std::max(dtop[d - d0], D);
+            ltop[d - d0] = std::max(ltop[d - d0], M - d);
+        }
+    }
+    if (!any)
+        return fail(HALDA_E_ARG, "halda_change_subsets: min_drop " + std::to_string(d0) +
+                                     " is beyond min(q, M - 1) of every fleet");
+    for (int j = 0; j < D1; ++j) {
+        if (dtop[j] < 0) continue;
+        if (2 * int64_t(P) + dtop[j] > kChangeMaxE)
+            return fail(HALDA_E_ARG, std::string(who) + ": d = " + std::to_string(d0 + j) + ": 2 max_p + deficit = " +
+                                         std::to_string(2 * int64_t(P) + dtop[j]) + " must be at most 254");
+        const int64_t lds = halda_change_lds_bytes(ltop[j], P, int32_t(dtop[j]), k);
+        if (lds > kLdsBudget)
+            return fail(HALDA_E_ARG, std::string(who) + ": d = " + std::to_string(d0 + j) + ": the slice of " +
+                                         std::to_string(lds) + " B exceeds the LDS budget of " +
+                                         std::to_string(kLdsBudget) + " B");
+    }
+    return HALDA_OK;
+}
+
+// table, cs->w0 / w_min / w_max and fr hold device arrays; Q: the call's gate, passed
+static int solve_change_subsets(void *ctx, const halda_model *model, const halda_fleets *table, int32_t k,
+                                const halda_change_subsets *cs, halda_change_subset_frontier *fr,
+                                const ChangeSubsetsGate &Q, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int nf = table->n_fleets, d0 = cs->min_drop, d1 = cs->max_drop, P = cs->max_p;
+    const int D1 = d1 - d0 + 1, P1 = P + 1;
+    const std::vector<uint64_t> &drop = Q.drop;
+    const std::vector<int> &qs = Q.qs, &Df = Q.Df, &sizes = Q.sizes;
+    const std::vector<int64_t> &dtop = Q.dtop;
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    // the combo lists of every (q, d) in use, the records per (d, fleet), the launches
+    const int64_t cap = c->scale_chunk > 0 ? c->scale_chunk : kChangeSubsetsChunkBytes;
+    std::vector<uint64_t> combos;
+    std::vector<int64_t> coff(65 * 64, -1);
+    std::vector<SubsetFleet> recs(size_t(D1) * nf);
+    std::vector<SubsetLaunch> launches;
+    int64_t max_items = 0, max_dev = 0;
+    for (int d = d0; d <= d1; ++d) {
+        SubsetFleet *R = recs.data() + size_t(d - d0) * nf;
+        int64_t items = 0, devs = 0;
+        for (int f = 0; f < nf; ++f) {
+            SubsetFleet &r = R[f];
+            r = SubsetFleet{};
+            r.drop_mask = drop[f];
+            r.M = sizes[f];
+            r.cnt = d <= Df[f] ? int32_t(binom_sat(qs[f], d)) : 0;
+            if (r.cnt > 0) {
+                int64_t &o = coff[size_t(qs[f]) * 64 + d];
+                if (o < 0) {
+                    o = int64_t(combos.size());
+                    subset_combos(qs[f], d, combos);
+                }
+                r.combo_off = o;
+            }
+            r.item_off = items;
+            r.list_off = devs;
+            items += r.cnt;
+            devs += int64_t(r.cnt) * (sizes[f] - d);
+        }
+        if (items == 0) {  // no fleet admits this d: the pick alone, which writes the empty cells
+            launches.push_back(SubsetLaunch{d, false, 0, 0, 0, 0, 0, 0});
+            continue;
+        }
+        // chunks within the byte cap, cut at candidate boundaries (one candidate at the least)
+        int f = 0;
+        int64_t a = 0;
+        while (a < items) {
+            SubsetLaunch L{d, false, a, 0, 0, 0, 64, 0};
+            while (R[f].cnt == 0 || R[f].item_off + R[f].cnt <= a) ++f;
+            L.l0 = R[f].list_off + (a - R[f].item_off) * (sizes[f] - d);
+            int64_t b = a, bytes = kChangeSubsetsFixedBytes;
+            for (int g = f; g < nf && b < items; ++g) {
+                if (R[g].cnt == 0) continue;
+                const int len = sizes[g] - d;
+                const int64_t left = R[g].item_off + R[g].cnt - b, each = change_subsets_item_bytes(len, P1);
+                int64_t take = std::min<int64_t>(left, (cap - bytes) / each);
+                if (take <= 0 && L.n == 0) take = 1;
+                if (take <= 0) break;
+                take = std::min<int64_t>(take, (INT32_MAX / 2) / P1 - L.n);
+                L.n += take;
+                L.nd += take * len;
+                bytes += take * each;
+                L.lmin = std::min(L.lmin, len);
+                L.lmax = std::max(L.lmax, len);
+                b += take;
+                if (take < left) break;
+            }
+            launches.push_back(L);
+            max_items = std::max(max_items, L.n);
+            max_dev = std::max(max_dev, L.nd);
+            a = b;
+        }
+    }
+    stage::Bump lay;
+    const size_t pts = size_t(max_items) * P1, pl = size_t(max_dev) * P1;
+    const size_t o_combo = lay.take(8 * combos.size()), o_rec = lay.take(sizeof(SubsetFleet) * recs.size()),
+                 o_par = lay.take(4 * size_t(max_items)), o_soff = lay.take(8 * size_t(max_items + 1)),
+                 o_sidx = lay.take(4 * size_t(max_dev)), o_w0 = lay.take(4 * size_t(max_dev)),
+                 o_lo = lay.take(4 * size_t(max_dev)), o_hi = lay.take(4 * size_t(max_dev)), o_st = lay.take(4 * pts),
+                 o_obj = lay.take(8 * pts), o_ld = lay.take(4 * pts), o_rl = lay.take(4 * pts), o_w = lay.take(4 * pl),
+                 o_n = lay.take(4 * pl);
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sel_buf, &c->sel_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
+    }
+    char *base = reinterpret_cast<char *>(c->sel_buf);
+    // (pageable sources: the copies are staged before the calls return)
+    if (!combos.empty())
+        HIP_TRY(hipMemcpyAsync(base + o_combo, combos.data(), 8 * combos.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_rec, recs.data(), sizeof(SubsetFleet) * recs.size(), hipMemcpyHostToDevice, s));
+    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+    const ChangeSubsetsSrc G{table->dev_off, cs->w0, cs->w_min, cs->w_max};
+    const ChangeSubsetsItems O{i32(o_par), reinterpret_cast<int64_t *>(base + o_soff), i32(o_sidx), i32(o_w0), i32(o_lo),
+                               i32(o_hi)};
+    const ChangeSubsetGrid GR{fr->status, fr->obj, fr->dropped_mask, fr->loaded, fr->released, fr->w, fr->n};
+    for (const SubsetLaunch &L : launches) {
+        SubsetArgs U = {};
+        U.fl = reinterpret_cast<const SubsetFleet *>(base + o_rec) + size_t(L.d - d0) * nf;
+        U.combos = reinterpret_cast<const uint64_t *>(base + o_combo);
+        U.i0 = L.i0;
+        U.l0 = L.l0;
+        U.n = int32_t(L.n);
+        U.n_fleets = nf;
+        U.d = L.d;
+        if (L.n > 0) {
+            hipLaunchKernelGGL(halda_change_subsets_index_kernel, dim3(unsigned((L.n + 3) / 4)), dim3(256), 0, s, U, G, O);
+            HIP_TRY(hipGetLastError());
+            // halda_solve_change, unedited, on the items just written
+            halda_subfleets I;
+            I.n_items = int32_t(L.n);
+            I.min_devices = L.lmin;
+            I.max_devices = L.lmax;
+            I.parent = O.parent;
+            I.sub_off = O.sub_off;
+            I.sub_idx = O.sub_idx;
+            const halda_change ch{O.w0, cs->w_min ? O.w_min : nullptr, cs->w_max ? O.w_max : nullptr, P,
+                                  int32_t(dtop[L.d - d0])};
+            halda_change_frontier cf;
+            cf.n_devices = L.nd;
+            cf.status = i32(o_st);
+            cf.obj = reinterpret_cast<double *>(base + o_obj);
+            cf.loaded = i32(o_ld);
+            cf.released = i32(o_rl);
+            cf.w = i32(o_w);
+            cf.n = i32(o_n);
+            const int rc = halda_solve_change(ctx, model, table, &I, k, &ch, &cf, s);
+            if (rc != HALDA_OK) return rc;
+        }
+        const ChangeSubsetsChunk C{reinterpret_cast<const double *>(base + o_obj), i32(o_ld), i32(o_rl), i32(o_w), i32(o_n),
+                                   L.nd, P1, D1, d0};
+        hipLaunchKernelGGL(halda_change_subsets_pick_kernel, dim3(unsigned(nf)), dim3(256), 0, s, U, C, GR);
+        HIP_TRY(hipGetLastError());
+    }
+    return HALDA_OK;
+}
+
+int halda_solve_change_subsets(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                               const halda_change_subsets *subsets, halda_change_subset_frontier *frontier,
+                               void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fleets || !subsets || !frontier)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/frontier");
+    const int64_t nf = fleets->n_fleets;
+    if (nf <= 0) return HALDA_OK;
+    if (!fleets->dev_off) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!subsets->w0) return fail(HALDA_E_ARG, "halda_change_subsets.w0 is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    // the gate reads dev_off and w0: both come back once
+    std::vector<int64_t> off(size_t(nf) + 1);
+    HIP_TRY(hipMemcpyAsync(off.data(), fleets->dev_off, 8 * (nf + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (off[0] != 0) return fail(HALDA_E_ARG, "halda_solve_change_subsets: dev_off[0] must be 0");
+    for (int64_t f = 0; f < nf; ++f)
+        if (off[f + 1] - off[f] < 1 || off[f + 1] - off[f] > 64)
+            return fail(HALDA_E_ARG, "halda_solve_change_subsets: fleet " + std::to_string(f) + " has " +
+                                         std::to_string(off[f + 1] - off[f]) + " devices (1..64)");
+    std::vector<int32_t> w0(static_cast<size_t>(off[nf]), 0);
+    HIP_TRY(hipMemcpyAsync(w0.data(), subsets->w0, 4 * size_t(off[nf]), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ChangeSubsetsGate Q;
+    const int rc = change_subsets_gate(model, fleets, off.data(), w0.data(), k, subsets, frontier, Q);
+    if (rc != HALDA_OK) return rc;
+    return solve_change_subsets(ctx, model, fleets, k, subsets, frontier, Q, stream);
+}
+
+int halda_solve_change_subsets_host(void *ctx, const halda_model *model, const halda_fleets *th, int32_t k,
+                                    const halda_change_subsets *subsets, halda_change_subset_frontier *fh) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !subsets || !fh) return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/frontier");
+    if (th->n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!fh->status || !fh->obj || !fh->dropped_mask || !fh->loaded || !fh->released || !fh->w || !fh->n)
+        return fail(HALDA_E_ARG, "halda_change_subset_frontier has a NULL array");
+    if (!subsets->w0) return fail(HALDA_E_ARG, "halda_change_subsets.w0 is NULL");
+    if (subsets->min_drop < 0 || subsets->max_drop < subsets->min_drop || subsets->max_drop > 63)
+        return fail(HALDA_E_ARG, "halda_solve_change_subsets_host: needs 0 <= min_drop <= max_drop <= 63");
+    if (subsets->max_p < 0 || subsets->max_p > kBudgetMaxP)
+        return fail(HALDA_E_ARG, "halda_solve_change_subsets_host: max_p must be in 0 .. 63");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf];
+    if (th->dev_off[0] != 0 || nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    for (int64_t f = 0; f < nf; ++f)
+        if (th->dev_off[f + 1] - th->dev_off[f] < 1 || th->dev_off[f + 1] - th->dev_off[f] > 64)
+            return fail(HALDA_E_ARG, "halda_solve_change_subsets_host: fleet " + std::to_string(f) + " has " +
+                                         std::to_string(th->dev_off[f + 1] - th->dev_off[f]) + " devices (1..64)");
+    ChangeSubsetsGate Q;
+    int rc = change_subsets_gate(model, th, th->dev_off, subsets->w0, k, subsets, fh, Q);
+    if (rc != HALDA_OK) return rc;
+    const size_t pts = size_t(nf) * size_t(subsets->max_drop - subsets->min_drop + 1) * size_t(subsets->max_p + 1);
+    const int32_t *bsrc[3] = {subsets->w0, subsets->w_min, subsets->w_max};
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    size_t o_b[3];
+    for (int a = 0; a < 3; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nd) : 0;
+    const stage::ChangeSubsetSlots R = stage::lay_change_subsets(lay, pts);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    for (int a = 0; a < 3 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nd, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    halda_change_subsets dc = *subsets;
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    dc.w0 = bdev(0);
+    dc.w_min = bdev(1);
+    dc.w_max = bdev(2);
+    halda_change_subset_frontier r = stage::bind_change_subsets(base, R);
+    rc = solve_change_subsets(ctx, model, &d, k, &dc, &r, Q, s);
+    if (rc == HALDA_OK) rc = download(stage::change_subsets_copies(R, *fh), base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;

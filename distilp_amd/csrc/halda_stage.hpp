@@ -262,4 +262,45 @@ inline int64_t bad_change(const int64_t *sub_off, int64_t n_items, const int32_t
     return -1;
 }
 
+// A halda_change_subset_frontier in a staging buffer: the five per-cell arrays over pts = n_fleets x D1 x
+// (max_p + 1) cells, then the w and n plans of 64 entries per cell.
+struct ChangeSubsetSlots {
+    size_t pts;
+    size_t status, obj, dropped_mask, loaded, released, w, n;
+};
+
+inline ChangeSubsetSlots lay_change_subsets(Bump &b, size_t pts) {
+    ChangeSubsetSlots s{pts, 0, 0, 0, 0, 0, 0, 0};
+    s.status = b.take(4 * pts);
+    s.obj = b.take(8 * pts);
+    s.dropped_mask = b.take(8 * pts);
+    s.loaded = b.take(4 * pts);
+    s.released = b.take(4 * pts);
+    s.w = b.take(4 * 64 * pts);
+    s.n = b.take(4 * 64 * pts);
+    return s;
+}
+
+inline halda_change_subset_frontier bind_change_subsets(char *base, const ChangeSubsetSlots &s) {
+    halda_change_subset_frontier r;
+    r.status = reinterpret_cast<int32_t *>(base + s.status);
+    r.obj = reinterpret_cast<double *>(base + s.obj);
+    r.dropped_mask = reinterpret_cast<uint64_t *>(base + s.dropped_mask);
+    r.loaded = reinterpret_cast<int32_t *>(base + s.loaded);
+    r.released = reinterpret_cast<int32_t *>(base + s.released);
+    r.w = reinterpret_cast<int32_t *>(base + s.w);
+    r.n = reinterpret_cast<int32_t *>(base + s.n);
+    return r;
+}
+
+inline std::array<Copy, 7> change_subsets_copies(const ChangeSubsetSlots &s, const halda_change_subset_frontier &h) {
+    return {{{h.status, s.status, 4 * s.pts},
+             {h.obj, s.obj, 8 * s.pts},
+             {h.dropped_mask, s.dropped_mask, 8 * s.pts},
+             {h.loaded, s.loaded, 4 * s.pts},
+             {h.released, s.released, 4 * s.pts},
+             {h.w, s.w, 4 * 64 * s.pts},
+             {h.n, s.n, 4 * 64 * s.pts}}};
+}
+
 }  // namespace stage

@@ -2882,6 +2882,158 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_ch
     for (int64_t it = blockIdx.x; it < n; it += gridDim.x) sweep_item_change(A, Cg, int(it), w, c, Wave(lane));
 }
 
+// ---------------------------------------------------------------- scale-in / scale-out (halda_solve_change_subsets)
+// Which devices to drop (or, from a pool, to add) under a released-layer budget: the candidates are
+// halda_solve_subsets' (SubsetFleet / SubsetArgs, one combo per candidate, the same enumeration order), a
+// candidate's value at point p is what halda_sweep_change_kernel writes for its list with w0 restricted to it.
+// Per (d, chunk): halda_change_subsets_index_kernel writes the chunk's candidates as change items in context
+// scratch, the unedited change kernel runs on them, and halda_change_subsets_pick_kernel folds the chunk into
+// the frontier grid [fleet][d - min_drop][p]. No atomics, no spin-waits, nothing shared between workgroups.
+struct ChangeSubsetsSrc {
+    const int64_t *dev_off;             // the table's
+    const int32_t *w0, *w_min, *w_max;  // per parent device, laid out by dev_off; w_min / w_max may be NULL
+};
+
+struct ChangeSubsetsItems {
+    int32_t *parent;             // [n]
+    int64_t *sub_off;            // [n + 1]
+    int32_t *sub_idx;            // [listed devices of the launch]
+    int32_t *w0, *w_min, *w_max; // the same layout (w_min / w_max unused where the source has none)
+};
+
+// One wave per candidate: the item as halda_subsets_index_kernel writes it, and beside it the kept devices'
+// w0 / w_min / w_max gathered from the per-parent-device arrays (lane j: the j-th kept device).
+__global__ __launch_bounds__(256) void halda_change_subsets_index_kernel(SubsetArgs U, ChangeSubsetsSrc G,
+                                                                         ChangeSubsetsItems O) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * 4 + int(threadIdx.x >> 6));
+    if (i >= U.n) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t g = U.i0 + i;
+    int lo = 0, hi = U.n_fleets - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (sload_i64(&U.fl[mid].item_off) <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    const SubsetFleet sf = subset_fleet(U, lo);
+    const int64_t cand = g - sf.item_off;
+    const uint64_t combo = sload_u64(U.combos + sf.combo_off + cand);
+    const int64_t base = sload_i64(G.dev_off + lo);
+    int nk;
+    const int idx = subset_kept_index(sf.drop_mask, combo, sf.M, lane, &nk);
+    const int64_t so = sf.list_off + cand * int64_t(sf.M - U.d) - U.l0;
+    if (lane < nk) {
+        O.sub_idx[so + lane] = idx;
+        O.w0[so + lane] = G.w0[base + idx];
+        if (G.w_min) O.w_min[so + lane] = G.w_min[base + idx];
+        if (G.w_max) O.w_max[so + lane] = G.w_max[base + idx];
+    }
+    if (lane == 0) {
+        O.parent[i] = lo;
+        O.sub_off[i] = so;
+        if (i == U.n - 1) O.sub_off[i + 1] = so + nk;
+    }
+}
+
+struct ChangeSubsetsChunk {  // one launch's halda_change_frontier in context scratch
+    const double *obj;                 // [n][P1]
+    const int32_t *loaded, *released;  // [n][P1]
+    const int32_t *w, *n;              // [P1][nd]
+    int64_t nd;
+    int32_t P1, D1, d0;                // points per item; the grid's d rows and its first d (min_drop)
+};
+
+struct ChangeSubsetGrid {  // halda_change_subset_frontier
+    int32_t *status;
+    double *obj;
+    uint64_t *dropped_mask;
+    int32_t *loaded, *released;
+    int32_t *w, *n;
+};
+
+// One workgroup per fleet, for the launch's d: per point p the arg-min of the launch's items of the fleet's
+// group on (raw obj, candidate index), lexicographic with strict <, as halda_subsets_pick_kernel takes it
+// -- per thread over its candidates in ascending order, a wave reduction, the four waves' results through
+// LDS behind ONE workgroup barrier (every p at once). Then wave v takes the points v, v + 4, ...: a cell
+// whose group began in an earlier launch moves only for a strictly lower value; lane j writes parent device
+// j's entry of the winner's point-p plan, read from the chunk's planes at the device's rank among the kept
+// (0 for a dropped device). A group without candidates, or a cell whose candidates all have no plan at p,
+// reads INFEASIBLE, +inf, mask 0, zero counts and a zero plan.
+__global__ __launch_bounds__(256) void halda_change_subsets_pick_kernel(SubsetArgs U, ChangeSubsetsChunk C,
+                                                                        ChangeSubsetGrid R) {
+    const int f = int(blockIdx.x);
+    const SubsetFleet sf = subset_fleet(U, f);
+    const int lane = int(threadIdx.x & 63), wv = int(threadIdx.x >> 6);
+    const int P1 = C.P1;
+    const int64_t at = (int64_t(f) * C.D1 + (U.d - C.d0)) * P1;
+    if (sf.cnt == 0) {
+        if (U.i0 == 0)
+            for (int p = wv; p < P1; p += 4) {
+                if (lane == 0) {
+                    R.status[at + p] = HALDA_STATUS_INFEASIBLE;
+                    R.obj[at + p] = kInf;
+                    R.dropped_mask[at + p] = 0;
+                    R.loaded[at + p] = 0;
+                    R.released[at + p] = 0;
+                }
+                R.w[(at + p) * 64 + lane] = 0;
+                R.n[(at + p) * 64 + lane] = 0;
+            }
+        return;
+    }
+    const int64_t a = sf.item_off > U.i0 ? sf.item_off : U.i0;
+    const int64_t e = sf.item_off + sf.cnt, lim = U.i0 + U.n;
+    const int64_t b = e < lim ? e : lim;
+    if (a >= b) return;
+    __shared__ double so[4][64];
+    __shared__ int64_t sc[4][64];
+    for (int p = 0; p < P1; ++p) {
+        double o = kInf;
+        int64_t c = -1;
+        for (int64_t g = a + threadIdx.x; g < b; g += 256) subset_min(o, c, C.obj[(g - U.i0) * P1 + p], g - sf.item_off);
+        for (int s = 32; s >= 1; s >>= 1) {
+            const double o2 = __shfl_xor(o, s);
+            const int64_t c2 = (int64_t(__shfl_xor(int(uint64_t(c) >> 32), s)) << 32) | uint32_t(__shfl_xor(int(c), s));
+            subset_min(o, c, o2, c2);
+        }
+        if (lane == 0) {
+            so[wv][p] = o;
+            sc[wv][p] = c;
+        }
+    }
+    __syncthreads();
+    const bool first = a == sf.item_off;
+    const uint64_t below = (uint64_t(1) << lane) - 1;
+    const uint64_t all = sf.M >= 64 ? ~uint64_t(0) : (uint64_t(1) << sf.M) - 1;
+    for (int p = wv; p < P1; p += 4) {
+        double o = so[0][p];
+        int64_t c = sc[0][p];
+        for (int v = 1; v < 4; ++v) subset_min(o, c, so[v][p], sc[v][p]);
+        if (!first && !(o < R.obj[at + p])) continue;  // the group began earlier: only a strictly lower value moves it
+        const bool ok = o < kInf;
+        const uint64_t combo = U.combos[sf.combo_off + c];
+        const int slot = __popcll(sf.drop_mask & below);
+        const bool kept = lane < sf.M && !(((sf.drop_mask >> lane) & 1) && ((combo >> slot) & 1));
+        const uint64_t km = __ballot(kept);
+        const int64_t src = int64_t(p) * C.nd + sf.list_off + c * int64_t(sf.M - U.d) - U.l0 + __popcll(km & below);
+        int wl = 0, nl = 0;
+        if (ok && kept) {
+            wl = C.w[src];
+            nl = C.n[src];
+        }
+        R.w[(at + p) * 64 + lane] = wl;
+        R.n[(at + p) * 64 + lane] = nl;
+        if (lane == 0) {
+            const int64_t it = (sf.item_off + c - U.i0) * P1 + p;
+            R.status[at + p] = ok ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+            R.obj[at + p] = o;
+            R.dropped_mask[at + p] = ok ? ~km & all : 0;
+            R.loaded[at + p] = ok ? C.loaded[it] : 0;
+            R.released[at + p] = ok ? C.released[it] : 0;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- resident single-fleet solver
 // halda_resident_kernel: ONE wave that stays resident between single-fleet calls (halda_solve's
 // latency path through halda_solve_fleets_host): the host writes the call's sweep arguments and the

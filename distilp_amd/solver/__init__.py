@@ -11,6 +11,8 @@ from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
 from .plans import (PlanEvaluation, Replacement, evaluate_plan_np, halda_evaluate_plan,  # noqa: F401
                     halda_evaluate_plans_batch, halda_replace_or_keep, halda_replace_or_keep_batch)
+from .scale import (ScalePoint, halda_scale_in, halda_scale_in_frontier, halda_scale_in_frontier_batch,  # noqa: F401
+                    halda_scale_out_frontier)
 from .subfleets import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
                         halda_solve_subfleets)
 from .subsets import (SubsetPoint, halda_select_devices_exact, halda_subset_frontier,  # noqa: F401
@@ -26,6 +28,7 @@ __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solv
            "PlanEvaluation", "Replacement", "HALDAResult", "halda_subset_frontier", "halda_subset_frontier_batch",
            "halda_select_devices_exact", "SubsetPoint", "halda_change_frontier", "halda_change_frontiers",
            "halda_failover_frontiers", "halda_join_frontiers", "halda_failover_plan", "ChangePoint",
-           "ILPResult"]
+           "halda_scale_in_frontier", "halda_scale_in_frontier_batch", "halda_scale_in", "halda_scale_out_frontier",
+           "ScalePoint", "ILPResult"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

@@ -94,7 +94,9 @@ EXPORTS = ("halda_version", "halda_init", "halda_solve_batch", "halda_solve_batc
            "halda_set_bounds_path", "halda_solve_fleets_boxed", "halda_solve_fleets_boxed_host",
            "halda_solve_fleets_budget", "halda_solve_fleets_budget_host", "halda_budget_lds_bytes",
            "halda_solve_subsets", "halda_solve_subsets_host", "halda_subsets_count", "halda_last_subsets_route",
-           "halda_set_subsets_path", "halda_solve_change", "halda_solve_change_host", "halda_change_lds_bytes")
+           "halda_set_subsets_path", "halda_solve_change", "halda_solve_change_host", "halda_change_lds_bytes",
+           "halda_solve_change_subsets", "halda_solve_change_subsets_host", "halda_change_subsets_max_deficit",
+           "halda_change_subsets_launch_bytes", "halda_set_change_subsets_chunk")
 
 _lib = None
 _lib_lock = threading.Lock()

@@ -721,6 +721,83 @@ int halda_last_subsets_route(void *ctx, int *route);
  * (test path: the fused route is compared against it). HALDA_E_ARG for any other path. */
 int halda_set_subsets_path(void *ctx, int path);
 
+/* ------------------------------------------------------------------------
+ * Scale-in and scale-out: WHICH devices to drop (or, from a pool, to add) under a released-layer budget.
+ *
+ * Per fleet of M <= 64 devices: w0_i >= 0 are the layers each device holds now (a pool device that has not
+ * joined holds 0; sum w0 <= W = L / k), keep_mask names the devices that may not be dropped. A candidate is
+ * halda_solve_subsets' -- the fleet without d of its q droppable devices, the kept devices in their order,
+ * one 64-bit combo over droppable slots, enumerated by d ascending, then by ascending dropped-index lists in
+ * lexicographic order. Its value at point p is exactly what halda_solve_change writes for that list with w0
+ * (and w_min / w_max) restricted to it; its deficit is W - sum of the kept devices' w0.
+ *
+ * The frontier is a grid [fleet][d - min_drop][p], min_drop <= d <= max_drop, 0 <= p <= max_p: each cell is
+ * the candidate with exactly d drops whose point p has the least raw objective, the earliest among equals
+ * (strict <). Per cell: status HALDA_STATUS_OPTIMAL or _INFEASIBLE, obj, the dropped devices as a mask,
+ * loaded / released of the winner's point p, and its plan w / n indexed by PARENT device (64 entries per cell,
+ * 0 for a dropped device and past M). A (fleet, d) without a candidate (d > min(q, M - 1)), or a cell where no
+ * candidate has a plan at p, reads INFEASIBLE, +inf, mask 0, zero counts and a zero plan.
+ * Scale-out is the same call: the parent is the fleet followed by the pool, keep_mask the whole fleet, the
+ * pool's w0 zero; "add a of the q pool devices" is d = q - a.
+ *
+ * Gate, from the shapes and w0 alone, before any GPU work (HALDA_E_ARG; there is no fallback): every fleet has
+ * 1 .. 64 devices; 0 <= min_drop <= max_drop <= 63 and min_drop <= min(q, M - 1) of at least one fleet; no
+ * keep bit at or above M; at most HALDA_SUBSETS_MAX candidates per fleet over the d range; every w0_i >= 0 and
+ * sum w0 <= W; 0 <= max_p <= 63; and for every d in range that has a candidate, halda_solve_change's gate with
+ * that d's longest list and largest deficit Dmax_d (halda_change_subsets_max_deficit over the fleets that
+ * admit d): 2 max_p + Dmax_d <= 254 and halda_change_lds_bytes(len_d, max_p, Dmax_d, k) <= 160 KiB.
+ *
+ * One halda_solve_change launch per (d, chunk), each with its d's list lengths and max_deficit = Dmax_d (a
+ * small d is not gated by a large d's deficit): halda_change_subsets_index_kernel writes the chunk's
+ * candidates as items with their w0 / w_min / w_max in context scratch, halda_sweep_change_kernel runs on
+ * them, halda_change_subsets_pick_kernel folds the chunk into the grid and copies each new winner's plan.
+ * Chunks are cut at candidate boundaries so that halda_change_subsets_launch_bytes of a launch stays within
+ * the context's cap (256 MiB; halda_set_change_subsets_chunk), one candidate at the least. The scratch is per
+ * context, so the call runs after the previous user of the context's shared scratch on another stream.
+ * ------------------------------------------------------------------------ */
+typedef struct halda_change_subsets {
+    const int32_t *w0;            /* [dev_off[n_fleets]] per parent device, laid out by dev_off */
+    const int32_t *w_min, *w_max; /* as halda_bounds, per parent device; either may be NULL */
+    int32_t min_drop, max_drop;   /* the d range */
+    int32_t max_p;                /* P: the most released layers asked for */
+    const uint64_t *keep_mask;    /* HOST memory, [n_fleets], or NULL */
+} halda_change_subsets;
+
+typedef struct halda_change_subset_frontier {
+    int32_t *status;        /* [n_fleets * D1 * (max_p + 1)], D1 = max_drop - min_drop + 1 */
+    double *obj;            /* the same extent */
+    uint64_t *dropped_mask; /* the same extent */
+    int32_t *loaded;        /* the same extent */
+    int32_t *released;      /* the same extent */
+    int32_t *w, *n;         /* [n_fleets * D1 * (max_p + 1) * 64], by parent device */
+} halda_change_subset_frontier;
+
+/* Asynchronous on `stream` (NULL = the context's stream) once the gate is formed: fleets, w0 / w_min / w_max
+ * and frontier hold device arrays, keep_mask is host memory; the call reads dev_off and w0 back for the gate
+ * (it waits for `stream`). */
+int halda_solve_change_subsets(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                               const halda_change_subsets *subsets, halda_change_subset_frontier *frontier,
+                               void *stream);
+
+/* Synchronous variant on HOST arrays: the table and w0 / w_min / w_max cross PCIe on the way in, the grid on
+ * the way back. */
+int halda_solve_change_subsets_host(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                                    const halda_change_subsets *subsets, halda_change_subset_frontier *frontier);
+
+/* The largest deficit of a fleet's candidates with d drops: W - sum w0 plus the d largest droppable w0 (w0:
+ * HOST memory, M entries). -1 for M outside 1 .. 64, d < 0, a keep bit at or above M, or d beyond the
+ * droppable devices. No context needed. */
+int64_t halda_change_subsets_max_deficit(const int32_t *w0, int32_t M, uint64_t keep_mask, int32_t d, int32_t W);
+
+/* Scratch bytes of one launch of n_items candidates of `len` listed devices at max_p: the items, the three
+ * int arrays, the four per-point arrays and the two planes, plus a fixed 4096 for alignment. -1 for len < 1,
+ * max_p < 0 or n_items < 0. No context needed. */
+int64_t halda_change_subsets_launch_bytes(int32_t len, int32_t max_p, int64_t n_items);
+
+/* The byte cap of one launch's scratch (test hook): 0 restores the default of 256 MiB; a launch always holds
+ * at least one candidate. HALDA_E_ARG for a negative value. */
+int halda_set_change_subsets_chunk(void *ctx, int64_t bytes);
+
 /* Ask the context's resident wave (above) to leave now and wait until it has (a no-op when none
  * runs); the next one-fleet call relaunches it. For callers about to synchronise the whole device. */
 int halda_resident_release(void *ctx);
