@@ -327,6 +327,20 @@ int upload(char *base, const stage::TableLayout &t, const halda_fleets &F, hipSt
     return rc;
 }
 
+int upload(char *base, const stage::ItemsLayout &t, const halda_subfleets &I, hipStream_t s) {
+    int rc = upload(base, t.parent, I.parent, 4 * t.n, s);
+    if (rc == HALDA_OK) rc = upload(base, t.sub_off, I.sub_off, 8 * (t.n + 1), s);
+    if (rc == HALDA_OK) rc = upload(base, t.sub_idx, I.sub_idx, 4 * t.tot, s);
+    return rc;
+}
+
+int upload(char *base, const stage::TripleLayout &t, hipStream_t s) {
+    int rc = HALDA_OK;
+    for (int a = 0; a < 3 && rc == HALDA_OK; ++a)
+        if (t.host[a]) rc = upload(base, t.off[a], t.host[a], 4 * t.count, s);
+    return rc;
+}
+
 template <size_t N>
 int download(const std::array<stage::Copy, N> &copies, const char *base, hipStream_t s) {
     for (const stage::Copy &k : copies)
@@ -1717,6 +1731,34 @@ int group_check(FleetsGroup *G) {
     G->persistent = true;
     return HALDA_OK;
 }
+
+// The launch of a frontier kernel (halda_solve_fleets_budget, halda_solve_change): `view` is the table under
+// the count and length summary of what is solved (the fleets, or the items), `slice` the wave's LDS bytes,
+// J the kernel's own arguments.
+template <class Args>
+int launch_frontier(Ctx *c, void (*kernel)(SweepArgs, Args), const halda_model &model,
+                    const halda_fleets &view, int32_t k, int64_t slice, const Args &J, void *stream) {
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    SweepArgs A = {};
+    static_cast<halda_model &>(A.Mo) = model;
+    A.Mo.bvo = model_bvo(model);
+    A.F = view;
+    A.ks[0] = k;
+    A.Ws[0] = model.L / k;
+    A.n_k = 1;
+    A.mmax = view.max_devices;
+    A.uM = view.min_devices == view.max_devices ? view.max_devices : 0;
+    A.xstride = 7 * int64_t(view.max_devices) + 1;
+    int per_cu = 0;
+    HIP_TRY(c->occupancy(reinterpret_cast<const void *>(kernel), slice, &per_cu));  // also raises the dynamic-LDS limit
+    const unsigned grid =
+        unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(view.n_fleets))));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), size_t(slice), s, A, J);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2141,7 +2183,7 @@ int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_
     // layout: the parent table, the item arrays, the results over the items
     stage::Bump lay;
     const stage::TableLayout T = stage::lay_table(lay, nf, nd);
-    const size_t o_par = lay.take(4 * n), o_soff = lay.take(8 * (n + 1)), o_sidx = lay.take(4 * tot);
+    const stage::ItemsLayout IL = stage::lay_items(lay, n, tot);
     const bool xsel = stage::compact(*out_h);
     const size_t xs = stage::xc_extent(ih->sub_off, n, n_k, 1, lmax, xsel ? out_h->x_off : nullptr);
     const stage::ResultSlots R = stage::lay_result(lay, *out_h, n, tot, size_t(n) * n_k, xs);
@@ -2151,18 +2193,13 @@ int halda_solve_subfleets_host(void *ctx, const halda_model *model, const halda_
     char *base = static_cast<char *>(c->scratch);
     // in: one copy per array; the call (it knows the total: no read-back); out and wait
     if (rc == HALDA_OK) rc = upload(base, T, *th, s);
-    if (rc == HALDA_OK) rc = upload(base, o_par, ih->parent, 4 * n, s);
-    if (rc == HALDA_OK) rc = upload(base, o_soff, ih->sub_off, 8 * (n + 1), s);
-    if (rc == HALDA_OK) rc = upload(base, o_sidx, ih->sub_idx, 4 * tot, s);
+    if (rc == HALDA_OK) rc = upload(base, IL, *ih, s);
     if (rc == HALDA_OK && xsel) rc = upload(base, R.x_off, out_h->x_off, 8 * R.n_inst, s);
     if (rc != HALDA_OK) return rc;
     const halda_fleets d = stage::rebase(*th, base, T);
-    halda_subfleets di = *ih;
+    halda_subfleets di = stage::rebase(*ih, base, IL);
     di.min_devices = int32_t(lmin);
     di.max_devices = int32_t(lmax);
-    di.parent = reinterpret_cast<const int32_t *>(base + o_par);
-    di.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
-    di.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
     halda_fleet_result r = stage::bind_result(base, R, *out_h);
     rc = solve_subfleets(ctx, model, &d, &di, ks, n_k, &r, s, tot);
     if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
@@ -3118,12 +3155,38 @@ int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const hal
     return solve_boxed_host(ctx, model, fh, ks, n_k, box ? *box : none, out_h, "halda_solve_fleets_boxed");
 }
 
-// ---------------------------------------------------------------- a total move budget and its frontier
-// halda_solve_fleets_budget: ONE launch of halda_sweep_budget_kernel under a gate formed from the shapes
-// alone (fleets of 1 .. kK1MaxM devices, one k, max_p <= 63, the slice within the LDS budget). No context
-// scratch, no flags, nothing handed back; outside the gate an error and no launch.
+// ---------------------------------------------------------------- the frontier launches (budget and change)
+// Both entries run ONE launch of their kernel under a gate formed from the shapes alone. No context scratch,
+// no flags, nothing handed back; outside the gate an error and no launch.
 constexpr int kBudgetMaxP = 63;
 
+// The gate's common part, in the order both entries report it: the table, the model, k, the incumbent array,
+// the result arrays, 1 .. kK1MaxM devices per fleet / list, max_p. `in` / `out` / `unit` name the entry's
+// input struct, result struct and what a row of devices is called.
+static int check_frontier_gate(const halda_fleets &table, const halda_model &model, int32_t k, bool has_w0,
+                               bool has_out, int min_devices, int max_devices, int max_p, const std::string &who,
+                               const char *in, const char *out, const char *unit) {
+    if (!stage::complete(table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (model.L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    if (k < 1) return fail(HALDA_E_ARG, who + ": k must be >= 1");
+    if (!has_w0) return fail(HALDA_E_ARG, who + ": " + in + ".w0 is NULL");
+    if (!has_out) return fail(HALDA_E_ARG, who + ": " + out + " has a NULL array");
+    if (min_devices < 1 || max_devices < min_devices || max_devices > kK1MaxM)
+        return fail(HALDA_E_ARG, who + ": every " + unit + " must have 1 .. 64 devices");
+    if (max_p < 0 || max_p > kBudgetMaxP) return fail(HALDA_E_ARG, who + ": max_p must be in 0 .. 63");
+    return HALDA_OK;
+}
+
+static int check_frontier_lds(int64_t lds, const std::string &who) {
+    if (lds > kLdsBudget)
+        return fail(HALDA_E_ARG, who + ": the slice of " + std::to_string(lds) + " B exceeds the LDS budget of " +
+                                     std::to_string(kLdsBudget) + " B");
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- a total move budget and its frontier
+// halda_solve_fleets_budget: halda_sweep_budget_kernel; the gate is fleets of 1 .. kK1MaxM devices, one k,
+// max_p <= 63, the slice within the LDS budget.
 int64_t halda_budget_lds_bytes(int32_t max_devices, int32_t max_p, int32_t k) {
     if (max_devices < 1 || max_p < 0 || k < 1) return -1;
     if (max_devices > 4096 || max_p > 4096) return INT64_MAX;  // far outside the gate; no overflow below
@@ -3136,56 +3199,25 @@ static int check_budget_args(void *ctx, const halda_model *model, const halda_fl
         return fail(HALDA_E_ARG, std::string(who) + ": NULL ctx/model/fleets/budget/frontier");
     const halda_fleets &F = *fleets;
     if (F.n_fleets <= 0) return HALDA_OK;
-    if (!stage::complete(F)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
-    if (k < 1) return fail(HALDA_E_ARG, std::string(who) + ": k must be >= 1");
-    if (!budget->w0) return fail(HALDA_E_ARG, std::string(who) + ": halda_budget.w0 is NULL");
-    if (!fr->status || !fr->obj || !fr->moved || !fr->w || !fr->n)
-        return fail(HALDA_E_ARG, std::string(who) + ": halda_frontier has a NULL array");
-    if (F.min_devices < 1 || F.max_devices < F.min_devices || F.max_devices > kK1MaxM)
-        return fail(HALDA_E_ARG, std::string(who) + ": every fleet must have 1 .. 64 devices");
-    if (budget->max_p < 0 || budget->max_p > kBudgetMaxP)
-        return fail(HALDA_E_ARG, std::string(who) + ": max_p must be in 0 .. 63");
-    const int64_t lds = halda_budget_lds_bytes(F.max_devices, budget->max_p, k);
-    if (lds > kLdsBudget)
-        return fail(HALDA_E_ARG, std::string(who) + ": the slice of " + std::to_string(lds) +
-                                     " B exceeds the LDS budget of " + std::to_string(kLdsBudget) + " B");
-    return HALDA_OK;
+    const int rc = check_frontier_gate(F, *model, k, budget->w0, fr->status && fr->obj && fr->moved && fr->w && fr->n,
+                                       F.min_devices, F.max_devices, budget->max_p, who, "halda_budget",
+                                       "halda_frontier", "fleet");
+    if (rc != HALDA_OK) return rc;
+    return check_frontier_lds(halda_budget_lds_bytes(F.max_devices, budget->max_p, k), who);
 }
 
 int halda_solve_fleets_budget(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
                               const halda_budget *budget, halda_frontier *frontier, void *stream) {
     const int rc = check_budget_args(ctx, model, fleets, k, budget, frontier, "halda_solve_fleets_budget");
     if (rc != HALDA_OK) return rc;
-    Ctx *c = static_cast<Ctx *>(ctx);
     const halda_fleets &F = *fleets;
     if (F.n_fleets <= 0) return HALDA_OK;
     if (frontier->n_devices < F.n_fleets)
         return fail(HALDA_E_ARG, "halda_solve_fleets_budget: halda_frontier.n_devices is not dev_off[n_fleets]");
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    SweepArgs A = {};
-    static_cast<halda_model &>(A.Mo) = *model;
-    A.Mo.bvo = model_bvo(*model);
-    A.F = F;
-    A.ks[0] = k;
-    A.Ws[0] = model->L / k;
-    A.n_k = 1;
-    A.mmax = F.max_devices;
-    A.uM = F.min_devices == F.max_devices ? F.max_devices : 0;
-    A.xstride = 7 * int64_t(F.max_devices) + 1;
     const BudgetArgs Bg{budget->w0,       budget->w_min,   budget->w_max,   budget->max_p, frontier->n_devices,
                         frontier->status, frontier->obj,   frontier->moved, frontier->w,   frontier->n};
-    const int64_t slice = budget_slice(F.max_devices, budget->max_p, k > 1).total;
-    int per_cu = 0;
-    const void *fn = reinterpret_cast<const void *>(halda_sweep_budget_kernel);
-    HIP_TRY(c->occupancy(fn, slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
-    const unsigned grid =
-        unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(F.n_fleets))));
-    hipLaunchKernelGGL(halda_sweep_budget_kernel, dim3(grid), dim3(64), size_t(slice), s, A, Bg);
-    HIP_TRY(hipGetLastError());
-    return HALDA_OK;
+    return launch_frontier(static_cast<Ctx *>(ctx), halda_sweep_budget_kernel, *model, F, k,
+                           budget_slice(F.max_devices, budget->max_p, k > 1).total, Bg, stream);
 }
 
 int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const halda_fleets *fh, int32_t k,
@@ -3203,23 +3235,19 @@ int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const ha
             return fail(HALDA_E_ARG, "halda_solve_fleets_budget_host: fleet " + std::to_string(f) +
                                          ": the incumbent needs every w0_i >= 1 and sum w0 = L / k");
     }
-    const int32_t *bsrc[3] = {budget->w0, budget->w_min, budget->w_max};
     stage::Bump lay;
     const stage::TableLayout T = stage::lay_table(lay, nf, nd);
-    size_t o_b[3];
-    for (int a = 0; a < 3; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nd) : 0;
+    const stage::TripleLayout B = stage::lay_triple(lay, budget->w0, budget->w_min, budget->w_max, nd);
     const stage::FrontierSlots R = stage::lay_frontier(lay, nf, nd, budget->max_p);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     rc = ensure_scratch(c, lay.off);
     char *base = static_cast<char *>(c->scratch);
     if (rc == HALDA_OK) rc = upload(base, T, *fh, s);
-    for (int a = 0; a < 3 && rc == HALDA_OK; ++a)
-        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nd, s);
+    if (rc == HALDA_OK) rc = upload(base, B, s);
     if (rc != HALDA_OK) return rc;
     const halda_fleets d = stage::rebase(*fh, base, T);
-    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
-    const halda_budget db = {bdev(0), bdev(1), bdev(2), budget->max_p};
+    const halda_budget db = {B.at(base, 0), B.at(base, 1), B.at(base, 2), budget->max_p};
     halda_frontier r = stage::bind_frontier(base, R, nd);
     rc = halda_solve_fleets_budget(ctx, model, &d, k, &db, &r, s);
     if (rc == HALDA_OK) rc = download(stage::frontier_copies(R, *fr_h), base, s);
@@ -3229,9 +3257,8 @@ int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const ha
 }
 
 // ---------------------------------------------------------------- a changed fleet and its frontier
-// halda_solve_change: ONE launch of halda_sweep_change_kernel under a gate formed from the shapes alone (lists
-// of 1 .. kK1MaxM devices, one k, max_p <= 63, 2 max_p + max_deficit <= 254, the slice within the LDS
-// budget). No context scratch, no flags, nothing handed back; outside the gate an error and no launch.
+// halda_solve_change: halda_sweep_change_kernel; the gate is lists of 1 .. kK1MaxM devices, one k,
+// max_p <= 63, 2 max_p + max_deficit <= 254, the slice within the LDS budget.
 constexpr int kChangeMaxE = 254;  // the arg-min byte: table entries 0 .. 2 P + D, 255 marks "unreached"
 
 int64_t halda_change_lds_bytes(int32_t max_devices, int32_t max_p, int32_t max_deficit, int32_t k) {
@@ -3249,53 +3276,31 @@ static int check_change_args(void *ctx, const halda_model *model, const halda_fl
     if (I.n_items <= 0) return HALDA_OK;
     if (!I.parent || !I.sub_off || !I.sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
     if (table->n_fleets <= 0) return fail(HALDA_E_ARG, std::string(who) + ": the table has no fleets");
-    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
-    if (k < 1) return fail(HALDA_E_ARG, std::string(who) + ": k must be >= 1");
-    if (!change->w0) return fail(HALDA_E_ARG, std::string(who) + ": halda_change.w0 is NULL");
-    if (!fr->status || !fr->obj || !fr->loaded || !fr->released || !fr->w || !fr->n)
-        return fail(HALDA_E_ARG, std::string(who) + ": halda_change_frontier has a NULL array");
-    if (I.min_devices < 1 || I.max_devices < I.min_devices || I.max_devices > kK1MaxM)
-        return fail(HALDA_E_ARG, std::string(who) + ": every list must have 1 .. 64 devices");
-    if (change->max_p < 0 || change->max_p > kBudgetMaxP)
-        return fail(HALDA_E_ARG, std::string(who) + ": max_p must be in 0 .. 63");
+    const int rc = check_frontier_gate(*table, *model, k, change->w0,
+                                       fr->status && fr->obj && fr->loaded && fr->released && fr->w && fr->n,
+                                       I.min_devices, I.max_devices, change->max_p, who, "halda_change",
+                                       "halda_change_frontier", "list");
+    if (rc != HALDA_OK) return rc;
     if (change->max_deficit < (host ? -1 : 0))
         return fail(HALDA_E_ARG, std::string(who) + ": max_deficit must be >= 0");
     const int dmax = std::max(change->max_deficit, 0);
     if (2 * int64_t(change->max_p) + dmax > kChangeMaxE)
         return fail(HALDA_E_ARG, std::string(who) + ": 2 max_p + max_deficit must be at most 254");
-    const int64_t lds = halda_change_lds_bytes(I.max_devices, change->max_p, dmax, k);
-    if (lds > kLdsBudget)
-        return fail(HALDA_E_ARG, std::string(who) + ": the slice of " + std::to_string(lds) +
-                                     " B exceeds the LDS budget of " + std::to_string(kLdsBudget) + " B");
-    return HALDA_OK;
+    return check_frontier_lds(halda_change_lds_bytes(I.max_devices, change->max_p, dmax, k), who);
 }
 
 int halda_solve_change(void *ctx, const halda_model *model, const halda_fleets *table, const halda_subfleets *items,
                        int32_t k, const halda_change *change, halda_change_frontier *frontier, void *stream) {
     const int rc = check_change_args(ctx, model, table, items, k, change, frontier, false, "halda_solve_change");
     if (rc != HALDA_OK) return rc;
-    Ctx *c = static_cast<Ctx *>(ctx);
     const halda_subfleets &I = *items;
     if (I.n_items <= 0) return HALDA_OK;
     if (frontier->n_devices < I.n_items)
         return fail(HALDA_E_ARG, "halda_solve_change: halda_change_frontier.n_devices is not sub_off[n_items]");
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    SweepArgs A = {};
-    static_cast<halda_model &>(A.Mo) = *model;
-    A.Mo.bvo = model_bvo(*model);
-    A.F = *table;  // the parent table under the items' count and length summary
-    A.F.n_fleets = I.n_items;
-    A.F.min_devices = I.min_devices;
-    A.F.max_devices = I.max_devices;
-    A.ks[0] = k;
-    A.Ws[0] = model->L / k;
-    A.n_k = 1;
-    A.mmax = I.max_devices;
-    A.uM = I.min_devices == I.max_devices ? I.max_devices : 0;
-    A.xstride = 7 * int64_t(I.max_devices) + 1;
+    halda_fleets view = *table;  // the parent table under the items' count and length summary
+    view.n_fleets = I.n_items;
+    view.min_devices = I.min_devices;
+    view.max_devices = I.max_devices;
     const ChangeArgs Cg{SubArgs{I.parent, I.sub_off, I.sub_idx},
                         change->w0,
                         change->w_min,
@@ -3309,15 +3314,8 @@ int halda_solve_change(void *ctx, const halda_model *model, const halda_fleets *
                         frontier->released,
                         frontier->w,
                         frontier->n};
-    const int64_t slice = change_slice(I.max_devices, change->max_p, change->max_deficit, k > 1).total;
-    int per_cu = 0;
-    const void *fn = reinterpret_cast<const void *>(halda_sweep_change_kernel);
-    HIP_TRY(c->occupancy(fn, slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
-    const unsigned grid =
-        unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(I.n_items))));
-    hipLaunchKernelGGL(halda_sweep_change_kernel, dim3(grid), dim3(64), size_t(slice), s, A, Cg);
-    HIP_TRY(hipGetLastError());
-    return HALDA_OK;
+    return launch_frontier(static_cast<Ctx *>(ctx), halda_sweep_change_kernel, *model, view, k,
+                           change_slice(I.max_devices, change->max_p, change->max_deficit, k > 1).total, Cg, stream);
 }
 
 int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fleets *th, const halda_subfleets *ih,
@@ -3359,32 +3357,24 @@ int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fle
         if (rc != HALDA_OK) return rc;
     }
     const int64_t tot = ih->sub_off[n];
-    const int32_t *bsrc[3] = {change->w0, change->w_min, change->w_max};
     stage::Bump lay;
     const stage::TableLayout T = stage::lay_table(lay, nf, nd);
-    const size_t o_par = lay.take(4 * n), o_soff = lay.take(8 * (n + 1)), o_sidx = lay.take(4 * tot);
-    size_t o_b[3];
-    for (int a = 0; a < 3; ++a) o_b[a] = bsrc[a] ? lay.take(4 * tot) : 0;
+    const stage::ItemsLayout IL = stage::lay_items(lay, n, tot);
+    const stage::TripleLayout B = stage::lay_triple(lay, change->w0, change->w_min, change->w_max, tot);
     const stage::ChangeSlots R = stage::lay_change(lay, n, tot, dc.max_p);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     rc = ensure_scratch(c, lay.off);
     char *base = static_cast<char *>(c->scratch);
     if (rc == HALDA_OK) rc = upload(base, T, *th, s);
-    if (rc == HALDA_OK) rc = upload(base, o_par, ih->parent, 4 * n, s);
-    if (rc == HALDA_OK) rc = upload(base, o_soff, ih->sub_off, 8 * (n + 1), s);
-    if (rc == HALDA_OK) rc = upload(base, o_sidx, ih->sub_idx, 4 * tot, s);
-    for (int a = 0; a < 3 && rc == HALDA_OK; ++a)
-        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * tot, s);
+    if (rc == HALDA_OK) rc = upload(base, IL, *ih, s);
+    if (rc == HALDA_OK) rc = upload(base, B, s);
     if (rc != HALDA_OK) return rc;
     const halda_fleets d = stage::rebase(*th, base, T);
-    di.parent = reinterpret_cast<const int32_t *>(base + o_par);
-    di.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
-    di.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
-    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
-    dc.w0 = bdev(0);
-    dc.w_min = bdev(1);
-    dc.w_max = bdev(2);
+    di = stage::rebase(di, base, IL);
+    dc.w0 = B.at(base, 0);
+    dc.w_min = B.at(base, 1);
+    dc.w_max = B.at(base, 2);
     halda_change_frontier r = stage::bind_change(base, R, tot);
     rc = halda_solve_change(ctx, model, &d, &di, k, &dc, &r, s);
     if (rc == HALDA_OK) rc = download(stage::change_copies(R, *fr_h), base, s);
@@ -3726,26 +3716,22 @@ int halda_solve_change_subsets_host(void *ctx, const halda_model *model, const h
     int rc = change_subsets_gate(model, th, th->dev_off, subsets->w0, k, subsets, fh, Q);
     if (rc != HALDA_OK) return rc;
     const size_t pts = size_t(nf) * size_t(subsets->max_drop - subsets->min_drop + 1) * size_t(subsets->max_p + 1);
-    const int32_t *bsrc[3] = {subsets->w0, subsets->w_min, subsets->w_max};
     stage::Bump lay;
     const stage::TableLayout T = stage::lay_table(lay, nf, nd);
-    size_t o_b[3];
-    for (int a = 0; a < 3; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nd) : 0;
+    const stage::TripleLayout B = stage::lay_triple(lay, subsets->w0, subsets->w_min, subsets->w_max, nd);
     const stage::ChangeSubsetSlots R = stage::lay_change_subsets(lay, pts);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     rc = ensure_scratch(c, lay.off);
     char *base = static_cast<char *>(c->scratch);
     if (rc == HALDA_OK) rc = upload(base, T, *th, s);
-    for (int a = 0; a < 3 && rc == HALDA_OK; ++a)
-        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nd, s);
+    if (rc == HALDA_OK) rc = upload(base, B, s);
     if (rc != HALDA_OK) return rc;
     const halda_fleets d = stage::rebase(*th, base, T);
     halda_change_subsets dc = *subsets;
-    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
-    dc.w0 = bdev(0);
-    dc.w_min = bdev(1);
-    dc.w_max = bdev(2);
+    dc.w0 = B.at(base, 0);
+    dc.w_min = B.at(base, 1);
+    dc.w_max = B.at(base, 2);
     halda_change_subset_frontier r = stage::bind_change_subsets(base, R);
     rc = solve_change_subsets(ctx, model, &d, k, &dc, &r, Q, s);
     if (rc == HALDA_OK) rc = download(stage::change_subsets_copies(R, *fh), base, s);

@@ -73,6 +73,42 @@ inline halda_fleets shifted(const halda_fleets &F, int64_t d0) {
     return s;
 }
 
+// The arrays of a halda_subfleets of n items / tot = sub_off[n] listed devices in a staging buffer.
+struct ItemsLayout {
+    int64_t n, tot;
+    size_t parent, sub_off, sub_idx;
+};
+
+inline ItemsLayout lay_items(Bump &b, int64_t n, int64_t tot) {
+    return {n, tot, b.take(4 * n), b.take(8 * (n + 1)), b.take(4 * tot)};
+}
+
+// I with its arrays at `base` + the layout's offsets (the scalar members copied).
+inline halda_subfleets rebase(const halda_subfleets &I, const char *base, const ItemsLayout &t) {
+    halda_subfleets d = I;
+    d.parent = reinterpret_cast<const int32_t *>(base + t.parent);
+    d.sub_off = reinterpret_cast<const int64_t *>(base + t.sub_off);
+    d.sub_idx = reinterpret_cast<const int32_t *>(base + t.sub_idx);
+    return d;
+}
+
+// The per-device int32 inputs of a frontier call -- w0, w_min, w_max, `count` entries each -- in a staging
+// buffer: an array the host did not pass takes no room and stays NULL on the device.
+struct TripleLayout {
+    int64_t count;
+    const int32_t *host[3];
+    size_t off[3];
+    const int32_t *at(const char *base, int a) const {
+        return host[a] ? reinterpret_cast<const int32_t *>(base + off[a]) : nullptr;
+    }
+};
+
+inline TripleLayout lay_triple(Bump &b, const int32_t *w0, const int32_t *w_min, const int32_t *w_max, int64_t count) {
+    TripleLayout t{count, {w0, w_min, w_max}, {0, 0, 0}};
+    for (int a = 0; a < 3; ++a) t.off[a] = t.host[a] ? b.take(4 * count) : 0;
+    return t;
+}
+
 // Doubles that x (and c) hold. Row r has off[r + 1] - off[r] devices (dev_off, or the items' sub_off), and
 // the slot of (repeat v, row r, k index j) is (v * n_rows + r) * n_k + j: n_repeat the variants (else 1),
 // n_k = 1 for the plan evaluation's one slot per fleet. Without x_off the dense layout, stride

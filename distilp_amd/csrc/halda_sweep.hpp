@@ -2269,10 +2269,9 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bo
 // devices, so it is not a narrowing of column bounds. Both plans sum to W, hence sum |delta| = 2 sum delta+;
 // the solver works in p = sum_i max(0, w_i - w0_i) with P = B / 2 and answers every budget p = 0 .. P at once.
 // Only w_i in [w0_i - P, w0_i + P] can matter: the tables G / H are built on that window by table_pass
-// (rows of at most 2 P + 1 entries), and a DP over the devices carries the state (d, p): d the net deviation
-// of the devices so far, p the sum of their positive deviations, valid while the sum of the negative ones,
-// p - d, is in [0, P]. k > 1 scans the cycle-time thresholds T pass by pass (DESIGN.md section 2's exact scan
-// in its pass-per-candidate form: nothing is assumed of the rows' shape).
+// (rows of at most 2 P + 1 entries), and the frontier DP below carries the layers released and loaded so far
+// (both end at p). k > 1 scans the cycle-time thresholds T pass by pass (DESIGN.md section 2's exact scan in
+// its pass-per-candidate form: nothing is assumed of the rows' shape).
 struct BudgetArgs {
     const int32_t *w0, *w_min, *w_max;  // device layout; w_min / w_max may be NULL
     int P;                              // halda_budget.max_p
@@ -2283,18 +2282,46 @@ struct BudgetArgs {
     int32_t *w, *n;                     // [P + 1][nd]
 };
 
-// The wave's LDS slice (bytes): G and, for k > 1, H as mmax rows of 2 P + 1 doubles (an odd stride); two
-// value planes of S = (2 P + 1)(P + 1) doubles; one arg-min byte plane of S per device; per device wlo - w0;
-// per point the plan's table indices (bytes) and its n (ints).
-struct BudgetSlice {
+// ---------------------------------------------------------------- a changed fleet (halda_solve_change)
+// Re-placement after a device is lost or joins. An item is a sub-fleet of a parent fleet (SubArgs: the listed
+// devices in list order) with the layers each listed device holds now, w0_i >= 0 (0: a joiner). The deficit
+// D = W - sum w0 >= 0 is what the lost devices held. With delta_i = w_i - w0_i, loaded = sum max(0, delta)
+// and released = sum max(0, -delta), every plan has loaded = D + released; point p of the frontier is the
+// optimum of the list's fixed-k problem over the plans with released <= p. Only w_i in
+// [w0_i - P, w0_i + D + P] can matter: G / H are built on that window by table_pass (rows of at most
+// 2 P + D + 1 entries), and the frontier DP below carries the state (r, l): r the layers released so far,
+// in [0, P], l the layers loaded so far, in [0, D + P]. The exact-p answers are the final states (p, D + p).
+// With D = 0 and every w0_i >= 1 this is the budget problem, solved by the same body: hence its bits.
+struct ChangeArgs {
+    SubArgs S;                          // the items; A.F is the parent table with n_fleets = the item count
+    const int32_t *w0, *w_min, *w_max;  // laid out by sub_off; w_min / w_max may be NULL
+    int P, Dmax;                        // halda_change.max_p / max_deficit
+    int64_t nd;                         // sub_off[n_items]: the stride of the w / n planes
+    int32_t *status;                    // [item][P + 1]
+    double *obj;                        // [item][P + 1]
+    int32_t *loaded, *released;         // [item][P + 1]
+    int32_t *w, *n;                     // [P + 1][nd]
+};
+
+// ---------------------------------------------------------------- the frontier body of both kernels
+// Both problems are one: devices that hold w0_i layers, a deficit D >= 0 of layers nobody holds (0 under a
+// move budget), and per point p the best plan that releases at most p layers (and so loads at most D + p).
+// frontier_item solves one fleet or item; a job (BudgetJob, ChangeJob) supplies where a lane's device and
+// inputs are read, the incumbent rule and the deficit, how a state is laid out in the value plane, and the
+// integers a point reports. The two kernels differ in nothing else.
+//
+// The wave's LDS slice (bytes): G and, for k > 1, H as mmax rows of RS doubles (RS odd); two value planes of
+// S doubles; one arg-min byte plane of S per device; per device wlo - w0; per point the plan's table indices
+// (bytes) and its n (ints).
+struct FrontierSlice {
     int64_t G, H, V, arg, off, plan, nplan, total;
     int S, RS;
 };
 
-__host__ __device__ inline BudgetSlice budget_slice(int mmax, int P, bool kc) {
-    BudgetSlice s;
-    s.RS = 2 * P + 1;
-    s.S = (2 * P + 1) * (P + 1);
+__host__ __device__ inline FrontierSlice frontier_slice(int mmax, int P, int RS, int S, bool kc) {
+    FrontierSlice s;
+    s.RS = RS;
+    s.S = S;
     int64_t o = 0;
     s.G = o;     o = align16(o + int64_t(mmax) * s.RS * 8);
     s.H = o;     o = align16(o + (kc ? int64_t(mmax) * s.RS * 8 : 0));
@@ -2307,7 +2334,17 @@ __host__ __device__ inline BudgetSlice budget_slice(int mmax, int P, bool kc) {
     return s;
 }
 
-struct BudgetCtx {
+// The budget kernel's: rows of 2 P + 1 entries, S = (2 P + 1)(P + 1) states (BudgetMap).
+__host__ __device__ inline FrontierSlice budget_slice(int mmax, int P, bool kc) {
+    return frontier_slice(mmax, P, 2 * P + 1, (2 * P + 1) * (P + 1), kc);
+}
+
+// The change kernel's: rows of (2 P + Dmax + 1) | 1 entries, S = (P + 1)(Dmax + P + 1) states (ChangeMap).
+__host__ __device__ inline FrontierSlice change_slice(int mmax, int P, int Dmax, bool kc) {
+    return frontier_slice(mmax, P, (2 * P + Dmax + 1) | 1, (P + 1) * (Dmax + P + 1), kc);
+}
+
+struct FrontierCtx {
     double *V;       // two planes of S
     uint8_t *arg;    // [device][S]
     int *off;        // [device] wlo - w0
@@ -2316,32 +2353,82 @@ struct BudgetCtx {
     int S, RS, P, mmax;
 };
 
-constexpr uint8_t kBudgetNone = 255;  // arg-min of a state no transition reaches (2 P <= 126 < 255)
+// The kernels' slice binding: w.G / w.H and the frontier's own regions.
+__device__ inline FrontierCtx frontier_ctx(unsigned char *smem, const FrontierSlice &sl, int P, int mmax, WaveCtx &w) {
+    w.G = reinterpret_cast<double *>(smem + sl.G);
+    w.H = reinterpret_cast<double *>(smem + sl.H);
+    FrontierCtx c;
+    c.V = reinterpret_cast<double *>(smem + sl.V);
+    c.arg = smem + sl.arg;
+    c.off = reinterpret_cast<int *>(smem + sl.off);
+    c.plan = smem + sl.plan;
+    c.nplan = reinterpret_cast<int *>(smem + sl.nplan);
+    c.S = sl.S;
+    c.RS = sl.RS;
+    c.P = P;
+    c.mmax = mmax;
+    return c;
+}
 
-// One budget DP over the M devices with the entries H > T masked (kc == 0: no mask). Lanes own states; a
-// transition tries the device's R1 entries in ascending order and keeps the first least value (strict "<":
-// the least w_i). Returns the plane that holds F_M; arg holds every device's arg-min plane.
-__device__ inline const double *budget_dp(const WaveCtx &w, const BudgetCtx &b, int M, int R1, double kc, double T,
-                                          int lane) {
-    const int P = b.P, P1 = b.P + 1, S = b.S;
-    double *cur = b.V, *nxt = b.V + S;
-    for (int s = lane; s < S; s += 64) cur[s] = s == P * P1 ? 0.0 : kInf;
+constexpr uint8_t kFrontierNone = 255;  // arg-min of a state no transition reaches (an entry is at most 254)
+
+// How a state (r released, l loaded) lies in a value plane. The budget kernel's plane is indexed by the net
+// deviation l - r in [-P, P] and l in [0, P]: of its (2 P + 1)(P + 1) slots those with r outside [0, P] hold
+// no state. (Its slice, and with it the gate and the occupancy, rest on that plane.)
+struct BudgetMap {
+    int P, P1;
+    __device__ int count() const { return (2 * P + 1) * P1; }
+    __device__ bool decode(int s, int &r, int &l) const {
+        const int dq = s / P1;
+        l = s - dq * P1;
+        r = l - (dq - P);
+        return r >= 0 && r <= P;
+    }
+    __device__ int at(int r, int l) const { return (l - r + P) * P1 + l; }
+    __device__ int start() const { return P * P1; }
+    __device__ int final(int p) const { return P * P1 + p; }
+};
+
+// The change kernel's plane: r in [0, P] by l in [0, D + P], LQ = D + P + 1 the item's own row length
+// (LQ (P + 1) <= S). Every slot is a state.
+struct ChangeMap {
+    int P, LQ, D;
+    __device__ int count() const { return (P + 1) * LQ; }
+    __device__ bool decode(int s, int &r, int &l) const {
+        r = s / LQ;
+        l = s - r * LQ;
+        return true;
+    }
+    __device__ int at(int r, int l) const { return r * LQ + l; }
+    __device__ int start() const { return 0; }
+    __device__ int final(int p) const { return p * LQ + D + p; }
+};
+
+// One DP over the M devices with the entries H > T masked (kc == 0: no mask). Lanes own states; a transition
+// tries the device's R1 entries in ascending order and keeps the first least value (strict "<": the least
+// w_i). Returns the plane that holds the values after the last device; arg holds every device's arg-min plane.
+template <class Map>
+__device__ inline const double *frontier_dp(const WaveCtx &w, const FrontierCtx &c, const Map &m, int M, int R1,
+                                            double kc, double T, int lane) {
+    const int Sn = m.count(), s0 = m.start();
+    double *cur = c.V, *nxt = c.V + c.S;
+    for (int s = lane; s < Sn; s += 64) cur[s] = s == s0 ? 0.0 : kInf;
     wave_sync();
     for (int i = 0; i < M; ++i) {
-        const int oi = b.off[i];
-        const double *Gi = w.G + i * b.RS, *Hi = w.H + i * b.RS;
-        uint8_t *ai = b.arg + int64_t(i) * S;
-        for (int s = lane; s < S; s += 64) {
-            const int dq = s / P1, p = s - dq * P1, d = dq - P, q = p - d;
+        const int oi = c.off[i];
+        const double *Gi = w.G + i * c.RS, *Hi = w.H + i * c.RS;
+        uint8_t *ai = c.arg + int64_t(i) * c.S;
+        for (int s = lane; s < Sn; s += 64) {
+            int r, l;
             double best = kInf;
-            int be = kBudgetNone;
-            if (q >= 0 && q <= P) {
+            int be = kFrontierNone;
+            if (m.decode(s, r, l)) {
                 for (int e = 0; e < R1; ++e) {
                     const int delta = oi + e;
-                    const int pp = p - max(0, delta), qp = q - max(0, -delta);
-                    if (pp < 0 || qp < 0) continue;
+                    const int lp = l - max(0, delta), rp = r - max(0, -delta);
+                    if (lp < 0 || rp < 0) continue;
                     if (kc > 0.0 && !(Hi[e] <= T)) continue;
-                    const double v = cur[(pp - qp + P) * P1 + pp] + Gi[e];
+                    const double v = cur[m.at(rp, lp)] + Gi[e];
                     if (v < best) {
                         best = v;
                         be = e;
@@ -2359,318 +2446,14 @@ __device__ inline const double *budget_dp(const WaveCtx &w, const BudgetCtx &b, 
     return cur;
 }
 
-// The plan of point p (lane p) with a finite F_M[0][p]: from state (d = 0, p) after the last device back to
-// (0, 0). Every state on that path has a finite value, so its arg-min is an entry of the row and the
-// predecessor it names is a valid state.
-__device__ inline void budget_backtrack(const BudgetCtx &b, int M, int p) {
-    const int P = b.P, P1 = b.P + 1;
-    int d = 0, pc = p;
-    for (int i = M - 1; i >= 0; --i) {
-        const int e = b.arg[int64_t(i) * b.S + (d + P) * P1 + pc];
-        b.plan[p * b.mmax + i] = uint8_t(e);
-        const int delta = b.off[i] + e;
-        d -= delta;
-        pc -= max(0, delta);
-    }
-}
-
-__device__ inline void sweep_fleet_budget(const SweepArgs &A, const BudgetArgs &Bg, int f, const WaveCtx &w,
-                                          const BudgetCtx &b, const Wave &sg) {
-    const int lane = sg.sl;
-    const int P = Bg.P, P1 = P + 1;
-    const int k = A.ks[0], W = A.Ws[0];
-    const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
-    const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
-    const bool act = lane < M;
-    const bool pt = lane < P1;
-    const int64_t g0 = d0 + (act ? lane : 0);
-    const DevFields mf = load_fields(A.F, g0);
-    const int wmn = Bg.w_min ? Bg.w_min[g0] : 0;
-    const int wmx = Bg.w_max ? Bg.w_max[g0] : 0x7fffffff;
-    const int w0 = min(max(Bg.w0[g0], -kBoundCap), kBoundCap);
-    BoundRec me = {};
-    int bad = 0;
-    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
-    bad = act ? bad : 0;
-    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
-    fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
-    bad = sg.any(bad != 0) ? 1 : 0;
-    const int lo = min(max(1, wmn), kBoundCap);
-    const int sumlo = sg.sum_i(act ? lo : 0);
-    const int sumw0 = sg.sum_i(act ? w0 : 0);
-    const bool w0bad = sg.any(act && w0 < 1) || sumw0 != W;  // the host entries reject it before the launch
-    // the window: only w_i within P of w0_i can matter
-    const int wlo = max(lo, w0 - P), whi = min(min(W, wmx), w0 + P);
-    const int sumwlo = sg.sum_i(act ? min(wlo, kBoundCap) : 0);
-    constexpr int kOpen = 1000;
-    int st = kOpen;
-    if (!(W < 1000000)) st = HALDA_STATUS_UNSUPPORTED;
-    else if (sumlo > W) st = HALDA_STATUS_INFEASIBLE;
-    else if (bad || w0bad) st = HALDA_STATUS_UNSUPPORTED;
-    else if (sumwlo > W) st = HALDA_STATUS_INFEASIBLE;  // the budget cannot reach the box
-    const int64_t fo = int64_t(f) * P1;
-    if (st != kOpen) {
-        if (pt) {
-            Bg.status[fo + lane] = st;
-            Bg.obj[fo + lane] = kInf;
-            Bg.moved[fo + lane] = 0;
-        }
-        if (act)
-            for (int p = 0; p < P1; ++p) {
-                Bg.w[int64_t(p) * Bg.nd + d0 + lane] = 0;
-                Bg.n[int64_t(p) * Bg.nd + d0 + lane] = 0;
-            }
-        return;
-    }
-    opaque_rec(me);
-    const double kc = double(k - 1);
-    me.W = W;
-    me.wlo = wlo;
-    me.whi = whi;
-    if (act) b.off[lane] = wlo - w0;
-    Inst I = {};
-    I.inst = f;
-    I.M = M;
-    I.W = W;
-    I.Wd = double(W);
-    I.kc = kc;
-    I.iC = 7 * M;
-    I.R1 = min(W - sumwlo, 2 * P) + 1;
-    I.RS = b.RS;
-    const int R1 = I.R1;
-    table_pass<64>(bound_src(&me), w, I, lane);
-    wave_sync();
-    // best[p] (lane p): the least (k - 1) T + F^T_M[0][p] and the T that gave it
-    double best = kInf, bT = kInf;
-    if (kc == 0.0) {
-        const double *F = budget_dp(w, b, M, R1, 0.0, kInf, lane);
-        if (pt) best = F[P * P1 + lane];
-        wave_sync();
-        if (pt && best < kInf) budget_backtrack(b, M, lane);
-    } else {
-        const double *F = budget_dp(w, b, M, R1, 0.0, kInf, lane);
-        const double sinf = pt ? F[P * P1 + lane] : kInf;
-        // the first threshold that leaves every device an entry: max_i min_e H_i[e]
-        double hmin = kInf;
-        if (act)
-            for (int e = 0; e < R1; ++e) hmin = fmin(hmin, w.H[lane * b.RS + e]);
-        double T = sg.max_f64(act ? hmin : 0.0);
-        while (T < kInf) {
-            // point p is closed once (k - 1) T + S_inf[p] >= best[p]; the scan stops when every point is
-            if (!sg.any(pt && !(kc * T + sinf >= best))) break;
-            wave_sync();
-            F = budget_dp(w, b, M, R1, kc, T, lane);
-            if (pt) {
-                const double c = kc * T + F[P * P1 + lane];
-                if (c < best) {  // strict: the earliest T wins
-                    best = c;
-                    bT = T;
-                }
-            }
-            double nx = kInf;  // the next distinct finite H above T
-            for (int t = lane; t < M * R1; t += 64) {
-                const int i = t / R1, e = t - i * R1;
-                const double h = w.H[i * b.RS + e];
-                if (h > T) nx = fmin(nx, h);
-            }
-            T = sg.min_f64(nx);
-        }
-        // the arg-min planes of each distinct winning T, once, for the points it won
-        bool left = pt && best < kInf;
-        while (sg.any(left)) {
-            const double Tw = sg.min_f64(left ? bT : kInf);
-            wave_sync();
-            budget_dp(w, b, M, R1, kc, Tw, lane);
-            if (left && bT == Tw) {
-                budget_backtrack(b, M, lane);
-                left = false;
-            }
-        }
-    }
-    wave_sync();
-    // price every exact-p plan lane-per-device, the constants added in sweep_fleet's order
-    double objv = kInf;
-    int movedv = 0;
-    for (int p = 0; p < P1; ++p) {
-        if (!(sg.bcast(best, p) < kInf)) continue;
-        double gd = 0.0, H = 0.0;
-        int wl = 0, n = 0;
-        if (act) {
-            wl = wlo + b.plan[p * b.mmax + lane];
-            double Pc, Qc;
-            int sl[4] = {0, 0, 0, 0};
-            split_full(me, wl, gd, n, sl);
-            dev_cycle(me, wl, n, sl, Pc, Qc);
-            H = fmax(0.0, Qc >= Pc ? 0.5 * (Pc + Qc) : Pc);
-            b.nplan[p * b.mmax + lane] = n;
-        }
-        const double hmax = sg.max_f64(act ? H : 0.0);
-        double obj = sg.sum_f64(act ? gd : 0.0) + kc * hmax;
-        obj = obj + tsum;
-        obj = obj + xsum;
-        obj = obj + kappa;
-        const int mv = sg.sum_i(act ? abs(wl - w0) : 0);
-        if (lane == p) {
-            objv = obj;
-            movedv = mv;
-        }
-    }
-    wave_sync();
-    // point p: the best exact point p' <= p, the fewest moves among equal objectives (strict "<", ascending)
-    double run = kInf;
-    int src = -1, runmv = 0;
-    for (int p = 0; p < P1; ++p) {
-        const double o = sg.bcast(objv, p);
-        const int mv = sg.bcast(movedv, p);
-        if (lane >= p && o < run) {
-            run = o;
-            src = p;
-            runmv = mv;
-        }
-    }
-    if (pt) {
-        Bg.status[fo + lane] = src >= 0 ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
-        Bg.obj[fo + lane] = run;
-        Bg.moved[fo + lane] = runmv;
-    }
-    for (int p = 0; p < P1; ++p) {
-        const int sp = sg.bcast(src, p);
-        if (act) {
-            Bg.w[int64_t(p) * Bg.nd + d0 + lane] = sp >= 0 ? wlo + b.plan[sp * b.mmax + lane] : 0;
-            Bg.n[int64_t(p) * Bg.nd + d0 + lane] = sp >= 0 ? b.nplan[sp * b.mmax + lane] : 0;
-        }
-    }
-    wave_sync();  // the slice is rewritten by the wave's next fleet
-}
-
-// halda_sweep_budget_kernel: one wave per fleet in 64-thread workgroups on a persistent grid, each with its
-// dynamic LDS slice (budget_slice of the launch's shape); workgroup b takes fleets b, b + grid, .... No
-// spin-wait and nothing shared between waves: the only synchronisation is wave_sync within the one wave.
-__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_budget_kernel(SweepArgs A,
-                                                                                           BudgetArgs Bg) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x;
-    const BudgetSlice sl = budget_slice(A.mmax, Bg.P, A.ks[0] > 1);
-    WaveCtx w = {};
-    w.G = reinterpret_cast<double *>(smem + sl.G);
-    w.H = reinterpret_cast<double *>(smem + sl.H);
-    BudgetCtx b;
-    b.V = reinterpret_cast<double *>(smem + sl.V);
-    b.arg = smem + sl.arg;
-    b.off = reinterpret_cast<int *>(smem + sl.off);
-    b.plan = smem + sl.plan;
-    b.nplan = reinterpret_cast<int *>(smem + sl.nplan);
-    b.S = sl.S;
-    b.RS = sl.RS;
-    b.P = Bg.P;
-    b.mmax = A.mmax;
-    const int nf = A.F.n_fleets;
-    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) sweep_fleet_budget(A, Bg, int(f), w, b, Wave(lane));
-}
-
-// ---------------------------------------------------------------- a changed fleet (halda_solve_change)
-// Re-placement after a device is lost or joins. An item is a sub-fleet of a parent fleet (SubArgs: the listed
-// devices in list order) with the layers each listed device holds now, w0_i >= 0 (0: a joiner). The deficit
-// D = W - sum w0 >= 0 is what the lost devices held. With delta_i = w_i - w0_i, loaded = sum max(0, delta)
-// and released = sum max(0, -delta), every plan has loaded = D + released; point p of the frontier is the
-// optimum of the list's fixed-k problem over the plans with released <= p. Only w_i in
-// [w0_i - P, w0_i + D + P] can matter: G / H are built on that window by table_pass (rows of at most
-// 2 P + D + 1 entries), and the DP over the devices carries the state (r, l): r the layers released so far,
-// in [0, P], l the layers loaded so far, in [0, D + P]. The exact-p answers are the final states (p, D + p).
-// With D = 0 and every w0_i >= 1 states, transitions and their order are the budget kernel's, hence its bits.
-struct ChangeArgs {
-    SubArgs S;                          // the items; A.F is the parent table with n_fleets = the item count
-    const int32_t *w0, *w_min, *w_max;  // laid out by sub_off; w_min / w_max may be NULL
-    int P, Dmax;                        // halda_change.max_p / max_deficit
-    int64_t nd;                         // sub_off[n_items]: the stride of the w / n planes
-    int32_t *status;                    // [item][P + 1]
-    double *obj;                        // [item][P + 1]
-    int32_t *loaded, *released;         // [item][P + 1]
-    int32_t *w, *n;                     // [P + 1][nd]
-};
-
-// The wave's LDS slice (bytes): G and, for k > 1, H as mmax rows of RS doubles, RS the odd number
-// (2 P + Dmax + 1) | 1; two value planes of S = (P + 1)(Dmax + P + 1) doubles; one arg-min byte plane of S
-// per device; per device wlo - w0; per point the plan's table indices (bytes) and its n (ints).
-struct ChangeSlice {
-    int64_t G, H, V, arg, off, plan, nplan, total;
-    int S, RS;
-};
-
-__host__ __device__ inline ChangeSlice change_slice(int mmax, int P, int Dmax, bool kc) {
-    ChangeSlice s;
-    s.RS = (2 * P + Dmax + 1) | 1;
-    s.S = (P + 1) * (Dmax + P + 1);
-    int64_t o = 0;
-    s.G = o;     o = align16(o + int64_t(mmax) * s.RS * 8);
-    s.H = o;     o = align16(o + (kc ? int64_t(mmax) * s.RS * 8 : 0));
-    s.V = o;     o = align16(o + 2 * int64_t(s.S) * 8);
-    s.arg = o;   o = align16(o + int64_t(mmax) * s.S);
-    s.off = o;   o = align16(o + int64_t(mmax) * 4);
-    s.plan = o;  o = align16(o + int64_t(P + 1) * mmax);
-    s.nplan = o; o = align16(o + int64_t(P + 1) * mmax * 4);
-    s.total = o;
-    return s;
-}
-
-struct ChangeCtx {
-    double *V;       // two planes of S
-    uint8_t *arg;    // [device][S]
-    int *off;        // [device] wlo - w0
-    uint8_t *plan;   // [point][mmax]
-    int *nplan;      // [point][mmax]
-    int S, RS, P, mmax;
-};
-
-constexpr uint8_t kChangeNone = 255;  // arg-min of a state no transition reaches (2 P + Dmax <= 254 < 255)
-
-// One DP over the item's M devices with the entries H > T masked (kc == 0: no mask). The item's states are
-// s = r * LQ + l, LQ = D + P + 1 (the item's own D: LQ (P + 1) <= S). Lanes own states; a transition tries
-// the device's R1 entries in ascending order and keeps the first least value (strict "<": the least w_i).
-// Returns the plane that holds the values after the last device; arg holds every device's arg-min plane.
-__device__ inline const double *change_dp(const WaveCtx &w, const ChangeCtx &c, int M, int R1, int LQ, double kc,
-                                          double T, int lane) {
-    const int Sn = (c.P + 1) * LQ;
-    double *cur = c.V, *nxt = c.V + c.S;
-    for (int s = lane; s < Sn; s += 64) cur[s] = s == 0 ? 0.0 : kInf;
-    wave_sync();
-    for (int i = 0; i < M; ++i) {
-        const int oi = c.off[i];
-        const double *Gi = w.G + i * c.RS, *Hi = w.H + i * c.RS;
-        uint8_t *ai = c.arg + int64_t(i) * c.S;
-        for (int s = lane; s < Sn; s += 64) {
-            const int r = s / LQ, l = s - r * LQ;
-            double best = kInf;
-            int be = kChangeNone;
-            for (int e = 0; e < R1; ++e) {
-                const int delta = oi + e;
-                const int lp = l - max(0, delta), rp = r - max(0, -delta);
-                if (lp < 0 || rp < 0) continue;
-                if (kc > 0.0 && !(Hi[e] <= T)) continue;
-                const double v = cur[rp * LQ + lp] + Gi[e];
-                if (v < best) {
-                    best = v;
-                    be = e;
-                }
-            }
-            nxt[s] = best;
-            ai[s] = uint8_t(be);
-        }
-        wave_sync();
-        double *t = cur;
-        cur = nxt;
-        nxt = t;
-    }
-    return cur;
-}
-
 // The plan of point p (lane p) with a finite final value: from state (p, D + p) after the last device back
 // to (0, 0). Every state on that path has a finite value, so its arg-min is an entry of the row and the
 // predecessor it names is a valid state.
-__device__ inline void change_backtrack(const ChangeCtx &c, int M, int LQ, int D, int p) {
+template <class Map>
+__device__ inline void frontier_backtrack(const FrontierCtx &c, const Map &m, int M, int D, int p) {
     int r = p, l = D + p;
     for (int i = M - 1; i >= 0; --i) {
-        const int e = c.arg[int64_t(i) * c.S + r * LQ + l];
+        const int e = c.arg[int64_t(i) * c.S + m.at(r, l)];
         c.plan[p * c.mmax + i] = uint8_t(e);
         const int delta = c.off[i] + e;
         l -= max(0, delta);
@@ -2678,23 +2461,75 @@ __device__ inline void change_backtrack(const ChangeCtx &c, int M, int LQ, int D
     }
 }
 
-__device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &Cg, int it, const WaveCtx &w,
-                                         const ChangeCtx &c, const Wave &sg) {
+// What a lane of an item reads and writes: the item's length, its device in the table, its entry of w0 /
+// w_min / w_max and its entry of a w / n plane (lanes past M read the first device's and write nothing).
+struct FrontierLane {
+    int M;
+    int64_t dev, in, out;
+};
+
+// A move budget: item f is fleet f of the table, every array in device layout; the incumbent is a plan
+// (w0_i >= 1, sum w0 = W), so nothing is orphaned; a point reports moved = sum |w - w0|.
+struct BudgetJob {
+    using Args = BudgetArgs;
+    using Map = BudgetMap;
+    __device__ static FrontierLane lane_of(const SweepArgs &A, const Args &, int f, int lane) {
+        // the fleet's extent through the scalar cache (dev_off is read-only to the kernel)
+        const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
+        const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
+        const int64_t g0 = d0 + (lane < M ? lane : 0);
+        return {M, g0, g0, d0 + lane};
+    }
+    __device__ static bool bad_w0(const Args &, const Wave &sg, bool act, int w0, int sumw0, int W) {
+        return sg.any(act && w0 < 1) || sumw0 != W;
+    }
+    __device__ static int deficit(bool, int, int) { return 0; }
+    __device__ static Map map(int P, int) { return {P, P + 1}; }
+    __device__ static int count(int w0, int wl) { return abs(wl - w0); }
+    __device__ static void report(const Args &J, int64_t at, bool, int, int moved) { J.moved[at] = moved; }
+};
+
+// A changed fleet: item `it` lists devices of its parent (lane j gathers the j-th: halda_sweep_subfleets_kernel's
+// index read), every array laid out by sub_off; w0_i >= 0 and the deficit D = W - sum w0 in [0, Dmax]; a point
+// reports released = sum max(0, w0 - w) and loaded = D + released.
+struct ChangeJob {
+    using Args = ChangeArgs;
+    using Map = ChangeMap;
+    __device__ static FrontierLane lane_of(const SweepArgs &A, const Args &J, int it, int lane) {
+        // the item's extent, parent and the parent's first device: wave-uniform reads through the scalar cache
+        const int64_t so = sload_i64(J.S.sub_off + it);
+        const int M = A.uM > 0 ? A.uM : int(sload_i64(J.S.sub_off + it + 1) - so);
+        const int64_t base = sload_i64(A.F.dev_off + sload_i32(J.S.parent + it));
+        const int64_t o0 = so + (lane < M ? lane : 0);
+        return {M, base + J.S.sub_idx[o0], o0, so + lane};
+    }
+    __device__ static bool bad_w0(const Args &J, const Wave &sg, bool act, int w0, int sumw0, int W) {
+        return sg.any(act && w0 < 0) || sumw0 > W || W - sumw0 > J.Dmax;
+    }
+    // 0 where the incumbent is rejected, so that nothing is formed from it
+    __device__ static int deficit(bool w0bad, int W, int sumw0) { return w0bad ? 0 : W - sumw0; }
+    __device__ static Map map(int P, int D) { return {P, D + P + 1, D}; }
+    __device__ static int count(int w0, int wl) { return max(0, w0 - wl); }
+    __device__ static void report(const Args &J, int64_t at, bool plan, int D, int released) {
+        J.loaded[at] = plan ? D + released : 0;
+        J.released[at] = released;
+    }
+};
+
+template <class Job>
+__device__ inline void frontier_item(const SweepArgs &A, const typename Job::Args &J, int it, const WaveCtx &w,
+                                     const FrontierCtx &c, const Wave &sg) {
     const int lane = sg.sl;
-    const int P = Cg.P, P1 = P + 1;
+    const int P = J.P, P1 = P + 1;
     const int k = A.ks[0], W = A.Ws[0];
-    // the item's extent, parent and the parent's first device: wave-uniform reads through the scalar cache
-    const int64_t so = sload_i64(Cg.S.sub_off + it);
-    const int M = A.uM > 0 ? A.uM : int(sload_i64(Cg.S.sub_off + it + 1) - so);
-    const int64_t base = sload_i64(A.F.dev_off + sload_i32(Cg.S.parent + it));
+    const FrontierLane at = Job::lane_of(A, J, it, lane);
+    const int M = at.M;
     const bool act = lane < M;
     const bool pt = lane < P1;
-    const int64_t o0 = so + (act ? lane : 0);
-    const int idx = Cg.S.sub_idx[o0];
-    const int wmn = Cg.w_min ? Cg.w_min[o0] : 0;
-    const int wmx = Cg.w_max ? Cg.w_max[o0] : 0x7fffffff;
-    const int w0 = min(max(Cg.w0[o0], -kBoundCap), kBoundCap);
-    const DevFields mf = load_fields(A.F, base + idx);
+    const int wmn = J.w_min ? J.w_min[at.in] : 0;
+    const int wmx = J.w_max ? J.w_max[at.in] : 0x7fffffff;
+    const int w0 = min(max(J.w0[at.in], -kBoundCap), kBoundCap);
+    const DevFields mf = load_fields(A.F, at.dev);
     BoundRec me = {};
     int bad = 0;
     static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
@@ -2705,9 +2540,8 @@ __device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &C
     const int lo = min(max(1, wmn), kBoundCap);
     const int sumlo = sg.sum_i(act ? lo : 0);
     const int sumw0 = sg.sum_i(act ? w0 : 0);
-    // the deficit; 0 where the incumbent is rejected, so that nothing below is formed from it
-    const bool w0bad = sg.any(act && w0 < 0) || sumw0 > W || W - sumw0 > Cg.Dmax;  // the host entries reject it
-    const int D = w0bad ? 0 : W - sumw0;
+    const bool w0bad = Job::bad_w0(J, sg, act, w0, sumw0, W);  // the host entries reject it before the launch
+    const int D = Job::deficit(w0bad, W, sumw0);
     // the window: a device gives up at most P layers and takes at most D + P
     const int wlo = max(lo, w0 - P), whi = min(min(W, wmx), w0 + D + P);
     const int sumwlo = sg.sum_i(act ? min(wlo, kBoundCap) : 0);
@@ -2720,15 +2554,14 @@ __device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &C
     const int64_t fo = int64_t(it) * P1;
     if (st != kOpen) {
         if (pt) {
-            Cg.status[fo + lane] = st;
-            Cg.obj[fo + lane] = kInf;
-            Cg.loaded[fo + lane] = 0;
-            Cg.released[fo + lane] = 0;
+            J.status[fo + lane] = st;
+            J.obj[fo + lane] = kInf;
+            Job::report(J, fo + lane, false, 0, 0);
         }
         if (act)
             for (int p = 0; p < P1; ++p) {
-                Cg.w[int64_t(p) * Cg.nd + so + lane] = 0;
-                Cg.n[int64_t(p) * Cg.nd + so + lane] = 0;
+                J.w[int64_t(p) * J.nd + at.out] = 0;
+                J.n[int64_t(p) * J.nd + at.out] = 0;
             }
         return;
     }
@@ -2747,19 +2580,20 @@ __device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &C
     I.iC = 7 * M;
     I.R1 = min(W - sumwlo, 2 * P + D) + 1;
     I.RS = c.RS;
-    const int R1 = I.R1, LQ = D + P + 1;
+    const int R1 = I.R1;
+    const typename Job::Map m = Job::map(P, D);
     table_pass<64>(bound_src(&me), w, I, lane);
     wave_sync();
-    // best[p] (lane p): the least (k - 1) T + F^T_M[p][D + p] and the T that gave it
+    // best[p] (lane p): the least (k - 1) T + F^T_M[final state of p] and the T that gave it
     double best = kInf, bT = kInf;
     if (kc == 0.0) {
-        const double *F = change_dp(w, c, M, R1, LQ, 0.0, kInf, lane);
-        if (pt) best = F[lane * LQ + D + lane];
+        const double *F = frontier_dp(w, c, m, M, R1, 0.0, kInf, lane);
+        if (pt) best = F[m.final(lane)];
         wave_sync();
-        if (pt && best < kInf) change_backtrack(c, M, LQ, D, lane);
+        if (pt && best < kInf) frontier_backtrack(c, m, M, D, lane);
     } else {
-        const double *F = change_dp(w, c, M, R1, LQ, 0.0, kInf, lane);
-        const double sinf = pt ? F[lane * LQ + D + lane] : kInf;
+        const double *F = frontier_dp(w, c, m, M, R1, 0.0, kInf, lane);
+        const double sinf = pt ? F[m.final(lane)] : kInf;
         // the first threshold that leaves every device an entry: max_i min_e H_i[e]
         double hmin = kInf;
         if (act)
@@ -2769,9 +2603,9 @@ __device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &C
             // point p is closed once (k - 1) T + S_inf[p] >= best[p]; the scan stops when every point is
             if (!sg.any(pt && !(kc * T + sinf >= best))) break;
             wave_sync();
-            F = change_dp(w, c, M, R1, LQ, kc, T, lane);
+            F = frontier_dp(w, c, m, M, R1, kc, T, lane);
             if (pt) {
-                const double v = kc * T + F[lane * LQ + D + lane];
+                const double v = kc * T + F[m.final(lane)];
                 if (v < best) {  // strict: the earliest T wins
                     best = v;
                     bT = T;
@@ -2790,9 +2624,9 @@ __device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &C
         while (sg.any(left)) {
             const double Tw = sg.min_f64(left ? bT : kInf);
             wave_sync();
-            change_dp(w, c, M, R1, LQ, kc, Tw, lane);
+            frontier_dp(w, c, m, M, R1, kc, Tw, lane);
             if (left && bT == Tw) {
-                change_backtrack(c, M, LQ, D, lane);
+                frontier_backtrack(c, m, M, D, lane);
                 left = false;
             }
         }
@@ -2800,7 +2634,7 @@ __device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &C
     wave_sync();
     // price every exact-p plan lane-per-device, the constants added in sweep_fleet's order
     double objv = kInf;
-    int relv = 0;
+    int cntv = 0;
     for (int p = 0; p < P1; ++p) {
         if (!(sg.bcast(best, p) < kInf)) continue;
         double gd = 0.0, H = 0.0;
@@ -2819,67 +2653,63 @@ __device__ inline void sweep_item_change(const SweepArgs &A, const ChangeArgs &C
         obj = obj + tsum;
         obj = obj + xsum;
         obj = obj + kappa;
-        const int rl = sg.sum_i(act ? max(0, w0 - wl) : 0);
+        const int cnt = sg.sum_i(act ? Job::count(w0, wl) : 0);
         if (lane == p) {
             objv = obj;
-            relv = rl;
+            cntv = cnt;
         }
     }
     wave_sync();
-    // point p: the best exact point p' <= p, the fewest released layers among equal objectives (strict "<",
-    // ascending)
+    // point p: the best exact point p' <= p, the fewest layers moved (released) among equal objectives (strict
+    // "<", ascending)
     double run = kInf;
-    int src = -1, runrl = 0;
+    int src = -1, runcnt = 0;
     for (int p = 0; p < P1; ++p) {
         const double o = sg.bcast(objv, p);
-        const int rl = sg.bcast(relv, p);
+        const int cnt = sg.bcast(cntv, p);
         if (lane >= p && o < run) {
             run = o;
             src = p;
-            runrl = rl;
+            runcnt = cnt;
         }
     }
     if (pt) {
-        Cg.status[fo + lane] = src >= 0 ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
-        Cg.obj[fo + lane] = run;
-        Cg.loaded[fo + lane] = src >= 0 ? D + runrl : 0;
-        Cg.released[fo + lane] = runrl;
+        J.status[fo + lane] = src >= 0 ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+        J.obj[fo + lane] = run;
+        Job::report(J, fo + lane, src >= 0, D, runcnt);
     }
     for (int p = 0; p < P1; ++p) {
         const int sp = sg.bcast(src, p);
         if (act) {
-            Cg.w[int64_t(p) * Cg.nd + so + lane] = sp >= 0 ? wlo + c.plan[sp * c.mmax + lane] : 0;
-            Cg.n[int64_t(p) * Cg.nd + so + lane] = sp >= 0 ? c.nplan[sp * c.mmax + lane] : 0;
+            J.w[int64_t(p) * J.nd + at.out] = sp >= 0 ? wlo + c.plan[sp * c.mmax + lane] : 0;
+            J.n[int64_t(p) * J.nd + at.out] = sp >= 0 ? c.nplan[sp * c.mmax + lane] : 0;
         }
     }
     wave_sync();  // the slice is rewritten by the wave's next item
 }
 
-// halda_sweep_change_kernel: the budget kernel's launch shape -- one wave per item in 64-thread workgroups on
-// a persistent grid, each with its dynamic LDS slice (change_slice of the launch's shape); workgroup b takes
-// items b, b + grid, .... Lane j gathers the item's j-th listed device from the parent table
-// (halda_sweep_subfleets_kernel's index read). No spin-wait, no atomics and nothing shared between waves:
-// the only synchronisation is wave_sync within the one wave.
+// halda_sweep_budget_kernel / halda_sweep_change_kernel: one wave per fleet (item) in 64-thread workgroups on a
+// persistent grid, each with its dynamic LDS slice (budget_slice / change_slice of the launch's shape);
+// workgroup b takes items b, b + grid, .... No spin-wait, no atomics and nothing shared between waves: the
+// only synchronisation is wave_sync within the one wave.
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_budget_kernel(SweepArgs A,
+                                                                                           BudgetArgs Bg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    WaveCtx w = {};
+    const FrontierCtx c = frontier_ctx(smem, budget_slice(A.mmax, Bg.P, A.ks[0] > 1), Bg.P, A.mmax, w);
+    const int nf = A.F.n_fleets;
+    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) frontier_item<BudgetJob>(A, Bg, int(f), w, c, Wave(lane));
+}
+
 __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_change_kernel(SweepArgs A,
                                                                                            ChangeArgs Cg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
-    const ChangeSlice sl = change_slice(A.mmax, Cg.P, Cg.Dmax, A.ks[0] > 1);
     WaveCtx w = {};
-    w.G = reinterpret_cast<double *>(smem + sl.G);
-    w.H = reinterpret_cast<double *>(smem + sl.H);
-    ChangeCtx c;
-    c.V = reinterpret_cast<double *>(smem + sl.V);
-    c.arg = smem + sl.arg;
-    c.off = reinterpret_cast<int *>(smem + sl.off);
-    c.plan = smem + sl.plan;
-    c.nplan = reinterpret_cast<int *>(smem + sl.nplan);
-    c.S = sl.S;
-    c.RS = sl.RS;
-    c.P = Cg.P;
-    c.mmax = A.mmax;
+    const FrontierCtx c = frontier_ctx(smem, change_slice(A.mmax, Cg.P, Cg.Dmax, A.ks[0] > 1), Cg.P, A.mmax, w);
     const int n = A.F.n_fleets;
-    for (int64_t it = blockIdx.x; it < n; it += gridDim.x) sweep_item_change(A, Cg, int(it), w, c, Wave(lane));
+    for (int64_t it = blockIdx.x; it < n; it += gridDim.x) frontier_item<ChangeJob>(A, Cg, int(it), w, c, Wave(lane));
 }
 
 // ---------------------------------------------------------------- scale-in / scale-out (halda_solve_change_subsets)

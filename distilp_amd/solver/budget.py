@@ -42,12 +42,11 @@ def _align16(x: int) -> int:
     return (x + 15) & ~15
 
 
-def budget_lds_bytes(max_devices: int, max_p: int, k: int) -> int:
-    """The LDS slice of one wave of halda_sweep_budget_kernel (csrc/halda_sweep.hpp budget_slice, the figure
-    halda_budget_lds_bytes returns): the tables G and, for k > 1, H as max_devices rows of 2 P + 1 doubles, two
-    value planes of S = (2 P + 1)(P + 1) doubles, one arg-min byte plane of S per device, and the plans."""
+def frontier_lds_bytes(max_devices: int, max_p: int, RS: int, S: int, k: int) -> int:
+    """The LDS slice of one wave of a frontier kernel (csrc/halda_sweep.hpp frontier_slice): the tables G and, for
+    k > 1, H as max_devices rows of RS doubles, two value planes of S doubles, one arg-min byte plane of S per
+    device, and the plans."""
     M, P = int(max_devices), int(max_p)
-    RS, S = 2 * P + 1, (2 * P + 1) * (P + 1)
     o = _align16(M * RS * 8)
     o = _align16(o + (M * RS * 8 if k > 1 else 0))
     o = _align16(o + 2 * S * 8)
@@ -56,6 +55,13 @@ def budget_lds_bytes(max_devices: int, max_p: int, k: int) -> int:
     o = _align16(o + (P + 1) * M)
     o = _align16(o + (P + 1) * M * 4)
     return o
+
+
+def budget_lds_bytes(max_devices: int, max_p: int, k: int) -> int:
+    """halda_sweep_budget_kernel's slice (budget_slice, the figure halda_budget_lds_bytes returns): rows of
+    2 P + 1 entries and S = (2 P + 1)(P + 1) states."""
+    P = int(max_p)
+    return frontier_lds_bytes(max_devices, P, 2 * P + 1, (2 * P + 1) * (P + 1), k)
 
 
 def check_gate(max_devices: int, min_devices: int, max_p: int, k: int) -> None:
@@ -124,6 +130,35 @@ class FrontierSolve:
     n: np.ndarray
     k: int
     max_p: int
+
+
+def distinct_plans(raw) -> List[tuple]:
+    """The (row, point) pairs of a kernel frontier that need a price. raw[row][p] is a tuple (w, n, ...) or None
+    (no plan); a point whose (w, n) is the previous point's shares its price."""
+    return [(i, p) for i, pts in enumerate(raw) for p, r in enumerate(pts)
+            if r is not None and (p == 0 or pts[p - 1] is None or pts[p - 1][:2] != r[:2])]
+
+
+def host_frontier(raw, need, objs) -> List[list]:
+    """Per row and point None (no plan) or (the point's tuple of raw, its obj_value), `objs` being the host-formed
+    objectives of the plans at `need` = distinct_plans(raw). The kernel's prefix-min orders the points by the
+    GPU-formed objective; two different plans within an ulp of each other can order the other way once re-formed
+    on the host, so the running minimum is taken here too: such a point keeps the previous point's plan, which
+    its budget also admits."""
+    slot = dict(zip(need, objs))
+    out = []
+    for i, pts in enumerate(raw):
+        row, obj = [], None
+        for p, r in enumerate(pts):
+            obj = slot.get((i, p), obj)
+            if r is None:
+                row.append(None)
+            elif row and row[-1] is not None and row[-1][1] < obj:
+                row.append(row[-1])
+            else:
+                row.append((r, obj))
+        out.append(row)
+    return out
 
 
 def solve_budget_table(table: FleetTable, model: ModelProfile, k: int, w0: np.ndarray, max_p: int,
@@ -199,8 +234,7 @@ def halda_move_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], model: 
     for k, fs in by_k.items():
         sizes = [len(fleets[f]) for f in fs]
         check_gate(max(sizes), min(sizes), P, k)
-    out: List[Optional[List[FrontierPoint]]] = [None] * len(fleets)
-    raw = {}  # fleet -> [(w, n, moved) or None per point]
+    raw: list = [None] * len(fleets)  # fleet -> [(w, n, moved) or None per point]
     for k, fs in sorted(by_k.items()):
         table = fleet_table([fleets[f] for f in fs], model)
         w0 = np.concatenate([np.asarray(plans[f][1], np.int32) for f in fs])
@@ -213,32 +247,21 @@ def halda_move_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], model: 
     # obj_value = c.x + sum t_comm + sum xi + kappa formed on the host as every entry of this package forms it:
     # the incumbents and every distinct returned plan priced in ONE evaluation call (so a point's obj_value is
     # halda_evaluate_plan's of its plan, bit for bit)
-    ev_fleets, ev_plans, slot = list(fleets), list(plans), {}
-    for f in range(len(fleets)):
-        for p, r in enumerate(raw[f]):
-            if r is not None and (p == 0 or raw[f][p - 1] is None or raw[f][p - 1][:2] != r[:2]):
-                slot[(f, p)] = len(ev_fleets)
-                ev_fleets.append(fleets[f])
-                ev_plans.append((plans[f][0], r[0], r[1]))
-    ev = halda_evaluate_plans_batch(ev_fleets, model, ev_plans, kv_bits, device)
-    for f in range(len(fleets)):
-        inc, k, sets, pts, at = ev[f], plans[f][0], assign_sets(fleets[f]), [], None
-        for p, r in enumerate(raw[f]):
-            if r is None:
+    need = distinct_plans(raw)
+    ev = halda_evaluate_plans_batch(fleets + [fleets[f] for f, _ in need], model,
+                                    plans + [(plans[f][0], *raw[f][p][:2]) for f, p in need], kv_bits, device)
+    rows = host_frontier(raw, need, [e.obj_value for e in ev[len(fleets):]])
+    out = []
+    for f, row in enumerate(rows):
+        inc, k, sets, pts = ev[f], plans[f][0], assign_sets(fleets[f]), []
+        for p, c in enumerate(row):
+            if c is None:
                 pts.append(FrontierPoint(2 * p, None, math.inf, 0, -math.inf if inc.feasible else math.inf))
                 continue
-            at = slot.get((f, p), at)
-            obj = ev[at].obj_value
-            # the kernel's prefix-min orders the points by the GPU-formed objective; two different plans within
-            # an ulp of each other can order the other way once re-formed here, so the running minimum is taken
-            # on the host too: such a point keeps the previous point's plan, which its budget also admits
-            if pts and pts[-1].plan is not None and pts[-1].obj_value < obj:
-                prev = pts[-1]
-                pts.append(FrontierPoint(2 * p, prev.plan, prev.obj_value, prev.moved_layers, prev.regret))
-                continue
-            plan = HALDAResult(w=r[0], n=r[1], k=k, obj_value=obj, sets=sets)
-            pts.append(FrontierPoint(2 * p, plan, obj, r[2], inc.obj_value - obj if inc.feasible else math.inf))
-        out[f] = pts
+            (w, n, moved), obj = c
+            plan = HALDAResult(w=w, n=n, k=k, obj_value=obj, sets=sets)
+            pts.append(FrontierPoint(2 * p, plan, obj, moved, inc.obj_value - obj if inc.feasible else math.inf))
+        out.append(pts)
     return out
 
 

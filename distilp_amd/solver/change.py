@@ -29,7 +29,7 @@ import numpy as np
 from ..common import DeviceProfile, ModelProfile
 from ._libhalda import STATUS_OPTIMAL, get_context, last_error
 from .bounds import INT32_MAX, check_bounds
-from .budget import check_incumbent
+from .budget import check_incumbent, distinct_plans, frontier_lds_bytes, host_frontier
 from .coefficients import HALDAResult, assign_sets
 from .fleets import (FleetTable, HaldaChangeC, HaldaChangeFrontierC, HaldaFleetsC, HaldaModelC, _bind, _host_struct,
                      fleet_table, model_struct)
@@ -45,24 +45,11 @@ MAX_ENTRY = 254          # 2 P + max_deficit: a table index is one byte, 255 mar
 Lost = Union[int, Sequence[int]]
 
 
-def _align16(x: int) -> int:
-    return (x + 15) & ~15
-
-
 def change_lds_bytes(max_devices: int, max_p: int, max_deficit: int, k: int) -> int:
-    """The LDS slice of one wave of halda_sweep_change_kernel (csrc/halda_sweep.hpp change_slice, the figure
-    halda_change_lds_bytes returns): G and, for k > 1, H as max_devices rows of RS = (2 P + Dmax + 1) | 1 doubles,
-    two value planes of S = (P + 1)(Dmax + P + 1) doubles, one arg-min byte plane of S per device, and the plans."""
-    M, P, D = int(max_devices), int(max_p), int(max_deficit)
-    RS, S = (2 * P + D + 1) | 1, (P + 1) * (D + P + 1)
-    o = _align16(M * RS * 8)
-    o = _align16(o + (M * RS * 8 if k > 1 else 0))
-    o = _align16(o + 2 * S * 8)
-    o = _align16(o + M * S)
-    o = _align16(o + M * 4)
-    o = _align16(o + (P + 1) * M)
-    o = _align16(o + (P + 1) * M * 4)
-    return o
+    """halda_sweep_change_kernel's slice (change_slice, the figure halda_change_lds_bytes returns): rows of
+    RS = (2 P + Dmax + 1) | 1 entries and S = (P + 1)(Dmax + P + 1) states."""
+    P, D = int(max_p), int(max_deficit)
+    return frontier_lds_bytes(max_devices, P, (2 * P + D + 1) | 1, (P + 1) * (D + P + 1), k)
 
 
 def check_gate(max_devices: int, min_devices: int, max_p: int, max_deficit: int, k: int) -> None:
@@ -263,33 +250,20 @@ def halda_change_frontiers(fleets: Sequence[Sequence[DeviceProfile]], model: Mod
     # obj_value formed on the host as every entry of this package forms it: every distinct returned plan priced
     # on its materialised list in ONE evaluation call
     lists = [[fleets[f][j] for j in s] for f, s in items]
-    ev_fleets, ev_plans, slot = [], [], {}
-    for i, pts in enumerate(raw):
-        for p, r in enumerate(pts):
-            if r is not None and (p == 0 or pts[p - 1] is None or pts[p - 1][:2] != r[:2]):
-                slot[(i, p)] = len(ev_fleets)
-                ev_fleets.append(lists[i])
-                ev_plans.append((k, r[0], r[1]))
-    ev = halda_evaluate_plans_batch(ev_fleets, model, ev_plans, kv_bits, device) if ev_fleets else []
+    need = distinct_plans(raw)
+    ev = halda_evaluate_plans_batch([lists[i] for i, _ in need], model, [(k, *raw[i][p][:2]) for i, p in need],
+                                    kv_bits, device) if need else []
     out = []
-    for i, rpts in enumerate(raw):
-        sets, pts, at = assign_sets(lists[i]), [], None
+    for i, row in enumerate(host_frontier(raw, need, [e.obj_value for e in ev])):
+        sets, pts = assign_sets(lists[i]), []
         base = free[i].obj_value if free[i] is not None else math.inf
-        for p, r in enumerate(rpts):
-            if r is None:
+        for p, c in enumerate(row):
+            if c is None:
                 pts.append(ChangePoint(p, None, math.inf, 0, 0, math.inf))
                 continue
-            at = slot.get((i, p), at)
-            obj = ev[at].obj_value
-            # the kernel's prefix-min orders the points by the GPU-formed objective; two different plans within
-            # an ulp of each other can order the other way once re-formed here, so the running minimum is taken
-            # on the host too: such a point keeps the previous point's plan, which its budget also admits
-            if pts and pts[-1].plan is not None and pts[-1].obj_value < obj:
-                prev = pts[-1]
-                pts.append(ChangePoint(p, prev.plan, prev.obj_value, prev.loaded, prev.released, prev.regret))
-                continue
-            plan = HALDAResult(w=r[0], n=r[1], k=k, obj_value=obj, sets=sets)
-            pts.append(ChangePoint(p, plan, obj, r[2], r[3], obj - base))
+            (w, n, loaded, released), obj = c
+            plan = HALDAResult(w=w, n=n, k=k, obj_value=obj, sets=sets)
+            pts.append(ChangePoint(p, plan, obj, loaded, released, obj - base))
         out.append(pts)
     return out
 

@@ -178,8 +178,61 @@ static void check_extent(const std::vector<int64_t> &sizes, int64_t n_k, int64_t
             }
 }
 
+// The items of the given list lengths: regions in order, 256-aligned, the total the sum of the rounded sizes;
+// rebasing keeps the scalar members.
+static void check_items(const std::vector<int64_t> &lens) {
+    const int64_t n = int64_t(lens.size());
+    int64_t tot = 0;
+    for (int64_t m : lens) tot += m;
+    stage::Bump b;
+    b.take(1);
+    const size_t start = b.off;
+    const stage::ItemsLayout t = stage::lay_items(b, n, tot);
+    CHECK(t.n == n && t.tot == tot);
+    CHECK(t.parent == start && t.sub_off == t.parent + up256(size_t(4 * n)));
+    CHECK(t.sub_idx == t.sub_off + up256(size_t(8 * (n + 1))) && b.off == t.sub_idx + up256(size_t(4 * tot)));
+    halda_subfleets I = {};
+    I.n_items = n;
+    I.min_devices = 1;
+    I.max_devices = 5;
+    std::vector<char> buf(b.off);
+    const halda_subfleets d = stage::rebase(I, buf.data(), t);
+    CHECK(d.n_items == n && d.min_devices == 1 && d.max_devices == 5);
+    CHECK(reinterpret_cast<const char *>(d.parent) == buf.data() + t.parent);
+    CHECK(reinterpret_cast<const char *>(d.sub_off) == buf.data() + t.sub_off);
+    CHECK(reinterpret_cast<const char *>(d.sub_idx) == buf.data() + t.sub_idx);
+}
+
+// w0 / w_min / w_max of `count` entries, each subset of them passed: an array that is not passed takes no
+// room and stays NULL; the others lie in order, 256-aligned.
+static void check_triple(int64_t count) {
+    std::vector<int32_t> a(size_t(count), 0);
+    for (int mask = 0; mask < 8; ++mask) {
+        const int32_t *src[3];
+        for (int i = 0; i < 3; ++i) src[i] = mask >> i & 1 ? a.data() : nullptr;
+        stage::Bump b;
+        b.take(1);
+        size_t want = b.off;
+        const stage::TripleLayout t = stage::lay_triple(b, src[0], src[1], src[2], count);
+        std::vector<char> buf(b.off);
+        CHECK(t.count == count);
+        for (int i = 0; i < 3; ++i) {
+            CHECK(t.host[i] == src[i]);
+            if (!src[i]) {
+                CHECK(t.at(buf.data(), i) == nullptr);
+                continue;
+            }
+            CHECK(t.off[i] == want && reinterpret_cast<const char *>(t.at(buf.data(), i)) == buf.data() + want);
+            want += up256(size_t(4 * count));
+        }
+        CHECK(b.off == want);
+    }
+}
+
 int main() {
     const std::vector<int64_t> ragged = {2, 3, 5}, one = {1};
+    for (const auto &lens : {ragged, one}) check_items(lens);
+    for (int64_t count : {1, 10, 64, 65}) check_triple(count);
     for (const auto &sizes : {ragged, one})
         for (int split : {stage::kFields, 10}) check_table(sizes, 3, split);
     for (const auto &sizes : {ragged, one}) {
