@@ -16,6 +16,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
+from ._abi import EXPORTS, PROTOTYPES, HaldaBatchC, HaldaResultC  # noqa: F401 -- EXPORTS: the binding's surface
+
 LIB_PATH = Path(os.environ.get("HALDA_LIB", Path(__file__).resolve().parent.parent / "libhalda.so"))
 
 ABI_VERSION = 3  # include/halda.h HALDA_ABI_VERSION (2: halda_fleet_result.x_off; 3: byte counts as double)
@@ -26,77 +28,10 @@ STATUS_INFEASIBLE = 2
 STATUS_UNSUPPORTED = -1
 STATUS_TOO_LARGE = -2
 
-_c_i32p = ctypes.POINTER(ctypes.c_int32)
-_c_i64p = ctypes.POINTER(ctypes.c_int64)
-_c_dp = ctypes.POINTER(ctypes.c_double)
-_c_u8p = ctypes.POINTER(ctypes.c_uint8)
-
 
 class HaldaUnavailable(RuntimeError):
     """libhalda.so is not built or no gfx950 device is present."""
 
-
-class HaldaBatchC(ctypes.Structure):
-    _fields_ = [
-        ("n_inst", ctypes.c_int32),
-        ("max_cols", ctypes.c_int32),
-        ("max_R1", ctypes.c_int32),
-        ("max_tab", ctypes.c_int32),
-        ("max_tab_kc", ctypes.c_int32),
-        ("n_cols", ctypes.c_void_p),
-        ("n_rows", ctypes.c_void_p),
-        ("csr_off", ctypes.c_void_p),
-        ("col_off", ctypes.c_void_p),
-        ("row_off", ctypes.c_void_p),
-        ("row_ptr", ctypes.c_void_p),
-        ("col_idx", ctypes.c_void_p),
-        ("val", ctypes.c_void_p),
-        ("c", ctypes.c_void_p),
-        ("col_lb", ctypes.c_void_p),
-        ("col_ub", ctypes.c_void_p),
-        ("row_lb", ctypes.c_void_p),
-        ("row_ub", ctypes.c_void_p),
-        ("integrality", ctypes.c_void_p),
-        ("mip_rel_gap", ctypes.c_double),
-        ("mip_abs_gap", ctypes.c_double),
-        ("time_limit", ctypes.c_double),
-        ("x0", ctypes.c_void_p),
-        ("y0", ctypes.c_void_p),
-    ]
-
-
-class HaldaResultC(ctypes.Structure):
-    _fields_ = [
-        ("status", ctypes.c_void_p),
-        ("x", ctypes.c_void_p),
-        ("obj_lin", ctypes.c_void_p),
-        ("dual_bound", ctypes.c_void_p),
-        ("gap", ctypes.c_void_p),
-        ("nodes", ctypes.c_void_p),
-    ]
-
-
-EXPORTS = ("halda_version", "halda_init", "halda_solve_batch", "halda_solve_batch_device",
-           "halda_solve_batch_device_settled", "halda_last_kernel_ms",
-           "halda_last_solve_kernel_ms", "halda_last_phase_ms", "halda_lds_bytes", "halda_last_error", "halda_free",
-           "halda_solve_fleets", "halda_solve_fleets_host", "halda_last_lowered", "halda_set_timing",
-           "halda_last_fleet_ms", "halda_set_fleets_path", "halda_init_multi", "halda_solve_fleets_multi",
-           "halda_free_multi", "halda_comm_unique_id", "halda_comm_init", "halda_comm_destroy",
-           "halda_solve_fleets_sharded", "halda_fleets_plan_create", "halda_fleets_plan_launch",
-           "halda_fleets_plan_free", "halda_solve_fleets_sharded_emulated", "halda_fleets_plan_launch_many",
-           "halda_fleets_group_create", "halda_fleets_group_launch", "halda_fleets_group_free",
-           "halda_resident_release", "halda_host_alloc", "halda_host_free", "halda_solve_subfleets",
-           "halda_solve_subfleets_host", "halda_set_subfleets_path", "halda_last_subfleets_route",
-           "halda_solve_variants", "halda_solve_variants_host", "halda_set_variants_path",
-           "halda_last_variants_route", "halda_eval_plans", "halda_eval_plans_host", "halda_solve_fleets_plans",
-           "halda_solve_fleets_plans_host", "halda_last_plans_route", "halda_set_plans_path",
-           "halda_solve_fleets_bounded", "halda_solve_fleets_bounded_host", "halda_last_bounds_route",
-           "halda_set_bounds_path", "halda_solve_fleets_boxed", "halda_solve_fleets_boxed_host",
-           "halda_solve_fleets_budget", "halda_solve_fleets_budget_host", "halda_budget_lds_bytes",
-           "halda_solve_subsets", "halda_solve_subsets_host", "halda_subsets_count", "halda_last_subsets_route",
-           "halda_set_subsets_path", "halda_solve_change", "halda_solve_change_host", "halda_change_lds_bytes",
-           "halda_solve_change_subsets", "halda_solve_change_subsets_host", "halda_change_subsets_max_deficit",
-           "halda_change_subsets_launch_bytes", "halda_set_change_subsets_chunk")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -132,44 +67,11 @@ def load_library(path: Path | str | None = None):
             raise HaldaUnavailable(f"{p} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                    "or `make -C distilp_amd/csrc`")
         lib = ctypes.CDLL(str(p))
-        lib.halda_version.restype = ctypes.c_int
         if lib.halda_version() != ABI_VERSION:
             raise HaldaUnavailable(f"{p} has ABI {lib.halda_version()}, this binding needs {ABI_VERSION}: rebuild it")
-        lib.halda_init.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-        lib.halda_init.restype = ctypes.c_int
-        lib.halda_solve_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaBatchC), ctypes.POINTER(HaldaResultC)]
-        lib.halda_solve_batch.restype = ctypes.c_int
-        lib.halda_solve_batch_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaBatchC),
-                                                 ctypes.POINTER(HaldaResultC), ctypes.c_void_p]
-        lib.halda_solve_batch_device.restype = ctypes.c_int
-        lib.halda_solve_batch_device_settled.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaBatchC),
-                                                         ctypes.POINTER(HaldaResultC), ctypes.c_void_p,
-                                                         ctypes.c_void_p]
-        lib.halda_solve_batch_device_settled.restype = ctypes.c_int
-        lib.halda_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
-        lib.halda_last_kernel_ms.restype = ctypes.c_int
-        lib.halda_last_solve_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
-        lib.halda_last_solve_kernel_ms.restype = ctypes.c_int
-        lib.halda_last_phase_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
-        lib.halda_last_phase_ms.restype = ctypes.c_int
-        lib.halda_set_fleets_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        lib.halda_set_fleets_path.restype = ctypes.c_int
-        lib.halda_last_fleet_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
-        lib.halda_last_fleet_ms.restype = ctypes.c_int
-        lib.halda_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        lib.halda_set_timing.restype = ctypes.c_int
-        lib.halda_lds_bytes.argtypes = [ctypes.c_int32] * 4
-        lib.halda_lds_bytes.restype = ctypes.c_int64
-        lib.halda_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-        lib.halda_last_error.restype = ctypes.c_int
-        lib.halda_free.argtypes = [ctypes.c_void_p]
-        lib.halda_free.restype = None
-        lib.halda_resident_release.argtypes = [ctypes.c_void_p]
-        lib.halda_resident_release.restype = ctypes.c_int
-        lib.halda_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
-        lib.halda_host_alloc.restype = ctypes.c_int
-        lib.halda_host_free.argtypes = [ctypes.c_void_p]
-        lib.halda_host_free.restype = None
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if path is None:
             _lib = lib
         return lib
@@ -179,6 +81,37 @@ def last_error(lib) -> str:
     buf = ctypes.create_string_buffer(1024)
     lib.halda_last_error(buf, len(buf))
     return buf.value.decode(errors="replace")
+
+
+def failure(lib, what: str, rc: int, exc=RuntimeError) -> Exception:
+    """The exception of a non-zero status `rc` of the call `what`, with the library's message."""
+    return exc(f"{what} failed ({rc}): {last_error(lib)}")
+
+
+def ptr(a) -> Optional[int]:
+    """The address of a torch tensor's or a NumPy array's data; None (a NULL pointer) for None."""
+    return None if a is None else a.data_ptr() if hasattr(a, "data_ptr") else int(a.ctypes.data)
+
+
+# The path / route knobs of the entry families: halda_set_<family>_path's codes are documented by each
+# family's module; halda_last_<family>_route answers an index into these names.
+ROUTES = {"subfleets": ("none", "fused", "expand"), "subsets": ("none", "fused", "expand", "mixed"),
+          "variants": ("none", "fused", "loop"), "plans": ("none", "fused", "two_launch"),
+          "bounds": ("none", "fused", "general", "tables")}
+
+
+def set_path(ctx: "HaldaContext", family: str, path: int) -> None:
+    """halda_set_<family>_path on a context (no lock taken: a caller that holds it may switch per call). The
+    library has no getter, so the context remembers the path."""
+    ctx.call(f"halda_set_{family}_path", ctx.ctx, int(path), lock=False)
+    ctx.paths[family] = int(path)
+
+
+def last_route(ctx: "HaldaContext", family: str) -> str:
+    """The route the context's last call of `family` took (halda_last_<family>_route), by name."""
+    r = ctypes.c_int(0)
+    ctx.call(f"halda_last_{family}_route", ctx.ctx, ctypes.byref(r), lock=False)
+    return ROUTES[family][r.value]
 
 
 @dataclass
@@ -229,10 +162,6 @@ class BatchResult:
     nodes: np.ndarray
 
 
-def _ptr(a: np.ndarray) -> int:
-    return int(a.ctypes.data)
-
-
 class HaldaContext:
     """One libhalda context bound to one GPU (halda_init / halda_free)."""
 
@@ -241,10 +170,23 @@ class HaldaContext:
         ctx = ctypes.c_void_p()
         rc = self.lib.halda_init(int(device), ctypes.byref(ctx))
         if rc != 0:
-            raise HaldaUnavailable(f"halda_init({device}) failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, f"halda_init({device})", rc, HaldaUnavailable)
         self.ctx = ctx
         self.device = device
         self._lock = threading.Lock()
+        self.paths: Dict[str, int] = {}  # family -> the path set_path last set (0, automatic, when absent)
+
+    def call(self, name: str, *args, lock: bool = True) -> None:
+        """The library's `name`(*args), under the context's lock unless the caller holds it (lock=False) or the
+        call needs none; RuntimeError with the library's message for a non-zero status."""
+        fn = getattr(self.lib, name)
+        if lock:
+            with self._lock:
+                rc = fn(*args)
+        else:
+            rc = fn(*args)
+        if rc != 0:
+            raise failure(self.lib, name, rc)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -254,10 +196,7 @@ class HaldaContext:
     def release_resident(self):
         """Let the context's resident single-fleet wave go now (halda_resident_release) instead of after
         its 2 ms idle limit: for a caller about to wait on the whole device through libhalda's runtime."""
-        with self._lock:
-            rc = self.lib.halda_resident_release(self.ctx)
-        if rc != 0:
-            raise RuntimeError(f"halda_resident_release failed ({rc}): {last_error(self.lib)}")
+        self.call("halda_resident_release", self.ctx)
 
     def __del__(self):  # pragma: no cover - interpreter shutdown order
         try:
@@ -271,7 +210,7 @@ class HaldaContext:
         s.max_cols, s.max_R1, s.max_tab, s.max_tab_kc = b.max_cols, b.max_R1, b.max_tab, b.max_tab_kc
         for f in ("n_cols", "n_rows", "csr_off", "col_off", "row_off", "row_ptr", "col_idx", "val", "c", "col_lb",
                   "col_ub", "row_lb", "row_ub", "integrality"):
-            setattr(s, f, _ptr(getattr(b, f)))
+            setattr(s, f, ptr(getattr(b, f)))
         s.mip_rel_gap = b.mip_rel_gap
         s.mip_abs_gap = 1e-6
         s.time_limit = 3600.0
@@ -283,13 +222,9 @@ class HaldaContext:
         n = b.n_inst
         out = BatchResult(status=np.empty(n, np.int32), x=np.zeros(b.total_cols), obj_lin=np.empty(n),
                           dual_bound=np.empty(n), gap=np.empty(n), nodes=np.empty(n, np.int64))
-        r = HaldaResultC(_ptr(out.status), _ptr(out.x), _ptr(out.obj_lin), _ptr(out.dual_bound), _ptr(out.gap),
-                         _ptr(out.nodes))
+        r = HaldaResultC(*(ptr(getattr(out, f)) for f in ("status", "x", "obj_lin", "dual_bound", "gap", "nodes")))
         s = self._batch_struct(b)
-        with self._lock:
-            rc = self.lib.halda_solve_batch(self.ctx, ctypes.byref(s), ctypes.byref(r))
-        if rc != 0:
-            raise RuntimeError(f"halda_solve_batch failed ({rc}): {last_error(self.lib)}")
+        self.call("halda_solve_batch", self.ctx, ctypes.byref(s), ctypes.byref(r))
         return out
 
     def solve_device(self, dev_ptrs: Dict[str, int], b: HostBatch, out_ptrs: Dict[str, int],
@@ -313,7 +248,7 @@ class HaldaContext:
             else:
                 rc = self.lib.halda_solve_batch_device(self.ctx, ctypes.byref(s), ctypes.byref(r), st)
         if rc != 0:
-            raise RuntimeError(f"halda_solve_batch_device failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, "halda_solve_batch_device", rc)  # (the settled form under this name too)
 
     def last_kernel_ms(self, solve_only: bool = False) -> float:
         """Device time of the last launch sequence (or of halda_solve_kernel alone)."""
@@ -321,7 +256,7 @@ class HaldaContext:
         fn = self.lib.halda_last_solve_kernel_ms if solve_only else self.lib.halda_last_kernel_ms
         rc = fn(self.ctx, ctypes.byref(ms))
         if rc != 0:
-            raise RuntimeError(f"halda_last_kernel_ms failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, "halda_last_kernel_ms", rc)  # (the solve-only form under this name too)
         return ms.value
 
     FLEET_PATHS = {"csr": 0, "fused": 1, "wave": 2, "dp": 3, "seg": 4, "kslot_unsplit": 5, "kslot_sequential": 6}
@@ -335,9 +270,7 @@ class HaldaContext:
         k = 2 threshold scan unsplit ("kslot_unsplit"; the default splits it over two waves), or split
         in sequential order ("kslot_sequential": part 1 makes its leaf checks and phase 0 itself)."""
         code = self.FLEET_PATHS[path] if isinstance(path, str) else int(bool(path))
-        rc = self.lib.halda_set_fleets_path(self.ctx, code)
-        if rc != 0:
-            raise RuntimeError(f"halda_set_fleets_path failed ({rc}): {last_error(self.lib)}")
+        self.call("halda_set_fleets_path", self.ctx, code, lock=False)
 
     def set_timing(self, on: bool) -> None:
         """Record (or not) the per-launch HIP events behind last_kernel_ms / last_phase_ms."""
@@ -346,9 +279,7 @@ class HaldaContext:
     def last_fleet_ms(self) -> Dict[str, float]:
         """Device time of each launch of the last halda_solve_fleets call (zero entries dropped)."""
         ms = (ctypes.c_double * 9)()
-        rc = self.lib.halda_last_fleet_ms(self.ctx, ms)
-        if rc != 0:
-            raise RuntimeError(f"halda_last_fleet_ms failed ({rc}): {last_error(self.lib)}")
+        self.call("halda_last_fleet_ms", self.ctx, ms, lock=False)
         names = ("halda_sweep_kernel", "halda_sweep_tables_kernel", "halda_lower_kernel", "halda_screen_kernel",
                  "halda_solve_k1_kernel", "halda_solve_kernel", "halda_pick_kernel", "halda_sweep_seg_kernel",
                  "halda_sweep_kslot_kernel")
@@ -358,9 +289,7 @@ class HaldaContext:
         """Device time of each launch of the last solve: screen, k = 1 fast path, general kernel. A settled
         batch has no screen launch: its k = 1 kernel is halda_solve_k1_settled_kernel (include/halda.h)."""
         ms = (ctypes.c_double * 3)()
-        rc = self.lib.halda_last_phase_ms(self.ctx, ms)
-        if rc != 0:
-            raise RuntimeError(f"halda_last_phase_ms failed ({rc}): {last_error(self.lib)}")
+        self.call("halda_last_phase_ms", self.ctx, ms, lock=False)
         if ms[0] == 0.0:
             return {"halda_solve_k1_settled_kernel": ms[1], "halda_solve_kernel": ms[2]}
         return {"halda_screen_kernel": ms[0], "halda_solve_k1_kernel": ms[1], "halda_solve_kernel": ms[2]}

@@ -28,10 +28,10 @@ from typing import Iterable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import get_context, last_error
+from ._abi import HaldaBoundsC, HaldaBoxC, HaldaFleetResultC
+from ._libhalda import ROUTES, failure, get_context, last_route, ptr, set_path
 from .coefficients import HALDAResult
-from .fleets import (FleetSolve, FleetTable, HaldaBoundsC, HaldaBoxC, HaldaFleetResultC, _bind_bounds, _host_struct,
-                     fleet_table, model_struct, open_x_offsets)
+from .fleets import FleetSolve, FleetTable, _host_struct, fleet_table, model_struct, open_x_offsets
 from .halda import _batch_k_list, _batch_results, _positive_ks
 from .lower import kv_bits_to_factor
 from .plans import Incumbent, PlanEvaluation, _as_plan, halda_replace_or_keep_batch
@@ -41,22 +41,15 @@ INT32_MAX = 2**31 - 1
 Bounds = Optional[Tuple[Optional[Sequence[int]], ...]]
 
 
-BOUNDS_ROUTES = ("none", "fused", "general", "tables")  # halda_last_bounds_route's values 0 .. 3
+BOUNDS_ROUTES = ROUTES["bounds"]  # halda_last_bounds_route's values 0 .. 3
 _ROUTE_PATH = {"auto": None, "general": 1, "tables": 3}  # the `route` keyword -> halda_set_bounds_path
-
-
-def _set_path(ctx, lib, path: int) -> None:
-    rc = lib.halda_set_bounds_path(ctx.ctx, int(path))
-    if rc != 0:
-        raise RuntimeError(f"halda_set_bounds_path failed ({rc}): {last_error(lib)}")
-    ctx._bounds_path = int(path)  # the library has no getter: the per-call `route` restores this
 
 
 def set_bounds_path(ctx, path: int) -> None:
     """halda_set_bounds_path on a HaldaContext: 0 automatic, 1 always the general route, 2 the fused launch
     where it applies, 3 the fused launch where it applies, else the table launch
     (halda_sweep_bounds_tables_kernel: fleets of 1 .. 64 devices, any k, one launch) where that applies."""
-    _set_path(ctx, _bind_bounds(ctx.lib), path)
+    set_path(ctx, "bounds", path)
 
 
 def check_route(route) -> Optional[int]:
@@ -71,12 +64,7 @@ def check_route(route) -> Optional[int]:
 def last_bounds_route(ctx) -> str:
     """The route of the context's last halda_solve_fleets_bounded call: "fused", "general", "tables" or
     "none"."""
-    lib = _bind_bounds(ctx.lib)
-    r = ctypes.c_int(0)
-    rc = lib.halda_last_bounds_route(ctx.ctx, ctypes.byref(r))
-    if rc != 0:
-        raise RuntimeError(f"halda_last_bounds_route failed ({rc}): {last_error(lib)}")
-    return BOUNDS_ROUTES[r.value]
+    return last_route(ctx, "bounds")
 
 
 _NO_N = object()  # check_bounds' "called without the n arguments": the 2-tuple answer, as before they existed
@@ -195,7 +183,6 @@ def solve_bounded_table(table: FleetTable, model: ModelProfile, pos: List[int], 
     halda_solve_fleets_boxed_host."""
     path = check_route(route)
     ctx = get_context(device)
-    lib = _bind_bounds(ctx.lib)
     nf, nd, nk = table.n_fleets, table.n_devices, len(pos)
     xsel = open_x_offsets(table, model, pos)
     ext = int(np.max(xsel + np.repeat(7 * table.sizes() + 1, nk), initial=0)) if (xsel >= 0).any() else 0
@@ -210,28 +197,26 @@ def solve_bounded_table(table: FleetTable, model: ModelProfile, pos: List[int], 
     fs, keep = _host_struct(table)
     lo = None if w_min is None else np.ascontiguousarray(w_min, np.int32)
     hi = None if w_max is None else np.ascontiguousarray(w_max, np.int32)
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     boxed = n_min is not None or n_max is not None
     nlo = None if n_min is None else np.ascontiguousarray(n_min, np.int32)
     nhi = None if n_max is None else np.ascontiguousarray(n_max, np.int32)
     bd = HaldaBoxC(ptr(lo), ptr(hi), ptr(nlo), ptr(nhi)) if boxed else HaldaBoundsC(ptr(lo), ptr(hi))
-    entry = lib.halda_solve_fleets_boxed_host if boxed else lib.halda_solve_fleets_bounded_host
     name = "halda_solve_fleets_boxed_host" if boxed else "halda_solve_fleets_bounded_host"
     karr = np.asarray(pos, np.int32)
     m = model_struct(model, kv_factor)
     with ctx._lock:
-        prev = getattr(ctx, "_bounds_path", 0)
+        prev = ctx.paths.get("bounds", 0)  # (the library has no getter)
         if path is not None:
-            _set_path(ctx, lib, path)
+            set_path(ctx, "bounds", path)
         try:
-            rc = entry(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk, ctypes.byref(bd),
-                       ctypes.byref(r))
+            rc = getattr(ctx.lib, name)(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
+                                        ctypes.byref(bd), ctypes.byref(r))
         finally:
             if path is not None:
-                _set_path(ctx, lib, prev)
+                set_path(ctx, "bounds", prev)
     del keep
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {last_error(lib)}")
+    if rc != 0:  # (checked once the path is back and the lock released)
+        raise failure(ctx.lib, name, rc)
     return out
 
 

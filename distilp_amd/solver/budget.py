@@ -25,11 +25,12 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import STATUS_OPTIMAL, get_context, last_error
+from ._abi import HaldaBudgetC, HaldaFrontierC
+from ._libhalda import STATUS_OPTIMAL, get_context, ptr
 from .bounds import INT32_MAX, _int_list, check_bounds
 from .coefficients import HALDAResult, assign_sets
-from .fleets import (FleetTable, HaldaBudgetC, HaldaFrontierC, _bind_budget, _host_struct, fleet_table,  # noqa: F401
-                     model_struct)
+from .fleets import FleetTable, _host_struct, fleet_table, model_struct
+from .fleets import _bind as _bind_budget  # noqa: F401 -- the identity, for callers from before load_library bound all
 from .lower import kv_bits_to_factor
 from .plans import Incumbent, _as_plan, halda_evaluate_plans_batch
 
@@ -168,24 +169,18 @@ def solve_budget_table(table: FleetTable, model: ModelProfile, k: int, w0: np.nd
     sizes = table.sizes()
     check_gate(int(sizes.max()), int(sizes.min()), int(max_p), int(k))
     ctx = get_context(device)
-    lib = _bind_budget(ctx.lib)
     nf, nd, P1 = table.n_fleets, table.n_devices, int(max_p) + 1
     out = FrontierSolve(status=np.zeros((nf, P1), np.int32), obj=np.zeros((nf, P1)),
                         moved=np.zeros((nf, P1), np.int32), w=np.zeros((P1, nd), np.int32),
                         n=np.zeros((P1, nd), np.int32), k=int(k), max_p=int(max_p))
     fs, keep = _host_struct(table)
     arrs = [None if a is None else np.ascontiguousarray(a, np.int32) for a in (w0, w_min, w_max)]
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     bg = HaldaBudgetC(ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(max_p))
-    fr = HaldaFrontierC(nd, out.status.ctypes.data, out.obj.ctypes.data, out.moved.ctypes.data, out.w.ctypes.data,
-                        out.n.ctypes.data)
+    fr = HaldaFrontierC(nd, *(ptr(getattr(out, f)) for f in ("status", "obj", "moved", "w", "n")))
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_solve_fleets_budget_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k), ctypes.byref(bg),
-                                                ctypes.byref(fr))
+    ctx.call("halda_solve_fleets_budget_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k), ctypes.byref(bg),
+             ctypes.byref(fr))
     del keep
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_fleets_budget_host failed ({rc}): {last_error(lib)}")
     return out
 
 

@@ -27,15 +27,16 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import STATUS_OPTIMAL, get_context, last_error
+from ._abi import HaldaChangeC, HaldaChangeFrontierC, HaldaSubfleetsC
+from ._libhalda import STATUS_OPTIMAL, get_context, ptr
 from .bounds import INT32_MAX, check_bounds
 from .budget import check_incumbent, distinct_plans, frontier_lds_bytes, host_frontier
 from .coefficients import HALDAResult, assign_sets
-from .fleets import (FleetTable, HaldaChangeC, HaldaChangeFrontierC, HaldaFleetsC, HaldaModelC, _bind, _host_struct,
-                     fleet_table, model_struct)
+from .fleets import FleetTable, _host_struct, fleet_table, model_struct
+from .fleets import _bind as _bind_change  # noqa: F401 -- the identity, for callers from before load_library bound all
 from .lower import kv_bits_to_factor
 from .plans import Incumbent, halda_evaluate_plans_batch
-from .subfleets import HaldaSubfleetsC, halda_solve_subfleets, pack_items
+from .subfleets import halda_solve_subfleets, pack_items
 
 LDS_BUDGET = 160 * 1024  # csrc/halda.hip kLdsBudget
 MAX_P = 63               # one lane per frontier point
@@ -128,24 +129,6 @@ class ChangeSolve:
     max_deficit: int
 
 
-def _bind_change(lib):
-    """The change entries' prototypes (halda_solve_change, its host form, halda_change_lds_bytes)."""
-    lib = _bind(lib)
-    if getattr(lib, "_change_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_solve_change.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaSubfleetsC),
-                                       ctypes.c_int32, P(HaldaChangeC), P(HaldaChangeFrontierC), ctypes.c_void_p]
-    lib.halda_solve_change.restype = ctypes.c_int
-    lib.halda_solve_change_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaSubfleetsC),
-                                            ctypes.c_int32, P(HaldaChangeC), P(HaldaChangeFrontierC)]
-    lib.halda_solve_change_host.restype = ctypes.c_int
-    lib.halda_change_lds_bytes.argtypes = [ctypes.c_int32] * 4
-    lib.halda_change_lds_bytes.restype = ctypes.c_int64
-    lib._change_bound = True
-    return lib
-
-
 def solve_change_table(table: FleetTable, model: ModelProfile, k: int, items, w0: np.ndarray, max_p: int,
                        kv_factor: float, w_min: Optional[np.ndarray] = None, w_max: Optional[np.ndarray] = None,
                        max_deficit: Optional[int] = None, device: int = 0) -> ChangeSolve:
@@ -160,7 +143,6 @@ def solve_change_table(table: FleetTable, model: ModelProfile, k: int, items, w0
     dmax = top if max_deficit is None else int(max_deficit)
     check_gate(int(lens.max()), int(lens.min()), int(max_p), dmax, int(k))
     ctx = get_context(device)
-    lib = _bind_change(ctx.lib)
     n, tot, P1 = len(parent), int(sub_off[-1]), int(max_p) + 1
     out = ChangeSolve(status=np.zeros((n, P1), np.int32), obj=np.zeros((n, P1)), loaded=np.zeros((n, P1), np.int32),
                       released=np.zeros((n, P1), np.int32), w=np.zeros((P1, tot), np.int32),
@@ -172,18 +154,13 @@ def solve_change_table(table: FleetTable, model: ModelProfile, k: int, items, w0
             raise ValueError(f"bound array of {len(a)} entries for {tot} listed devices")
     parent, sub_idx = np.ascontiguousarray(parent, np.int32), np.ascontiguousarray(sub_idx, np.int32)
     sub_off = np.ascontiguousarray(sub_off, np.int64)
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     it = HaldaSubfleetsC(n, int(lens.min()), int(lens.max()), ptr(parent), ptr(sub_off), ptr(sub_idx))
     ch = HaldaChangeC(ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(max_p), dmax)
-    fr = HaldaChangeFrontierC(tot, *(getattr(out, f).ctypes.data for f in
-                                     ("status", "obj", "loaded", "released", "w", "n")))
+    fr = HaldaChangeFrontierC(tot, *(ptr(getattr(out, f)) for f in ("status", "obj", "loaded", "released", "w", "n")))
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_solve_change_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it), int(k),
-                                         ctypes.byref(ch), ctypes.byref(fr))
+    ctx.call("halda_solve_change_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it), int(k),
+             ctypes.byref(ch), ctypes.byref(fr))
     del keep
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_change_host failed ({rc}): {last_error(lib)}")
     return out
 
 

@@ -32,208 +32,23 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import HaldaBatchC, HaldaResultC, get_context, last_error
+from ._abi import (BYTE_FIELDS, F64_FIELDS, HaldaBatchC, HaldaBoundsC, HaldaBoxC, HaldaBudgetC,  # noqa: F401
+                   HaldaChangeC, HaldaChangeFrontierC, HaldaFleetResultC, HaldaFleetsC, HaldaFrontierC, HaldaModelC,
+                   HaldaPlanResultC, HaldaPlansC, HaldaResultC, HaldaSubfleetsC)  # (this module's names of old too)
+from ._libhalda import HaldaUnavailable, failure, get_context, load_library, ptr
 from .coefficients import HALDAResult, assign_sets, b_prime, gpu_flops_table, gpu_load_throughput
 from .lower import kv_bits_to_factor
 
 DEV_HEAD, DEV_UMA, DEV_CPU_RATE, DEV_GPU, DEV_GPU_RATE, DEV_CUDA_OK, DEV_METAL_OK, DEV_METAL_AVAIL = (
     1, 2, 4, 8, 16, 32, 64, 128)
 
-F64_FIELDS = ("scpu_b1", "sgpu_b1", "T_cpu", "T_gpu", "t_kvcpy_cpu", "t_kvcpy_gpu", "t_ram2vram", "t_vram2ram",
-              "t_comm", "s_disk")
-# the profiles' integer byte counts, held as float64 (ABI 3): exact below 2^53, so the reference's integer
-# sums and differences of them are exact in the kernels' double arithmetic
-BYTE_FIELDS = ("d_avail_ram", "c_cpu", "c_gpu", "d_avail_cuda", "d_avail_metal", "swap")
-
-
-class HaldaModelC(ctypes.Structure):
-    _fields_ = [("f_q_b1", ctypes.c_double), ("f_out_b1", ctypes.c_double), ("has_f_q", ctypes.c_int32),
-                ("has_f_out", ctypes.c_int32), ("b_prime", ctypes.c_double), ("b_layer", ctypes.c_double),
-                ("b_in", ctypes.c_double), ("b_out", ctypes.c_double), ("V", ctypes.c_double), ("L", ctypes.c_int32)]
-
-
-class HaldaFleetsC(ctypes.Structure):
-    _fields_ = ([("n_fleets", ctypes.c_int32), ("min_devices", ctypes.c_int32), ("max_devices", ctypes.c_int32),
-                 ("dev_off", ctypes.c_void_p), ("os_class", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
-                + [(f, ctypes.c_void_p) for f in F64_FIELDS] + [(f, ctypes.c_void_p) for f in BYTE_FIELDS])
-
-
-class HaldaFleetResultC(ctypes.Structure):
-    _fields_ = [("best_k", ctypes.c_void_p), ("obj_value", ctypes.c_void_p), ("w", ctypes.c_void_p),
-                ("n", ctypes.c_void_p), ("obj_by_k", ctypes.c_void_p), ("status", ctypes.c_void_p),
-                ("x", ctypes.c_void_p), ("c", ctypes.c_void_p), ("x_off", ctypes.c_void_p)]
-
-
-class HaldaPlansC(ctypes.Structure):
-    _fields_ = [("k", ctypes.c_void_p), ("w", ctypes.c_void_p), ("n", ctypes.c_void_p)]
-
-
-class HaldaPlanResultC(ctypes.Structure):
-    _fields_ = [("status", ctypes.c_void_p), ("obj_value", ctypes.c_void_p), ("cycle", ctypes.c_void_p),
-                ("bottleneck", ctypes.c_void_p), ("reason", ctypes.c_void_p), ("x", ctypes.c_void_p),
-                ("c", ctypes.c_void_p), ("x_off", ctypes.c_void_p)]
-
-
-def _bind_plans(lib):
-    """The plan entries' prototypes (halda_eval_plans .. halda_set_plans_path), on top of _bind's."""
-    lib = _bind(lib)
-    if getattr(lib, "_plans_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_eval_plans.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaPlansC),
-                                     P(HaldaPlanResultC), ctypes.c_void_p]
-    lib.halda_eval_plans.restype = ctypes.c_int
-    lib.halda_eval_plans_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaPlansC),
-                                          P(HaldaPlanResultC)]
-    lib.halda_eval_plans_host.restype = ctypes.c_int
-    lib.halda_solve_fleets_plans.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
-                                             ctypes.c_int32, P(HaldaPlansC), P(HaldaPlanResultC),
-                                             P(HaldaFleetResultC), ctypes.c_void_p]
-    lib.halda_solve_fleets_plans.restype = ctypes.c_int
-    lib.halda_solve_fleets_plans_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
-                                                  ctypes.c_int32, P(HaldaPlansC), P(HaldaPlanResultC),
-                                                  P(HaldaFleetResultC)]
-    lib.halda_solve_fleets_plans_host.restype = ctypes.c_int
-    lib.halda_last_plans_route.argtypes = [ctypes.c_void_p, P(ctypes.c_int)]
-    lib.halda_last_plans_route.restype = ctypes.c_int
-    lib.halda_set_plans_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.halda_set_plans_path.restype = ctypes.c_int
-    lib._plans_bound = True
-    return lib
-
-
-class HaldaBoundsC(ctypes.Structure):
-    _fields_ = [("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p)]
-
-
-class HaldaBoxC(ctypes.Structure):  # halda_box: halda_bounds and the n columns' two arrays
-    _fields_ = [("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p), ("n_min", ctypes.c_void_p),
-                ("n_max", ctypes.c_void_p)]
-
-
-def _bind_bounds(lib):
-    """The bounded-sweep entries' prototypes (halda_solve_fleets_bounded .. halda_set_bounds_path)."""
-    lib = _bind(lib)
-    if getattr(lib, "_bounds_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_solve_fleets_bounded.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
-                                               ctypes.c_int32, P(HaldaBoundsC), P(HaldaFleetResultC), ctypes.c_void_p]
-    lib.halda_solve_fleets_bounded.restype = ctypes.c_int
-    lib.halda_solve_fleets_bounded_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
-                                                    ctypes.c_int32, P(HaldaBoundsC), P(HaldaFleetResultC)]
-    lib.halda_solve_fleets_bounded_host.restype = ctypes.c_int
-    lib.halda_solve_fleets_boxed.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
-                                             ctypes.c_int32, P(HaldaBoxC), P(HaldaFleetResultC), ctypes.c_void_p]
-    lib.halda_solve_fleets_boxed.restype = ctypes.c_int
-    lib.halda_solve_fleets_boxed_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_void_p,
-                                                  ctypes.c_int32, P(HaldaBoxC), P(HaldaFleetResultC)]
-    lib.halda_solve_fleets_boxed_host.restype = ctypes.c_int
-    lib.halda_last_bounds_route.argtypes = [ctypes.c_void_p, P(ctypes.c_int)]
-    lib.halda_last_bounds_route.restype = ctypes.c_int
-    lib.halda_set_bounds_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.halda_set_bounds_path.restype = ctypes.c_int
-    lib._bounds_bound = True
-    return lib
-
-
-class HaldaBudgetC(ctypes.Structure):
-    _fields_ = [("w0", ctypes.c_void_p), ("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p),
-                ("max_p", ctypes.c_int32)]
-
-
-class HaldaFrontierC(ctypes.Structure):
-    _fields_ = [("n_devices", ctypes.c_int64), ("status", ctypes.c_void_p), ("obj", ctypes.c_void_p),
-                ("moved", ctypes.c_void_p), ("w", ctypes.c_void_p), ("n", ctypes.c_void_p)]
-
-
-def _bind_budget(lib):
-    """The budget entries' prototypes (halda_solve_fleets_budget, its host form, halda_budget_lds_bytes)."""
-    lib = _bind(lib)
-    if getattr(lib, "_budget_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_solve_fleets_budget.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_int32,
-                                              P(HaldaBudgetC), P(HaldaFrontierC), ctypes.c_void_p]
-    lib.halda_solve_fleets_budget.restype = ctypes.c_int
-    lib.halda_solve_fleets_budget_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_int32,
-                                                   P(HaldaBudgetC), P(HaldaFrontierC)]
-    lib.halda_solve_fleets_budget_host.restype = ctypes.c_int
-    lib.halda_budget_lds_bytes.argtypes = [ctypes.c_int32] * 3
-    lib.halda_budget_lds_bytes.restype = ctypes.c_int64
-    lib._budget_bound = True
-    return lib
-
-
-class HaldaChangeC(ctypes.Structure):
-    _fields_ = [("w0", ctypes.c_void_p), ("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p),
-                ("max_p", ctypes.c_int32), ("max_deficit", ctypes.c_int32)]
-
-
-class HaldaChangeFrontierC(ctypes.Structure):
-    _fields_ = [("n_devices", ctypes.c_int64), ("status", ctypes.c_void_p), ("obj", ctypes.c_void_p),
-                ("loaded", ctypes.c_void_p), ("released", ctypes.c_void_p), ("w", ctypes.c_void_p),
-                ("n", ctypes.c_void_p)]
-
 
 def _bind(lib):
-    if getattr(lib, "_fleets_bound", False):
-        return lib
-    lib.halda_solve_fleets.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaModelC), ctypes.POINTER(HaldaFleetsC),
-                                       ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(HaldaFleetResultC),
-                                       ctypes.c_void_p]
-    lib.halda_solve_fleets.restype = ctypes.c_int
-    lib.halda_solve_fleets_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaModelC),
-                                            ctypes.POINTER(HaldaFleetsC), ctypes.c_void_p, ctypes.c_int32,
-                                            ctypes.POINTER(HaldaFleetResultC)]
-    lib.halda_solve_fleets_host.restype = ctypes.c_int
-    lib.halda_last_lowered.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaBatchC), ctypes.POINTER(HaldaResultC)]
-    lib.halda_last_lowered.restype = ctypes.c_int
-    lib.halda_init_multi.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-    lib.halda_init_multi.restype = ctypes.c_int
-    lib.halda_solve_fleets_multi.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaModelC),
-                                             ctypes.POINTER(HaldaFleetsC), ctypes.c_void_p, ctypes.c_int32,
-                                             ctypes.POINTER(HaldaFleetResultC)]
-    lib.halda_solve_fleets_multi.restype = ctypes.c_int
-    lib.halda_free_multi.argtypes = [ctypes.c_void_p]
-    lib.halda_free_multi.restype = None
-    lib.halda_comm_unique_id.argtypes = [ctypes.c_void_p]
-    lib.halda_comm_unique_id.restype = ctypes.c_int
-    lib.halda_comm_init.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
-                                    ctypes.c_int]
-    lib.halda_comm_init.restype = ctypes.c_int
-    lib.halda_comm_destroy.argtypes = [ctypes.c_void_p]
-    lib.halda_comm_destroy.restype = None
-    lib.halda_solve_fleets_sharded.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HaldaModelC),
-                                               ctypes.POINTER(HaldaFleetsC), ctypes.c_void_p, ctypes.c_int32,
-                                               ctypes.POINTER(HaldaFleetResultC), ctypes.c_void_p]
-    lib.halda_solve_fleets_sharded.restype = ctypes.c_int
-    lib.halda_solve_fleets_sharded_emulated.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                        ctypes.POINTER(HaldaModelC), ctypes.POINTER(HaldaFleetsC),
-                                                        ctypes.c_void_p, ctypes.c_int32,
-                                                        ctypes.POINTER(HaldaFleetResultC), ctypes.c_void_p]
-    lib.halda_solve_fleets_sharded_emulated.restype = ctypes.c_int
-    lib.halda_fleets_plan_create.argtypes = [ctypes.c_void_p, ctypes.POINTER(HaldaModelC), ctypes.POINTER(HaldaFleetsC),
-                                             ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(HaldaFleetResultC),
-                                             ctypes.POINTER(ctypes.c_void_p)]
-    lib.halda_fleets_plan_create.restype = ctypes.c_int
-    lib.halda_fleets_plan_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.halda_fleets_plan_launch.restype = ctypes.c_int
-    lib.halda_fleets_plan_free.argtypes = [ctypes.c_void_p]
-    lib.halda_fleets_plan_free.restype = None
-    lib.halda_fleets_plan_launch_many.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int64,
-                                                  ctypes.c_int32]
-    lib.halda_fleets_plan_launch_many.restype = ctypes.c_int
-    lib.halda_fleets_group_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32)]
-    lib.halda_fleets_group_create.restype = ctypes.c_int
-    lib.halda_fleets_group_launch.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]
-    lib.halda_fleets_group_launch.restype = ctypes.c_int
-    lib.halda_fleets_group_free.argtypes = [ctypes.c_void_p]
-    lib.halda_fleets_group_free.restype = None
-    lib._fleets_bound = True
+    """Kept for callers from before load_library declared every prototype itself: the library as it is."""
     return lib
+
+
+_bind_plans = _bind_bounds = _bind_budget = _bind  # (the per-family names such callers know)
 
 
 _MODEL_STRUCTS: dict = {}
@@ -374,13 +189,11 @@ class _HostBlock:
     halda_solve_fleets_host DMAs straight from / to arrays that all lie in such blocks (include/halda.h)."""
 
     def __init__(self, nbytes: int):
-        from ._libhalda import last_error, load_library
-
         self.lib = load_library()
         p = ctypes.c_void_p()
         rc = self.lib.halda_host_alloc(nbytes, ctypes.byref(p))
         if rc != 0:
-            raise RuntimeError(f"halda_host_alloc({nbytes}) failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, f"halda_host_alloc({nbytes})", rc)
         self.ptr = p.value
 
     def __del__(self):
@@ -622,13 +435,13 @@ class FleetSolve:
     x_off: Optional[np.ndarray] = None  # want_x="open": [n_fleets * n_k] offsets into the flat x / c
 
 
-def _fleets_struct(t: FleetTable, ptr) -> HaldaFleetsC:
+def _fleets_struct(t: FleetTable, addr) -> HaldaFleetsC:
     s = HaldaFleetsC()
     s.n_fleets = t.n_fleets
     sz = t.sizes()
     s.min_devices, s.max_devices = int(sz.min()), int(sz.max())
     for f in ("dev_off", "os_class", "flags") + F64_FIELDS + BYTE_FIELDS:
-        setattr(s, f, ptr(f))
+        setattr(s, f, addr(f))
     return s
 
 
@@ -671,17 +484,13 @@ class MultiDeviceContext:
     solve() deals a FleetTable's fleets out over them (halda_solve_fleets_multi)."""
 
     def __init__(self, devices: Sequence[int]):
-        from ._libhalda import HaldaUnavailable, load_library
-
-        self.lib = _bind(load_library())
-        import threading
-
+        self.lib = load_library()
         self._lock = threading.Lock()  # the per-GPU contexts' staging buffers are not reentrant
         ords = (ctypes.c_int * len(devices))(*[int(d) for d in devices])
         self.ctx = ctypes.c_void_p()
         rc = self.lib.halda_init_multi(len(devices), ords, ctypes.byref(self.ctx))
         if rc != 0:
-            raise HaldaUnavailable(f"halda_init_multi({list(devices)}) failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, f"halda_init_multi({list(devices)})", rc, HaldaUnavailable)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -771,12 +580,11 @@ def sweep_one(ws: "_OneFleet", model: ModelProfile, kv_factor: float, device: in
     sum xi, kappa in the reference's order, the packer's C loops) in ws.consts. The thread's next call
     overwrites them."""
     ctx = get_context(device)
-    lib = _bind(ctx.lib)
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_solve_fleets_host(ctx.ctx, ctypes.byref(m), ws.fs_ref, ws.karr_p, len(ws.ks), ws.res_ref)
+    with ctx._lock:  # (every halda_solve's call: made directly, as the launches are, not through ctx.call)
+        rc = ctx.lib.halda_solve_fleets_host(ctx.ctx, ctypes.byref(m), ws.fs_ref, ws.karr_p, len(ws.ks), ws.res_ref)
     if rc != 0:
-        raise RuntimeError(f"halda_solve_fleets_host failed ({rc}): {last_error(lib)}")
+        raise failure(ctx.lib, "halda_solve_fleets_host", rc)
     fo = model.f_out
     has_o = "b_1" in fo
     _PACKER.consts(ws.f64, ws.b64, ws.u8, ws.off, ws.heads, has_o, float(fo["b_1"]) if has_o else 0.0,
@@ -797,8 +605,6 @@ def solve_table(table: FleetTable, model: ModelProfile, ks: Sequence[int], kv_fa
         raise ValueError("no k-candidates")
     if ks[0] <= 0:
         raise ZeroDivisionError("integer division or modulo by zero")
-    ctx = get_context(device) if _multi is None else None
-    lib = _bind(ctx.lib) if _multi is None else _multi.lib
     fs, keep = _host_struct(table)
     nf, nd, nk = table.n_fleets, table.n_devices, len(ks)
     # results in two buffers (f64, int32) viewed per field: two pointer reads
@@ -833,16 +639,15 @@ def solve_table(table: FleetTable, model: ModelProfile, ks: Sequence[int], kv_fa
                           xsel.ctypes.data if xsel is not None else None)
     karr = np.asarray(ks, np.int32)
     m = model_struct(model, kv_factor)
-    if _multi is not None:
-        with _multi._lock:
-                rc = lib.halda_solve_fleets_multi(_multi.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
-                                              ctypes.byref(r))
-    else:
-        with ctx._lock:
-            rc = lib.halda_solve_fleets_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
-                                             ctypes.byref(r))
+    args = (ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk, ctypes.byref(r))
+    if _multi is None:
+        ctx = get_context(device)
+        ctx.call("halda_solve_fleets_host", ctx.ctx, *args)
+        return out
+    with _multi._lock:
+        rc = _multi.lib.halda_solve_fleets_multi(_multi.ctx, *args)
     if rc != 0:
-        raise RuntimeError(f"halda_solve_fleets_host failed ({rc}): {last_error(lib)}")
+        raise failure(_multi.lib, "halda_solve_fleets_host", rc)  # (reported under the host entry's name)
     return out
 
 
@@ -871,6 +676,15 @@ def halda_solve_fleets(
     return out
 
 
+def _check_counts(k, **counts) -> None:
+    """set_budget's / set_change's integer arguments: each of `counts` a non-negative integer, k positive."""
+    for name, v in counts.items():
+        if isinstance(v, bool) or int(v) != v or v < 0:
+            raise ValueError(f"{name}: {v!r} is not a non-negative integer")
+    if int(k) < 1:
+        raise ValueError(f"k = {k} must be positive")
+
+
 class DeviceFleetTable:
     """A FleetTable resident in device memory (torch tensors) plus device result buffers, for
     back-to-back asynchronous halda_solve_fleets launches (bench / streaming): nothing crosses PCIe
@@ -893,16 +707,34 @@ class DeviceFleetTable:
             self.out["obj_by_k"] = torch.empty(nf * nk, dtype=torch.float64, device=torch_device)
             self.out["status"] = torch.empty(nf * nk, dtype=torch.int32, device=torch_device)
         self.fs = _fleets_struct(table, lambda f: self.arrs[f].data_ptr())
-        o = self.out
-        self.res = HaldaFleetResultC(o["best_k"].data_ptr(), o["obj_value"].data_ptr(), o["w"].data_ptr(),
-                                     o["n"].data_ptr(), o["obj_by_k"].data_ptr() if want_per_k else None,
-                                     o["status"].data_ptr() if want_per_k else None, None, None)
+        self.res = HaldaFleetResultC(*(ptr(self.out.get(f)) for f in ("best_k", "obj_value", "w", "n", "obj_by_k",
+                                                                      "status")))
         self.model = model_struct(model, kv_factor)
         self._plans = {}
         self.epoch = 0  # bumped whenever the prepared plans are freed (PlanRotation re-reads the handles)
 
     def nbytes(self) -> int:
         return sum(int(t.numel() * t.element_size()) for t in self.arrs.values())
+
+    def _sweep_args(self) -> tuple:
+        """(model, fleets, ks, n_k, out): what every sweep entry takes between its context and its stream."""
+        return (ctypes.byref(self.model), ctypes.byref(self.fs), self.ks.ctypes.data, len(self.ks),
+                ctypes.byref(self.res))
+
+    def _tensor(self, a, count: int, what: str, fill=None, dtype=None, cast=np.int32):
+        """`a` -- a tensor, an array or None -- as an owned contiguous tensor of `count` entries of `dtype` (int32
+        unless given) on the table's device. None gives a tensor of `fill`, or None where there is no fill.
+        What is no tensor becomes a NumPy array of dtype `cast` first (None: of its own dtype). ValueError,
+        naming the `what` array, for another count."""
+        import torch
+
+        dev, dtype = self.out["best_k"].device, dtype or torch.int32
+        if a is None:
+            return None if fill is None else torch.full((count,), fill, dtype=dtype, device=dev)
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, cast))
+        if t.numel() != count:
+            raise ValueError(f"{what} array of {t.numel()} entries, expected {count}")
+        return t.to(device=dev, dtype=dtype).contiguous().clone()
 
     def plan(self, ctx):
         """The prepared launch of this table on `ctx` (halda_fleets_plan_create: kernel choice, grids and
@@ -914,15 +746,9 @@ class DeviceFleetTable:
         if p is not None and p[0] is not ctx:  # a new context at a recycled id()
             p = None
         if p is None:
-            lib = _bind(ctx.lib)
             h = ctypes.c_void_p()
-            with ctx._lock:
-                rc = lib.halda_fleets_plan_create(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
-                                                  self.ks.ctypes.data, len(self.ks), ctypes.byref(self.res),
-                                                  ctypes.byref(h))
-            if rc != 0:
-                raise RuntimeError(f"halda_fleets_plan_create failed ({rc}): {last_error(lib)}")
-            p = (ctx, h, lib.halda_fleets_plan_launch)
+            ctx.call("halda_fleets_plan_create", ctx.ctx, *self._sweep_args(), ctypes.byref(h))
+            p = (ctx, h, ctx.lib.halda_fleets_plan_launch)
             self._plans[id(ctx)] = p
         return p
 
@@ -930,7 +756,7 @@ class DeviceFleetTable:
         """Free the prepared launches (the next launch prepares a new one). A PlanRotation over this
         table takes the new handles at its next launch; a PlanGroup keeps its own copy."""
         for ctx, h, _ in self._plans.values():
-            _bind(ctx.lib).halda_fleets_plan_free(h)
+            ctx.lib.halda_fleets_plan_free(h)
         self._plans.clear()
         self.epoch += 1
 
@@ -948,17 +774,11 @@ class DeviceFleetTable:
         with ctx._lock:
             rc = fn(h, stream)
         if rc != 0:
-            raise RuntimeError(f"halda_fleets_plan_launch failed ({rc}): {last_error(ctx.lib)}")
+            raise failure(ctx.lib, "halda_fleets_plan_launch", rc)
 
     def launch_unplanned(self, ctx, stream: int) -> None:
         """The same k-sweep through halda_solve_fleets (shapes re-derived on every call)."""
-        lib = _bind(ctx.lib)
-        with ctx._lock:
-            rc = lib.halda_solve_fleets(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
-                                        self.ks.ctypes.data, len(self.ks), ctypes.byref(self.res),
-                                        ctypes.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError(f"halda_solve_fleets failed ({rc}): {last_error(lib)}")
+        ctx.call("halda_solve_fleets", ctx.ctx, *self._sweep_args(), ctypes.c_void_p(stream))
 
     def set_plans(self, k=None, w=None, n=None) -> None:
         """Give the table its resident plan: device tensors plan_k [n_fleets], plan_w / plan_n [n_devices]
@@ -969,65 +789,40 @@ class DeviceFleetTable:
 
         dev = self.out["best_k"].device
         nf, nd = self.table.n_fleets, self.table.n_devices
-
-        def tensor(a, size):
-            if a is None:
-                return torch.zeros(size, dtype=torch.int32, device=dev)
-            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))
-            if t.numel() != size:
-                raise ValueError(f"plan array of {t.numel()} entries, expected {size}")
-            return t.to(device=dev, dtype=torch.int32).contiguous().clone()
-
-        self.plan_k, self.plan_w, self.plan_n = tensor(k, nf), tensor(w, nd), tensor(n, nd)
+        self.plan_k, self.plan_w, self.plan_n = (self._tensor(a, c, "plan", 0) for a, c in ((k, nf), (w, nd), (n, nd)))
         self.plan_out = {"status": torch.empty(nf, dtype=torch.int32, device=dev),
                          "obj_value": torch.empty(nf, dtype=torch.float64, device=dev),
                          "cycle": torch.empty(nf, dtype=torch.float64, device=dev),
                          "bottleneck": torch.empty(nf, dtype=torch.int32, device=dev),
                          "reason": torch.empty(nf, dtype=torch.int32, device=dev)}
         o = self.plan_out
-        self._plans_c = HaldaPlansC(self.plan_k.data_ptr(), self.plan_w.data_ptr(), self.plan_n.data_ptr())
-        self._plan_res = HaldaPlanResultC(o["status"].data_ptr(), o["obj_value"].data_ptr(), o["cycle"].data_ptr(),
-                                          o["bottleneck"].data_ptr(), o["reason"].data_ptr(), None, None, None)
+        self._plans_c = HaldaPlansC(ptr(self.plan_k), ptr(self.plan_w), ptr(self.plan_n))
+        self._plan_res = HaldaPlanResultC(*(ptr(o[f]) for f in ("status", "obj_value", "cycle", "bottleneck",
+                                                                "reason")))
 
     def launch_with_plans(self, ctx, stream: int) -> None:
         """Enqueue the k-sweep of every fleet and the evaluation of the resident plan on `stream`
         (halda_solve_fleets_plans): self.out as launch() leaves it, self.plan_out the incumbents' evaluation."""
         if getattr(self, "_plans_c", None) is None:
             self.set_plans()
-        lib = _bind_plans(ctx.lib)
-        with ctx._lock:
-            rc = lib.halda_solve_fleets_plans(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
-                                              self.ks.ctypes.data, len(self.ks), ctypes.byref(self._plans_c),
-                                              ctypes.byref(self._plan_res), ctypes.byref(self.res),
-                                              ctypes.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError(f"halda_solve_fleets_plans failed ({rc}): {last_error(lib)}")
+        ctx.call("halda_solve_fleets_plans", ctx.ctx, *self._sweep_args()[:4], ctypes.byref(self._plans_c),
+                 ctypes.byref(self._plan_res), ctypes.byref(self.res), ctypes.c_void_p(stream))
 
     def set_bounds(self, w_min=None, w_max=None, n_min=None, n_max=None) -> None:
         """Give the table its resident per-device layer bounds: device tensors bound_min / bound_max
         [n_devices] (int32; zeros / INT32_MAX, "no bound", where not given), buffers of their own. A streaming
         caller rewrites them in place between launches. With n_min or n_max given, bound_nmin / bound_nmax
         too (the n columns' box), and launch_with_bounds calls halda_solve_fleets_boxed."""
-        import torch
-
-        dev = self.out["best_k"].device
         nd = self.table.n_devices
-
-        def tensor(a, fill):
-            if a is None:
-                return torch.full((nd,), fill, dtype=torch.int32, device=dev)
-            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))
-            if t.numel() != nd:
-                raise ValueError(f"bounds array of {t.numel()} entries, expected {nd}")
-            return t.to(device=dev, dtype=torch.int32).contiguous().clone()
-
-        self.bound_min, self.bound_max = tensor(w_min, 0), tensor(w_max, 2**31 - 1)
-        self._bounds_c = HaldaBoundsC(self.bound_min.data_ptr(), self.bound_max.data_ptr())
+        self.bound_min = self._tensor(w_min, nd, "bounds", 0)
+        self.bound_max = self._tensor(w_max, nd, "bounds", 2**31 - 1)
+        self._bounds_c = HaldaBoundsC(ptr(self.bound_min), ptr(self.bound_max))
         self.bound_nmin = self.bound_nmax = self._box_c = None
         if n_min is not None or n_max is not None:
-            self.bound_nmin, self.bound_nmax = tensor(n_min, 0), tensor(n_max, 2**31 - 1)
-            self._box_c = HaldaBoxC(self.bound_min.data_ptr(), self.bound_max.data_ptr(),
-                                    self.bound_nmin.data_ptr(), self.bound_nmax.data_ptr())
+            self.bound_nmin = self._tensor(n_min, nd, "bounds", 0)
+            self.bound_nmax = self._tensor(n_max, nd, "bounds", 2**31 - 1)
+            self._box_c = HaldaBoxC(ptr(self.bound_min), ptr(self.bound_max), ptr(self.bound_nmin),
+                                    ptr(self.bound_nmax))
 
     def launch_with_bounds(self, ctx, stream: int) -> None:
         """Enqueue the k-sweep of every fleet within the resident bounds on `stream`
@@ -1035,21 +830,10 @@ class DeviceFleetTable:
         launch() leaves it."""
         if getattr(self, "_bounds_c", None) is None:
             self.set_bounds()
-        lib = _bind_bounds(ctx.lib)
-        if self._box_c is not None:
-            with ctx._lock:
-                rc = lib.halda_solve_fleets_boxed(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
-                                                  self.ks.ctypes.data, len(self.ks), ctypes.byref(self._box_c),
-                                                  ctypes.byref(self.res), ctypes.c_void_p(stream))
-            if rc != 0:
-                raise RuntimeError(f"halda_solve_fleets_boxed failed ({rc}): {last_error(lib)}")
-            return
-        with ctx._lock:
-            rc = lib.halda_solve_fleets_bounded(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
-                                                self.ks.ctypes.data, len(self.ks), ctypes.byref(self._bounds_c),
-                                                ctypes.byref(self.res), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError(f"halda_solve_fleets_bounded failed ({rc}): {last_error(lib)}")
+        name, bd = (("halda_solve_fleets_bounded", self._bounds_c) if self._box_c is None else
+                    ("halda_solve_fleets_boxed", self._box_c))
+        ctx.call(name, ctx.ctx, *self._sweep_args()[:4], ctypes.byref(bd), ctypes.byref(self.res),
+                 ctypes.c_void_p(stream))
 
     def set_budget(self, k, w0, max_p: int, w_min=None, w_max=None) -> None:
         """Give the table its resident incumbents for halda_solve_fleets_budget: device tensors budget_w0
@@ -1060,52 +844,34 @@ class DeviceFleetTable:
         a shape outside the launch's gate (budget.check_gate)."""
         import torch
 
-        from .budget import check_gate
+        from .budget import check_gate  # (here: budget.py's own imports start from this module)
 
         sizes = self.table.sizes()
-        if isinstance(max_p, bool) or int(max_p) != max_p or max_p < 0:
-            raise ValueError(f"max_p: {max_p!r} is not a non-negative integer")
-        if int(k) < 1:
-            raise ValueError(f"k = {k} must be positive")
+        _check_counts(k, max_p=max_p)
         check_gate(int(sizes.max()), int(sizes.min()), int(max_p), int(k))
         dev = self.out["best_k"].device
         nf, nd, P1 = self.table.n_fleets, self.table.n_devices, int(max_p) + 1
 
-        def tensor(a):
-            if a is None:
-                return None
-            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))
-            if t.numel() != nd:
-                raise ValueError(f"budget array of {t.numel()} entries, expected {nd}")
-            return t.to(device=dev, dtype=torch.int32).contiguous().clone()
-
         if w0 is None:
             raise ValueError("set_budget needs the incumbents' w0")
         self.budget_k = int(k)
-        self.budget_w0, self.budget_min, self.budget_max = tensor(w0), tensor(w_min), tensor(w_max)
+        self.budget_w0, self.budget_min, self.budget_max = (self._tensor(a, nd, "budget") for a in (w0, w_min, w_max))
         self.budget_out = {"status": torch.empty((nf, P1), dtype=torch.int32, device=dev),
                            "obj": torch.empty((nf, P1), dtype=torch.float64, device=dev),
                            "moved": torch.empty((nf, P1), dtype=torch.int32, device=dev),
                            "w": torch.empty((P1, nd), dtype=torch.int32, device=dev),
                            "n": torch.empty((P1, nd), dtype=torch.int32, device=dev)}
         o = self.budget_out
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         self._budget_c = HaldaBudgetC(ptr(self.budget_w0), ptr(self.budget_min), ptr(self.budget_max), int(max_p))
-        self._frontier_c = HaldaFrontierC(nd, o["status"].data_ptr(), o["obj"].data_ptr(), o["moved"].data_ptr(),
-                                          o["w"].data_ptr(), o["n"].data_ptr())
+        self._frontier_c = HaldaFrontierC(nd, *(ptr(o[f]) for f in ("status", "obj", "moved", "w", "n")))
 
     def launch_with_budget(self, ctx, stream: int) -> None:
         """Enqueue the move frontier of every fleet around the resident incumbents on `stream`
         (halda_solve_fleets_budget): self.budget_out. set_budget has checked the gate."""
         if getattr(self, "_budget_c", None) is None:
             raise RuntimeError("launch_with_budget: call set_budget first")
-        lib = _bind_budget(ctx.lib)
-        with ctx._lock:
-            rc = lib.halda_solve_fleets_budget(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
-                                               self.budget_k, ctypes.byref(self._budget_c),
-                                               ctypes.byref(self._frontier_c), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError(f"halda_solve_fleets_budget failed ({rc}): {last_error(lib)}")
+        ctx.call("halda_solve_fleets_budget", ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs), self.budget_k,
+                 ctypes.byref(self._budget_c), ctypes.byref(self._frontier_c), ctypes.c_void_p(stream))
 
     def set_change(self, k, items, w0, max_p: int, max_deficit: int, w_min=None, w_max=None) -> None:
         """Give the table its resident items and incumbents for halda_solve_change. `items` is (parent, sub_off,
@@ -1117,15 +883,10 @@ class DeviceFleetTable:
         place between launches. ValueError for a shape outside the launch's gate (change.check_gate)."""
         import torch
 
-        from .change import check_gate, check_w0
-        from .subfleets import HaldaSubfleetsC, check_items
+        from .change import check_gate, check_w0  # (here: both modules' own imports start from this one)
+        from .subfleets import check_items
 
-        if isinstance(max_p, bool) or int(max_p) != max_p or max_p < 0:
-            raise ValueError(f"max_p: {max_p!r} is not a non-negative integer")
-        if isinstance(max_deficit, bool) or int(max_deficit) != max_deficit or max_deficit < 0:
-            raise ValueError(f"max_deficit: {max_deficit!r} is not a non-negative integer")
-        if int(k) < 1:
-            raise ValueError(f"k = {k} must be positive")
+        _check_counts(k, max_p=max_p, max_deficit=max_deficit)
         parent, sub_off, sub_idx = (np.ascontiguousarray(a, t) for a, t in zip(items, (np.int32, np.int64, np.int32)))
         check_items(self.table.sizes(), parent.astype(np.int64), sub_off, sub_idx.astype(np.int64))
         lens = np.diff(sub_off)
@@ -1138,18 +899,13 @@ class DeviceFleetTable:
         n, tot, P1 = len(parent), int(sub_off[-1]), int(max_p) + 1
         if not torch.is_tensor(w0):
             check_w0(sub_off, np.asarray(w0), int(self.model.L) // int(k), int(max_deficit))
-
-        def tensor(a, dtype=torch.int32, count=tot):
-            if a is None:
-                return None
-            t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
-            if t.numel() != count:
-                raise ValueError(f"change array of {t.numel()} entries, expected {count}")
-            return t.to(device=dev, dtype=dtype).contiguous().clone()
-
         self.change_k = int(k)
-        self.change_items = (tensor(parent, count=n), tensor(sub_off, torch.int64, n + 1), tensor(sub_idx))
-        self.change_w0, self.change_min, self.change_max = tensor(w0), tensor(w_min), tensor(w_max)
+        # (as before the helper: these arrays reach torch in their own dtype and are cast there)
+        self.change_items = (self._tensor(parent, n, "change", cast=None),
+                             self._tensor(sub_off, n + 1, "change", dtype=torch.int64, cast=None),
+                             self._tensor(sub_idx, tot, "change", cast=None))
+        self.change_w0, self.change_min, self.change_max = (self._tensor(a, tot, "change", cast=None)
+                                                            for a in (w0, w_min, w_max))
         self.change_out = {"status": torch.empty((n, P1), dtype=torch.int32, device=dev),
                            "obj": torch.empty((n, P1), dtype=torch.float64, device=dev),
                            "loaded": torch.empty((n, P1), dtype=torch.int32, device=dev),
@@ -1157,12 +913,10 @@ class DeviceFleetTable:
                            "w": torch.empty((P1, tot), dtype=torch.int32, device=dev),
                            "n": torch.empty((P1, tot), dtype=torch.int32, device=dev)}
         o = self.change_out
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        it = self.change_items
-        self._items_c = HaldaSubfleetsC(n, int(lens.min()), int(lens.max()), ptr(it[0]), ptr(it[1]), ptr(it[2]))
+        self._items_c = HaldaSubfleetsC(n, int(lens.min()), int(lens.max()), *(ptr(t) for t in self.change_items))
         self._change_c = HaldaChangeC(ptr(self.change_w0), ptr(self.change_min), ptr(self.change_max), int(max_p),
                                       int(max_deficit))
-        self._change_frontier_c = HaldaChangeFrontierC(tot, *(o[f].data_ptr() for f in
+        self._change_frontier_c = HaldaChangeFrontierC(tot, *(ptr(o[f]) for f in
                                                               ("status", "obj", "loaded", "released", "w", "n")))
 
     def launch_with_change(self, ctx, stream: int) -> None:
@@ -1170,15 +924,9 @@ class DeviceFleetTable:
         set_change has checked the gate."""
         if getattr(self, "_change_c", None) is None:
             raise RuntimeError("launch_with_change: call set_change first")
-        from .change import _bind_change
-
-        lib = _bind_change(ctx.lib)
-        with ctx._lock:
-            rc = lib.halda_solve_change(ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
-                                        ctypes.byref(self._items_c), self.change_k, ctypes.byref(self._change_c),
-                                        ctypes.byref(self._change_frontier_c), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError(f"halda_solve_change failed ({rc}): {last_error(lib)}")
+        ctx.call("halda_solve_change", ctx.ctx, ctypes.byref(self.model), ctypes.byref(self.fs),
+                 ctypes.byref(self._items_c), self.change_k, ctypes.byref(self._change_c),
+                 ctypes.byref(self._change_frontier_c), ctypes.c_void_p(stream))
 
 
 class RcclComm:
@@ -1186,23 +934,19 @@ class RcclComm:
     128-byte id from `RcclComm.unique_id()` on one rank handed to the others by any channel."""
 
     def __init__(self, world: int, rank: int, uid: bytes, device: int = 0):
-        from ._libhalda import HaldaUnavailable, load_library
-
-        self.lib = _bind(load_library())
+        self.lib = load_library()
         self.comm = ctypes.c_void_p()
         rc = self.lib.halda_comm_init(ctypes.byref(self.comm), world, rank, uid, device)
         if rc != 0:
-            raise HaldaUnavailable(f"halda_comm_init failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, "halda_comm_init", rc, HaldaUnavailable)
 
     @staticmethod
     def unique_id() -> bytes:
-        from ._libhalda import load_library
-
-        lib = _bind(load_library())
+        lib = load_library()
         buf = ctypes.create_string_buffer(128)
         rc = lib.halda_comm_unique_id(buf)
         if rc != 0:
-            raise RuntimeError(f"halda_comm_unique_id failed ({rc}): {last_error(lib)}")
+            raise failure(lib, "halda_comm_unique_id", rc)
         return buf.raw
 
     def close(self):
@@ -1219,7 +963,7 @@ class PlanRotation:
 
     def __init__(self, tables, ctx, streams):
         self.ctx = ctx
-        self.lib = _bind(ctx.lib)
+        self.lib = ctx.lib
         self.tables = list(tables)  # (the plans live with them)
         self.n_p, self.n_s = len(self.tables), len(streams)
         self.streams = (ctypes.c_void_p * self.n_s)(*[ctypes.c_void_p(int(x)).value for x in streams])
@@ -1237,7 +981,7 @@ class PlanRotation:
         with self.ctx._lock:
             rc = self.lib.halda_fleets_plan_launch_many(self.plans, self.n_p, self.streams, self.n_s, first, steps)
         if rc != 0:
-            raise RuntimeError(f"halda_fleets_plan_launch_many failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, "halda_fleets_plan_launch_many", rc)
 
 
 class PlanGroup:
@@ -1248,15 +992,12 @@ class PlanGroup:
 
     def __init__(self, tables, ctx):
         self.ctx = ctx
-        self.lib = _bind(ctx.lib)
+        self.lib = ctx.lib
         self.tables = list(tables)  # the group reads their device arrays: they stay alive with it
         plans = (ctypes.c_void_p * len(self.tables))(*[t.plan(ctx)[1].value for t in self.tables])
         self.group = ctypes.c_void_p()
         pers = ctypes.c_int32(0)
-        with ctx._lock:
-            rc = self.lib.halda_fleets_group_create(plans, len(self.tables), ctypes.byref(self.group), ctypes.byref(pers))
-        if rc != 0:
-            raise RuntimeError(f"halda_fleets_group_create failed ({rc}): {last_error(self.lib)}")
+        ctx.call("halda_fleets_group_create", plans, len(self.tables), ctypes.byref(self.group), ctypes.byref(pers))
         self.persistent = bool(pers.value)
 
     def launch(self, first: int, steps: int, stream: int) -> None:
@@ -1265,7 +1006,7 @@ class PlanGroup:
         with self.ctx._lock:
             rc = self.lib.halda_fleets_group_launch(self.group, first, steps, ctypes.c_void_p(stream))
         if rc != 0:
-            raise RuntimeError(f"halda_fleets_group_launch failed ({rc}): {last_error(self.lib)}")
+            raise failure(self.lib, "halda_fleets_group_launch", rc)
 
     def close(self) -> None:
         if getattr(self, "group", None):
@@ -1283,22 +1024,12 @@ def launch_sharded_emulated(dt: "DeviceFleetTable", ctx, world: int, report_rank
     """Latency mode's step sequence for `world` virtual ranks on this one GPU
     (halda_solve_fleets_sharded_emulated): each RCCL all-reduce replaced, in order, by a device reduction
     over the virtual ranks' arrays; virtual rank `report_rank`'s results land in dt.out."""
-    lib = _bind(ctx.lib)
-    with ctx._lock:
-        rc = lib.halda_solve_fleets_sharded_emulated(ctx.ctx, int(world), int(report_rank), ctypes.byref(dt.model),
-                                                     ctypes.byref(dt.fs), dt.ks.ctypes.data, len(dt.ks),
-                                                     ctypes.byref(dt.res), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_fleets_sharded_emulated failed ({rc}): {last_error(lib)}")
+    ctx.call("halda_solve_fleets_sharded_emulated", ctx.ctx, int(world), int(report_rank), *dt._sweep_args(),
+             ctypes.c_void_p(stream))
 
 
 def launch_sharded(dt: "DeviceFleetTable", ctx, comm: RcclComm, stream: int) -> None:
     """Latency mode over RCCL (halda_solve_fleets_sharded): this rank sweeps its share of dt's
     k-candidates and the ranks all-reduce to the same best k / obj_value / w / n (and obj_by_k / status
     when dt holds them) in dt.out, on every rank."""
-    lib = _bind(ctx.lib)
-    with ctx._lock:
-        rc = lib.halda_solve_fleets_sharded(ctx.ctx, comm.comm, ctypes.byref(dt.model), ctypes.byref(dt.fs),
-                                            dt.ks.ctypes.data, len(dt.ks), ctypes.byref(dt.res), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_fleets_sharded failed ({rc}): {last_error(lib)}")
+    ctx.call("halda_solve_fleets_sharded", ctx.ctx, comm.comm, *dt._sweep_args(), ctypes.c_void_p(stream))

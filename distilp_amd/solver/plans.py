@@ -20,11 +20,13 @@ from typing import Iterable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import STATUS_INFEASIBLE, STATUS_OPTIMAL, STATUS_UNSUPPORTED, get_context, last_error
+from ._abi import HaldaFleetResultC, HaldaPlanResultC, HaldaPlansC
+from ._libhalda import (STATUS_INFEASIBLE, STATUS_OPTIMAL, STATUS_UNSUPPORTED, get_context, last_route, ptr,
+                        set_path)
 from .coefficients import HALDAResult, b_prime
 from .fleets import (DEV_CPU_RATE, DEV_CUDA_OK, DEV_GPU, DEV_GPU_RATE, DEV_HEAD, DEV_METAL_AVAIL, DEV_METAL_OK,
-                     DEV_UMA, FleetSolve, FleetTable, HaldaFleetResultC, HaldaPlanResultC, HaldaPlansC, _bind_plans,
-                     _host_struct, fleet_constants, fleet_table, model_struct, open_x_offsets)
+                     DEV_UMA, FleetSolve, FleetTable, _host_struct, fleet_constants, fleet_table, model_struct,
+                     open_x_offsets)
 from .halda import _batch_k_list, _batch_results, _positive_ks
 from .lower import kv_bits_to_factor
 
@@ -42,20 +44,12 @@ Incumbent = Union[HALDAResult, Plan, None]
 def set_plans_path(ctx, path: int) -> None:
     """halda_set_plans_path on a HaldaContext: 0 automatic (default: two launches), 1 always two launches,
     2 the fused launch where it applies."""
-    lib = _bind_plans(ctx.lib)
-    rc = lib.halda_set_plans_path(ctx.ctx, int(path))
-    if rc != 0:
-        raise RuntimeError(f"halda_set_plans_path failed ({rc}): {last_error(lib)}")
+    set_path(ctx, "plans", path)
 
 
 def last_plans_route(ctx) -> str:
     """The route of the context's last halda_solve_fleets_plans call: "fused", "two_launch" or "none"."""
-    lib = _bind_plans(ctx.lib)
-    r = ctypes.c_int(0)
-    rc = lib.halda_last_plans_route(ctx.ctx, ctypes.byref(r))
-    if rc != 0:
-        raise RuntimeError(f"halda_last_plans_route failed ({rc}): {last_error(lib)}")
-    return ("none", "fused", "two_launch")[r.value]
+    return last_route(ctx, "plans")
 
 
 def reason_names(reason: int) -> Tuple[str, ...]:
@@ -285,9 +279,8 @@ class _EvalBuffers:
         self.status, self.bottleneck, self.reason = (np.zeros(nf, np.int32) for _ in range(3))
         self.obj, self.cycle = np.zeros(nf), np.zeros(nf)
         self.x, self.c = np.zeros(ext), np.zeros(ext)
-        p = lambda a: a.ctypes.data  # noqa: E731
-        self.res = HaldaPlanResultC(p(self.status), p(self.obj), p(self.cycle), p(self.bottleneck), p(self.reason),
-                                    p(self.x), p(self.c), p(self.x_off))
+        self.res = HaldaPlanResultC(*(ptr(a) for a in (self.status, self.obj, self.cycle, self.bottleneck,
+                                                       self.reason, self.x, self.c, self.x_off)))
 
     def evaluations(self, table: FleetTable, model: ModelProfile) -> List[PlanEvaluation]:
         """One PlanEvaluation per fleet, obj_value = c.x + sum t_comm + sum xi + kappa formed on the host as
@@ -316,18 +309,14 @@ def evaluate_table(table: FleetTable, model: ModelProfile, k: np.ndarray, w: np.
                    kv_factor: float, device: int = 0) -> _EvalBuffers:
     """halda_eval_plans_host of the plan arrays (int32: k per fleet, w / n in device layout) on a table."""
     ctx = get_context(device)
-    lib = _bind_plans(ctx.lib)
     buf = _EvalBuffers(table)
     fs, keep = _host_struct(table)
     k, w, n = (np.ascontiguousarray(a, np.int32) for a in (k, w, n))
-    pl = HaldaPlansC(k.ctypes.data, w.ctypes.data, n.ctypes.data)
+    pl = HaldaPlansC(ptr(k), ptr(w), ptr(n))
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_eval_plans_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(pl),
-                                       ctypes.byref(buf.res))
+    ctx.call("halda_eval_plans_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(pl),
+             ctypes.byref(buf.res))
     del keep
-    if rc != 0:
-        raise RuntimeError(f"halda_eval_plans_host failed ({rc}): {last_error(lib)}")
     return buf
 
 
@@ -376,7 +365,6 @@ def solve_plans_table(table: FleetTable, model: ModelProfile, pos: List[int], k:
     """One halda_solve_fleets_plans_host call on a packed table: the sweep's FleetSolve (want_x="open") and the
     incumbents' evaluation."""
     ctx = get_context(device)
-    lib = _bind_plans(ctx.lib)
     nf, nd, nk = table.n_fleets, table.n_devices, len(pos)
     xsel = open_x_offsets(table, model, pos)
     ext = int(np.max(xsel + np.repeat(7 * table.sizes() + 1, nk), initial=0)) if (xsel >= 0).any() else 0
@@ -391,15 +379,12 @@ def solve_plans_table(table: FleetTable, model: ModelProfile, pos: List[int], k:
     buf = _EvalBuffers(table)
     fs, keep = _host_struct(table)
     k, w, n = (np.ascontiguousarray(a, np.int32) for a in (k, w, n))
-    pl = HaldaPlansC(k.ctypes.data, w.ctypes.data, n.ctypes.data)
+    pl = HaldaPlansC(ptr(k), ptr(w), ptr(n))
     karr = np.asarray(pos, np.int32)
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_solve_fleets_plans_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
-                                               ctypes.byref(pl), ctypes.byref(buf.res), ctypes.byref(r))
+    ctx.call("halda_solve_fleets_plans_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
+             ctypes.byref(pl), ctypes.byref(buf.res), ctypes.byref(r))
     del keep
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_fleets_plans_host failed ({rc}): {last_error(lib)}")
     return out, buf
 
 

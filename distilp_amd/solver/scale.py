@@ -32,12 +32,14 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import STATUS_OPTIMAL, get_context, last_error
+from ._abi import HaldaChangeSubsetFrontierC, HaldaChangeSubsetsC
+from ._libhalda import STATUS_OPTIMAL, get_context, ptr
 from .bounds import INT32_MAX
 from .budget import check_incumbent
 from .change import ChangePoint, check_gate, check_released, halda_change_frontiers
 from .coefficients import HALDAResult
-from .fleets import HaldaFleetsC, HaldaModelC, _bind, _host_struct, fleet_table, model_struct
+from .fleets import _host_struct, fleet_table, model_struct
+from .fleets import _bind as _bind_scale  # noqa: F401 -- the identity, for callers from before load_library bound all
 from .lower import kv_bits_to_factor
 from .plans import Incumbent
 from .subsets import MAX_DEVICES, SUBSETS_MAX, candidate_lists, droppable
@@ -49,46 +51,9 @@ MAX_DROP = 63
 SolveLists = Callable[[int, List[List[int]]], List[List[ChangePoint]]]
 
 
-class HaldaChangeSubsetsC(ctypes.Structure):
-    _fields_ = [("w0", ctypes.c_void_p), ("w_min", ctypes.c_void_p), ("w_max", ctypes.c_void_p),
-                ("min_drop", ctypes.c_int32), ("max_drop", ctypes.c_int32), ("max_p", ctypes.c_int32),
-                ("keep_mask", ctypes.c_void_p)]
-
-
-class HaldaChangeSubsetFrontierC(ctypes.Structure):
-    _fields_ = [("status", ctypes.c_void_p), ("obj", ctypes.c_void_p), ("dropped_mask", ctypes.c_void_p),
-                ("loaded", ctypes.c_void_p), ("released", ctypes.c_void_p), ("w", ctypes.c_void_p),
-                ("n", ctypes.c_void_p)]
-
-
-def _bind_scale(lib):
-    lib = _bind(lib)
-    if getattr(lib, "_scale_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_solve_change_subsets.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_int32,
-                                               P(HaldaChangeSubsetsC), P(HaldaChangeSubsetFrontierC), ctypes.c_void_p]
-    lib.halda_solve_change_subsets.restype = ctypes.c_int
-    lib.halda_solve_change_subsets_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), ctypes.c_int32,
-                                                    P(HaldaChangeSubsetsC), P(HaldaChangeSubsetFrontierC)]
-    lib.halda_solve_change_subsets_host.restype = ctypes.c_int
-    lib.halda_change_subsets_max_deficit.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
-                                                     ctypes.c_int32]
-    lib.halda_change_subsets_max_deficit.restype = ctypes.c_int64
-    lib.halda_change_subsets_launch_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
-    lib.halda_change_subsets_launch_bytes.restype = ctypes.c_int64
-    lib.halda_set_change_subsets_chunk.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-    lib.halda_set_change_subsets_chunk.restype = ctypes.c_int
-    lib._scale_bound = True
-    return lib
-
-
 def set_change_subsets_chunk(ctx, nbytes: int) -> None:
     """halda_set_change_subsets_chunk on a HaldaContext: the scratch cap of one launch (0: the default)."""
-    lib = _bind_scale(ctx.lib)
-    rc = lib.halda_set_change_subsets_chunk(ctx.ctx, int(nbytes))
-    if rc != 0:
-        raise RuntimeError(f"halda_set_change_subsets_chunk failed ({rc}): {last_error(lib)}")
+    ctx.call("halda_set_change_subsets_chunk", ctx.ctx, int(nbytes), lock=False)
 
 
 # ---------------------------------------------------------------- the gate's arithmetic
@@ -191,7 +156,6 @@ def solve_change_subsets_table(table, model: ModelProfile, k: int, w0: np.ndarra
     of the table (laid out by dev_off), keep_masks uint64 per fleet or None. RuntimeError (HALDA_E_ARG) for a
     call outside the gate."""
     ctx = get_context(device)
-    lib = _bind_scale(ctx.lib)
     nf, D1, P1 = table.n_fleets, int(max_drop) - int(min_drop) + 1, int(max_p) + 1
     if D1 < 1 or P1 < 1:
         raise ValueError("needs min_drop <= max_drop and max_p >= 0")
@@ -207,17 +171,13 @@ def solve_change_subsets_table(table, model: ModelProfile, k: int, w0: np.ndarra
         if a is not None and len(a) != nd:
             raise ValueError(f"an array of {len(a)} entries for a table of {nd} devices")
     km = None if keep_masks is None else np.ascontiguousarray(keep_masks, np.uint64)
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     sub = HaldaChangeSubsetsC(ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(min_drop), int(max_drop), int(max_p), ptr(km))
-    fr = HaldaChangeSubsetFrontierC(*(getattr(out, f).ctypes.data for f in
+    fr = HaldaChangeSubsetFrontierC(*(ptr(getattr(out, f)) for f in
                                       ("status", "obj", "dropped_mask", "loaded", "released", "w", "n")))
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_solve_change_subsets_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k), ctypes.byref(sub),
-                                                 ctypes.byref(fr))
+    ctx.call("halda_solve_change_subsets_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k), ctypes.byref(sub),
+             ctypes.byref(fr))
     del hold
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_change_subsets_host failed ({rc}): {last_error(lib)}")
     return out
 
 

@@ -25,11 +25,12 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import get_context, last_error
+from ._abi import BYTE_FIELDS, F64_FIELDS, HaldaFleetResultC, HaldaSubfleetsC
+from ._libhalda import get_context, last_route, ptr, set_path
 from .coefficients import HALDAResult
-from .fleets import (_PACKER, BYTE_FIELDS, DEV_CPU_RATE, DEV_HEAD, F64_FIELDS, FleetSolve, FleetTable,
-                     HaldaFleetResultC, HaldaFleetsC, HaldaModelC, _bind, _host_struct, _scratch, fleet_constants,
-                     fleet_table, model_struct, open_x_offsets)
+from .fleets import (_PACKER, DEV_CPU_RATE, DEV_HEAD, FleetSolve, FleetTable, _host_struct, _scratch,
+                     fleet_constants, fleet_table, model_struct, open_x_offsets)
+from .fleets import _bind as _bind_sub  # noqa: F401 -- the identity, for callers from before load_library bound all
 from .halda import _batch_k_list, _batch_results, _positive_ks
 from .lower import kv_bits_to_factor
 
@@ -38,46 +39,14 @@ from .lower import kv_bits_to_factor
 SUBFLEET_CHUNK_DEVICES = 1 << 21
 
 
-class HaldaSubfleetsC(ctypes.Structure):
-    _fields_ = [("n_items", ctypes.c_int32), ("min_devices", ctypes.c_int32), ("max_devices", ctypes.c_int32),
-                ("parent", ctypes.c_void_p), ("sub_off", ctypes.c_void_p), ("sub_idx", ctypes.c_void_p)]
-
-
-def _bind_sub(lib):
-    lib = _bind(lib)
-    if getattr(lib, "_subfleets_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_solve_subfleets.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaSubfleetsC),
-                                          ctypes.c_void_p, ctypes.c_int32, P(HaldaFleetResultC), ctypes.c_void_p]
-    lib.halda_solve_subfleets.restype = ctypes.c_int
-    lib.halda_solve_subfleets_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaSubfleetsC),
-                                               ctypes.c_void_p, ctypes.c_int32, P(HaldaFleetResultC)]
-    lib.halda_solve_subfleets_host.restype = ctypes.c_int
-    lib.halda_set_subfleets_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.halda_set_subfleets_path.restype = ctypes.c_int
-    lib.halda_last_subfleets_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-    lib.halda_last_subfleets_route.restype = ctypes.c_int
-    lib._subfleets_bound = True
-    return lib
-
-
 def set_subfleets_path(ctx, path: int) -> None:
     """halda_set_subfleets_path on a HaldaContext: 0 automatic (default), 1 always expand (test path)."""
-    lib = _bind_sub(ctx.lib)
-    rc = lib.halda_set_subfleets_path(ctx.ctx, int(path))
-    if rc != 0:
-        raise RuntimeError(f"halda_set_subfleets_path failed ({rc}): {last_error(lib)}")
+    set_path(ctx, "subfleets", path)
 
 
 def last_subfleets_route(ctx) -> str:
     """The route of the context's last halda_solve_subfleets call: "fused", "expand" or "none"."""
-    lib = _bind_sub(ctx.lib)
-    r = ctypes.c_int(0)
-    rc = lib.halda_last_subfleets_route(ctx.ctx, ctypes.byref(r))
-    if rc != 0:
-        raise RuntimeError(f"halda_last_subfleets_route failed ({rc}): {last_error(lib)}")
-    return ("none", "fused", "expand")[r.value]
+    return last_route(ctx, "subfleets")
 
 
 def pack_items(sizes: np.ndarray, items: Sequence[Tuple[int, Sequence[int]]]):
@@ -233,7 +202,6 @@ def solve_items(table: FleetTable, parent: np.ndarray, sub_off: np.ndarray, sub_
     if fleets is not None:
         check_item_heads(fleets, table, parent, gt.heads, model)
     ctx = get_context(device)  # (after the items' own errors: those need no GPU)
-    lib = _bind_sub(ctx.lib)
     n, tot, nk = len(parent), int(sub_off[-1]), len(pos)
     lens = np.diff(sub_off)
     xsel = open_x_offsets(gt, model, pos)
@@ -254,16 +222,12 @@ def solve_items(table: FleetTable, parent: np.ndarray, sub_off: np.ndarray, sub_
     pp, po, px = _scratch("subitems", (((n,), np.int32), ((n + 1,), np.int64), ((max(tot, 1),), np.int32)), pinned=True)
     pp[:], po[:], px[:tot] = parent, sub_off, sub_idx
     parent, sub_off, sub_idx = pp, po, px
-    it = HaldaSubfleetsC(n, int(lens.min()), int(lens.max()), parent.ctypes.data, sub_off.ctypes.data,
-                         sub_idx.ctypes.data)
+    it = HaldaSubfleetsC(n, int(lens.min()), int(lens.max()), ptr(parent), ptr(sub_off), ptr(sub_idx))
     karr = np.asarray(pos, np.int32)
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_solve_subfleets_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it),
-                                            karr.ctypes.data, nk, ctypes.byref(r))
+    ctx.call("halda_solve_subfleets_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it),
+             karr.ctypes.data, nk, ctypes.byref(r))
     del keep
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_subfleets_host failed ({rc}): {last_error(lib)}")
     return _batch_results(gt, res, pos, model, consts=gt.consts)
 
 

@@ -27,9 +27,11 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import STATUS_OPTIMAL, get_context, last_error
+from ._abi import HaldaSubsetFrontierC, HaldaSubsetsC
+from ._libhalda import STATUS_OPTIMAL, get_context, last_route, ptr, set_path
 from .coefficients import HALDAResult
-from .fleets import DEV_HEAD, HaldaFleetsC, HaldaModelC, _bind, _host_struct, fleet_table, model_struct
+from .fleets import DEV_HEAD, _host_struct, fleet_table, model_struct
+from .fleets import _bind as _bind_subsets  # noqa: F401 -- the identity, for callers from before load_library bound all
 from .halda import _batch_k_list, _positive_ks
 from .lower import kv_bits_to_factor
 from .subfleets import check_item_heads, halda_solve_subfleets
@@ -40,52 +42,14 @@ SUBSETS_MAX = 1 << 20  # include/halda.h HALDA_SUBSETS_MAX: candidates per fleet
 SolveLists = Callable[[List[List[int]]], List[Optional[HALDAResult]]]
 
 
-class HaldaSubsetsC(ctypes.Structure):
-    _fields_ = [("max_drop", ctypes.c_int32), ("keep_mask", ctypes.c_void_p)]
-
-
-class HaldaSubsetFrontierC(ctypes.Structure):
-    _fields_ = [("status", ctypes.c_void_p), ("obj", ctypes.c_void_p), ("dropped_mask", ctypes.c_void_p),
-                ("best_k", ctypes.c_void_p)]
-
-
-def _bind_subsets(lib):
-    lib = _bind(lib)
-    if getattr(lib, "_subsets_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_solve_subsets.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaSubsetsC),
-                                        ctypes.c_void_p, ctypes.c_int32, P(HaldaSubsetFrontierC), ctypes.c_void_p]
-    lib.halda_solve_subsets.restype = ctypes.c_int
-    lib.halda_solve_subsets_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), P(HaldaFleetsC), P(HaldaSubsetsC),
-                                             ctypes.c_void_p, ctypes.c_int32, P(HaldaSubsetFrontierC)]
-    lib.halda_solve_subsets_host.restype = ctypes.c_int
-    lib.halda_subsets_count.argtypes = [ctypes.c_int32, ctypes.c_int32]
-    lib.halda_subsets_count.restype = ctypes.c_int64
-    lib.halda_set_subsets_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.halda_set_subsets_path.restype = ctypes.c_int
-    lib.halda_last_subsets_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-    lib.halda_last_subsets_route.restype = ctypes.c_int
-    lib._subsets_bound = True
-    return lib
-
-
 def set_subsets_path(ctx, path: int) -> None:
     """halda_set_subsets_path on a HaldaContext: 0 automatic (default), 1 always expand (test path)."""
-    lib = _bind_subsets(ctx.lib)
-    rc = lib.halda_set_subsets_path(ctx.ctx, int(path))
-    if rc != 0:
-        raise RuntimeError(f"halda_set_subsets_path failed ({rc}): {last_error(lib)}")
+    set_path(ctx, "subsets", path)
 
 
 def last_subsets_route(ctx) -> str:
     """The routes of the context's last halda_solve_subsets call: "fused", "expand", "mixed" or "none"."""
-    lib = _bind_subsets(ctx.lib)
-    r = ctypes.c_int(0)
-    rc = lib.halda_last_subsets_route(ctx.ctx, ctypes.byref(r))
-    if rc != 0:
-        raise RuntimeError(f"halda_last_subsets_route failed ({rc}): {last_error(lib)}")
-    return ("none", "fused", "expand", "mixed")[r.value]
+    return last_route(ctx, "subsets")
 
 
 # ---------------------------------------------------------------- enumeration
@@ -193,22 +157,18 @@ def solve_subsets_table(table, model: ModelProfile, pos: List[int], kv_factor: f
     """One halda_solve_subsets_host call on a packed table: (status, obj, dropped_mask, best_k), each
     [n_fleets, max_drop + 1]. obj is the GPU-formed objective."""
     ctx = get_context(device)
-    lib = _bind_subsets(ctx.lib)
     nf, P1 = table.n_fleets, int(max_drop) + 1
     status, obj = np.zeros((nf, P1), np.int32), np.zeros((nf, P1))
     mask, best_k = np.zeros((nf, P1), np.uint64), np.zeros((nf, P1), np.int32)
     fs, hold = _host_struct(table)
     km = None if keep_masks is None else np.ascontiguousarray(keep_masks, np.uint64)
-    sub = HaldaSubsetsC(int(max_drop), None if km is None else km.ctypes.data)
-    fr = HaldaSubsetFrontierC(status.ctypes.data, obj.ctypes.data, mask.ctypes.data, best_k.ctypes.data)
+    sub = HaldaSubsetsC(int(max_drop), ptr(km))
+    fr = HaldaSubsetFrontierC(ptr(status), ptr(obj), ptr(mask), ptr(best_k))
     karr = np.asarray(pos, np.int32)
     m = model_struct(model, kv_factor)
-    with ctx._lock:
-        rc = lib.halda_solve_subsets_host(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(sub),
-                                          karr.ctypes.data, len(pos), ctypes.byref(fr))
+    ctx.call("halda_solve_subsets_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(sub),
+             karr.ctypes.data, len(pos), ctypes.byref(fr))
     del hold
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_subsets_host failed ({rc}): {last_error(lib)}")
     return status, obj, mask, best_k
 
 

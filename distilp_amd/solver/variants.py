@@ -18,10 +18,11 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._libhalda import get_context, last_error
+from ._abi import HaldaFleetResultC, HaldaModelC
+from ._libhalda import get_context, last_route, set_path
 from .coefficients import HALDAResult
-from .fleets import (FleetSolve, HaldaFleetResultC, HaldaFleetsC, HaldaModelC, _bind, _host_struct, _scratch,
-                     fleet_constants, fleet_table, model_struct, open_x_offsets)
+from .fleets import FleetSolve, _host_struct, _scratch, fleet_constants, fleet_table, model_struct, open_x_offsets
+from .fleets import _bind as _bind_var  # noqa: F401 -- the identity, for callers from before load_library bound all
 from .halda import _batch_k_list, _batch_results, _positive_ks
 from .lower import kv_bits_to_factor
 
@@ -30,41 +31,14 @@ Variant = Tuple[ModelProfile, str]
 MAX_VARIANTS = 65535  # halda_solve_variants: blockIdx.y is the variant
 
 
-def _bind_var(lib):
-    lib = _bind(lib)
-    if getattr(lib, "_variants_bound", False):
-        return lib
-    P = ctypes.POINTER
-    lib.halda_solve_variants.argtypes = [ctypes.c_void_p, P(HaldaModelC), ctypes.c_int32, P(HaldaFleetsC),
-                                         ctypes.c_void_p, ctypes.c_int32, P(HaldaFleetResultC), ctypes.c_void_p]
-    lib.halda_solve_variants.restype = ctypes.c_int
-    lib.halda_solve_variants_host.argtypes = [ctypes.c_void_p, P(HaldaModelC), ctypes.c_int32, P(HaldaFleetsC),
-                                              ctypes.c_void_p, ctypes.c_int32, P(HaldaFleetResultC)]
-    lib.halda_solve_variants_host.restype = ctypes.c_int
-    lib.halda_set_variants_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.halda_set_variants_path.restype = ctypes.c_int
-    lib.halda_last_variants_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-    lib.halda_last_variants_route.restype = ctypes.c_int
-    lib._variants_bound = True
-    return lib
-
-
 def set_variants_path(ctx, path: int) -> None:
     """halda_set_variants_path on a HaldaContext: 0 automatic (default), 1 always loop (test path)."""
-    lib = _bind_var(ctx.lib)
-    rc = lib.halda_set_variants_path(ctx.ctx, int(path))
-    if rc != 0:
-        raise RuntimeError(f"halda_set_variants_path failed ({rc}): {last_error(lib)}")
+    set_path(ctx, "variants", path)
 
 
 def last_variants_route(ctx) -> str:
     """The route of the context's last halda_solve_variants call: "fused", "loop" or "none"."""
-    lib = _bind_var(ctx.lib)
-    r = ctypes.c_int(0)
-    rc = lib.halda_last_variants_route(ctx.ctx, ctypes.byref(r))
-    if rc != 0:
-        raise RuntimeError(f"halda_last_variants_route failed ({rc}): {last_error(lib)}")
-    return ("none", "fused", "loop")[r.value]
+    return last_route(ctx, "variants")
 
 
 def model_grid(model: ModelProfile, kv_bits: Sequence[str] = ("8bit",), n_kv: Optional[Iterable[int]] = None
@@ -129,7 +103,6 @@ def solve_variants_table(table, variants: Sequence[Variant], pos: List[int], dev
     """One halda_solve_variants_host call on a packed table: per variant the FleetSolve (want_x="open") of
     its slice -- views of one result buffer, with the variant's x / c rows from 0 and the per-table x_off."""
     ctx = get_context(device)
-    lib = _bind_var(ctx.lib)
     nv, nf, nd, nk = len(variants), table.n_fleets, table.n_devices, len(pos)
     m0 = variants[0][0]
     xsel = open_x_offsets(table, m0, pos)
@@ -147,11 +120,8 @@ def solve_variants_table(table, variants: Sequence[Variant], pos: List[int], dev
     fs, keep = _host_struct(table)
     karr = np.asarray(pos, np.int32)
     ms = model_structs(variants)
-    with ctx._lock:
-        rc = lib.halda_solve_variants_host(ctx.ctx, ms, nv, ctypes.byref(fs), karr.ctypes.data, nk, ctypes.byref(r))
+    ctx.call("halda_solve_variants_host", ctx.ctx, ms, nv, ctypes.byref(fs), karr.ctypes.data, nk, ctypes.byref(r))
     del keep
-    if rc != 0:
-        raise RuntimeError(f"halda_solve_variants_host failed ({rc}): {last_error(lib)}")
     o = variant_offsets(nv, nf, nd, nk)
     out = []
     for v in range(nv):

@@ -2,9 +2,12 @@
 
 import ctypes
 import re
+import shutil
+import subprocess
 
 import pytest
 
+from distilp_amd.solver import _abi
 from distilp_amd.solver import _libhalda as lh
 
 from .conftest import REPO
@@ -12,13 +15,95 @@ from .conftest import REPO
 HEADER = REPO / "include" / "halda.h"
 
 
+def declared_parameters():
+    """name -> (return type, [parameter declarations]) of every function the header declares."""
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"^\s*(int|int64_t|void)\s+\**(halda_\w+)\s*\(([^)]*)\)\s*;", text, re.M):
+        params = " ".join(params.split())
+        out[name] = (ret, [] if params == "void" else [p.strip() for p in params.split(",")])
+    return out
+
+
+def declared_prototypes():
+    """name -> (return type, parameter count) of every function the header declares."""
+    return {name: (ret, len(params)) for name, (ret, params) in declared_parameters().items()}
+
+
 def declared_functions():
-    text = HEADER.read_text()
-    return sorted(set(re.findall(r"^\s*(?:int|int64_t|void)\s+\**(halda_\w+)\s*\(", text, re.M)))
+    return sorted(declared_prototypes())
 
 
 def test_header_declares_the_binding_exports():
     assert declared_functions() == sorted(lh.EXPORTS)
+
+
+def test_prototype_table_matches_the_header():
+    """Every declaration's parameter count and return type (int, int64_t, void) against _abi.PROTOTYPES."""
+    restype = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None}
+    decl = declared_prototypes()
+    assert len(decl) == 71 and sorted(decl) == sorted(_abi.PROTOTYPES)
+    for name, (ret, n_params) in decl.items():
+        got_ret, got_args = _abi.PROTOTYPES[name]
+        assert got_ret is restype[ret], name
+        assert len(got_args) == n_params, name
+
+
+def test_prototype_table_argument_types_match_the_header():
+    """Beyond the counts: a scalar parameter has exactly its ctypes type, a pointer to one of the header's structs
+    is POINTER of that struct's class, and every other pointer parameter is some pointer type."""
+    scalar = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+              "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t}
+    struct = {cname: cls for cls, cname in _abi.STRUCTS.items()}
+    for name, (_, params) in declared_parameters().items():
+        for decl, got in zip(params, _abi.PROTOTYPES[name][1]):
+            base = [w for w in re.sub(r"\*", " ", decl).split() if w != "const"][0]
+            if "*" not in decl:
+                assert got is scalar[base], (name, decl)
+            elif base in struct:
+                assert decl.count("*") == 1 and got is ctypes.POINTER(struct[base]), (name, decl)
+            else:
+                assert got in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(got, ctypes._Pointer), (name, decl)
+
+
+def test_load_library_declares_every_prototype(lib):
+    """No entry point is left with ctypes' defaults (int arguments, int result): the default library and one
+    opened by path alike."""
+    for L in (lib, lh.load_library(lh.LIB_PATH)):
+        for name, (ret, args) in _abi.PROTOTYPES.items():
+            fn = getattr(L, name)
+            assert fn.argtypes is not None and list(fn.argtypes) == args, name
+            assert fn.restype is ret, name
+
+
+def host_cc():
+    """The host C compiler: cc, else ROCm's clang."""
+    return shutil.which("cc") or (str(LLVM / "clang") if (LLVM / "clang").exists() else None)
+
+
+def test_every_struct_layout_matches_the_compiled_header(tmp_path):
+    """sizeof of each of the 18 structs and offsetof of every field, printed by a C program generated from
+    _abi.STRUCTS and compiled against include/halda.h, against ctypes.sizeof and Class.field.offset."""
+    cc = host_cc()
+    if cc is None:
+        pytest.skip("no host C compiler")
+    assert len(_abi.STRUCTS) == 18
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "halda.h"', "int main(void) {"]
+    want = []
+    for cls, cname in _abi.STRUCTS.items():
+        lines.append(f'    printf("%zu\\n", sizeof({cname}));')
+        want.append((cname, ctypes.sizeof(cls)))
+        for field, _ in cls._fields_:
+            lines.append(f'    printf("%zu\\n", offsetof({cname}, {field}));')
+            want.append((f"{cname}.{field}", getattr(cls, field).offset))
+    lines += ["    return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c99", "-I", str(HEADER.parent), "-o", str(exe), str(src)], check=True,
+                   capture_output=True)
+    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert len(got) == len(want)
+    assert [(n, g) for (n, _), g in zip(want, got)] == want
 
 
 @pytest.fixture(scope="module")

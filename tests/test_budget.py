@@ -191,7 +191,7 @@ def test_c_gate_equals_python_gate_and_entries_reject_bad_arguments():
     HALDA_E_ARG (-22) for a NULL argument before any HIP call."""
     if not lh.LIB_PATH.exists():
         pytest.fail(f"{lh.LIB_PATH} not built (run __graft_entry__.build())")
-    lib = bg._bind_budget(lh.load_library())
+    lib = lh.load_library()
     for M, P, k in ((1, 0, 1), (16, 8, 2), (64, 8, 1), (64, 2, 1), (16, 63, 1), (64, 63, 2), (3, 5, 4)):
         assert lib.halda_budget_lds_bytes(M, P, k) == bg.budget_lds_bytes(M, P, k), (M, P, k)
     assert lib.halda_budget_lds_bytes(0, 1, 1) == -1 and lib.halda_budget_lds_bytes(4, -1, 1) == -1

@@ -211,7 +211,7 @@ def test_c_gate_equals_python_gate_and_entries_reject_bad_arguments():
     (-22) for a NULL argument before any HIP call."""
     if not lh.LIB_PATH.exists():
         pytest.fail(f"{lh.LIB_PATH} not built (run __graft_entry__.build())")
-    lib = ch._bind_change(lh.load_library())
+    lib = lh.load_library()
     for a in ((1, 0, 0, 1), (16, 8, 12, 2), (64, 8, 1, 1), (64, 2, 74, 1), (16, 63, 0, 1), (64, 63, 128, 2),
               (3, 5, 7, 4), (15, 4, 30, 2)):
         assert lib.halda_change_lds_bytes(*a) == ch.change_lds_bytes(*a), a

@@ -15,7 +15,7 @@ from distilp_amd.solver import (halda_replace_within, halda_solve, halda_solve_b
 from distilp_amd.solver import bounds as bd
 from distilp_amd.solver import plans as pl
 from distilp_amd.solver.fleets import (BYTE_FIELDS, F64_FIELDS, DeviceFleetTable, HaldaBoundsC, HaldaFleetResultC,
-                                       _bind_bounds, _fleets_struct, fleet_table, model_struct, solve_table)
+                                       _fleets_struct, fleet_table, model_struct, solve_table)
 from distilp_amd.synth import synth_fleet
 
 from . import bounds_cases as bc
@@ -82,7 +82,7 @@ class Run:
         return out
 
     def plain(self, ctx):
-        lib = _bind_bounds(ctx.lib)
+        lib = ctx.lib
         rc = lib.halda_solve_fleets(ctx.ctx, ctypes.byref(self.m), ctypes.byref(self.fs), self.ks.ctypes.data,
                                     len(self.ks), ctypes.byref(self.res), None)
         assert rc == 0, lh.last_error(lib)
@@ -90,7 +90,7 @@ class Run:
 
     def bounded(self, ctx, w_min, w_max, null_struct=False):
         """One halda_solve_fleets_bounded call; w_min / w_max host int arrays or None (a NULL pointer)."""
-        lib = _bind_bounds(ctx.lib)
+        lib = ctx.lib
         keep = [None if a is None else self.torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.dev)
                 for a in (w_min, w_max)]
         b = HaldaBoundsC(*[None if t is None else t.data_ptr() for t in keep])

@@ -17,7 +17,7 @@ from distilp_amd.solver import (halda_replace_within, halda_solve_batch, halda_s
                                 halda_solve_bounded_batch)
 from distilp_amd.solver import bounds as bd
 from distilp_amd.solver import plans as pl
-from distilp_amd.solver.fleets import DeviceFleetTable, HaldaBoxC, _bind_bounds, fleet_table
+from distilp_amd.solver.fleets import DeviceFleetTable, HaldaBoxC, fleet_table
 
 from . import bounds_cases as bc
 from . import box_cases as xc
@@ -41,7 +41,7 @@ def ctx():
 class BoxRun(Run):
     def boxed(self, ctx, box, null_struct=False):
         """One halda_solve_fleets_boxed call; box: four host int arrays or None (a NULL pointer) each."""
-        lib = _bind_bounds(ctx.lib)
+        lib = ctx.lib
         keep = [None if a is None else self.torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.dev)
                 for a in box]
         b = HaldaBoxC(*[None if t is None else t.data_ptr() for t in keep])

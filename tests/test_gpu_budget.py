@@ -450,11 +450,11 @@ def test_launches_on_two_streams_give_the_synchronous_answers(llama_online_model
 def test_c_entry_rejects_what_is_outside_the_gate(llama_online_model):
     import ctypes
 
-    from distilp_amd.solver.fleets import HaldaBudgetC, HaldaFrontierC, _bind_budget, _host_struct, model_struct
+    from distilp_amd.solver.fleets import HaldaBudgetC, HaldaFrontierC, _host_struct, model_struct
 
     model = llama_online_model
     ctx = lh.get_context(0)
-    lib = _bind_budget(ctx.lib)
+    lib = ctx.lib
     table = fleet_table([list(bc.devices(4, 0))], model)
     fs, keep = _host_struct(table)
     m = model_struct(model, bc.KV)

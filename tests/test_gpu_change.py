@@ -335,7 +335,7 @@ def test_c_entry_rejects_what_is_outside_the_gate(llama_online_model):
 
     model = llama_online_model
     ctx = lh.get_context(0)
-    lib = ch._bind_change(ctx.lib)
+    lib = ctx.lib
     table = fleet_table([list(bc.devices(4, 0))], model)
     fs, keep = _host_struct(table)
     m = model_struct(model, bc.KV)

@@ -262,7 +262,7 @@ def _c_entry(model, e, out_fill=-9):
 
     m = dc.model_at(model, e["L"])
     ctx = lh.get_context(0)
-    lib = ch._bind_change(ctx.lib)
+    lib = ctx.lib
     table = fleet_table([e["devs"]], m)
     fs, keep = _host_struct(table)
     ms = model_struct(m, bc.KV)

@@ -139,7 +139,7 @@ def test_emulated_sharding_rejects_bad_k_lists_before_any_allocation():
 
     from distilp_amd.common import DeviceProfile, ModelProfileSplit
     from distilp_amd.solver._libhalda import get_context
-    from distilp_amd.solver.fleets import DeviceFleetTable, _bind, fleet_table, launch_sharded_emulated
+    from distilp_amd.solver.fleets import DeviceFleetTable, fleet_table, launch_sharded_emulated
     from distilp_amd.synth import load_model_dict, synth_fleet
 
     m2 = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
@@ -152,7 +152,7 @@ def test_emulated_sharding_rejects_bad_k_lists_before_any_allocation():
     a.launch(ctx, stream.cuda_stream)
     b = DeviceFleetTable(table, m2, ks, 0.5, dev, want_per_k=True)
     launch_sharded_emulated(b, ctx, 2, 0, stream.cuda_stream)  # the scratch exists before the bad calls
-    lib = _bind(ctx.lib)
+    lib = ctx.lib
     bad = [(-1, ks), (0, ks), (2000, ks), (3, [2, 1, 4]), (2, [1, 1]), (2, [0, 1]), (2, [-2, 1])]
     for n_k, kl in bad:
         karr = np.zeros(max(len(kl), 1), np.int32)

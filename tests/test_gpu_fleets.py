@@ -11,7 +11,7 @@ import pytest
 from distilp_amd.common import DeviceProfile
 from distilp_amd.solver import halda_solve_batch
 from distilp_amd.solver._libhalda import HaldaBatchC, HaldaResultC, get_context
-from distilp_amd.solver.fleets import _bind, fleet_table, halda_solve_fleets, solve_table
+from distilp_amd.solver.fleets import fleet_table, halda_solve_fleets, solve_table
 from distilp_amd.solver.lower import lower_fleet
 from distilp_amd.synth import synth_fleet
 
@@ -36,7 +36,7 @@ def _d2h(ptr, count, dtype):
 
 def _lowered():
     ctx = get_context(0)
-    lib = _bind(ctx.lib)
+    lib = ctx.lib
     b, r = HaldaBatchC(), HaldaResultC()
     assert lib.halda_last_lowered(ctx.ctx, ctypes.byref(b), ctypes.byref(r)) == 0
     return b

@@ -29,7 +29,7 @@ from distilp_amd.solver import _libhalda as lh
 from distilp_amd.solver import subfleets as sf
 from distilp_amd.solver import variants as va
 from distilp_amd.solver.fleets import (BYTE_FIELDS, F64_FIELDS, HaldaBoxC, HaldaFleetResultC, HaldaPlanResultC,
-                                       HaldaPlansC, _bind_bounds, _bind_plans, _fleets_struct, _host_arrays,
+                                       HaldaPlansC, _fleets_struct, _host_arrays,
                                        fleet_table, model_struct)
 from distilp_amd.synth import synth_fleet
 
@@ -65,7 +65,7 @@ def _table(model):
 
 
 def _lib(ctx):
-    return va._bind_var(sf._bind_sub(_bind_plans(_bind_bounds(ctx.lib))))
+    return ctx.lib
 
 
 @lru_cache(maxsize=None)

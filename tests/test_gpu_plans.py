@@ -14,7 +14,7 @@ from distilp_amd.solver import (halda_evaluate_plan, halda_evaluate_plans_batch,
                                 halda_solve, halda_solve_batch)
 from distilp_amd.solver import plans as pl
 from distilp_amd.solver.fleets import (BYTE_FIELDS, F64_FIELDS, DeviceFleetTable, HaldaFleetResultC,
-                                       HaldaPlanResultC, HaldaPlansC, _bind_plans, _fleets_struct, fleet_table,
+                                       HaldaPlanResultC, HaldaPlansC, _fleets_struct, fleet_table,
                                        model_struct, solve_table)
 from distilp_amd.synth import synth_fleet
 
@@ -201,7 +201,7 @@ class Run:
         return out
 
     def both(self, ctx, stream=None):
-        lib = _bind_plans(ctx.lib)
+        lib = ctx.lib
         rc = lib.halda_solve_fleets_plans(ctx.ctx, ctypes.byref(self.m), ctypes.byref(self.fs), self.ks.ctypes.data,
                                           len(self.ks), ctypes.byref(self.pc), ctypes.byref(self.eres),
                                           ctypes.byref(self.res), ctypes.c_void_p(stream) if stream else None)
@@ -209,7 +209,7 @@ class Run:
         return pl.last_plans_route(ctx)
 
     def separate(self, ctx):
-        lib = _bind_plans(ctx.lib)
+        lib = ctx.lib
         rc = lib.halda_eval_plans(ctx.ctx, ctypes.byref(self.m), ctypes.byref(self.fs), ctypes.byref(self.pc),
                                   ctypes.byref(self.eres), None)
         assert rc == 0, lh.last_error(lib)

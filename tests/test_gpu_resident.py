@@ -16,7 +16,7 @@ import pytest
 
 from distilp_amd.common import DeviceProfile
 from distilp_amd.solver._libhalda import HaldaContext, get_context
-from distilp_amd.solver.fleets import HaldaFleetResultC, _bind, _host_struct, fleet_table, model_struct
+from distilp_amd.solver.fleets import HaldaFleetResultC, _host_struct, fleet_table, model_struct
 from distilp_amd.synth import synth_fleet
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 def _call(ctx, table, model, ks):
     """halda_solve_fleets_host on `ctx` for a one-fleet table, x / c of every k (dense layout)."""
-    lib = _bind(ctx.lib)
+    lib = ctx.lib
     fs, keep = _host_struct(table)
     nd, nk = table.n_devices, len(ks)
     xs = 7 * nd + 1

@@ -150,7 +150,7 @@ def test_chunked_run_is_byte_identical(llama_online_model, name, per):
     fleets, k, w0s, dmin, dmax, P, keeps, got, _, count, win = shape_call(model, name)
     ctx = lh.get_context(0)
     cap = sc.launch_bytes(max(len(d) for d in fleets), P, per)
-    lib = sc._bind_scale(ctx.lib)
+    lib = ctx.lib
     assert lib.halda_change_subsets_launch_bytes(max(len(d) for d in fleets), P, per) == cap
     sc.set_change_subsets_chunk(ctx, cap)
     try:
@@ -282,7 +282,7 @@ def test_scale_out_equals_the_oracle_and_the_join_entry(llama_online_model):
 def c_call(model, devs, k, w0, dmin, dmax, P, keep=0):
     """halda_solve_change_subsets_host on one fleet: (rc, status array prefilled with -9)."""
     ctx = lh.get_context(0)
-    lib = sc._bind_scale(ctx.lib)
+    lib = ctx.lib
     table = fleet_table([devs], model)
     fs, hold = _host_struct(table)
     m = model_struct(model, bc.KV)
@@ -305,7 +305,7 @@ def test_gate_inside_and_outside(llama_online_model):
     """One case just inside and one just outside each of 2 P + Dmax_d <= 254, the LDS budget and the 2^20
     candidates; the outside ones are refused (HALDA_E_ARG, ValueError) and nothing is written."""
     ctx = lh.get_context(0)
-    lib = sc._bind_scale(ctx.lib)
+    lib = ctx.lib
     # (a) 2 P + Dmax_d <= 254 on a 250-layer model: three devices, d = 1 drops the one that holds 243
     deep = model_at(llama_online_model, 250)
     devs = list(bc.devices(3, 0))
@@ -350,7 +350,7 @@ def test_gate_inside_and_outside(llama_online_model):
 def test_other_refusals_before_any_launch(llama_online_model):
     model = llama_online_model
     devs, w = cc.stale_parent(model, 4, 1, 0)
-    lib = sc._bind_scale(lh.get_context(0).lib)
+    lib = lh.get_context(0).lib
     for args in ((w, 2, 1, 0), (w, 0, 64, 0), (w, 0, 1, 64), (w, 0, 1, -1), (w, 4, 4, 0), ([81, 1, 1, 1], 0, 1, 0),
                  ([-1, 1, 1, 1], 0, 1, 0)):
         rc, st = c_call(model, devs, 1, *args)
@@ -384,7 +384,7 @@ def test_call_on_another_stream_between_two_scratch_users(llama_online_model):
     fleets, k, w0s, dmin, dmax, P, keeps, got, _, _, _ = shape_call(model, "M8_k2_P3")
     dev = torch.device("cuda", 0)
     ctx = lh.get_context(0)
-    lib = sc._bind_scale(ctx.lib)
+    lib = ctx.lib
     table = fleet_table(fleets, model)
     dt = DeviceFleetTable(table, model, [k], bc.KV, dev)
     nf, D1, P1 = len(fleets), dmax - dmin + 1, P + 1

@@ -142,7 +142,7 @@ def test_plans_and_groups_fail_cleanly_after_the_context_is_freed(llama_online_m
 
     import torch
 
-    from distilp_amd.solver.fleets import DeviceFleetTable, PlanGroup, PlanRotation, _bind
+    from distilp_amd.solver.fleets import DeviceFleetTable, PlanGroup, PlanRotation
 
     dev = torch.device("cuda", 0)
     ctx = HaldaContext(0)
@@ -155,7 +155,7 @@ def test_plans_and_groups_fail_cleanly_after_the_context_is_freed(llama_online_m
     torch.cuda.synchronize(dev)
     _, h, fn = dt._plans[id(ctx)]
     ctx.close()
-    lib = _bind(ctx.lib)
+    lib = ctx.lib
     assert fn(h, ctypes.c_void_p(stream.cuda_stream)) != 0  # the raw C call on the stale plan
     with pytest.raises(RuntimeError):
         dt.launch(ctx, stream.cuda_stream)

@@ -77,7 +77,7 @@ def solve_fleets_device(table, model, ks, x_off=None):
     """halda_solve_fleets on a device copy of `table`: every output, as NumPy arrays."""
     torch, dev = _torch()
     ctx = lh.get_context(0)
-    lib = sf._bind_sub(ctx.lib)
+    lib = ctx.lib
     arrs, fs = _upload(table)
     sizes, nk = table.sizes(), len(ks)
     o, r, xo = _results(table.n_fleets, table.n_devices, nk, _xlen(sizes, nk, x_off), x_off)
@@ -95,7 +95,7 @@ def solve_items_device(table, items, model, ks, path=0, x_off=None, stream=None)
     """halda_solve_subfleets on device copies of `table` and the item arrays: every output."""
     torch, dev = _torch()
     ctx = lh.get_context(0)
-    lib = sf._bind_sub(ctx.lib)
+    lib = ctx.lib
     arrs, fs = _upload(table)
     parent, sub_off, sub_idx = sf.pack_items(table.sizes(), items)
     d = [torch.from_numpy(a).to(dev) for a in (parent, sub_off, sub_idx)]
@@ -197,7 +197,7 @@ def test_host_variant_equals_a_call_on_another_stream(llama_online_model):
     model = llama_online_model
     fleets = [fleet(64, 4600), fleet(9, 4601)]
     ctx = lh.get_context(0)
-    lib = sf._bind_sub(ctx.lib)
+    lib = ctx.lib
     for items in (leave_one_out(0, 64), leave_one_out(1, 9) + [(0, [5, 4, 3])]):
         table = fleet_table(fleets, model)
         got = solve_items_device(table, items, model, KS80, stream=torch.cuda.Stream(dev))
@@ -228,7 +228,7 @@ def test_host_variant_rejects_bad_items(llama_online_model):
     model = llama_online_model
     table = fleet_table([fleet(4, 4700), fleet(2, 4701)], model)
     ctx = lh.get_context(0)
-    lib = sf._bind_sub(ctx.lib)
+    lib = ctx.lib
     fs, keep = _host_struct(table)
     karr = np.asarray(KS80, np.int32)
     m = model_struct(model, 0.5)

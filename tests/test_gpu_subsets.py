@@ -34,7 +34,7 @@ def solve_subsets_device(table, model, D, keep_masks=None, ks=KS80, path=0, stre
     """halda_solve_subsets on a device copy of `table`: (status, obj, dropped_mask, best_k) [nf, D + 1], route."""
     torch, dev = _torch()
     ctx = lh.get_context(0)
-    lib = ss._bind_subsets(ctx.lib)
+    lib = ctx.lib
     arrs, fs = _upload(table)
     n = table.n_fleets * (D + 1)
     o = {"status": torch.full((n,), -7, dtype=torch.int32, device=dev),

@@ -278,7 +278,7 @@ def test_uniform_fleets_viewed_from_an_offset_dev_off(llama_online_model, M):
 
     import torch
 
-    from distilp_amd.solver.fleets import DeviceFleetTable, HaldaFleetResultC, HaldaFleetsC, _bind
+    from distilp_amd.solver.fleets import DeviceFleetTable, HaldaFleetResultC, HaldaFleetsC
 
     ks = [1, 2, 4, 5, 8, 10, 16, 20, 40]
     dev = torch.device("cuda", 0)
@@ -300,7 +300,7 @@ def test_uniform_fleets_viewed_from_an_offset_dev_off(llama_online_model, M):
            "n": torch.full((table.n_devices,), -1, dtype=torch.int32, device=dev)}
     res = HaldaFleetResultC(out["best_k"].data_ptr(), out["obj_value"].data_ptr(), out["w"].data_ptr(),
                             out["n"].data_ptr(), None, None, None, None)
-    lib = _bind(ctx.lib)
+    lib = ctx.lib
     with ctx._lock:
         rc = lib.halda_solve_fleets(ctx.ctx, ctypes.byref(dt.model), ctypes.byref(fs), dt.ks.ctypes.data,
                                     len(dt.ks), ctypes.byref(res), ctypes.c_void_p(stream))

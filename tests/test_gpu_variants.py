@@ -87,7 +87,7 @@ def solve_fleets_device(table, mstruct, ks, x_off=None, want=OUTS):
     """halda_solve_fleets on a device copy of `table` for one halda_model: every output, as NumPy arrays."""
     torch, dev = _torch()
     ctx = lh.get_context(0)
-    lib = va._bind_var(ctx.lib)
+    lib = ctx.lib
     arrs, fs = _upload(table)
     sizes, nk, nf = table.sizes(), len(ks), table.n_fleets
     o, r, xo = _results(nf, table.n_devices, nf * nk, _xlen(sizes, nk, x_off), x_off, want)
@@ -104,7 +104,7 @@ def solve_variants_device(table, variants, ks, path=0, x_off=None, want=OUTS, st
     """halda_solve_variants on a device copy of `table`: every output (variant-major) and the route."""
     torch, dev = _torch()
     ctx = lh.get_context(0)
-    lib = va._bind_var(ctx.lib)
+    lib = ctx.lib
     arrs, fs = _upload(table)
     sizes, nk, nf, nd, nv = table.sizes(), len(ks), table.n_fleets, table.n_devices, len(variants)
     o, r, xo = _results(nv * nf, nv * nd, nv * nf * nk, _xlen(sizes, nk, x_off, nv), x_off, want)
@@ -255,7 +255,7 @@ def test_on_a_callers_stream(llama_online_model):
 def test_argument_errors_launch_nothing(llama_online_model):
     torch, dev = _torch()
     ctx = lh.get_context(0)
-    lib = va._bind_var(ctx.lib)
+    lib = ctx.lib
     m = llama_online_model
     table = fleet_table([fleet(64, 5100)], m)
     arrs, fs = _upload(table)

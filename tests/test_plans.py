@@ -330,11 +330,11 @@ def test_plan_entries_reject_bad_arguments_before_any_hip_call():
     import ctypes
 
     from distilp_amd.solver.fleets import (HaldaFleetResultC, HaldaFleetsC, HaldaModelC, HaldaPlanResultC,
-                                           HaldaPlansC, _bind_plans)
+                                           HaldaPlansC)
 
     if not lh.LIB_PATH.exists():
         pytest.fail(f"{lh.LIB_PATH} not built (run __graft_entry__.build())")
-    lib = _bind_plans(lh.load_library())
+    lib = lh.load_library()
     m, fs, p, o, r = HaldaModelC(), HaldaFleetsC(), HaldaPlansC(), HaldaPlanResultC(), HaldaFleetResultC()
     m.L = 80
     ks = (ctypes.c_int32 * 1)(1)

@@ -47,7 +47,7 @@ def test_new_entry_points_are_exported_and_reject_bad_arguments():
 
 @pytest.mark.parametrize("q", [1, 3, 6, 16])
 def test_combo_lists_are_itertools_combinations_in_the_stated_order(q):
-    lib = ss._bind_subsets(lh.load_library())
+    lib = lh.load_library()
     total = 0
     for d in range(0, min(q, 3) + 1):
         combos = ss.combo_list(q, d)
@@ -60,7 +60,7 @@ def test_combo_lists_are_itertools_combinations_in_the_stated_order(q):
 
 
 def test_subsets_count_limits():
-    lib = ss._bind_subsets(lh.load_library())
+    lib = lh.load_library()
     assert lib.halda_subsets_count(64, 2) == 2081 and lib.halda_subsets_count(16, 16) == 65536
     assert lib.halda_subsets_count(20, 20) == ss.SUBSETS_MAX == 1 << 20
     assert lib.halda_subsets_count(64, 64) == 2 ** 63 - 1  # saturated

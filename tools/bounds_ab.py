@@ -43,14 +43,14 @@ def child() -> None:
     from distilp_amd.solver._libhalda import get_context, last_error
     from distilp_amd.solver.batch import assemble
     from distilp_amd.solver.fleets import (BYTE_FIELDS, F64_FIELDS, FleetTable, HaldaBoundsC, HaldaFleetResultC,
-                                           _bind_bounds, _fleets_struct, fleet_table, model_struct, solve_table)
+                                           _fleets_struct, fleet_table, model_struct, solve_table)
     from distilp_amd.solver.lower import lower_fleet
     from distilp_amd.synth import load_model_dict, synth_fleet
 
     model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = _bind_bounds(ctx.lib)
+    lib = ctx.lib
     ks = sorted(k for k in range(1, model.L) if model.L % k == 0)
     karr = np.asarray(ks, np.int32)
     stream = torch.cuda.Stream(dev)

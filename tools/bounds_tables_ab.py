@@ -45,13 +45,13 @@ def child() -> None:
     from distilp_amd.solver import halda_solve_bounded_batch
     from distilp_amd.solver._libhalda import get_context, last_error
     from distilp_amd.solver.fleets import (BYTE_FIELDS, F64_FIELDS, FleetTable, HaldaBoundsC, HaldaFleetResultC,
-                                           _bind_bounds, _fleets_struct, fleet_table, model_struct, solve_table)
+                                           _fleets_struct, fleet_table, model_struct, solve_table)
     from distilp_amd.synth import load_model_dict, synth_fleet
 
     model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = _bind_bounds(ctx.lib)
+    lib = ctx.lib
     stream = torch.cuda.Stream(dev)
     out = {"gpu": torch.cuda.get_device_name(0), "reps": REPS, "rounds": ROUNDS}
     fields = ("os_class", "flags") + F64_FIELDS + BYTE_FIELDS

@@ -46,14 +46,14 @@ def child() -> None:
     from distilp_amd.solver import budget as bg
     from distilp_amd.solver._libhalda import get_context, last_error
     from distilp_amd.solver.fleets import (BYTE_FIELDS, F64_FIELDS, FleetTable, HaldaBoundsC, HaldaBudgetC,
-                                           HaldaFleetResultC, HaldaFrontierC, _bind_bounds, _bind_budget,
-                                           _fleets_struct, fleet_table, model_struct, solve_table)
+                                           HaldaFleetResultC, HaldaFrontierC, _fleets_struct, fleet_table,
+                                           model_struct, solve_table)
     from distilp_amd.synth import load_model_dict, synth_fleet
 
     model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = _bind_budget(_bind_bounds(ctx.lib))
+    lib = ctx.lib
     stream = torch.cuda.Stream(dev)
     out = {"gpu": torch.cuda.get_device_name(0), "reps": REPS, "rounds": ROUNDS}
     fields = ("os_class", "flags") + F64_FIELDS + BYTE_FIELDS

@@ -54,7 +54,7 @@ def child() -> None:
     model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = sc._bind_scale(ch._bind_change(ctx.lib))
+    lib = ctx.lib
     stream = torch.cuda.Stream(dev)
     sp = ctypes.c_void_p(stream.cuda_stream)
     out = {"gpu": torch.cuda.get_device_name(0), "reps": REPS, "rounds": ROUNDS, "reps_end_to_end": REPS_E2E, "k": K,

@@ -52,7 +52,7 @@ def main():
 
     from distilp_amd.common import DeviceProfile, ModelProfileSplit
     from distilp_amd.solver._libhalda import get_context
-    from distilp_amd.solver.fleets import (F64_FIELDS, BYTE_FIELDS, HaldaFleetResultC, _bind, _fleets_struct,
+    from distilp_amd.solver.fleets import (F64_FIELDS, BYTE_FIELDS, HaldaFleetResultC, _fleets_struct,
                                            fleet_table, model_struct, solve_table)
     from distilp_amd.synth import load_model_dict, synth_fleet
 
@@ -65,7 +65,7 @@ def main():
     # ---- GPU-resident: two device copies of a perturbed batch, launches back to back
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = _bind(ctx.lib)
+    lib = ctx.lib
     stream = torch.cuda.Stream(dev)
     m = model_struct(model, 0.5)
     karr = np.asarray(KS, np.int32)

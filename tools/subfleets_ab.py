@@ -62,7 +62,7 @@ def child() -> None:
     # (c) device arrays, HIP events on one stream
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = sf._bind_sub(ctx.lib)
+    lib = ctx.lib
     table = fleet_table(fleets, model)
     arrs = {f: torch.from_numpy(np.ascontiguousarray(getattr(table, f))).to(dev)
             for f in ("dev_off", "os_class", "flags") + F64_FIELDS + BYTE_FIELDS}

@@ -51,7 +51,7 @@ def child(only) -> None:
     model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = ss._bind_subsets(sf._bind_sub(ctx.lib))
+    lib = ctx.lib
     ks = sorted(k for k in range(1, model.L) if model.L % k == 0)
     karr = np.asarray(ks, np.int32)
     stream = torch.cuda.Stream(dev)

@@ -52,7 +52,7 @@ def child() -> None:
     }
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = va._bind_var(ctx.lib)
+    lib = ctx.lib
     ks = np.asarray(sorted(k for k in range(1, model.L) if model.L % k == 0), np.int32)
     stream = torch.cuda.Stream(dev)
     out = {"gpu": torch.cuda.get_device_name(0), "reps": REPS, "rounds": ROUNDS}
