@@ -16,6 +16,8 @@ from distilp_amd.solver import (ChangePoint, halda_change_frontier, halda_change
                                 halda_failover_frontiers, halda_failover_plan, halda_join_frontiers)
 from distilp_amd.solver import (ScalePoint, halda_scale_in, halda_scale_in_frontier,  # noqa: F401
                                 halda_scale_in_frontier_batch, halda_scale_out_frontier)
+from distilp_amd.solver import (ReloadPoint, halda_reload_frontier, halda_solve_boxes,  # noqa: F401
+                                halda_solve_boxes_batch, reload_caps)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

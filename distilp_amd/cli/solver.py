@@ -23,6 +23,10 @@ away from that plan's: the line becomes `within D (n within Dn): k=..., obj=...,
 moved_gpu_layers=...`. --move-frontier B (with --evaluate-solution) prints, after those, one line per point
 p = 0 .. B // 2 of the total-move-budget frontier at that plan's k (halda_move_frontier: at most p layers change
 device, moved_layers <= 2 p): `frontier p: moved_layers=..., obj=..., regret=...`, or `frontier p: infeasible`.
+--reload-frontier [SECONDS] (with --evaluate-solution) prints, after those, one line per point of the reload-time
+frontier at that plan's k (halda_reload_frontier: the best plan reachable when every device that gains layers has
+that many seconds to read them from its own disk; up to SECONDS, default every point):
+`reload j: seconds=..., obj=..., regret=..., gained=[...]`, or `reload j: infeasible`.
 --scale-in D (with --evaluate-solution and --failover P; --keep names devices that may not be dropped) prints, last,
 one line per (d, p): `scale-in d, p: dropped=[names], loaded=..., released=..., obj=..., regret=...` or
 `scale-in d, p: infeasible` (halda_scale_in_frontier's cells).
@@ -170,6 +174,21 @@ def frontier_lines(devices: List[DeviceProfile], model: ModelProfile, plan, budg
     return out
 
 
+def reload_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_seconds: Optional[float]) -> List[str]:
+    """--reload-frontier [SECONDS]: one line per point of halda_reload_frontier around the incumbent (kv_bits
+    "4bit" like the solve above)."""
+    from ..solver.boxes import halda_reload_frontier
+
+    out = []
+    for j, pt in enumerate(halda_reload_frontier(devices, model, plan, max_seconds, kv_bits="4bit")):
+        if pt.plan is None:
+            out.append(f"reload {j}: infeasible")
+        else:
+            out.append(f"reload {j}: seconds={pt.seconds:.6f}, obj={pt.obj_value:.6f}, regret={pt.regret:.6f}, "
+                       f"gained={pt.gained}")
+    return out
+
+
 def failover_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_released: int) -> List[str]:
     """--failover P: per device, the last point of its halda_failover_frontiers entry -- the best plan of the
     fleet without it that takes at most P layers off the survivors (kv_bits "4bit" like the solve above)."""
@@ -292,6 +311,9 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--move-frontier", type=int, metavar="B",
                    help="With --evaluate-solution: also print, for every total budget up to B moved layers, the best "
                         "plan at that plan's k within it")
+    o.add_argument("--reload-frontier", nargs="?", type=float, const=float("inf"), default=None, metavar="SECONDS",
+                   help="With --evaluate-solution: also print, for every reload time up to SECONDS (default: every "
+                        "point), the best plan at that plan's k whose gained layers load from disk within it")
     o.add_argument("--failover", type=int, metavar="P",
                    help="With --evaluate-solution: also print, for the loss of each device, the best plan of the "
                         "survivors at that plan's k that takes at most P layers off them")
@@ -338,6 +360,10 @@ def main(argv=None) -> int:
         parser.error("--move-frontier requires --evaluate-solution")
     if args.move_frontier is not None and args.move_frontier < 0:
         parser.error("--move-frontier must be >= 0")
+    if args.reload_frontier is not None and not args.evaluate_solution:
+        parser.error("--reload-frontier requires --evaluate-solution")
+    if args.reload_frontier is not None and not args.reload_frontier >= 0:
+        parser.error("--reload-frontier must be >= 0")
     if args.failover is not None and not args.evaluate_solution:
         parser.error("--failover requires --evaluate-solution")
     if args.failover is not None and args.failover < 0:
@@ -428,6 +454,15 @@ def main(argv=None) -> int:
                 lines = frontier_lines(devices, model, incumbent, args.move_frontier)
             except ValueError as e:
                 print(f"error: --move-frontier: {e}", file=sys.stderr)
+                return 2
+            for line in lines:
+                print(line)
+        if args.reload_frontier is not None:
+            try:
+                lines = reload_lines(devices, model, incumbent,
+                                     None if args.reload_frontier == float("inf") else args.reload_frontier)
+            except ValueError as e:
+                print(f"error: --reload-frontier: {e}", file=sys.stderr)
                 return 2
             for line in lines:
                 print(line)

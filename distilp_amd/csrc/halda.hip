@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "halda.h"
+#include "halda_boxes.h"
 #include "halda_stage.hpp"
 
 namespace {
@@ -177,6 +178,9 @@ struct Ctx {
     int bounds_path = 0;            // halda_set_bounds_path: 0 automatic, 1 always general, 2 fused where it applies,
                                     // 3 fused, else the table launch, where they apply
     int bounds_route = 0;           // the last halda_solve_fleets_bounded call: 1 fused, 2 general, 3 table launch
+                                    // (0: none yet)
+    int boxes_path = 0;             // halda_set_boxes_path: 0 automatic, 1 always loop
+    int boxes_route = 0;            // the last halda_solve_fleets_boxes call: 1 register launch, 3 table launch, 2 loop
                                     // (0: none yet)
     halda_batch last_lowered = {};
     halda_result last_solved = {};
@@ -3153,6 +3157,186 @@ int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const hal
                                   int32_t n_k, const halda_box *box, halda_fleet_result *out_h) {
     const halda_box none = {nullptr, nullptr, nullptr, nullptr};
     return solve_boxed_host(ctx, model, fh, ks, n_k, box ? *box : none, out_h, "halda_solve_fleets_boxed");
+}
+
+// ---------------------------------------------------------------- one table under many boxes
+// halda_solve_fleets_boxes: one fleet table under n_box boxes, the bound planes and the outputs box-major,
+// slice b bit for bit what halda_solve_fleets_boxed writes for box b alone under bounds path 3.
+// Loop route (the specification; every call on path 1): n_box calls of halda_solve_fleets_boxed on the
+// caller's stream under bounds path 3, the bound and output pointers moved to the box's slice; the context's
+// bounds path is put back before the call returns.
+// Register route: under the boxed entry's fused gate, one launch of halda_sweep_boxes_kernel, blockIdx.y the
+// box. Table route: else under path 3's table gate, one launch of halda_sweep_boxes_tables_kernel, its
+// persistent grid over the n_box * n_fleets items. Neither uses context scratch.
+int halda_set_boxes_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "boxes path must be 0 (automatic) or 1 (always loop)");
+    c->boxes_path = path;
+    return HALDA_OK;
+}
+
+int halda_last_boxes_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->boxes_route;
+    return HALDA_OK;
+}
+
+static int check_boxes(const halda_boxes *boxes) {
+    if (!boxes) return fail(HALDA_E_ARG, "halda_solve_fleets_boxes: NULL boxes");
+    if (boxes->n_box < 1 || boxes->n_box > 65535) return fail(HALDA_E_ARG, "n_box must be in 1..65535");
+    return HALDA_OK;
+}
+
+// total: dev_off[n_fleets] when the caller knows it (the host variant), -1 to read it back where needed
+static int solve_boxes(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks, int32_t n_k,
+                       const halda_boxes *boxes, halda_fleet_result *out, void *stream, int64_t total) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fleets || !ks || !out)
+        return fail(HALDA_E_ARG, "halda_solve_fleets_boxes: NULL ctx/model/fleets/ks/out");
+    {
+        const int rc = check_boxes(boxes);
+        if (rc != HALDA_OK) return rc;
+    }
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    {
+        const int rc = check_fleets_args(model, fleets, ks, n_k, out);
+        if (rc != HALDA_OK) return rc;
+    }
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const halda_boxes &B = *boxes;
+    const int64_t nf = F.n_fleets, nb = B.n_box;
+    // the fused kernels index fleets and (fleet, k) instances over all boxes with 32 bits
+    if (c->boxes_path == 0 && c->fleets_fused && n_k <= 64 && nb * nf * n_k < (int64_t(1) << 31)) {
+        SweepPlan p;
+        const int rc = plan_sweep(c, *model, F, ks, n_k, *out, &p);
+        if (rc != HALDA_OK) return rc;
+        const bool reg = p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM;
+        if (reg || (F.min_devices >= 1 && F.max_devices <= kK1MaxM && p.slice <= kLdsBudget)) {
+            SweepArgs &A = p.A;
+            A.fflag = nullptr;  // every (box, fleet) is solved in the one launch: nothing is flagged or handed back
+            A.hb_flag = c->hb_flag;
+            A.launch_id = ++c->launch_id;
+            A.want = 0;
+            c->fleet_timed = false;
+            c->have_lowered = false;
+            const BoxesArgs Bs{B.w_min, B.w_max, B.n_min, B.n_max, int(nb)};
+            if (reg) {
+                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+                hipLaunchKernelGGL(halda_sweep_boxes_kernel, dim3(p.grid1, unsigned(nb)), dim3(p.block1), 0, s, A, Bs);
+            } else {
+                const void *fn = reinterpret_cast<const void *>(halda_sweep_boxes_tables_kernel);
+                int per_cu = 0;
+                HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
+                const unsigned grid =
+                    unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, nb * nf)));
+                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+                hipLaunchKernelGGL(halda_sweep_boxes_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bs);
+            }
+            HIP_TRY(hipGetLastError());
+            if (c->timing) {
+                HIP_TRY(hipEventRecord(c->evf1, s));
+                c->fleet_timed = true;
+            }
+            c->fleet_two = false;
+            c->fleet_reg_alone = reg;
+            c->fleet_seg = false;
+            c->fleet_kslot = false;
+            c->last_fleet_fused = true;
+            c->boxes_route = reg ? 1 : 3;
+            return HALDA_OK;
+        }
+    }
+    // the loop: box b's planes in, box b's slice of every output
+    int64_t nd = total;
+    if (nd < 0 && nb > 1) {
+        HIP_TRY(hipMemcpyAsync(&nd, F.dev_off + nf, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (nd < 0) return fail(HALDA_E_ARG, "halda_fleets: dev_off[n_fleets] < 0");
+    }
+    const int64_t xstride = 7 * int64_t(std::max(F.max_devices, 1)) + 1;
+    const int caller_path = c->bounds_path;
+    c->bounds_path = 3;
+    c->boxes_route = 2;
+    int rc = HALDA_OK;
+    for (int64_t b = 0; b < nb && rc == HALDA_OK; ++b) {
+        const int64_t at = b ? b * nd : 0;
+        const halda_box one = {B.w_min ? B.w_min + at : nullptr, B.w_max ? B.w_max + at : nullptr,
+                               B.n_min ? B.n_min + at : nullptr, B.n_max ? B.n_max + at : nullptr};
+        halda_fleet_result o = *out;
+        o.best_k += b * nf;
+        o.obj_value += b * nf;
+        o.w += at;
+        o.n += at;
+        if (o.obj_by_k) o.obj_by_k += b * nf * n_k;
+        if (o.status) o.status += b * nf * n_k;
+        if (o.x_off) {
+            o.x_off += b * nf * n_k;  // absolute offsets into the one x / c
+        } else {
+            if (o.x) o.x += b * nf * n_k * xstride;
+            if (o.c) o.c += b * nf * n_k * xstride;
+        }
+        rc = halda_solve_fleets_boxed(ctx, model, fleets, ks, n_k, &one, &o, s);
+    }
+    c->bounds_path = caller_path;
+    return rc;
+}
+
+int halda_solve_fleets_boxes(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                             int32_t n_k, const halda_boxes *boxes, halda_fleet_result *out, void *stream) {
+    return solve_boxes(ctx, model, fleets, ks, n_k, boxes, out, stream, -1);
+}
+
+// The host variant: the table crosses PCIe once, the bound planes that were passed once, and the n_box result
+// slices come back, through the context's staging scratch. It knows dev_off[n_fleets]: no read-back.
+int halda_solve_fleets_boxes_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks,
+                                  int32_t n_k, const halda_boxes *boxes, halda_fleet_result *out_h) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fh || !ks || !out_h)
+        return fail(HALDA_E_ARG, "halda_solve_fleets_boxes_host: NULL ctx/model/fleets/ks/out");
+    {
+        const int rc = check_boxes(boxes);
+        if (rc != HALDA_OK) return rc;
+    }
+    const int64_t nf = fh->n_fleets, nb = boxes->n_box;
+    if (nf <= 0) return HALDA_OK;
+    {
+        const int rc = check_fleets_args(model, fh, ks, n_k, out_h);
+        if (rc != HALDA_OK) return rc;
+    }
+    const int64_t nd = fh->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    // layout: the table, once; the planes that were passed; the results box-major over (box, fleet, k)
+    const int32_t *bsrc[4] = {boxes->w_min, boxes->w_max, boxes->n_min, boxes->n_max};
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    size_t o_b[4];
+    for (int a = 0; a < 4; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nb * nd) : 0;
+    const bool xsel = stage::compact(*out_h);
+    const size_t xs = stage::xc_extent(fh->dev_off, nf, n_k, nb, fh->max_devices, xsel ? out_h->x_off : nullptr);
+    const stage::ResultSlots R = stage::lay_result(lay, *out_h, nb * nf, nb * nd, size_t(nb) * nf * n_k, xs);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *fh, s);
+    for (int a = 0; a < 4 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nb * nd, s);
+    if (rc == HALDA_OK && xsel) rc = upload(base, R.x_off, out_h->x_off, 8 * R.n_inst, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*fh, base, T);
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    const halda_boxes db = {boxes->n_box, bdev(0), bdev(1), bdev(2), bdev(3)};
+    halda_fleet_result r = stage::bind_result(base, R, *out_h);
+    rc = solve_boxes(ctx, model, &d, ks, n_k, &db, &r, s, nd);
+    if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
 }
 
 // ---------------------------------------------------------------- the frontier launches (budget and change)

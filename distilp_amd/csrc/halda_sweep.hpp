@@ -2264,6 +2264,79 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bo
     bounded_tables<BoxRec>(A, Bx);
 }
 
+// ---------------------------------------------------------------- many boxes on one table
+// halda_solve_fleets_boxes: one fleet table under n_box boxes in one launch. The bound arrays are box-major
+// (box b's plane of array a at a + b * nd, nd = dev_off[n_fleets], device layout inside a plane) and so are
+// the outputs, which is the layout of a batch of n_box * n_fleets fleets -- halda_sweep_variants_kernel's, with
+// "variant" read as "box": box b's fleet f is output fleet b * n_fleets + f for best_k / obj_value / obj_by_k /
+// status / x / c / x_off (bounded_fleet's fleet index), and its devices' w / n lie at b * nd + their table
+// index. A wave runs bounded_fleet on the lane bounded_lane forms from the box's planes, with the lane's d0 --
+// which the body uses for the w / n stores alone -- moved to the box's slice: the same code on the same fields
+// and bounds as the box's own halda_solve_fleets_boxed launch, so the same bits. The record type is that call's
+// choice too, made once per launch (wave-uniform): a box record when an n array was passed, else a bound record.
+struct BoxesArgs {
+    const int32_t *w_min, *w_max, *n_min, *n_max;  // halda_boxes: [n_box * dev_off[n_fleets]]; any may be NULL
+    int n_box;
+};
+
+__device__ inline const int32_t *boxes_plane(const int32_t *a, int64_t off) { return a ? a + off : nullptr; }
+
+template <class Rec, bool kTables>
+__device__ inline void boxes_fleet(const SweepArgs &A, const BoxesArgs &Bs, int b, int f, int64_t d0, int M, int64_t nd,
+                                   const WaveCtx &w, int lane) {
+    const int64_t off = int64_t(b) * nd;
+    BoundedLane in;
+    if constexpr (std::is_same<Rec, BoxRec>::value)
+        in = bounded_lane(A, BoxArgs{boxes_plane(Bs.w_min, off), boxes_plane(Bs.w_max, off), boxes_plane(Bs.n_min, off),
+                                     boxes_plane(Bs.n_max, off)},
+                          lane, d0, M);
+    else
+        in = bounded_lane(A, BoundArgs{boxes_plane(Bs.w_min, off), boxes_plane(Bs.w_max, off)}, lane, d0, M);
+    in.d0 = off + d0;  // where the slice's w / n go
+    bounded_fleet<Rec, kTables>(A, b * A.F.n_fleets + f, w, Wave(lane), in);
+}
+
+// The register form: bounded_regs' body, one wave per (box, fleet), blockIdx.y the box.
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_boxes_kernel(
+    SweepArgs A, BoxesArgs Bs) {
+    const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    const int nf = A.F.n_fleets;
+    if (f >= nf) return;
+    const int b = int(blockIdx.y);
+    const int lane = int(threadIdx.x & 63);
+    const int M = A.uM;
+    const int64_t base = sload_i64(A.F.dev_off), nd = sload_i64(A.F.dev_off + nf);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    const int64_t d0 = base + int64_t(f) * M;
+    if (Bs.n_min || Bs.n_max) boxes_fleet<BoxRec, false>(A, Bs, b, f, d0, M, nd, w, lane);
+    else boxes_fleet<BoundRec, false>(A, Bs, b, f, d0, M, nd, w, lane);
+}
+
+// The table form: bounded_tables' persistent loop over the n_box * n_fleets (box, fleet) items, box-major, on
+// the one LDS slice (it depends on the unbounded shape only, so it serves every box).
+template <class Rec>
+__device__ inline void boxes_tables(const SweepArgs &A, const BoxesArgs &Bs, unsigned char *smem) {
+    const int lane = threadIdx.x;
+    const WaveCtx w = wave_ctx(smem, make_slice(A.mmax, A.r1max, A.tab, A.tab_kc));
+    const int nf = A.F.n_fleets;
+    const int64_t nd = sload_i64(A.F.dev_off + nf), items = int64_t(Bs.n_box) * nf;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const int b = int(it / nf), f = int(it - int64_t(b) * nf);
+        const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
+        const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
+        boxes_fleet<Rec, true>(A, Bs, b, f, d0, M, nd, w, lane);
+    }
+}
+
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_boxes_tables_kernel(SweepArgs A,
+                                                                                                 BoxesArgs Bs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (Bs.n_min || Bs.n_max) boxes_tables<BoxRec>(A, Bs, smem);
+    else boxes_tables<BoundRec>(A, Bs, smem);
+}
+
 // ---------------------------------------------------------------- total move budget (halda_solve_fleets_budget)
 // The fixed-k problem at the incumbent's k with sum_i |w_i - w0_i| <= B added: the constraint couples the
 // devices, so it is not a narrowing of column bounds. Both plans sum to W, hence sum |delta| = 2 sum delta+;

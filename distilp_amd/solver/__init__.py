@@ -2,6 +2,8 @@
 
 from .bounds import (ReplacementWithin, halda_replace_within, halda_replace_within_batch,  # noqa: F401
                      halda_solve_bounded, halda_solve_bounded_batch, move_bounds, move_box)
+from .boxes import (ReloadPoint, halda_reload_frontier, halda_solve_boxes, halda_solve_boxes_batch,  # noqa: F401
+                    reload_caps)
 from .budget import (FrontierPoint, halda_move_frontier, halda_move_frontier_batch,  # noqa: F401
                      halda_solve_budget)
 from .change import (ChangePoint, halda_change_frontier, halda_change_frontiers,  # noqa: F401
@@ -29,6 +31,7 @@ __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solv
            "halda_select_devices_exact", "SubsetPoint", "halda_change_frontier", "halda_change_frontiers",
            "halda_failover_frontiers", "halda_join_frontiers", "halda_failover_plan", "ChangePoint",
            "halda_scale_in_frontier", "halda_scale_in_frontier_batch", "halda_scale_in", "halda_scale_out_frontier",
-           "ScalePoint", "ILPResult"]
+           "ScalePoint", "halda_solve_boxes", "halda_solve_boxes_batch", "reload_caps", "halda_reload_frontier",
+           "ReloadPoint", "ILPResult"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

@@ -1,8 +1,8 @@
-"""The C ABI of libhalda (include/halda.h) as ctypes declarations: every struct, in header order, and the
-prototype of every function. `_libhalda.load_library` applies PROTOTYPES to the library it opens, so no call
-can reach a function with ctypes' default `int` arguments and result. tests/test_abi.py compiles the header
-and compares every struct's size and field offsets, and every prototype's arity and result type, with this
-module.
+"""The C ABI of libhalda (include/halda.h, and include/halda_boxes.h beside it) as ctypes declarations: every
+struct, in header order, and the prototype of every function. `_libhalda.load_library` applies PROTOTYPES and
+BOXES_PROTOTYPES to the library it opens, so no call can reach a function with ctypes' default `int` arguments
+and result. tests/test_abi.py compiles halda.h and compares every struct's size and field offsets, and every
+prototype's arity and result type, with this module; tests/test_boxes.py does the same for halda_boxes.h.
 """
 
 from __future__ import annotations
@@ -68,6 +68,10 @@ class HaldaBoundsC(ctypes.Structure):
 
 class HaldaBoxC(ctypes.Structure):  # halda_box: halda_bounds and the n columns' two arrays
     _fields_ = _ptrs("w_min", "w_max", "n_min", "n_max")
+
+
+class HaldaBoxesC(ctypes.Structure):  # include/halda_boxes.h halda_boxes: n_box planes of halda_box's arrays
+    _fields_ = [("n_box", c_int32)] + _ptrs("w_min", "w_max", "n_min", "n_max")
 
 
 class HaldaBudgetC(ctypes.Structure):
@@ -192,3 +196,11 @@ PROTOTYPES = {
 }
 
 EXPORTS = tuple(PROTOTYPES)
+
+# include/halda_boxes.h, the companion header of the many-boxes entry: its struct and prototypes, declared here
+# once like halda.h's and applied by load_library with them (tests/test_boxes.py holds them to that header)
+BOXES_STRUCTS = {HaldaBoxesC: "halda_boxes"}
+BOXES_PROTOTYPES = {
+    **_with_host("halda_solve_fleets_boxes", *_table, *_ks, POINTER(HaldaBoxesC), _out),
+    **_knob("boxes"),
+}

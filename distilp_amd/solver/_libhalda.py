@@ -16,7 +16,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from ._abi import EXPORTS, PROTOTYPES, HaldaBatchC, HaldaResultC  # noqa: F401 -- EXPORTS: the binding's surface
+from ._abi import BOXES_PROTOTYPES, EXPORTS, PROTOTYPES, HaldaBatchC, HaldaResultC  # noqa: F401 -- EXPORTS: the binding's surface
 
 LIB_PATH = Path(os.environ.get("HALDA_LIB", Path(__file__).resolve().parent.parent / "libhalda.so"))
 
@@ -69,7 +69,7 @@ def load_library(path: Path | str | None = None):
         lib = ctypes.CDLL(str(p))
         if lib.halda_version() != ABI_VERSION:
             raise HaldaUnavailable(f"{p} has ABI {lib.halda_version()}, this binding needs {ABI_VERSION}: rebuild it")
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **BOXES_PROTOTYPES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         if path is None:
@@ -97,7 +97,7 @@ def ptr(a) -> Optional[int]:
 # family's module; halda_last_<family>_route answers an index into these names.
 ROUTES = {"subfleets": ("none", "fused", "expand"), "subsets": ("none", "fused", "expand", "mixed"),
           "variants": ("none", "fused", "loop"), "plans": ("none", "fused", "two_launch"),
-          "bounds": ("none", "fused", "general", "tables")}
+          "bounds": ("none", "fused", "general", "tables"), "boxes": ("none", "register", "loop", "tables")}
 
 
 def set_path(ctx: "HaldaContext", family: str, path: int) -> None:

@@ -548,6 +548,8 @@ int halda_solve_fleets_boxed(void *ctx, const halda_model *model, const halda_fl
 int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
                                   int32_t n_k, const halda_box *box, halda_fleet_result *out);
 
+/* Many boxes on one table (n_box planes of halda_box's arrays, one launch): include/halda_boxes.h. */
+
 /* A total move budget around a deployed plan: the best plan within B moved layers, and its frontier.
  *
  * The problem is the fixed-k MILP at the incumbent's k (one k per call, W = L / k) with the optional w_min /
