@@ -219,8 +219,9 @@ def _row(P: int, picks: List[Optional[Tuple[int, ...]]], frontier_of) -> List[Sc
 def _picks_by_lists(M: int, slots: Sequence[int], d: int, P: int, solve) -> Tuple[List[Optional[tuple]], dict]:
     """The picks of one (fleet, d) by enumeration: every candidate's frontier through `solve`, per p the strict
     earliest arg-min (the specification of the device's pick)."""
-    cands = [tuple(k) for _, k in candidate_lists(M, slots, d)]
-    frs = solve([list(c) for c in cands]) if cands else []
+    # d <= M - 1, as on the device: the empty fleet is no candidate
+    cands = [tuple(k) for _, k in candidate_lists(M, slots, d)] if d <= min(len(slots), M - 1) else []
+    frs =solve([list(c) for c in cands]) if cands else []
     picks = []
     for p in range(P + 1):
         best, least = None, math.inf
