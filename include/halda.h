@@ -264,6 +264,8 @@ void halda_fleets_group_free(void *group);
  *   workgroup), or, when its LDS does not fit (and at most 16 k), every k in turn in one wave
  *   (halda_sweep_seg_kernel);
  * 2 the fused sweep, one fleet per wave only;
+ * 3 (test path) the fused sweep with every k = 1 solve of the register launch done by the exact DP
+ *   that launch falls back to, never by its register greedy;
  * 4 the fused sweep with the segment kernel instead of the k-slot kernel;
  * 5 (test path) the fused sweep with the k-slot kernel's k = 2 threshold scan unsplit (path 1 splits
  *   it over two waves);
@@ -271,7 +273,9 @@ void halda_fleets_group_free(void *group);
  *   its part 1 take rows finite at both ends unchecked, the leaf checks and phase 0 made by other waves
  *   of the workgroup; here part 1 makes them itself, as it does for any other row);
  * 0 the CSR pipeline (lowering kernel -> the halda_solve_batch kernels -> pick kernel), which also
- *   keeps the lowered batch for halda_last_lowered. All give the same statuses, x and k.
+ *   keeps the lowered batch for halda_last_lowered. All give the same statuses and k, an optimal x
+ *   of the same objective, and the same x wherever the optimum is unique; among several optimal
+ *   plans (fleets with equal devices) the greedy and the DP may return different ones.
  * HALDA_E_ARG for any other path. */
 int halda_set_fleets_path(void *ctx, int path);
 

@@ -33,6 +33,22 @@ def fixture_twice(folder):
     return load_devices_and_model([str(dev), str(dev)], str(base / "model_profile.json"))
 
 
+KINDS = ("copies", "two", "half")
+
+
+def tied_dicts(kind, src, s, M=16):
+    """The device dicts of one tied fleet of M devices drawn from `src` (at least max(M, 16) device dicts), s the
+    fleet's number in its list: M copies of one device (the head, s even, or a non-head one); ceil(M/2) +
+    floor(M/2) copies of two devices; the first ceil(M/2) devices twice, cut to M."""
+    h = -(-M // 2)
+    if kind == "copies":
+        return [src[s % 2]] * M
+    if kind == "two":
+        return [src[1]] * h + [src[2 + s % 14]] * (M - h)
+    assert kind == "half", kind
+    return (src[:h] + src[:h])[:M]
+
+
 def tied_fleets(n_each=20, seed0=21000):
     """[(kind, devices)] -- n_each synthetic fleets of each kind but 'twice'."""
     from distilp_amd.synth import load_templates, synth_fleet
@@ -41,10 +57,7 @@ def tied_fleets(n_each=20, seed0=21000):
     out = []
     for s in range(n_each):
         src = synth_fleet(seed0 + s, 16, tpl)
-        one = src[s % 2]  # the head device (s even) or a non-head one
-        out.append(("copies", _validate([one] * 16)))
-        out.append(("two", _validate([src[1]] * 8 + [src[2 + s % 14]] * 8)))
-        out.append(("half", _validate(src[:8] + src[:8])))
+        out += [(kind, _validate(tied_dicts(kind, src, s))) for kind in KINDS]
     return out
 
 
