@@ -9,6 +9,7 @@ sweep, check_sweep and check_resident are those of test_gpu_irregular.py, readin
 
 import contextlib
 import io
+from functools import lru_cache
 
 import numpy as np
 import pytest
@@ -334,33 +335,52 @@ def test_plans_on_both_sides(ctx, name, alone, path):
         restore(ctx)
 
 
+def move_boxes(cases, W, D=2):
+    """Per case the (w_min, w_max) of the D-layer move box around the oracle's k = 1 optimum."""
+    boxes = []
+    for case in cases:
+        w0 = [int(v) for v in np.rint(pe.exact(case, 1)[1][:case[0]])]
+        boxes.append(([max(1, v - D) for v in w0], [min(W, v + D) for v in w0]))
+    return boxes
+
+
+@lru_cache(maxsize=None)
+def _boxed_exact(case, lo, hi):
+    """(the dense k = 1 problem of `case` with the w columns' bounds narrowed, the exact oracle's answer)."""
+    M = case[0]
+    p = dict(pe.problem(case, 1))
+    p["lb"], p["ub"] = p["lb"].copy(), p["ub"].copy()
+    p["lb"][:M], p["ub"][:M] = lo, hi
+    return p, mo.exact_solve(p)
+
+
+def check_bounded(cases, boxes, got, ask):
+    """halda_solve_bounded_batch's results at k = 1 against the exact oracle on the dense problem with the w
+    columns' bounds narrowed to the boxes."""
+    for case, (lo, hi), r in zip(cases, boxes, got):
+        M = case[0]
+        p, (st, xo, b1, b2, _) = _boxed_exact(case, tuple(lo), tuple(hi))
+        assert st == 0, (case, st)  # the move box around the optimum holds the optimum
+        assert r is not None and r.k == 1, (case, ask)
+        assert pe.close(r.obj_value, mo.objective_value(p, xo)), (case, ask, r.obj_value)
+        assert pe.close(r.obj_value, pe.objective(case, 1)), (case, ask)
+        assert all(a <= v <= b for a, v, b in zip(lo, r.w, hi)), (case, ask)
+        if mo.uniqueness_margin_ok(b1, b2):
+            assert r.w == [int(v) for v in xo[:M]] and r.n == [int(v) for v in xo[M:2 * M]], (case, ask, r)
+
+
 @pytest.mark.parametrize("name,alone", SIDES)
 def test_bounded_sweep_on_both_sides(ctx, name, alone):
     """halda_solve_bounded_batch within the D = 2 move box around the oracle's optimum: the fused bounded sweep
     at R + 1 = 64; at 65 the general route ("auto") and the table route: each against the exact oracle on the
     dense problem with the w columns' bounds narrowed."""
     sh, model, cases, fleets = two(name)
-    M, W = 64, sh.L
-    boxes = []
-    for case in cases:
-        w0 = [int(v) for v in np.rint(pe.exact(case, 1)[1][:M])]
-        boxes.append(([max(1, v - 2) for v in w0], [min(W, v + 2) for v in w0]))
+    boxes = move_boxes(cases, sh.L)
     try:
         for ask, route in ((("auto", "fused"),) if alone else (("auto", "general"), ("tables", "tables"))):
             got = bd.halda_solve_bounded_batch(fleets, model, boxes, k_candidates=[1], kv_bits=pe.KV, route=ask)
             assert bd.last_bounds_route(ctx) == route, (ask, bd.last_bounds_route(ctx))
-            for case, (lo, hi), r in zip(cases, boxes, got):
-                p = dict(pe.problem(case, 1))
-                p["lb"], p["ub"] = p["lb"].copy(), p["ub"].copy()
-                p["lb"][:M], p["ub"][:M] = lo, hi
-                st, xo, b1, b2, _ = mo.exact_solve(p)
-                assert st == 0, (case, st)  # the move box around the optimum holds the optimum
-                assert r is not None and r.k == 1, (case, ask)
-                assert pe.close(r.obj_value, mo.objective_value(p, xo)), (case, ask, r.obj_value)
-                assert pe.close(r.obj_value, pe.objective(case, 1)), (case, ask)
-                assert all(a <= v <= b for a, v, b in zip(lo, r.w, hi)), (case, ask)
-                if mo.uniqueness_margin_ok(b1, b2):
-                    assert r.w == [int(v) for v in xo[:M]] and r.n == [int(v) for v in xo[M:2 * M]], (case, ask, r)
+            check_bounded(cases, boxes, got, ask)
     finally:
         restore(ctx)
 
