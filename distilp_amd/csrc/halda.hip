@@ -5,13 +5,14 @@
 // the whole halda_solve k-sweep of :369-436 (halda_solve_fleets); the C ABI is in
 // include/halda.h, the design (and why the solve is exact) in DESIGN.md.
 //
-// One translation unit in five files:
+// One translation unit in six files:
 //   halda_prims.hpp  constants, stamps, LDS slices, wave / segment reductions;
 //   halda_solve.hpp  the milp() replacement: records, splits, greedy, DP, CSR decode,
 //                    screen / k = 1 / general kernels;
 //   halda_sweep.hpp  the k-sweep: GPU lowering, fused sweep kernels, k-slot kernel, pick;
 //   halda.hip        host side: contexts, launch sequences, the C ABI, RCCL latency mode;
-//   halda_stage.hpp  the host entries' staging layout (no HIP: also built alone by a CPU test).
+//   halda_stage.hpp  the host entries' staging layout (no HIP: also built alone by a CPU test);
+//   halda_launch.hpp the launch record, the families' path / route knobs, result slices (no HIP either).
 // Floating point keeps the reference's operation order (-ffp-contract=off).
 
 #include <hip/hip_runtime.h>
@@ -34,6 +35,7 @@
 
 #include "halda.h"
 #include "halda_boxes.h"
+#include "halda_launch.hpp"
 #include "halda_stage.hpp"
 
 namespace {
@@ -110,10 +112,7 @@ struct Ctx {
     hipEvent_t ev_host = nullptr;   // completion of a small synchronous call (polled, not waited on)
     hipEvent_t evf0 = nullptr, evf1 = nullptr;  // around a halda_solve_fleets sequence (lowering .. pick)
     hipEvent_t evfm = nullptr;                   // fused sweep: between its first and second launch
-    bool fleet_two = false;                      // fused sweep: a second launch was enqueued
-    bool fleet_reg_alone = false;                // fused sweep: the register launch alone
-    bool fleet_seg = false;                      // fused sweep: the first launch was the segment kernel
-    bool fleet_kslot = false;                    // fused sweep: the first launch was the k-slot kernel
+    lrec::Record fleet_record = lrec::Record::none;  // what the last timed sequence was (halda_last_fleet_ms)
     bool kslot_sweep = true;                     // fused sweep: k-slot launch where it applies (else segment)
     int kslot_split = 2;                         // k-slot launch: the longest scan split over 2 waves (0: unsplit)
     bool kslot_opt = true;                       // ... its part 1 optimistic (leaf checks / phase 0 by other waves)
@@ -132,7 +131,6 @@ struct Ctx {
     bool host_copy = false;        // halda_solve_fleets_host: PCIe copies even for small calls (HALDA_HOST_PATH=copy)
     bool fused_screen = true;      // a settled batch screens inside its k = 1 kernel (HALDA_FUSED_SCREEN=0: screen launch)
     bool fused_last = false;       // the last CSR launch screened in its k = 1 kernel (halda_last_phase_ms)
-    bool last_fleet_fused = false;
     int path_gen = 0;              // bumped by halda_set_fleets_path: prepared plans re-plan on their next launch
     void *shard = nullptr;         // rank-local results of halda_solve_fleets_sharded
     size_t shard_bytes = 0;
@@ -162,26 +160,16 @@ struct Ctx {
     size_t fleet_scratch_bytes = 0;
     uint8_t *sub_tab = nullptr;     // halda_solve_subfleets: the expanded table of the expansion route
     size_t sub_tab_bytes = 0;
-    int sub_path = 0;               // halda_set_subfleets_path: 0 automatic, 1 always expand
-    int sub_route = 0;              // the last halda_solve_subfleets call: 1 fused, 2 expansion (0: none yet)
     uint8_t *sel_buf = nullptr;     // halda_solve_subsets: combo lists, per-(d, fleet) records, per-candidate results
     size_t sel_bytes = 0;
-    int sel_path = 0;               // halda_set_subsets_path: 0 automatic, 1 always expand
-    int sel_route = 0;              // the last halda_solve_subsets call: 1 fused, 2 expansion, 3 mixed (0: none yet)
     int64_t scale_chunk = 0;        // halda_set_change_subsets_chunk: a launch's scratch cap (0: the default)
     uint8_t *var_desc = nullptr;    // halda_solve_variants: the fused route's per-variant models (SweepModel)
     size_t var_desc_bytes = 0;
-    int var_path = 0;               // halda_set_variants_path: 0 automatic, 1 always loop
-    int var_route = 0;              // the last halda_solve_variants call: 1 fused, 2 loop (0: none yet)
-    int plans_path = 0;             // halda_set_plans_path: 0 automatic, 1 always two launches, 2 fused where it applies
-    int plans_route = 0;            // the last halda_solve_fleets_plans call: 1 fused, 2 two launches (0: none yet)
-    int bounds_path = 0;            // halda_set_bounds_path: 0 automatic, 1 always general, 2 fused where it applies,
-                                    // 3 fused, else the table launch, where they apply
-    int bounds_route = 0;           // the last halda_solve_fleets_bounded call: 1 fused, 2 general, 3 table launch
-                                    // (0: none yet)
-    int boxes_path = 0;             // halda_set_boxes_path: 0 automatic, 1 always loop
-    int boxes_route = 0;            // the last halda_solve_fleets_boxes call: 1 register launch, 3 table launch, 2 loop
-                                    // (0: none yet)
+    // Per entry family the path halda_set_<family>_path chose (0: automatic; the admissible codes:
+    // lrec::kKnobRules) and the route of the family's last call (0: none yet). Routes -- sub-fleets: 1 fused,
+    // 2 expansion; subsets: 1 fused, 2 expansion, 3 mixed; variants: 1 fused, 2 loop; plans: 1 fused, 2 two
+    // launches; bounds: 1 fused, 2 general, 3 table launch; boxes: 1 register launch, 3 table launch, 2 loop.
+    lrec::Knob knob[lrec::kFamilies];
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -524,6 +512,16 @@ struct SweepPlan {
     const void *fn1;   // first kernel (for the occupancy / LDS attribute)
 };
 
+lrec::Record sweep_record(SweepKind k) {
+    switch (k) {
+        case kRegAlone: return lrec::Record::reg_alone;
+        case kTablesAlone: return lrec::Record::tables_alone;
+        case kSegGated: return lrec::Record::seg_then_tables;
+        case kKslotGated: return lrec::Record::kslot_then_tables;
+        default: return lrec::Record::reg_then_tables;  // kRegGated, kRegBig
+    }
+}
+
 int plan_sweep(Ctx *c, const halda_model &model, const halda_fleets &F, const int32_t *kh, int n_k,
                const halda_fleet_result &out, SweepPlan *P) {
     const int nf = F.n_fleets;
@@ -737,6 +735,80 @@ int plan_sweep(Ctx *c, const halda_model &model, const halda_fleets &F, const in
     return HALDA_OK;
 }
 
+// An entry's first step on the GPU: the context's device made current (only when it is not), and the caller's
+// stream, or the context's own for NULL.
+int enter(Ctx *c, void *stream, hipStream_t *s) {
+    int cur_dev = -1;
+    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
+    *s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    return HALDA_OK;
+}
+
+// ---- what every launch of a fused-sweep kernel shares (the record itself: halda_launch.hpp)
+// The per-launch fields of a plan's arguments: the scratch in use (none: the context's hand-back flag, never
+// written), a fresh launch id, the first pass.
+void stamp(Ctx *c, SweepArgs &A, uint8_t *fflag, int *hb_flag) {
+    A.fflag = fflag;
+    A.hb_flag = hb_flag;
+    A.launch_id = ++c->launch_id;
+    A.want = 0;
+}
+
+// From here on the context's last timed sequence and lowered batch are no longer the previous call's.
+void forget_last(Ctx *c) {
+    c->fleet_timed = false;
+    c->have_lowered = false;
+}
+
+// A family's single launch, step one: arguments stamped (nothing flags, nothing is handed back), the last
+// record forgotten. What the family must still look up (occupancy, an LDS limit) comes between this and launch_one.
+void begin_one(Ctx *c, SweepArgs &A) {
+    stamp(c, A, nullptr, c->hb_flag);
+    forget_last(c);
+}
+
+int launched() {
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+// The end of a timed sequence: evf1, and what ran.
+int finish(Ctx *c, hipStream_t s, lrec::Record r) {
+    if (c->timing) {
+        HIP_TRY(hipEventRecord(c->evf1, s));
+        c->fleet_timed = true;
+    }
+    c->fleet_record = r;
+    return HALDA_OK;
+}
+
+// Step two: evf0, the family's kernel (`enqueue` launches it and answers its status), evf1, the record and the
+// family's route. An error leaves the route and the record as they were.
+template <class Enqueue>
+int launch_one(Ctx *c, hipStream_t s, lrec::Record r, lrec::Family family, int route, Enqueue &&enqueue) {
+    if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+    int rc = enqueue();
+    if (rc == HALDA_OK) rc = finish(c, s, r);
+    if (rc == HALDA_OK) c->knob[family].route = route;
+    return rc;
+}
+
+// halda_set_<family>_path / halda_last_<family>_route (the admissible paths: lrec::kKnobRules)
+int set_family_path(void *ctx, lrec::Family family, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (const char *why = lrec::path_error(family, path)) return fail(HALDA_E_ARG, why);
+    c->knob[family].path = path;
+    return HALDA_OK;
+}
+
+int last_family_route(void *ctx, lrec::Family family, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->knob[family].route;
+    return HALDA_OK;
+}
+
 // Enqueue a planned sweep on stream s: the stream's scratch slot (when the plan uses scratch), the
 // first launch and the gated table launch behind it (global tables: after the previous launch on them).
 int run_sweep(Ctx *c, SweepPlan &p, hipStream_t s) {
@@ -746,12 +818,8 @@ int run_sweep(Ctx *c, SweepPlan &p, hipStream_t s) {
         const int rc = sweep_slot(c, s, p.nf, &slot);
         if (rc != HALDA_OK) return rc;
     }
-    A.fflag = p.scratch ? slot->fflag : nullptr;
-    A.hb_flag = p.scratch ? slot->hb : c->hb_flag;
-    A.launch_id = ++c->launch_id;
-    A.want = 0;
-    c->fleet_timed = false;
-    c->have_lowered = false;
+    stamp(c, A, p.scratch ? slot->fflag : nullptr, p.scratch ? slot->hb : c->hb_flag);
+    forget_last(c);
     if (p.lds > 0) HIP_TRY(Ctx::ensure_lds(p.fn1, p.lds));
     if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
     switch (p.kind) {
@@ -794,16 +862,7 @@ int run_sweep(Ctx *c, SweepPlan &p, hipStream_t s) {
         }
         HIP_TRY(hipGetLastError());
     }
-    if (c->timing) {
-        HIP_TRY(hipEventRecord(c->evf1, s));
-        c->fleet_timed = true;
-    }
-    c->fleet_two = two;
-    c->fleet_reg_alone = p.kind == kRegAlone;
-    c->fleet_seg = p.kind == kSegGated;
-    c->fleet_kslot = p.kind == kKslotGated;
-    c->last_fleet_fused = true;
-    return HALDA_OK;
+    return finish(c, s, sweep_record(p.kind));
 }
 
 // The last call's arguments and plan: a caller repeating a call on the same buffers (a single
@@ -889,10 +948,7 @@ int resident_sweep(Ctx *c, const SweepPlan &p, bool *done, bool *retry) {
     }
     ResidentBox *box = c->rbox;
     SweepArgs A = p.A;
-    A.fflag = nullptr;
-    A.hb_flag = c->hb_flag;
-    A.launch_id = ++c->launch_id;
-    A.want = 0;
+    stamp(c, A, nullptr, c->hb_flag);
     std::memcpy(static_cast<void *>(&box->req), &A, sizeof A);
     auto launch = [&](uint32_t last) -> int {
         ResidentArgs R;
@@ -1363,16 +1419,17 @@ int halda_last_fleet_ms(void *ctx, double *ms8) {
     if (!c->fleet_timed) return fail(HALDA_E_ARG, "no timed halda_solve_fleets call on this context");
     HIP_TRY(hipEventSynchronize(c->evf1));
     for (int i = 0; i < 9; ++i) ms8[i] = 0.0;
-    if (c->last_fleet_fused) {
+    const lrec::Slots at = lrec::record_slots(c->fleet_record);
+    if (at.first >= 0) {
         float a = 0.f, b = 0.f;
-        if (c->fleet_two) {
+        if (at.second >= 0) {
             HIP_TRY(hipEventElapsedTime(&a, c->evf0, c->evfm));
             HIP_TRY(hipEventElapsedTime(&b, c->evfm, c->evf1));
-            ms8[c->fleet_kslot ? 8 : c->fleet_seg ? 7 : 0] = a;
-            ms8[1] = b;
+            ms8[at.first] = a;
+            ms8[at.second] = b;
         } else {
             HIP_TRY(hipEventElapsedTime(&a, c->evf0, c->evf1));
-            ms8[c->fleet_reg_alone ? 0 : 1] = a;  // the register launch or the table launch alone
+            ms8[at.first] = a;  // the register launch or the table launch alone
         }
         return HALDA_OK;
     }
@@ -1467,9 +1524,8 @@ int halda_solve_fleets(void *ctx, const halda_model *model, const halda_fleets *
         const int rc = check_fleets_args(model, fleets, ks, n_k, out);
         if (rc != HALDA_OK) return rc;
     }
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     // the fused sweep orders itself: per-stream scratch slots, and order_after_previous before a launch
     // on the context's global tables
     if (c->fleets_fused && n_k <= 64) return sweep_fleets(c, *model, F, ks, n_k, *out, s);
@@ -1529,7 +1585,7 @@ static int fleets_csr(Ctx *c, const halda_model *model, const halda_fleets &F, c
     O.integrality = reinterpret_cast<uint8_t *>(base + o_int);
     O.offs = reinterpret_cast<double *>(base + o_offs);
     c->fleet_timed = false;
-    c->last_fleet_fused = false;
+    c->fleet_record = lrec::Record::csr;
     if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
     hipLaunchKernelGGL(halda_lower_kernel, dim3(unsigned(F.n_fleets)), dim3(64), 0, s, *model, F, ks_dev, int(n_k), D,
                        O);
@@ -1636,15 +1692,15 @@ int halda_fleets_plan_launch(void *plan, void *stream) {
     if (!P->c) return fail(HALDA_E_ARG, "halda_fleets_plan_launch: the plan's context was freed");
     if (P->F.n_fleets <= 0) return HALDA_OK;
     Ctx *c = P->c;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     if (P->gen != c->path_gen) {  // halda_set_fleets_path since: plan the context's current path
         const int rc = replan(P);
         if (rc != HALDA_OK) return rc;
     }
     if (!P->fused)
         return halda_solve_fleets(c, &P->model, &P->F, P->ks.data(), int32_t(P->ks.size()), &P->out, stream);
-    return run_sweep(c, P->p, stream ? static_cast<hipStream_t>(stream) : c->stream);
+    return run_sweep(c, P->p, s);
 }
 
 int halda_fleets_plan_launch_many(void *const *plans, int32_t n_plans, void *const *streams, int32_t n_streams,
@@ -1742,9 +1798,8 @@ int group_check(FleetsGroup *G) {
 template <class Args>
 int launch_frontier(Ctx *c, void (*kernel)(SweepArgs, Args), const halda_model &model,
                     const halda_fleets &view, int32_t k, int64_t slice, const Args &J, void *stream) {
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     SweepArgs A = {};
     static_cast<halda_model &>(A.Mo) = model;
     A.Mo.bvo = model_bvo(model);
@@ -1801,13 +1856,12 @@ int halda_fleets_group_launch(void *group, int64_t first, int32_t steps, void *s
     if (!G->c) return fail(HALDA_E_ARG, "halda_fleets_group_launch: the group's context was freed");
     if (steps < 0 || first < 0) return fail(HALDA_E_ARG, "halda_fleets_group_launch: steps and first must be >= 0");
     Ctx *c = G->c;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != c->device) HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     if (G->gen != c->path_gen) {
         const int rc = group_check(G);
         if (rc != HALDA_OK) return rc;
     }
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
     const int64_t n = int64_t(G->plans.size());
     if (steps == 0 || G->plans[0].F.n_fleets <= 0) return HALDA_OK;
     if (!G->persistent) {  // batch by batch, each its own launch(es), in order on the one stream
@@ -1825,17 +1879,13 @@ int halda_fleets_group_launch(void *group, int64_t first, int32_t steps, void *s
     SG.first = int(first % n);
     SG.steps = steps;
     SG.fflag = G->fflag;
-    c->fleet_timed = false;
-    c->have_lowered = false;
+    forget_last(c);
     const int nf = G->plans[0].F.n_fleets;
     if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
     if (G->kslot) {
         const SweepPlan &p = G->plans[0].p;
         SweepArgs A = G->A;
-        A.fflag = nullptr;  // per batch: SG.fflag
-        A.hb_flag = G->hb;
-        A.launch_id = ++c->launch_id;
-        A.want = 0;
+        stamp(c, A, nullptr, G->hb);  // (the flags per batch: SG.fflag)
         if (steps > 65535) return fail(HALDA_E_ARG, "halda_fleets_group_launch: more than 65,535 k-slot steps");
         // one workgroup per (batch, group of four fleets): the dispatcher's order is the items' order
         const unsigned ng = unsigned((nf + 64 / kSegLanes - 1) / (64 / kSegLanes));
@@ -1857,16 +1907,7 @@ int halda_fleets_group_launch(void *group, int64_t first, int32_t steps, void *s
                            dim3(64 * kSweepWavesPerBlock), 0, s, G->A, SG);
         HIP_TRY(hipGetLastError());
     }
-    if (c->timing) {
-        HIP_TRY(hipEventRecord(c->evf1, s));
-        c->fleet_timed = true;
-    }
-    c->fleet_two = G->kslot;
-    c->fleet_reg_alone = !G->kslot;
-    c->fleet_seg = false;
-    c->fleet_kslot = G->kslot;
-    c->last_fleet_fused = true;
-    return HALDA_OK;
+    return finish(c, s, G->kslot ? lrec::Record::kslot_steps_then_tables : lrec::Record::steps_alone);
 }
 
 void halda_fleets_group_free(void *group) {
@@ -2025,20 +2066,8 @@ int halda_solve_fleets_host(void *ctx, const halda_model *model, const halda_fle
 // sub_off, and the ordinary halda_solve_fleets runs on it into the caller's out. sub_tab is per context:
 // a call that uses it runs after the previous user of the context's shared scratch on another stream
 // (order_after_previous), like the global tables.
-int halda_set_subfleets_path(void *ctx, int path) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
-    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "sub-fleets path must be 0 (automatic) or 1 (always expand)");
-    c->sub_path = path;
-    return HALDA_OK;
-}
-
-int halda_last_subfleets_route(void *ctx, int *route) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
-    *route = c->sub_route;
-    return HALDA_OK;
-}
+int halda_set_subfleets_path(void *ctx, int path) { return set_family_path(ctx, lrec::kSubfleets, path); }
+int halda_last_subfleets_route(void *ctx, int *route) { return last_family_route(ctx, lrec::kSubfleets, route); }
 
 // total: sub_off[n_items] when the caller knows it (the host variant), -1 to read it back where needed
 static int solve_subfleets(void *ctx, const halda_model *model, const halda_fleets *table,
@@ -2060,37 +2089,20 @@ static int solve_subfleets(void *ctx, const halda_model *model, const halda_flee
         const int rc = check_fleets_args(model, &V, ks, n_k, out);
         if (rc != HALDA_OK) return rc;
     }
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     const SubArgs S{I.parent, I.sub_off, I.sub_idx};
-    if (c->sub_path == 0 && c->fleets_fused && n_k <= 64 && I.min_devices == I.max_devices &&
+    if (c->knob[lrec::kSubfleets].path == 0 && c->fleets_fused && n_k <= 64 && I.min_devices == I.max_devices &&
         I.max_devices <= kK1MaxM) {
         SweepPlan p;
         const int rc = plan_sweep(c, *model, V, ks, n_k, *out, &p);
         if (rc != HALDA_OK) return rc;
         if (p.kind == kRegAlone && !p.A.k1dp) {
-            SweepArgs &A = p.A;
-            A.fflag = nullptr;  // the register sweep alone never flags
-            A.hb_flag = c->hb_flag;
-            A.launch_id = ++c->launch_id;
-            A.want = 0;
-            c->fleet_timed = false;
-            c->have_lowered = false;
-            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            hipLaunchKernelGGL(halda_sweep_subfleets_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, S);
-            HIP_TRY(hipGetLastError());
-            if (c->timing) {
-                HIP_TRY(hipEventRecord(c->evf1, s));
-                c->fleet_timed = true;
-            }
-            c->fleet_two = false;
-            c->fleet_reg_alone = true;
-            c->fleet_seg = false;
-            c->fleet_kslot = false;
-            c->last_fleet_fused = true;
-            c->sub_route = 1;
-            return HALDA_OK;
+            begin_one(c, p.A);
+            return launch_one(c, s, lrec::Record::reg_alone, lrec::kSubfleets, 1, [&]() -> int {
+                hipLaunchKernelGGL(halda_sweep_subfleets_kernel, dim3(p.grid1), dim3(p.block1), 0, s, p.A, S);
+                return launched();
+            });
         }
     }
     // expansion: the listed devices as a compact table (16 double and 2 byte arrays of nd entries)
@@ -2119,7 +2131,7 @@ static int solve_subfleets(void *ctx, const halda_model *model, const halda_flee
     X.os_class = E.os_class;
     X.flags = E.flags;
     for (int a = 0; a < stage::kFields; ++a) X.*stage::kField[a] = E.f[a];
-    c->sub_route = 2;
+    c->knob[lrec::kSubfleets].route = 2;
     return halda_solve_fleets(ctx, model, &X, ks, n_k, out, s);
 }
 
@@ -2225,20 +2237,8 @@ constexpr int64_t kSubsetsChunkDevices = int64_t(1) << 21;
 constexpr int64_t kSubsetsFusedChunk = int64_t(1) << 22;
 constexpr int kSubsetsRing = 8192;  // 64-entry w / n strips of the fused route (written, never read)
 
-int halda_set_subsets_path(void *ctx, int path) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
-    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "subsets path must be 0 (automatic) or 1 (always expand)");
-    c->sel_path = path;
-    return HALDA_OK;
-}
-
-int halda_last_subsets_route(void *ctx, int *route) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
-    *route = c->sel_route;
-    return HALDA_OK;
-}
+int halda_set_subsets_path(void *ctx, int path) { return set_family_path(ctx, lrec::kSubsets, path); }
+int halda_last_subsets_route(void *ctx, int *route) { return last_family_route(ctx, lrec::kSubsets, route); }
 
 static int64_t binom_sat(int q, int d) {
     if (d < 0 || d > q) return 0;
@@ -2324,9 +2324,8 @@ static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets
     if (D > Dmax)
         return fail(HALDA_E_ARG, "halda_subsets: max_drop " + std::to_string(D) + " is beyond min(q, M - 1) = " +
                                      std::to_string(Dmax) + " of every fleet");
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     // the combo lists of every (q, d) in use, and the records per (d, fleet)
     std::vector<uint64_t> combos;
     std::vector<int64_t> coff(65 * 64, -1);
@@ -2357,7 +2356,7 @@ static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets
         bool fused = false;
         SweepPlan p;
         const int64_t padded = cmax * nf;
-        if (c->sel_path == 0 && c->fleets_fused && n_k <= 64 && uniform && padded < (int64_t(1) << 31)) {
+        if (c->knob[lrec::kSubsets].path == 0 && c->fleets_fused && n_k <= 64 && uniform && padded < (int64_t(1) << 31)) {
             halda_fleets V = *table;
             V.n_fleets = int32_t(std::min(padded, kSubsetsFusedChunk));
             V.min_devices = V.max_devices = sizes[0] - d;
@@ -2450,15 +2449,12 @@ static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets
             SweepPlan p;
             const int rc = plan_sweep(c, *model, V, ks, n_k, out, &p);
             if (rc != HALDA_OK) return rc;
-            SweepArgs &A = p.A;
-            A.fflag = nullptr;  // the register sweep alone never flags
-            A.hb_flag = c->hb_flag;
-            A.launch_id = ++c->launch_id;
-            A.want = 0;
+            // (no events, no record, and fleet_timed as an expansion launch of this call may have left it)
+            stamp(c, p.A, nullptr, c->hb_flag);
             c->have_lowered = false;
             hipLaunchKernelGGL(halda_sweep_subsets_kernel,
                                dim3(unsigned((L.n + kSweepWavesPerBlock - 1) / kSweepWavesPerBlock)),
-                               dim3(64 * kSweepWavesPerBlock), 0, s, A, U, kSubsetsRing - 1);
+                               dim3(64 * kSweepWavesPerBlock), 0, s, p.A, U, kSubsetsRing - 1);
             HIP_TRY(hipGetLastError());
         } else {
             U.l0 = L.l0;
@@ -2474,11 +2470,8 @@ static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets
                                reinterpret_cast<int32_t *>(base + o_sidx));
             HIP_TRY(hipGetLastError());
             // the sub-fleet entry's expansion route, unedited, on the items just written
-            const int path = c->sub_path, route = c->sub_route;
-            c->sub_path = 1;
+            const lrec::PathOverride expand(c->knob[lrec::kSubfleets], 1, /*keep_route=*/true);
             const int rc = solve_subfleets(ctx, model, table, &I, ks, n_k, &out, s, L.nd);
-            c->sub_path = path;
-            c->sub_route = route;
             if (rc != HALDA_OK) return rc;
         }
         hipLaunchKernelGGL(halda_subsets_pick_kernel, dim3(unsigned(nf)), dim3(256), 0, s, U,
@@ -2486,7 +2479,7 @@ static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets
                            D + 1);
         HIP_TRY(hipGetLastError());
     }
-    c->sel_route = any_fused && any_expand ? 3 : any_fused ? 1 : 2;
+    c->knob[lrec::kSubsets].route = any_fused && any_expand ? 3 : any_fused ? 1 : 2;
     return HALDA_OK;
 }
 
@@ -2567,20 +2560,8 @@ int halda_solve_subsets_host(void *ctx, const halda_model *model, const halda_fl
 // model, and compares the fleet count alone with kSweepSmallBatch). The variants' models go into the
 // context's grow-only var_desc with the stream; var_desc is per context, so the call runs after the
 // previous user of the context's shared scratch on another stream (order_after_previous).
-int halda_set_variants_path(void *ctx, int path) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
-    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "variants path must be 0 (automatic) or 1 (always loop)");
-    c->var_path = path;
-    return HALDA_OK;
-}
-
-int halda_last_variants_route(void *ctx, int *route) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
-    *route = c->var_route;
-    return HALDA_OK;
-}
+int halda_set_variants_path(void *ctx, int path) { return set_family_path(ctx, lrec::kVariants, path); }
+int halda_last_variants_route(void *ctx, int *route) { return last_family_route(ctx, lrec::kVariants, route); }
 
 static int check_variants(const halda_model *models, int32_t n_var) {
     if (n_var < 1 || n_var > 65535) return fail(HALDA_E_ARG, "n_var must be in 1..65535");
@@ -2611,12 +2592,11 @@ static int solve_variants(void *ctx, const halda_model *models, int32_t n_var, c
         const int rc = check_fleets_args(&models[v], fleets, ks, n_k, out);
         if (rc != HALDA_OK) return rc;
     }
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     const int64_t nf = F.n_fleets;
     // the fused kernels index fleets and (fleet, k) instances over all variants with 32 bits
-    if (c->var_path == 0 && c->fleets_fused && n_k <= 64 && int64_t(n_var) * nf * n_k < (int64_t(1) << 31)) {
+    if (c->knob[lrec::kVariants].path == 0 && c->fleets_fused && n_k <= 64 && int64_t(n_var) * nf * n_k < (int64_t(1) << 31)) {
         SweepPlan p;
         const int rc = plan_sweep(c, models[0], F, ks, n_k, *out, &p);
         if (rc != HALDA_OK) return rc;
@@ -2636,36 +2616,21 @@ static int solve_variants(void *ctx, const halda_model *models, int32_t n_var, c
             HIP_TRY(hipMemcpyAsync(c->var_desc, h.data(), sizeof(SweepModel) * h.size(), hipMemcpyHostToDevice, s));
             const VarArgs V{reinterpret_cast<const SweepModel *>(c->var_desc)};
             SweepArgs &A = p.A;
-            A.fflag = nullptr;  // neither plan flags: one launch, nothing behind it
-            A.hb_flag = c->hb_flag;
-            A.launch_id = ++c->launch_id;
-            A.want = 0;
-            c->fleet_timed = false;
-            c->have_lowered = false;
-            if (reg) {
-                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-                hipLaunchKernelGGL(halda_sweep_variants_kernel, dim3(p.grid1, unsigned(n_var)), dim3(p.block1), 0, s, A,
-                                   V);
-            } else {
-                A.uM = 0;  // every extent from dev_off (the kernel moves its view of it per variant)
-                const void *fn = reinterpret_cast<const void *>(halda_sweep_tables_variants_kernel);
-                HIP_TRY(Ctx::ensure_lds(fn, p.lds));
-                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+            begin_one(c, A);  // neither plan flags: one launch, nothing behind it
+            if (reg)
+                return launch_one(c, s, lrec::Record::reg_alone, lrec::kVariants, 1, [&]() -> int {
+                    hipLaunchKernelGGL(halda_sweep_variants_kernel, dim3(p.grid1, unsigned(n_var)), dim3(p.block1), 0,
+                                       s, A, V);
+                    return launched();
+                });
+            A.uM = 0;  // every extent from dev_off (the kernel moves its view of it per variant)
+            const void *fn = reinterpret_cast<const void *>(halda_sweep_tables_variants_kernel);
+            HIP_TRY(Ctx::ensure_lds(fn, p.lds));
+            return launch_one(c, s, lrec::Record::tables_alone, lrec::kVariants, 1, [&]() -> int {
                 hipLaunchKernelGGL(halda_sweep_tables_variants_kernel, dim3(p.grid1, unsigned(n_var)), dim3(64),
                                    size_t(p.lds), s, A, V);
-            }
-            HIP_TRY(hipGetLastError());
-            if (c->timing) {
-                HIP_TRY(hipEventRecord(c->evf1, s));
-                c->fleet_timed = true;
-            }
-            c->fleet_two = false;
-            c->fleet_reg_alone = reg;
-            c->fleet_seg = false;
-            c->fleet_kslot = false;
-            c->last_fleet_fused = true;
-            c->var_route = 1;
-            return HALDA_OK;
+                return launched();
+            });
         }
     }
     // the loop: variant v's slice of every output
@@ -2676,23 +2641,10 @@ static int solve_variants(void *ctx, const halda_model *models, int32_t n_var, c
         if (nd < 0) return fail(HALDA_E_ARG, "halda_fleets: dev_off[n_fleets] < 0");
     }
     const int64_t xstride = 7 * int64_t(std::max(F.max_devices, 1)) + 1;
-    c->var_route = 2;
+    c->knob[lrec::kVariants].route = 2;
     for (int64_t v = 0; v < n_var; ++v) {
-        halda_fleet_result o = *out;
-        o.best_k += v * nf;
-        o.obj_value += v * nf;
-        if (v) {
-            o.w += v * nd;
-            o.n += v * nd;
-        }
-        if (o.obj_by_k) o.obj_by_k += v * nf * n_k;
-        if (o.status) o.status += v * nf * n_k;
-        if (o.x_off) {
-            o.x_off += v * nf * n_k;  // absolute offsets into the one x / c
-        } else {
-            if (o.x) o.x += v * nf * n_k * xstride;
-            if (o.c) o.c += v * nf * n_k * xstride;
-        }
+        // (nd is not read back for one variant: slice 0 asks for no offset)
+        halda_fleet_result o = lrec::result_slice(*out, v, nf, v ? v * nd : 0, n_k, xstride);
         const int rc = halda_solve_fleets(ctx, &models[v], fleets, ks, n_k, &o, s);
         if (rc != HALDA_OK) return rc;
     }
@@ -2750,21 +2702,8 @@ int halda_solve_variants_host(void *ctx, const halda_model *models, int32_t n_va
 // caller's stream. Fused route (path 2): where the sweep is the register launch alone over fleets of one size
 // <= kK1MaxM (kRegAlone, the sub-fleet and variants kernels' gate), ONE launch of halda_sweep_plans_kernel --
 // each wave prices its fleet's plan on the fields it loads for the sweep.
-int halda_set_plans_path(void *ctx, int path) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
-    if (path < 0 || path > 2)
-        return fail(HALDA_E_ARG, "plans path must be 0 (automatic), 1 (always two launches) or 2 (fused where it applies)");
-    c->plans_path = path;
-    return HALDA_OK;
-}
-
-int halda_last_plans_route(void *ctx, int *route) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
-    *route = c->plans_route;
-    return HALDA_OK;
-}
+int halda_set_plans_path(void *ctx, int path) { return set_family_path(ctx, lrec::kPlans, path); }
+int halda_last_plans_route(void *ctx, int *route) { return last_family_route(ctx, lrec::kPlans, route); }
 
 // Argument checks of the plan entries, before any HIP call (HALDA_OK: go on).
 static int check_plans_args(const void *ctx, const halda_model *model, const halda_fleets *fleets,
@@ -2821,9 +2760,8 @@ int halda_eval_plans(void *ctx, const halda_model *model, const halda_fleets *fl
         const int rc = check_plans_table(F);
         if (rc != HALDA_OK) return rc;
     }
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     return launch_eval_plans(*model, F, plan_args(F, *plans, *out), s);
 }
 
@@ -2842,45 +2780,28 @@ int halda_solve_fleets_plans(void *ctx, const halda_model *model, const halda_fl
         const int rc = check_fleets_args(model, fleets, ks, n_k, out);
         if (rc != HALDA_OK) return rc;
     }
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     const PlanArgs E = plan_args(F, *plans, *eval_out);
     // automatic = two launches: the fused launch measured 7 % ahead of them on C3's shape, inside the
     // box-to-box spread, so it stays behind path 2
-    if (c->plans_path == 2 && c->fleets_fused && n_k <= 64) {
+    if (c->knob[lrec::kPlans].path == 2 && c->fleets_fused && n_k <= 64) {
         SweepPlan p;
         const int rc = plan_sweep(c, *model, F, ks, n_k, *out, &p);
         if (rc != HALDA_OK) return rc;
         if (p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM && !p.A.k1dp) {
-            SweepArgs &A = p.A;
-            A.fflag = nullptr;  // the register sweep alone never flags
-            A.hb_flag = c->hb_flag;
-            A.launch_id = ++c->launch_id;
-            A.want = 0;
-            c->fleet_timed = false;
-            c->have_lowered = false;
-            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            hipLaunchKernelGGL(halda_sweep_plans_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, E);
-            HIP_TRY(hipGetLastError());
-            if (c->timing) {
-                HIP_TRY(hipEventRecord(c->evf1, s));
-                c->fleet_timed = true;
-            }
-            c->fleet_two = false;
-            c->fleet_reg_alone = true;
-            c->fleet_seg = false;
-            c->fleet_kslot = false;
-            c->last_fleet_fused = true;
-            c->plans_route = 1;
-            return HALDA_OK;
+            begin_one(c, p.A);
+            return launch_one(c, s, lrec::Record::reg_alone, lrec::kPlans, 1, [&]() -> int {
+                hipLaunchKernelGGL(halda_sweep_plans_kernel, dim3(p.grid1), dim3(p.block1), 0, s, p.A, E);
+                return launched();
+            });
         }
     }
     {
         const int rc = launch_eval_plans(*model, F, E, s);
         if (rc != HALDA_OK) return rc;
     }
-    c->plans_route = 2;
+    c->knob[lrec::kPlans].route = 2;
     return halda_solve_fleets(ctx, model, fleets, ks, n_k, out, s);
 }
 
@@ -2987,22 +2908,8 @@ int halda_solve_fleets_plans_host(void *ctx, const halda_model *model, const hal
 // Table route (path 3 only, where the fused route does not apply): fleets of 1 .. kK1MaxM devices whose
 // unbounded table slice fits the LDS budget, ONE launch of halda_sweep_bounds_tables_kernel on that slice
 // (sum lo >= M, so it holds every bounded instance; nothing is handed back either).
-int halda_set_bounds_path(void *ctx, int path) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
-    if (path < 0 || path > 3)
-        return fail(HALDA_E_ARG, "bounds path must be 0 (automatic), 1 (always general), 2 (fused where it applies) or "
-                                 "3 (fused, else the table launch, where they apply)");
-    c->bounds_path = path;
-    return HALDA_OK;
-}
-
-int halda_last_bounds_route(void *ctx, int *route) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
-    *route = c->bounds_route;
-    return HALDA_OK;
-}
+int halda_set_bounds_path(void *ctx, int path) { return set_family_path(ctx, lrec::kBounds, path); }
+int halda_last_bounds_route(void *ctx, int *route) { return last_family_route(ctx, lrec::kBounds, route); }
 
 // halda_solve_fleets_bounded and halda_solve_fleets_boxed: one body on a halda_box (w bounds alone: its n
 // arrays NULL). Without n bounds every launch is the bounded call's own kernel; with them the box kernels
@@ -3018,9 +2925,8 @@ static int solve_boxed(void *ctx, const halda_model *model, const halda_fleets *
         const int rc = check_fleets_args(model, fleets, ks, n_k, out);
         if (rc != HALDA_OK) return rc;
     }
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     const bool nbox = B.n_min || B.n_max;
     // the fused kernels' second argument: the box kernels take all four arrays, the others the w pair
     BoundArgs Bd{B.w_min, B.w_max};
@@ -3028,43 +2934,24 @@ static int solve_boxed(void *ctx, const halda_model *model, const halda_fleets *
     void *bargs = nbox ? static_cast<void *>(&Bx) : static_cast<void *>(&Bd);
     // automatic = fused where admissible: one launch against the general route's lowering, patch, screen,
     // solve and pick launches
-    if (c->bounds_path != 1 && c->fleets_fused && n_k <= 64) {
+    if (c->knob[lrec::kBounds].path != 1 && c->fleets_fused && n_k <= 64) {
         SweepPlan p;
         const int rc = plan_sweep(c, *model, F, ks, n_k, *out, &p);
         if (rc != HALDA_OK) return rc;
         if (p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM) {
             SweepArgs &A = p.A;
-            A.fflag = nullptr;  // the register sweep alone never flags
-            A.hb_flag = c->hb_flag;
-            A.launch_id = ++c->launch_id;
-            A.want = 0;
-            c->fleet_timed = false;
-            c->have_lowered = false;
+            begin_one(c, A);
             const void *fn = nbox ? reinterpret_cast<const void *>(halda_sweep_box_kernel)
                                   : reinterpret_cast<const void *>(halda_sweep_bounds_kernel);
             void *args[] = {&A, bargs};
-            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            HIP_TRY(hipLaunchKernel(fn, dim3(p.grid1), dim3(p.block1), args, 0, s));
-            if (c->timing) {
-                HIP_TRY(hipEventRecord(c->evf1, s));
-                c->fleet_timed = true;
-            }
-            c->fleet_two = false;
-            c->fleet_reg_alone = true;
-            c->fleet_seg = false;
-            c->fleet_kslot = false;
-            c->last_fleet_fused = true;
-            c->bounds_route = 1;
-            return HALDA_OK;
+            return launch_one(c, s, lrec::Record::reg_alone, lrec::kBounds, 1, [&]() -> int {
+                HIP_TRY(hipLaunchKernel(fn, dim3(p.grid1), dim3(p.block1), args, 0, s));
+                return HALDA_OK;
+            });
         }
-        if (c->bounds_path == 3 && F.min_devices >= 1 && F.max_devices <= kK1MaxM && p.slice <= kLdsBudget) {
+        if (c->knob[lrec::kBounds].path == 3 && F.min_devices >= 1 && F.max_devices <= kK1MaxM && p.slice <= kLdsBudget) {
             SweepArgs &A = p.A;
-            A.fflag = nullptr;  // every fleet is solved here: nothing is flagged or handed back
-            A.hb_flag = c->hb_flag;
-            A.launch_id = ++c->launch_id;
-            A.want = 0;
-            c->fleet_timed = false;
-            c->have_lowered = false;
+            begin_one(c, A);  // every fleet is solved here: nothing is flagged or handed back
             const void *fn = nbox ? reinterpret_cast<const void *>(halda_sweep_box_tables_kernel)
                                   : reinterpret_cast<const void *>(halda_sweep_bounds_tables_kernel);
             int per_cu = 0;
@@ -3072,22 +2959,13 @@ static int solve_boxed(void *ctx, const halda_model *model, const halda_fleets *
             const unsigned grid =
                 unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(p.nf))));
             void *args[] = {&A, bargs};
-            if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-            HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(64), args, size_t(p.slice), s));
-            if (c->timing) {
-                HIP_TRY(hipEventRecord(c->evf1, s));
-                c->fleet_timed = true;
-            }
-            c->fleet_two = false;
-            c->fleet_reg_alone = false;
-            c->fleet_seg = false;
-            c->fleet_kslot = false;
-            c->last_fleet_fused = true;
-            c->bounds_route = 3;
-            return HALDA_OK;
+            return launch_one(c, s, lrec::Record::tables_alone, lrec::kBounds, 3, [&]() -> int {
+                HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(64), args, size_t(p.slice), s));
+                return HALDA_OK;
+            });
         }
     }
-    c->bounds_route = 2;
+    c->knob[lrec::kBounds].route = 2;
     return fleets_csr(c, model, F, ks, n_k, out, s, &B);
 }
 
@@ -3168,20 +3046,8 @@ int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const hal
 // Register route: under the boxed entry's fused gate, one launch of halda_sweep_boxes_kernel, blockIdx.y the
 // box. Table route: else under path 3's table gate, one launch of halda_sweep_boxes_tables_kernel, its
 // persistent grid over the n_box * n_fleets items. Neither uses context scratch.
-int halda_set_boxes_path(void *ctx, int path) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
-    if (path != 0 && path != 1) return fail(HALDA_E_ARG, "boxes path must be 0 (automatic) or 1 (always loop)");
-    c->boxes_path = path;
-    return HALDA_OK;
-}
-
-int halda_last_boxes_route(void *ctx, int *route) {
-    Ctx *c = static_cast<Ctx *>(ctx);
-    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
-    *route = c->boxes_route;
-    return HALDA_OK;
-}
+int halda_set_boxes_path(void *ctx, int path) { return set_family_path(ctx, lrec::kBoxes, path); }
+int halda_last_boxes_route(void *ctx, int *route) { return last_family_route(ctx, lrec::kBoxes, route); }
 
 static int check_boxes(const halda_boxes *boxes) {
     if (!boxes) return fail(HALDA_E_ARG, "halda_solve_fleets_boxes: NULL boxes");
@@ -3205,50 +3071,34 @@ static int solve_boxes(void *ctx, const halda_model *model, const halda_fleets *
         const int rc = check_fleets_args(model, fleets, ks, n_k, out);
         if (rc != HALDA_OK) return rc;
     }
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     const halda_boxes &B = *boxes;
     const int64_t nf = F.n_fleets, nb = B.n_box;
     // the fused kernels index fleets and (fleet, k) instances over all boxes with 32 bits
-    if (c->boxes_path == 0 && c->fleets_fused && n_k <= 64 && nb * nf * n_k < (int64_t(1) << 31)) {
+    if (c->knob[lrec::kBoxes].path == 0 && c->fleets_fused && n_k <= 64 && nb * nf * n_k < (int64_t(1) << 31)) {
         SweepPlan p;
         const int rc = plan_sweep(c, *model, F, ks, n_k, *out, &p);
         if (rc != HALDA_OK) return rc;
         const bool reg = p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM;
         if (reg || (F.min_devices >= 1 && F.max_devices <= kK1MaxM && p.slice <= kLdsBudget)) {
             SweepArgs &A = p.A;
-            A.fflag = nullptr;  // every (box, fleet) is solved in the one launch: nothing is flagged or handed back
-            A.hb_flag = c->hb_flag;
-            A.launch_id = ++c->launch_id;
-            A.want = 0;
-            c->fleet_timed = false;
-            c->have_lowered = false;
+            begin_one(c, A);  // every (box, fleet) is solved in the one launch: nothing is flagged or handed back
             const BoxesArgs Bs{B.w_min, B.w_max, B.n_min, B.n_max, int(nb)};
-            if (reg) {
-                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
-                hipLaunchKernelGGL(halda_sweep_boxes_kernel, dim3(p.grid1, unsigned(nb)), dim3(p.block1), 0, s, A, Bs);
-            } else {
-                const void *fn = reinterpret_cast<const void *>(halda_sweep_boxes_tables_kernel);
-                int per_cu = 0;
-                HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
-                const unsigned grid =
-                    unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, nb * nf)));
-                if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
+            if (reg)
+                return launch_one(c, s, lrec::Record::reg_alone, lrec::kBoxes, 1, [&]() -> int {
+                    hipLaunchKernelGGL(halda_sweep_boxes_kernel, dim3(p.grid1, unsigned(nb)), dim3(p.block1), 0, s, A,
+                                       Bs);
+                    return launched();
+                });
+            const void *fn = reinterpret_cast<const void *>(halda_sweep_boxes_tables_kernel);
+            int per_cu = 0;
+            HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
+            const unsigned grid = unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, nb * nf)));
+            return launch_one(c, s, lrec::Record::tables_alone, lrec::kBoxes, 3, [&]() -> int {
                 hipLaunchKernelGGL(halda_sweep_boxes_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A, Bs);
-            }
-            HIP_TRY(hipGetLastError());
-            if (c->timing) {
-                HIP_TRY(hipEventRecord(c->evf1, s));
-                c->fleet_timed = true;
-            }
-            c->fleet_two = false;
-            c->fleet_reg_alone = reg;
-            c->fleet_seg = false;
-            c->fleet_kslot = false;
-            c->last_fleet_fused = true;
-            c->boxes_route = reg ? 1 : 3;
-            return HALDA_OK;
+                return launched();
+            });
         }
     }
     // the loop: box b's planes in, box b's slice of every output
@@ -3259,30 +3109,16 @@ static int solve_boxes(void *ctx, const halda_model *model, const halda_fleets *
         if (nd < 0) return fail(HALDA_E_ARG, "halda_fleets: dev_off[n_fleets] < 0");
     }
     const int64_t xstride = 7 * int64_t(std::max(F.max_devices, 1)) + 1;
-    const int caller_path = c->bounds_path;
-    c->bounds_path = 3;
-    c->boxes_route = 2;
+    const lrec::PathOverride tables(c->knob[lrec::kBounds], 3);  // (put back on return)
+    c->knob[lrec::kBoxes].route = 2;
     int rc = HALDA_OK;
     for (int64_t b = 0; b < nb && rc == HALDA_OK; ++b) {
         const int64_t at = b ? b * nd : 0;
         const halda_box one = {B.w_min ? B.w_min + at : nullptr, B.w_max ? B.w_max + at : nullptr,
                                B.n_min ? B.n_min + at : nullptr, B.n_max ? B.n_max + at : nullptr};
-        halda_fleet_result o = *out;
-        o.best_k += b * nf;
-        o.obj_value += b * nf;
-        o.w += at;
-        o.n += at;
-        if (o.obj_by_k) o.obj_by_k += b * nf * n_k;
-        if (o.status) o.status += b * nf * n_k;
-        if (o.x_off) {
-            o.x_off += b * nf * n_k;  // absolute offsets into the one x / c
-        } else {
-            if (o.x) o.x += b * nf * n_k * xstride;
-            if (o.c) o.c += b * nf * n_k * xstride;
-        }
+        halda_fleet_result o = lrec::result_slice(*out, b, nf, at, n_k, xstride);
         rc = halda_solve_fleets_boxed(ctx, model, fleets, ks, n_k, &one, &o, s);
     }
-    c->bounds_path = caller_path;
     return rc;
 }
 
@@ -3717,9 +3553,8 @@ static int solve_change_subsets(void *ctx, const halda_model *model, const halda
     const std::vector<uint64_t> &drop = Q.drop;
     const std::vector<int> &qs = Q.qs, &Df = Q.Df, &sizes = Q.sizes;
     const std::vector<int64_t> &dtop = Q.dtop;
-    int cur_dev = -1;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != c->device) HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
     // the combo lists of every (q, d) in use, the records per (d, fleet), the launches
     const int64_t cap = c->scale_chunk > 0 ? c->scale_chunk : kChangeSubsetsChunkBytes;
     std::vector<uint64_t> combos;
