@@ -108,10 +108,12 @@ __device__ inline void screen_group(const halda_batch &B, const halda_result &Rz
 
     // round trip 3, per instance g (lane = device): its equality row entries -- loaded once for a run of
     // instances sharing the row (the k-instances of one fleet share its CSR) -- and the first
-    // pre = min(M, W + 1) w lower bounds. Each bound is >= 0 or makes the instance infeasible by itself
-    // (lb < 0, and ceil(lb) > W, are infeasible; NaN counts 0), so when those first bounds already need
-    // more than W layers the instance is infeasible whatever the others are (bound infeasibility, M > W
-    // = L / k: 8 of the 9 C3 instances), and the others are read only when they do not.
+    // pre = min(M, W + 1) w lower bounds. A bound counts max(0, ceil(lb)) layers (NaN counts 0; the link row
+    // n_i <= w_i with n_i >= 0 keeps w_i >= 0) and ceil(lb) > W is infeasible by itself, so when those first
+    // bounds already need more than W layers the instance is infeasible whatever the others are (bound
+    // infeasibility, M > W = L / k: 8 of the 9 C3 instances), and the others are read only when they do
+    // not. A negative bound that is read and leaves the instance feasible is not a HALDA column (w >= 0):
+    // UNSUPPORTED, after bound infeasibility.
     int cv[kScreenPer];
     double vv[kScreenPer];
     double lbv[kScreenPer];
@@ -159,33 +161,30 @@ __device__ inline void screen_group(const halda_batch &B, const halda_result &Rz
         const int64_t cg = shfl64(co, g);
         const double Wg = __shfl(Wd, g);
         int bad = 0, infeas = 0, sumlo = 0;
-        auto lbone = [&](double lb) {
+        auto lbone_to = [&](double lb, int &inf, int &sum) {
             const int wlo = int(ceil(lb));
-            infeas |= wlo > int(Wg) || lb < 0.0;
-            sumlo += wlo;
+            inf |= (wlo > int(Wg) ? 1 : 0) | (lb < 0.0 ? 2 : 0);  // bit 1: a negative bound
+            sum += max(wlo, 0);
         };
+        auto lbone = [&](double lb) { lbone_to(lb, infeas, sumlo); };
         if (lane < Mg) bad |= cv[g] != lane || vv[g] != 1.0;
         for (int i = lane + 64; i < Mg; i += 64) bad |= B.col_idx[eg + i] != i || B.val[eg + i] != 1.0;
         if (lane < pre) lbone(lbv[g]);
         for (int i = lane + 64; i < pre; i += 64) lbone(B.col_lb[cg + i]);
-        bad = wave_or(bad | (infeas << 1));
+        bad = wave_or(bad | (infeas << 1));  // 1 equality row, 2 ceil(lb) > W, 4 a negative bound
         sumlo = wave_sum(sumlo);
-        if (!bad && sumlo <= int(Wg) && pre < Mg) {  // the first bounds prove nothing: the rest of them
+        if (!(bad & 3) && sumlo <= int(Wg) && pre < Mg) {  // the first bounds prove nothing: the rest of them
             infeas = 0;
             int rest = 0;
-            for (int i = pre + lane; i < Mg; i += 64) {
-                const double lb = B.col_lb[cg + i];
-                const int wlo = int(ceil(lb));
-                infeas |= wlo > int(Wg) || lb < 0.0;
-                rest += wlo;
-            }
-            bad = wave_or(infeas << 1);
+            for (int i = pre + lane; i < Mg; i += 64) lbone_to(B.col_lb[cg + i], infeas, rest);
+            bad |= wave_or(infeas << 1);
             sumlo += wave_sum(rest);
         }
         const int W = int(Wg);
         int st = 0, v = CLS_DONE;
         if (bad & 1) st = HALDA_STATUS_UNSUPPORTED;
         else if ((bad & 2) || sumlo > W || (Mg == 0 && W > 0)) st = HALDA_STATUS_INFEASIBLE;
+        else if (bad & 4) st = HALDA_STATUS_UNSUPPORTED;  // feasible with w < 0 allowed: not a HALDA column
         else if (Mg == 0) st = HALDA_STATUS_OPTIMAL;  // no devices and W = 0: x = [C = 0]
         else {
             const int R1 = W - sumlo + 1;
@@ -818,10 +817,11 @@ __device__ inline int decode_cycle_row(const WaveCtx &w, const Inst &I, int nnz,
             const int j = cols[k];
             const int blk = block_of(j, M, I.invM);
             if (j >= 6 * M || j - blk * M != dev) rb = 1;
-            else if (blk == 0) coef0 = vals[k];
             else {
-                rb |= vals[k] != cst[blk];
+                rb |= (seen >> blk) & 1;  // a column entered twice
                 seen |= 1 << blk;
+                if (blk == 0) coef0 = vals[k];
+                else rb |= vals[k] != cst[blk];
             }
         }
     }
@@ -850,8 +850,9 @@ __device__ inline int decode_cap_row(const WaveCtx &w, const Inst &I, int nnz, d
             const int j = cols[k], blk = block_of(j, I.M, I.invM), i = j - blk * I.M;
             if (j >= 6 * I.M || (dev >= 0 && i != dev)) rb = 1;
             dev = i;
-            if (blk == 0) aw = vals[k];
-            else if (blk == 1) an = vals[k];
+            // a column entered twice is summed by a MILP solver: not taken (a first entry of 0 adds nothing)
+            if (blk == 0) { rb |= aw != 0.0; aw = vals[k]; }
+            else if (blk == 1) { rb |= an != 0.0; an = vals[k]; }
             else if (slack >= 0) rb = 1;
             else { slack = blk - 2; beta = -vals[k]; }
         }
@@ -2311,7 +2312,7 @@ __device__ int decode_k1(const halda_batch &B, const WaveCtx &w, unsigned char *
 #pragma unroll
     for (int j = 0; j < 4; ++j) dbad |= !(cv[2 + j] >= 0.0);
     int bad = act ? dbad : 0;
-    const int lo = act ? int(ceil(lbv[0])) : 0;
+    const int lo = act ? max(int(ceil(lbv[0])), 0) : 0;  // (a negative bound counts 0 layers: the screen's rule)
     if (act) w.cnt[lane] = 0;
     bad |= !(I.kc >= 0.0) || iC != 0 || lC != 0.0 || uC != kInf;
     sumlo = wave_sum(lo);
@@ -2341,11 +2342,13 @@ __device__ int decode_k1(const halda_batch &B, const WaveCtx &w, unsigned char *
     if constexpr (kScreen) {
         const bool eq_ext = eqe - eqs == M;
         eqb = eq_ext ? eqs : 0;
-        const bool lb_inf = wave_or(act && (int(ceil(lbv[0])) > I.W || lbv[0] < 0.0)) != 0;
+        const bool lb_inf = wave_or(act && int(ceil(lbv[0])) > I.W) != 0;
         if (!(Wl == I.Wd) || !(I.Wd >= 0.0 && I.Wd < 1e6 && I.Wd == floor(I.Wd)) || !eq_ext) {
             pre = HALDA_STATUS_UNSUPPORTED;
         } else if (lb_inf || sumlo > I.W) {
             pre = HALDA_STATUS_INFEASIBLE;
+        } else if (wave_or(act && lbv[0] < 0.0)) {
+            pre = HALDA_STATUS_UNSUPPORTED;  // the screen's rule for a negative w lower bound
         } else {
             const int R1 = I.W - sumlo + 1;
             const bool kc = I.kc > 0.0;
@@ -2488,8 +2491,10 @@ __device__ int decode_k1(const halda_batch &B, const WaveCtx &w, unsigned char *
                 const double v = sval[rs + k];
                 const int blk = block_of(j, M, I.invM);
                 if (j >= 6 * M || j - blk * M != dev) rb = 1;
-                else if (blk == 0) coef0 = v;
-                else {
+                else if (blk == 0) {
+                    rb |= coef0 != 0.0;  // w entered twice (a first entry of 0 adds nothing)
+                    coef0 = v;
+                } else {
                     double cb = cst[1];
 #pragma unroll
                     for (int b = 2; b < 6; ++b)

@@ -95,8 +95,9 @@ def settled_instances(b: HostBatch) -> np.ndarray:
     """The bound-infeasible instances of a host batch, one byte each (1 = settled), for
     halda_solve_batch_device_settled: instance i is settled when it is a HALDA instance (N = 7M + 1
     columns, the last row an equality sum_j w_j = W with integral W in [0, 1e6), its entries the first M
-    columns with coefficient 1) and its w lower bounds prove infeasibility -- a bound below 0, a ceil above
-    W, or ceilings summing past W (NaN bounds count 0, as on the GPU). That is the screen's own verdict
+    columns with coefficient 1) and its w lower bounds prove infeasibility -- a ceil above W, or ceilings
+    summing past W (NaN and negative bounds count 0, as on the GPU; a negative bound alone is not a proof: the
+    screen answers UNSUPPORTED for it). That is the screen's own verdict
     (HiGHS's presolve answer for M > W = L / k, res.success == False in halda_p_solver.py:369-436), so the
     settled call writes the same results while reading none of these instances' rows."""
     n = b.n_inst
@@ -122,7 +123,7 @@ def settled_instances(b: HostBatch) -> np.ndarray:
     with np.errstate(invalid="ignore"):
         up = np.ceil(lb)
         nan = np.isnan(lb)
-        hit = ~nan & ((lb < 0.0) | (up > W[inst]))
-        up = np.where(nan, 0.0, up)
+        hit = ~nan & (up > W[inst])
+        up = np.where(nan, 0.0, np.maximum(up, 0.0))
     infeas = (np.bincount(inst, weights=hit, minlength=n) > 0) | (np.bincount(inst, weights=up, minlength=n) > W)
     return (ok & infeas).astype(np.uint8)

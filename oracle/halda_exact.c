@@ -68,6 +68,11 @@ typedef struct {
 
 static int is_int(double v) { return isfinite(v) && v == floor(v); }
 
+/* ceil / floor of a column bound as an int inside [lo, hi] (NaN: lo): a bound of +-inf or beyond the int range
+ * must not reach the cast. */
+static int ceil_in(double v, int lo, int hi) { return v > lo ? (v < hi ? (int)ceil(v) : hi) : lo; }
+static int floor_in(double v, int lo, int hi) { return v > lo ? (v < hi ? (int)floor(v) : hi) : lo; }
+
 /* top-2 option record for one device & one w at a threshold */
 typedef struct {
     double g[2];
@@ -194,15 +199,20 @@ int halda_exact_solve(int n, int m, const double *A, const double *bl, const dou
     *nodes_out = 0;
     /* equality row: last row, sum_i w_i = W */
     const double *eq = &A[(size_t)(m - 1) * n];
-    if (!(bl[m - 1] == bu[m - 1]) || !is_int(bu[m - 1])) return EX_UNSUPPORTED;
+    if (!(bl[m - 1] == bu[m - 1]) || !is_int(bu[m - 1]) || !(bu[m - 1] >= 0.0 && bu[m - 1] < 1e6))
+        return EX_UNSUPPORTED;
     for (int j = 0; j < n; j++) {
         double want = j < M ? 1.0 : 0.0;
         if (eq[j] != want) return EX_UNSUPPORTED;
     }
     const int W = (int)bu[m - 1];
-    if (c[iC] < 0) return EX_UNSUPPORTED;
+    if (!(c[iC] >= 0) || integ[iC] || ub[iC] != INFINITY) return EX_UNSUPPORTED;
     for (int j = 6 * M; j < iC; j++)
-        if (c[j] != 0.0 || integ[j]) return EX_UNSUPPORTED;
+        if (c[j] != 0.0 || integ[j] || ub[j] != INFINITY) return EX_UNSUPPORTED;
+    /* w and n are layer counts: a negative lower bound is not a HALDA column (the tables below are indexed
+     * by w and n from 0) */
+    for (int j = 0; j < 2 * M; j++)
+        if (lb[j] < 0.0) return EX_UNSUPPORTED;
     for (int j = 0; j < 6 * M; j++)
         if (!integ[j]) return EX_UNSUPPORTED;
     /* column bounds */
@@ -212,11 +222,11 @@ int halda_exact_solve(int n, int m, const double *A, const double *bl, const dou
     int slo[4][M ? M : 1], shi[4][M ? M : 1];
     int status = EX_OK;
     for (int i = 0; i < M; i++) {
-        wlo[i] = (int)ceil(lb[i]); whi[i] = (int)floor(ub[i]);
-        nlo[i] = (int)ceil(lb[M + i]); nhi[i] = (int)floor(ub[M + i]);
+        wlo[i] = ceil_in(lb[i], 0, W + 1); whi[i] = floor_in(ub[i], -1, W);
+        nlo[i] = ceil_in(lb[M + i], 0, W + 1); nhi[i] = floor_in(ub[M + i], -1, W);
         for (int s = 0; s < 4; s++) {
-            slo[s][i] = (int)ceil(lb[(2 + s) * M + i]);
-            shi[s][i] = (int)floor(ub[(2 + s) * M + i]);
+            slo[s][i] = ceil_in(lb[(2 + s) * M + i], -100000000, 100000000);
+            shi[s][i] = floor_in(ub[(2 + s) * M + i], -100000000, 100000000);
         }
         if (wlo[i] > whi[i] || nlo[i] > nhi[i]) status = EX_INFEASIBLE;
     }
@@ -227,7 +237,7 @@ int halda_exact_solve(int n, int m, const double *A, const double *bl, const dou
     if (!dr) { free(wlo); return EX_NOMEM; }
     for (int r = 0; r < m - 1 && status == EX_OK; r++) {
         const double *row = &A[(size_t)r * n];
-        if (bl[r] != -INFINITY) { status = EX_UNSUPPORTED; break; }
+        if (bl[r] != -INFINITY || !(fabs(bu[r]) < 1e300)) { status = EX_UNSUPPORTED; break; }
         if (row[iC] != 0.0) {
             int dev = -1, sign = 0;
             for (int i = 0; i < M; i++)
@@ -242,6 +252,10 @@ int halda_exact_solve(int n, int m, const double *A, const double *bl, const dou
             device_rows *d = &dr[dev];
             double *dst = sign > 0 ? d->r1 : d->r2;
             for (int b = 0; b < 6; b++) dst[b] = row[b * M + dev];
+            /* busy(i) +- z_i - C <= rhs: the non-w part of busy is the device's objective entries */
+            for (int b = 1; b < 6; b++)
+                if (dst[b] != c[b * M + dev]) status = EX_UNSUPPORTED;
+            if (status != EX_OK) break;
             if (sign > 0) { d->have1++; d->rhs1 = bu[r]; } else { d->have2++; d->rhs2 = bu[r]; }
         } else {
             int dev = -1, slack = -1;
@@ -266,7 +280,12 @@ int halda_exact_solve(int n, int m, const double *A, const double *bl, const dou
             cr->an = row[M + dev];
             cr->beta = slack >= 0 ? -row[(2 + slack) * M + dev] : 0.0;
             cr->rhs = bu[r];
-            if (slack >= 0 && !(cr->beta > 0)) status = EX_UNSUPPORTED;
+            /* aw w + an n - beta s <= rhs with |aw|, |an| in {0, scale}, scale = beta (or the larger of the two
+             * in a pure row), and w, n coupled only through w - n: the structure include/halda.h promises */
+            const double scale = slack >= 0 ? cr->beta : fmax(fabs(cr->aw), fabs(cr->an));
+            if (!(scale > 0) || !(cr->aw == 0.0 || fabs(cr->aw) == scale) || !(cr->an == 0.0 || fabs(cr->an) == scale) ||
+                cr->aw * cr->an > 0)
+                status = EX_UNSUPPORTED;
         }
     }
     for (int i = 0; i < M && status == EX_OK; i++)

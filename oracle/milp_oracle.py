@@ -231,8 +231,8 @@ def highs_solve(prob, mip_gap: Optional[float] = 1e-4, relax: bool = False):
 
     cons = []
     if prob["A_ub"].shape[0]:
-        cons.append(LinearConstraint(prob["A_ub"], -np.inf, prob["b_ub"]))
-    cons.append(LinearConstraint(prob["A_eq"], prob["b_eq"], prob["b_eq"]))
+        cons.append(LinearConstraint(prob["A_ub"], prob.get("lb_ub", -np.inf), prob["b_ub"]))
+    cons.append(LinearConstraint(prob["A_eq"], prob.get("lb_eq", prob["b_eq"]), prob["b_eq"]))
     opts = {"time_limit": 3600.0}
     if mip_gap is not None:
         opts["mip_rel_gap"] = float(mip_gap)
@@ -299,7 +299,9 @@ def exact_solve(prob, eps: float = SLACK_EPS):
     lib = _load_exact()
     A = np.ascontiguousarray(np.vstack([prob["A_ub"], prob["A_eq"]]), dtype=np.float64)
     m, n = A.shape
-    bl = np.concatenate([np.full(prob["A_ub"].shape[0], -np.inf), prob["b_eq"]]).astype(np.float64)
+    # optional row lower bounds (tests/csr_mutation_cases.py); the lowering's are -inf and b_eq
+    bl = np.concatenate([prob.get("lb_ub", np.full(prob["A_ub"].shape[0], -np.inf)),
+                         prob.get("lb_eq", prob["b_eq"])]).astype(np.float64)
     bu = np.concatenate([prob["b_ub"], prob["b_eq"]]).astype(np.float64)
 
     def p(a):

@@ -44,8 +44,10 @@ def test_settled_instances_refuse_what_the_screen_would_not_settle(llama_online_
     for i in range(nan.n_inst):
         nan.col_lb[nan.col_off[i]:nan.col_off[i] + 16] = np.nan
     assert not settled_instances(nan).any()
-    # a negative bound is infeasible by itself, even at k = 1
-    neg = assemble([lower_fleet(devs, llama_online_model)], [[1]])[0]
+    # a negative bound proves nothing (the screen answers UNSUPPORTED for it) and counts 0 layers: k = 1 is
+    # not settled, k = 8 (15 > W = 10 from the other bounds) still is
+    neg = assemble([lower_fleet(devs, llama_online_model)], [[1, 8]])[0]
     neg.col_lb = neg.col_lb.copy()
-    neg.col_lb[neg.col_off[0] + 5] = -1.0
-    assert settled_instances(neg).tolist() == [1]
+    for i in range(neg.n_inst):
+        neg.col_lb[neg.col_off[i] + 5] = -1.0
+    assert settled_instances(neg).tolist() == [0, 1]
