@@ -35,6 +35,7 @@
 
 #include "halda.h"
 #include "halda_boxes.h"
+#include "halda_wide.h"
 #include "halda_launch.hpp"
 #include "halda_stage.hpp"
 
@@ -3240,9 +3241,17 @@ int halda_solve_fleets_budget(void *ctx, const halda_model *model, const halda_f
                            budget_slice(F.max_devices, budget->max_p, k > 1).total, Bg, stream);
 }
 
-int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const halda_fleets *fh, int32_t k,
-                                   const halda_budget *budget, halda_frontier *fr_h) {
-    int rc = check_budget_args(ctx, model, fh, k, budget, fr_h, "halda_solve_fleets_budget_host");
+// The _host form of a move-budget entry (`solve`, gated by `check`): the table, the incumbent triple and the
+// frontier staged through the context's scratch, one copy each way.
+using BudgetCheck = int (*)(void *, const halda_model *, const halda_fleets *, int32_t, const halda_budget *,
+                            const halda_frontier *, const char *);
+using BudgetSolve = int (*)(void *, const halda_model *, const halda_fleets *, int32_t, const halda_budget *,
+                            halda_frontier *, void *);
+
+static int budget_host(void *ctx, const halda_model *model, const halda_fleets *fh, int32_t k,
+                       const halda_budget *budget, halda_frontier *fr_h, const char *who, BudgetCheck check,
+                       BudgetSolve solve) {
+    int rc = check(ctx, model, fh, k, budget, fr_h, who);
     if (rc != HALDA_OK) return rc;
     Ctx *c = static_cast<Ctx *>(ctx);
     const int64_t nf = fh->n_fleets;
@@ -3252,7 +3261,7 @@ int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const ha
     {
         const int64_t f = stage::bad_incumbent(fh->dev_off, nf, budget->w0, model->L / k);
         if (f >= 0)
-            return fail(HALDA_E_ARG, "halda_solve_fleets_budget_host: fleet " + std::to_string(f) +
+            return fail(HALDA_E_ARG, std::string(who) + ": fleet " + std::to_string(f) +
                                          ": the incumbent needs every w0_i >= 1 and sum w0 = L / k");
     }
     stage::Bump lay;
@@ -3269,11 +3278,115 @@ int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const ha
     const halda_fleets d = stage::rebase(*fh, base, T);
     const halda_budget db = {B.at(base, 0), B.at(base, 1), B.at(base, 2), budget->max_p};
     halda_frontier r = stage::bind_frontier(base, R, nd);
-    rc = halda_solve_fleets_budget(ctx, model, &d, k, &db, &r, s);
+    rc = solve(ctx, model, &d, k, &db, &r, s);
     if (rc == HALDA_OK) rc = download(stage::frontier_copies(R, *fr_h), base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
+}
+
+int halda_solve_fleets_budget_host(void *ctx, const halda_model *model, const halda_fleets *fh, int32_t k,
+                                   const halda_budget *budget, halda_frontier *fr_h) {
+    return budget_host(ctx, model, fh, k, budget, fr_h, "halda_solve_fleets_budget_host", check_budget_args,
+                       halda_solve_fleets_budget);
+}
+
+// ---------------------------------------------------------------- the move budget beyond one wave
+// halda_solve_fleets_budget_wide: halda_sweep_budget_wide_kernel, one 256-thread workgroup per fleet; the gate is
+// fleets of 1 .. 256 devices, one k, max_p <= 127, the LDS slice within the LDS budget and one workgroup's
+// workspace slice within the global-table budget. halda_budget and halda_frontier are the wave entry's.
+int halda_budget_wide_bytes(int32_t max_devices, int32_t max_p, int32_t k, int64_t *lds, int64_t *global) {
+    if (max_devices < 1 || max_p < 0 || k < 1 || !lds || !global)
+        return fail(HALDA_E_ARG, "halda_budget_wide_bytes: max_devices < 1, max_p < 0, k < 1 or a NULL result");
+    if (max_devices > 4096 || max_p > 4096) {  // far outside the gate; no overflow below
+        *lds = *global = INT64_MAX;
+        return HALDA_OK;
+    }
+    const BudgetWideSlice sl = budget_wide_slice(max_devices, max_p, k > 1);
+    *lds = sl.lds;
+    *global = sl.global;
+    return HALDA_OK;
+}
+
+static int check_budget_wide_args(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                                  const halda_budget *budget, const halda_frontier *fr, const char *who_c) {
+    const std::string who = who_c;
+    if (!ctx || !model || !fleets || !budget || !fr)
+        return fail(HALDA_E_ARG, who + ": NULL ctx/model/fleets/budget/frontier");
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(F)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    if (k < 1) return fail(HALDA_E_ARG, who + ": k must be >= 1");
+    if (!budget->w0) return fail(HALDA_E_ARG, who + ": halda_budget.w0 is NULL");
+    if (!(fr->status && fr->obj && fr->moved && fr->w && fr->n))
+        return fail(HALDA_E_ARG, who + ": halda_frontier has a NULL array");
+    if (F.min_devices < 1 || F.max_devices < F.min_devices || F.max_devices > kWideMaxM)
+        return fail(HALDA_E_ARG, who + ": every fleet must have 1 .. " + std::to_string(kWideMaxM) + " devices");
+    if (budget->max_p < 0 || budget->max_p > kWideMaxP)
+        return fail(HALDA_E_ARG, who + ": max_p must be in 0 .. " + std::to_string(kWideMaxP));
+    const BudgetWideSlice sl = budget_wide_slice(F.max_devices, budget->max_p, k > 1);
+    if (const int rc = check_frontier_lds(sl.lds, who)) return rc;
+    if (sl.global > kGlobalTableBudget)
+        return fail(HALDA_E_ARG, who + ": the workspace slice of " + std::to_string(sl.global) +
+                                     " B exceeds the global-table budget of " + std::to_string(kGlobalTableBudget) +
+                                     " B");
+    return HALDA_OK;
+}
+
+int halda_solve_fleets_budget_wide(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                                   const halda_budget *budget, halda_frontier *frontier, void *stream) {
+    const int rc0 = check_budget_wide_args(ctx, model, fleets, k, budget, frontier, "halda_solve_fleets_budget_wide");
+    if (rc0 != HALDA_OK) return rc0;
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    if (frontier->n_devices < F.n_fleets)
+        return fail(HALDA_E_ARG, "halda_solve_fleets_budget_wide: halda_frontier.n_devices is not dev_off[n_fleets]");
+    Ctx *c = static_cast<Ctx *>(ctx);
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    const BudgetArgs Bg{budget->w0,       budget->w_min,   budget->w_max,   budget->max_p, frontier->n_devices,
+                        frontier->status, frontier->obj,   frontier->moved, frontier->w,   frontier->n};
+    const BudgetWideSlice sl = budget_wide_slice(F.max_devices, budget->max_p, k > 1);
+    SweepArgs A = {};
+    static_cast<halda_model &>(A.Mo) = *model;
+    A.Mo.bvo = model_bvo(*model);
+    A.F = F;
+    A.ks[0] = k;
+    A.Ws[0] = model->L / k;
+    A.n_k = 1;
+    A.mmax = F.max_devices;
+    A.uM = F.min_devices == F.max_devices ? F.max_devices : 0;
+    A.xstride = 7 * int64_t(F.max_devices) + 1;
+    A.gstride = (sl.global + 255) & ~int64_t(255);
+    // the grid, the shape of the sweep's global-table launch: the resident workgroups, the fleets, the workspace
+    const void *fn = reinterpret_cast<const void *>(halda_sweep_budget_wide_kernel);
+    HIP_TRY(Ctx::ensure_lds(fn, sl.lds));
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kWideThreads, size_t(sl.lds)));
+    const unsigned grid = unsigned(std::max<int64_t>(
+        1, std::min<int64_t>({int64_t(c->cus) * std::max(1, per_cu), int64_t(F.n_fleets),
+                              kGlobalTableBudget / A.gstride})));
+    const size_t gneed = size_t(A.gstride) * size_t(grid);
+    if (gneed > c->gtab_bytes) {
+        if (c->gtab) HIP_TRY(hipFree(c->gtab));
+        c->gtab = nullptr;
+        c->gtab_bytes = 0;
+        HIP_TRY(hipMalloc(&c->gtab, gneed));
+        c->gtab_bytes = gneed;
+    }
+    // the global tables are per context: this launch runs after their previous user on another stream
+    if (const int rc = order_after_previous(c, s)) return rc;
+    A.gtab = static_cast<unsigned char *>(c->gtab);
+    hipLaunchKernelGGL(halda_sweep_budget_wide_kernel, dim3(grid), dim3(kWideThreads), size_t(sl.lds), s, A, Bg);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+int halda_solve_fleets_budget_wide_host(void *ctx, const halda_model *model, const halda_fleets *fh, int32_t k,
+                                        const halda_budget *budget, halda_frontier *fr_h) {
+    return budget_host(ctx, model, fh, k, budget, fr_h, "halda_solve_fleets_budget_wide_host", check_budget_wide_args,
+                       halda_solve_fleets_budget_wide);
 }
 
 // ---------------------------------------------------------------- a changed fleet and its frontier

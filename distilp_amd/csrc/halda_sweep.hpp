@@ -2785,6 +2785,416 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_ch
     for (int64_t it = blockIdx.x; it < n; it += gridDim.x) frontier_item<ChangeJob>(A, Cg, int(it), w, c, Wave(lane));
 }
 
+// ---------------------------------------------------------------- the move budget beyond one wave
+// halda_sweep_budget_wide_kernel (halda_solve_fleets_budget_wide): the move budget's problem, status ladder,
+// window, R1, tie rules and pricing as frontier_item<BudgetJob> has them, on one 256-thread workgroup per fleet
+// with another memory split, for what the wave kernel's shape leaves out: fleets of up to 256 devices and
+// max_p up to 127 (the arg-min byte) wherever two compact planes fit the LDS.
+//   LDS        two value planes of (P + 1)^2 doubles (state (r, l) at r (P + 1) + l: ChangeMap{P, P + 1, 0},
+//              every slot a state), two row buffers per table (the DP's current row and the next one in flight),
+//              per device wlo - w0, the reduction slots, and per point best / obj / moved / source.
+//   workspace  (the workgroup's slice of the context's global tables) G and, for k > 1, H as rows of 2 P + 1
+//              doubles; one arg-min byte per (device, state), read only at backtrack time; the plan rows (table
+//              indices, bytes) and their n.
+// The DP's transition is frontier_dp's expression on the same G / H values in the same order of e, so its values,
+// arg-mins and plans are the wave kernel's wherever both run.
+constexpr int kWideWaves = 4, kWideThreads = 64 * kWideWaves;
+constexpr int kWideMaxP = 127, kWideMaxM = kWideThreads;  // an arg-min byte is at most 2 P; thread = device
+
+struct BudgetWideSlice {
+    int64_t V, rowG, rowH, off, red, best, objv, cnt, src, lds;  // LDS offsets, and the LDS total
+    int64_t G, H, arg, plan, nplan, global;                      // workspace offsets, and the workspace total
+    int S, RS;
+};
+
+__host__ __device__ inline BudgetWideSlice budget_wide_slice(int mmax, int P, bool kc) {
+    BudgetWideSlice s;
+    const int64_t P1 = P + 1;
+    s.RS = 2 * P + 1;
+    s.S = int(P1 * P1);
+    int64_t o = 0;
+    s.V = o;     o = align16(o + 2 * int64_t(s.S) * 8);
+    s.rowG = o;  o = align16(o + 2 * int64_t(s.RS) * 8);
+    s.rowH = o;  o = align16(o + (kc ? 2 * int64_t(s.RS) * 8 : 0));
+    s.off = o;   o = align16(o + int64_t(mmax) * 4);
+    s.red = o;   o = align16(o + 2 * kWideWaves * 8);
+    s.best = o;  o = align16(o + P1 * 8);
+    s.objv = o;  o = align16(o + P1 * 8);
+    s.cnt = o;   o = align16(o + P1 * 4);
+    s.src = o;   o = align16(o + P1 * 4);
+    s.lds = o;
+    o = 0;
+    s.G = o;     o = align16(o + int64_t(mmax) * s.RS * 8);
+    s.H = o;     o = align16(o + (kc ? int64_t(mmax) * s.RS * 8 : 0));
+    s.arg = o;   o = align16(o + int64_t(mmax) * s.S);
+    s.plan = o;  o = align16(o + P1 * mmax);
+    s.nplan = o; o = align16(o + P1 * mmax * 4);
+    s.global = o;
+    return s;
+}
+
+struct WideCtx {
+    double *V, *rowG, *rowH, *best, *objv;  // LDS
+    int *off, *cnt, *src;
+    double *G, *H;                          // workspace
+    uint8_t *arg, *plan;
+    int *nplan;
+    int S, RS, P, mmax;
+};
+
+__device__ inline WideCtx wide_ctx(unsigned char *smem, unsigned char *work, const BudgetWideSlice &sl, int P,
+                                   int mmax) {
+    WideCtx c;
+    c.V = reinterpret_cast<double *>(smem + sl.V);
+    c.rowG = reinterpret_cast<double *>(smem + sl.rowG);
+    c.rowH = reinterpret_cast<double *>(smem + sl.rowH);
+    c.best = reinterpret_cast<double *>(smem + sl.best);
+    c.objv = reinterpret_cast<double *>(smem + sl.objv);
+    c.off = reinterpret_cast<int *>(smem + sl.off);
+    c.cnt = reinterpret_cast<int *>(smem + sl.cnt);
+    c.src = reinterpret_cast<int *>(smem + sl.src);
+    c.G = reinterpret_cast<double *>(work + sl.G);
+    c.H = reinterpret_cast<double *>(work + sl.H);
+    c.arg = work + sl.arg;
+    c.plan = work + sl.plan;
+    c.nplan = reinterpret_cast<int *>(work + sl.nplan);
+    c.S = sl.S;
+    c.RS = sl.RS;
+    c.P = P;
+    c.mmax = mmax;
+    return c;
+}
+
+// A workgroup reduction: each wave's value (already reduced over the wave, uniform) into the wave's slot, ONE
+// barrier, the four combined in wave order by every thread -- the result is read back from LDS, so it is the same
+// bits on all 256 threads and every loop condition formed from it has the same trip count. Two slot sets
+// alternate: a set is rewritten only after the barrier of the reduction that followed its readers.
+struct WideRed {
+    unsigned char *slot;  // [2][kWideWaves] of 8 bytes
+    int set, q, lane;
+    template <class T, class Op>
+    __device__ inline T combine(T wave_value, Op op) {
+        static_assert(sizeof(T) == 8, "a slot is 8 bytes");
+        T *s = reinterpret_cast<T *>(slot) + set * kWideWaves;
+        set ^= 1;
+        if (lane == 0) s[q] = wave_value;
+        __syncthreads();
+        return op(op(s[0], s[1]), op(s[2], s[3]));
+    }
+    __device__ inline int64_t sum(const Wave &sg, int v) {
+        return combine(int64_t(sg.sum_i(v)), [](int64_t a, int64_t b) { return a + b; });
+    }
+    __device__ inline bool any(const Wave &sg, bool p) {
+        return combine(int64_t(sg.any(p)), [](int64_t a, int64_t b) { return a | b; }) != 0;
+    }
+    __device__ inline double min_f64(const Wave &sg, double v) {
+        return combine(sg.min_f64(v), [](double a, double b) { return fmin(a, b); });
+    }
+    __device__ inline double max_f64(const Wave &sg, double v) {
+        return combine(sg.max_f64(v), [](double a, double b) { return fmax(a, b); });
+    }
+};
+
+// One DP over the M devices on the compact planes, thread t owning states t, t + 256, ...; the entries H > T
+// masked (kc == 0: no mask). Device i's rows reach the inner loop through LDS: while the threads run device i's
+// transitions on row buffer i & 1, thread e holds entry e of device i + 1's rows in registers and stores it into
+// the other buffer before the step's one barrier. Every thread reads the same entry at a time (a broadcast).
+// kArg: the step also stores its arg-min plane (the scan's value passes need none). Returns the final plane.
+template <bool kArg>
+__device__ inline const double *wide_dp(const WideCtx &c, const ChangeMap &m, int M, int R1, double kc, double T,
+                                        int tid) {
+    const int Sn = m.count();
+    double *cur = c.V, *nxt = c.V + c.S;
+    for (int s = tid; s < Sn; s += kWideThreads) cur[s] = s == m.start() ? 0.0 : kInf;
+    const bool row = tid < R1;  // R1 <= 2 P + 1 <= 255: one entry per thread
+    if (row) {
+        c.rowG[tid] = c.G[tid];
+        if (kc > 0.0) c.rowH[tid] = c.H[tid];
+    }
+    __syncthreads();
+    for (int i = 0; i < M; ++i) {
+        const int b = (i & 1) * c.RS, nb = c.RS - b;
+        const bool more = row && i + 1 < M;
+        double gn = kInf, hn = kInf;
+        if (more) {
+            gn = c.G[int64_t(i + 1) * c.RS + tid];
+            if (kc > 0.0) hn = c.H[int64_t(i + 1) * c.RS + tid];
+        }
+        const int oi = c.off[i];
+        const double *Gi = c.rowG + b, *Hi = c.rowH + b;
+        uint8_t *ai = c.arg + int64_t(i) * c.S;
+        for (int s = tid; s < Sn; s += kWideThreads) {
+            int r, l;
+            m.decode(s, r, l);
+            double best = kInf;
+            int be = kFrontierNone;
+            for (int e = 0; e < R1; ++e) {
+                const int delta = oi + e;
+                const int lp = l - max(0, delta), rp = r - max(0, -delta);
+                if (lp < 0 || rp < 0) continue;
+                if (kc > 0.0 && !(Hi[e] <= T)) continue;
+                const double v = cur[m.at(rp, lp)] + Gi[e];
+                if (v < best) {
+                    best = v;
+                    be = e;
+                }
+            }
+            nxt[s] = best;
+            if constexpr (kArg) ai[s] = uint8_t(be);
+        }
+        if (more) {
+            c.rowG[nb + tid] = gn;
+            if (kc > 0.0) c.rowH[nb + tid] = hn;
+        }
+        __syncthreads();
+        double *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    return cur;
+}
+
+// The plan of point p (thread p) with a finite final value, from state (p, p) after the last device back to
+// (0, 0) through the workspace's arg-min planes (frontier_backtrack's walk).
+__device__ inline void wide_backtrack(const WideCtx &c, const ChangeMap &m, int M, int p) {
+    int r = p, l = p;
+    for (int i = M - 1; i >= 0; --i) {
+        const int e = c.arg[int64_t(i) * c.S + m.at(r, l)];
+        c.plan[int64_t(p) * c.mmax + i] = uint8_t(e);
+        const int delta = c.off[i] + e;
+        l -= max(0, delta);
+        r -= max(0, -delta);
+    }
+}
+
+// One fleet. A fleet of at most 64 devices lies lane = device in EVERY wave (each prices its points as
+// frontier_item does, with fleet_offsets_regs's constants); wave 0 builds its rows. A wider one lies thread =
+// device: wave q builds the rows of devices 64 q .. 64 q + 63 from its lanes' records, and a wave prices a point
+// in eval_plan_wide's order (lane-strided partial sums in ascending device order, the wave sum,
+// fleet_offsets_tree's constants). Either way the raw obj of an OPTIMAL point is halda_eval_plans' of the
+// returned plan.
+__device__ inline void budget_wide_item(const SweepArgs &A, const BudgetArgs &J, int f, const WideCtx &c, WideRed &R,
+                                        int tid) {
+    const int lane = tid & 63, q = tid >> 6;
+    const Wave sg(lane);
+    const int P = J.P, P1 = P + 1;
+    const int k = A.ks[0], W = A.Ws[0];
+    const int64_t d0 = A.uM > 0 ? sload_i64(A.F.dev_off) + int64_t(f) * A.uM : sload_i64(A.F.dev_off + f);
+    const int M = A.uM > 0 ? A.uM : int(sload_i64(A.F.dev_off + f + 1) - d0);
+    const bool narrow = M <= 64;
+    const int dev = narrow ? lane : tid;  // the device whose record the thread holds
+    const bool act = dev < M;
+    const bool own = tid < M;             // ... and whose rows, sums and plane entries are this thread's
+    const bool pt = tid < P1;
+    const int64_t g0 = d0 + (act ? dev : 0);
+    const int wmn = J.w_min ? J.w_min[g0] : 0;
+    const int wmx = J.w_max ? J.w_max[g0] : 0x7fffffff;
+    const int w0 = min(max(J.w0[g0], -kBoundCap), kBoundCap);
+    const DevFields mf = load_fields(A.F, g0);
+    BoundRec me = {};
+    int bad = 0;
+    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
+    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
+    if (narrow) fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
+    else fleet_offsets_tree(A.Mo, A.F, d0, M, lane, tsum, xsum, kappa);
+    bad = R.any(sg, own && bad != 0) ? 1 : 0;
+    const int lo = min(max(1, wmn), kBoundCap);
+    const int64_t sumlo = R.sum(sg, own ? lo : 0);
+    const int64_t sumw0 = R.sum(sg, own ? w0 : 0);
+    const bool w0bad = R.any(sg, own && w0 < 1) || sumw0 != W;  // the host entry rejects it before the launch
+    // the window: a device gives up at most P layers and takes at most P
+    const int wlo = max(lo, w0 - P), whi = min(min(W, wmx), w0 + P);
+    const int64_t sumwlo = R.sum(sg, own ? min(wlo, kBoundCap) : 0);
+    constexpr int kOpen = 1000;
+    int st = kOpen;
+    if (!(W < 1000000)) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumlo > W) st = HALDA_STATUS_INFEASIBLE;
+    else if (bad || w0bad) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumwlo > W) st = HALDA_STATUS_INFEASIBLE;  // the window cannot reach the box
+    const int64_t fo = int64_t(f) * P1;
+    if (st != kOpen) {
+        if (pt) {
+            J.status[fo + tid] = st;
+            J.obj[fo + tid] = kInf;
+            J.moved[fo + tid] = 0;
+        }
+        if (own)
+            for (int p = 0; p < P1; ++p) {
+                J.w[int64_t(p) * J.nd + d0 + tid] = 0;
+                J.n[int64_t(p) * J.nd + d0 + tid] = 0;
+            }
+        return;
+    }
+    opaque_rec(me);
+    const double kc = double(k - 1);
+    me.W = W;
+    me.wlo = wlo;
+    me.whi = whi;
+    if (own) c.off[tid] = wlo - w0;
+    const int R1 = min(int(W - sumwlo), 2 * P) + 1;
+    const ChangeMap m = {P, P1, 0};
+    {
+        // the wave's devices as one table_pass of their own: rows at the devices' places in the workspace
+        Inst I = {};
+        I.inst = f;
+        I.M = narrow ? (q == 0 ? M : 0) : min(max(M - 64 * q, 0), 64);
+        I.W = W;
+        I.Wd = double(W);
+        I.kc = kc;
+        I.iC = 7 * M;
+        I.R1 = R1;
+        I.RS = c.RS;
+        WaveCtx w = {};
+        w.G = c.G + int64_t(64 * q) * c.RS;
+        w.H = kc > 0.0 ? c.H + int64_t(64 * q) * c.RS : nullptr;
+        if (I.M > 0) table_pass<64>(bound_src(&me), w, I, lane);
+    }
+    __syncthreads();
+    // best[p] (thread p): the least (k - 1) T + F^T_M[final state of p] and the T that gave it
+    double best = kInf, bT = kInf;
+    if (kc == 0.0) {
+        const double *F = wide_dp<true>(c, m, M, R1, 0.0, kInf, tid);
+        if (pt) best = F[m.final(tid)];
+        if (pt && best < kInf) wide_backtrack(c, m, M, tid);
+    } else {
+        const double *F = wide_dp<false>(c, m, M, R1, 0.0, kInf, tid);
+        const double sinf = pt ? F[m.final(tid)] : kInf;
+        // the first threshold that leaves every device an entry: max_i min_e H_i[e]
+        double hmin = kInf;
+        if (own)
+            for (int e = 0; e < R1; ++e) hmin = fmin(hmin, c.H[int64_t(tid) * c.RS + e]);
+        double T = R.max_f64(sg, own ? hmin : 0.0);
+        while (T < kInf) {
+            // point p is closed once (k - 1) T + S_inf[p] >= best[p]; the scan stops when every point is
+            if (!R.any(sg, pt && !(kc * T + sinf >= best))) break;
+            F = wide_dp<false>(c, m, M, R1, kc, T, tid);
+            if (pt) {
+                const double v = kc * T + F[m.final(tid)];
+                if (v < best) {  // strict: the earliest T wins
+                    best = v;
+                    bT = T;
+                }
+            }
+            double nx = kInf;  // the next distinct finite H above T
+            for (int t = tid; t < M * R1; t += kWideThreads) {
+                const int i = t / R1, e = t - i * R1;
+                const double h = c.H[int64_t(i) * c.RS + e];
+                if (h > T) nx = fmin(nx, h);
+            }
+            T = R.min_f64(sg, nx);
+        }
+        // the arg-min planes of each distinct winning T, once, for the points it won
+        bool left = pt && best < kInf;
+        while (R.any(sg, left)) {
+            const double Tw = R.min_f64(sg, left ? bT : kInf);
+            wide_dp<true>(c, m, M, R1, kc, Tw, tid);
+            if (left && bT == Tw) {
+                wide_backtrack(c, m, M, tid);
+                left = false;
+            }
+        }
+    }
+    if (pt) c.best[tid] = best;
+    __syncthreads();
+    // price every exact-p plan, the waves taking the points round-robin
+    for (int p = q; p < P1; p += kWideWaves) {
+        double obj = kInf;
+        int cnt = 0;
+        if (c.best[p] < kInf) {
+            const uint8_t *pl = c.plan + int64_t(p) * c.mmax;
+            int *np = c.nplan + int64_t(p) * c.mmax;
+            double gsum, hmax;
+            if (narrow) {
+                double gd = 0.0, H = 0.0;
+                int wl = 0, n = 0;
+                if (act) {
+                    wl = wlo + pl[lane];
+                    double Pc, Qc;
+                    int sl[4] = {0, 0, 0, 0};
+                    split_full(me, wl, gd, n, sl);
+                    dev_cycle(me, wl, n, sl, Pc, Qc);
+                    H = fmax(0.0, Qc >= Pc ? 0.5 * (Pc + Qc) : Pc);
+                    np[lane] = n;
+                }
+                hmax = sg.max_f64(act ? H : 0.0);
+                gsum = sg.sum_f64(act ? gd : 0.0);
+                cnt = sg.sum_i(act ? abs(wl - w0) : 0);
+            } else {
+                double gs = 0.0, hm = 0.0;
+                int cn = 0;
+                for (int i = lane; i < M; i += 64) {
+                    BoundRec ri = {};
+                    int bi = 0;
+                    static_cast<FieldRec &>(ri) = field_rec(A.Mo, load_fields(A.F, d0 + i), bi);
+                    const int w0i = min(max(J.w0[d0 + i], -kBoundCap), kBoundCap);
+                    ri.W = W;
+                    ri.wlo = w0i + c.off[i];
+                    ri.whi = W;
+                    const int wl = ri.wlo + pl[i];
+                    double gd = 0.0, Pc, Qc;
+                    int n = 0, sl[4] = {0, 0, 0, 0};
+                    split_full(ri, wl, gd, n, sl);
+                    dev_cycle(ri, wl, n, sl, Pc, Qc);
+                    np[i] = n;
+                    gs += gd;
+                    hm = fmax(hm, fmax(0.0, Qc >= Pc ? 0.5 * (Pc + Qc) : Pc));
+                    cn += abs(wl - w0i);
+                }
+                hmax = sg.max_f64(hm);
+                gsum = sg.sum_f64(gs);
+                cnt = sg.sum_i(cn);
+            }
+            obj = gsum + kc * hmax;
+            obj = obj + tsum;
+            obj = obj + xsum;
+            obj = obj + kappa;
+        }
+        if (lane == 0) {
+            c.objv[p] = obj;
+            c.cnt[p] = cnt;
+        }
+    }
+    __syncthreads();
+    // point p: the best exact point p' <= p, the fewest layers moved among equal objectives (strict "<", ascending)
+    if (pt) {
+        double run = kInf;
+        int src = -1, runcnt = 0;
+        for (int pp = 0; pp <= tid; ++pp) {
+            const double o = c.objv[pp];
+            if (o < run) {
+                run = o;
+                src = pp;
+                runcnt = c.cnt[pp];
+            }
+        }
+        J.status[fo + tid] = src >= 0 ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+        J.obj[fo + tid] = run;
+        J.moved[fo + tid] = runcnt;
+        c.src[tid] = src;
+    }
+    __syncthreads();
+    if (own)
+        for (int p = 0; p < P1; ++p) {
+            const int sp = c.src[p];
+            J.w[int64_t(p) * J.nd + d0 + tid] = sp >= 0 ? wlo + c.plan[int64_t(sp) * c.mmax + tid] : 0;
+            J.n[int64_t(p) * J.nd + d0 + tid] = sp >= 0 ? c.nplan[int64_t(sp) * c.mmax + tid] : 0;
+        }
+    __syncthreads();  // the LDS and the workspace slice are rewritten by the workgroup's next fleet
+}
+
+// One 256-thread workgroup per fleet on a persistent grid (workgroup b takes fleets b, b + grid, ...), its LDS
+// and its workspace slice (A.gtab + b A.gstride) laid out by budget_wide_slice of the launch's shape. Every
+// barrier is reached by every thread; no spin-wait, no atomics, nothing shared between workgroups.
+__global__ __launch_bounds__(kWideThreads) void halda_sweep_budget_wide_kernel(SweepArgs A, BudgetArgs Bg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x;
+    const BudgetWideSlice sl = budget_wide_slice(A.mmax, Bg.P, A.ks[0] > 1);
+    const WideCtx c = wide_ctx(smem, A.gtab + int64_t(blockIdx.x) * A.gstride, sl, Bg.P, A.mmax);
+    WideRed R = {smem + sl.red, 0, tid >> 6, tid & 63};
+    const int nf = A.F.n_fleets;
+    for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) budget_wide_item(A, Bg, int(f), c, R, tid);
+}
+
 // ---------------------------------------------------------------- scale-in / scale-out (halda_solve_change_subsets)
 // Which devices to drop (or, from a pool, to add) under a released-layer budget: the candidates are
 // halda_solve_subsets' (SubsetFleet / SubsetArgs, one combo per candidate, the same enumeration order), a

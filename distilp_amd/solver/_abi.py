@@ -1,6 +1,6 @@
 """The C ABI of libhalda (include/halda.h, and include/halda_boxes.h beside it) as ctypes declarations: every
-struct, in header order, and the prototype of every function. `_libhalda.load_library` applies PROTOTYPES and
-BOXES_PROTOTYPES to the library it opens, so no call can reach a function with ctypes' default `int` arguments
+struct, in header order, and the prototype of every function. `_libhalda.load_library` applies PROTOTYPES,
+BOXES_PROTOTYPES and WIDE_PROTOTYPES (include/halda_wide.h) to the library it opens, so no call can reach a function with ctypes' default `int` arguments
 and result. tests/test_abi.py compiles halda.h and compares every struct's size and field offsets, and every
 prototype's arity and result type, with this module; tests/test_boxes.py does the same for halda_boxes.h.
 """
@@ -203,4 +203,11 @@ BOXES_STRUCTS = {HaldaBoxesC: "halda_boxes"}
 BOXES_PROTOTYPES = {
     **_with_host("halda_solve_fleets_boxes", *_table, *_ks, POINTER(HaldaBoxesC), _out),
     **_knob("boxes"),
+}
+
+# include/halda_wide.h, the companion header of the move budget's workgroup route: it adds no struct (the entries
+# take halda_budget and halda_frontier); its prototypes are applied by load_library with the others
+WIDE_PROTOTYPES = {
+    **_with_host("halda_solve_fleets_budget_wide", *_table, c_int32, POINTER(HaldaBudgetC), POINTER(HaldaFrontierC)),
+    "halda_budget_wide_bytes": (c_int, [c_int32] * 3 + [POINTER(c_int64)] * 2),
 }

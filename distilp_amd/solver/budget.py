@@ -66,7 +66,8 @@ def budget_lds_bytes(max_devices: int, max_p: int, k: int) -> int:
 
 
 def check_gate(max_devices: int, min_devices: int, max_p: int, k: int) -> None:
-    """The launch's gate, from the shapes alone: ValueError outside it (there is no other route)."""
+    """The wave launch's gate, from the shapes alone: ValueError outside it (route "wave" has no fallback; the
+    shapes beyond it are route "wide"'s, check_gate_wide)."""
     if min_devices < 1 or max_devices > MAX_DEVICES:
         raise ValueError(f"a move frontier needs fleets of 1 .. {MAX_DEVICES} devices, got {min_devices} .. "
                          f"{max_devices}")
@@ -76,6 +77,68 @@ def check_gate(max_devices: int, min_devices: int, max_p: int, k: int) -> None:
     if need > LDS_BUDGET:
         raise ValueError(f"a budget of {max_p} moved layers on fleets of up to {max_devices} devices needs "
                          f"{need} B of LDS per fleet, beyond the {LDS_BUDGET} B budget: lower max_moved_layers")
+
+
+GLOBAL_BUDGET = 2 << 30  # csrc/halda.hip kGlobalTableBudget
+WIDE_MAX_P = 127         # an arg-min byte holds a table entry of at most 2 P (255: unreached)
+WIDE_MAX_DEVICES = 256   # one thread per device of a 256-thread workgroup
+ROUTES = ("wave", "wide", "auto")
+
+
+def budget_wide_bytes(max_devices: int, max_p: int, k: int):
+    """(lds, global) of one workgroup of halda_sweep_budget_wide_kernel (csrc/halda_sweep.hpp budget_wide_slice,
+    the figures halda_budget_wide_bytes returns). LDS: two value planes of (P + 1)^2 doubles, two row buffers of
+    2 P + 1 doubles per table (G, and H for k > 1), per device wlo - w0, the reduction slots, per point best, obj,
+    moved and source. Workspace: G and H as max_devices rows of 2 P + 1 doubles, one arg-min byte per (device,
+    state), the plan rows and their n."""
+    M, P1, kc = int(max_devices), int(max_p) + 1, k > 1
+    RS, S = 2 * P1 - 1, P1 * P1
+    o = _align16(2 * S * 8)
+    o = _align16(o + 2 * RS * 8)
+    o = _align16(o + (2 * RS * 8 if kc else 0))
+    o = _align16(o + M * 4)
+    o = _align16(o + 2 * 4 * 8)
+    o = _align16(o + P1 * 8)
+    o = _align16(o + P1 * 8)
+    o = _align16(o + P1 * 4)
+    lds = _align16(o + P1 * 4)
+    g = _align16(M * RS * 8)
+    g = _align16(g + (M * RS * 8 if kc else 0))
+    g = _align16(g + M * S)
+    g = _align16(g + P1 * M)
+    return lds, _align16(g + P1 * M * 4)
+
+
+def check_gate_wide(max_devices: int, min_devices: int, max_p: int, k: int) -> None:
+    """The gate of route "wide", from the shapes alone: ValueError outside it."""
+    if min_devices < 1 or max_devices > WIDE_MAX_DEVICES:
+        raise ValueError(f"a move frontier on route 'wide' needs fleets of 1 .. {WIDE_MAX_DEVICES} devices, got "
+                         f"{min_devices} .. {max_devices}")
+    if max_p > WIDE_MAX_P:
+        raise ValueError(f"max_moved_layers // 2 = {max_p} exceeds {WIDE_MAX_P} on route 'wide' "
+                         f"(max_moved_layers <= {2 * WIDE_MAX_P + 1})")
+    lds, glob = budget_wide_bytes(max_devices, max_p, k)
+    if lds > LDS_BUDGET:
+        raise ValueError(f"a budget of {max_p} moved layers on fleets of up to {max_devices} devices needs {lds} B "
+                         f"of LDS per fleet on route 'wide', beyond the {LDS_BUDGET} B budget: lower max_moved_layers")
+    if glob > GLOBAL_BUDGET:
+        raise ValueError(f"a budget of {max_p} moved layers on fleets of up to {max_devices} devices needs {glob} B "
+                         f"of workspace per fleet, beyond the {GLOBAL_BUDGET} B budget")
+
+
+def pick_route(route: str, max_devices: int, min_devices: int, max_p: int, k: int) -> str:
+    """"wave" or "wide" for a call of these shapes, its gate checked (ValueError outside it). "auto": the wave
+    kernel wherever check_gate admits the call, the workgroup kernel elsewhere."""
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
+    if route == "auto":
+        try:
+            check_gate(max_devices, min_devices, max_p, k)
+            return "wave"
+        except ValueError:
+            route = "wide"
+    (check_gate if route == "wave" else check_gate_wide)(max_devices, min_devices, max_p, k)
+    return route
 
 
 def check_budget(max_moved_layers) -> int:
@@ -164,10 +227,12 @@ def host_frontier(raw, need, objs) -> List[list]:
 
 def solve_budget_table(table: FleetTable, model: ModelProfile, k: int, w0: np.ndarray, max_p: int,
                        kv_factor: float, w_min: Optional[np.ndarray] = None, w_max: Optional[np.ndarray] = None,
-                       device: int = 0) -> FrontierSolve:
-    """One halda_solve_fleets_budget_host call on a packed table (w0 / w_min / w_max int32, device layout)."""
+                       device: int = 0, route: str = "wave") -> FrontierSolve:
+    """One halda_solve_fleets_budget_host call on a packed table (w0 / w_min / w_max int32, device layout), or on
+    route "wide" (and on "auto" outside the wave kernel's gate) one halda_solve_fleets_budget_wide_host call."""
     sizes = table.sizes()
-    check_gate(int(sizes.max()), int(sizes.min()), int(max_p), int(k))
+    route = pick_route(route, int(sizes.max()), int(sizes.min()), int(max_p), int(k))
+    entry = "halda_solve_fleets_budget_host" if route == "wave" else "halda_solve_fleets_budget_wide_host"
     ctx = get_context(device)
     nf, nd, P1 = table.n_fleets, table.n_devices, int(max_p) + 1
     out = FrontierSolve(status=np.zeros((nf, P1), np.int32), obj=np.zeros((nf, P1)),
@@ -178,8 +243,7 @@ def solve_budget_table(table: FleetTable, model: ModelProfile, k: int, w0: np.nd
     bg = HaldaBudgetC(ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(max_p))
     fr = HaldaFrontierC(nd, *(ptr(getattr(out, f)) for f in ("status", "obj", "moved", "w", "n")))
     m = model_struct(model, kv_factor)
-    ctx.call("halda_solve_fleets_budget_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k), ctypes.byref(bg),
-             ctypes.byref(fr))
+    ctx.call(entry, ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k), ctypes.byref(bg), ctypes.byref(fr))
     del keep
     return out
 
@@ -200,13 +264,17 @@ def halda_move_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], model: 
                               incumbents: Sequence[Incumbent], max_moved_layers: int, kv_bits: str = "8bit",
                               w_min: Optional[Sequence[Optional[Sequence[int]]]] = None,
                               w_max: Optional[Sequence[Optional[Sequence[int]]]] = None,
-                              device: int = 0) -> List[List[FrontierPoint]]:
+                              device: int = 0, route: str = "wave") -> List[List[FrontierPoint]]:
     """Per fleet the move frontier around its incumbent: one FrontierPoint per p = 0 .. max_moved_layers // 2.
     One fleet table and one GPU call per distinct incumbent k, then one evaluation call that prices the incumbents
     (for `regret`) and every returned plan (obj_value formed on the host, as halda_evaluate_plan forms it).
     w_min / w_max: per fleet a list of per-device bounds or None. ValueError before any GPU work for a missing
     or malformed incumbent, a bad budget, or a shape outside the launch's gate (fleets of more than 64 devices,
-    max_moved_layers // 2 > 63, an LDS slice beyond 160 KiB)."""
+    max_moved_layers // 2 > 63, an LDS slice beyond 160 KiB). route: "wave" (the default) is that launch and
+    that gate; "wide" the workgroup kernel (halda_solve_fleets_budget_wide: fleets of up to 256 devices,
+    max_moved_layers // 2 <= 127 and two (P + 1)^2 planes within the LDS, check_gate_wide); "auto" the wave kernel
+    where its gate admits a k group and the workgroup kernel elsewhere. Where both admit a call their frontiers
+    are equal."""
     kv_factor = kv_bits_to_factor(kv_bits)
     fleets = [list(d) for d in fleets]
     P = check_budget(max_moved_layers)
@@ -228,13 +296,13 @@ def halda_move_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], model: 
         by_k.setdefault(p[0], []).append(f)
     for k, fs in by_k.items():
         sizes = [len(fleets[f]) for f in fs]
-        check_gate(max(sizes), min(sizes), P, k)
+        pick_route(route, max(sizes), min(sizes), P, k)
     raw: list = [None] * len(fleets)  # fleet -> [(w, n, moved) or None per point]
     for k, fs in sorted(by_k.items()):
         table = fleet_table([fleets[f] for f in fs], model)
         w0 = np.concatenate([np.asarray(plans[f][1], np.int32) for f in fs])
         res = solve_budget_table(table, model, k, w0, P, kv_factor, _flat(table, [los[f] for f in fs], 0),
-                                 _flat(table, [his[f] for f in fs], INT32_MAX), device)
+                                 _flat(table, [his[f] for f in fs], INT32_MAX), device, route)
         for j, f in enumerate(fs):
             a, b = int(table.dev_off[j]), int(table.dev_off[j + 1])
             raw[f] = [([int(v) for v in res.w[p, a:b]], [int(v) for v in res.n[p, a:b]], int(res.moved[j, p]))
@@ -262,20 +330,21 @@ def halda_move_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], model: 
 
 def halda_move_frontier(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent,
                         max_moved_layers: int, kv_bits: str = "8bit", w_min: Optional[Sequence[int]] = None,
-                        w_max: Optional[Sequence[int]] = None, device: int = 0) -> List[FrontierPoint]:
+                        w_max: Optional[Sequence[int]] = None, device: int = 0,
+                        route: str = "wave") -> List[FrontierPoint]:
     """halda_move_frontier_batch for one fleet: the best plan at the incumbent's k for every budget
     0, 2, .. 2 (max_moved_layers // 2) of moved layers, in one GPU solve."""
     return halda_move_frontier_batch([list(devs)], model, [incumbent], max_moved_layers, kv_bits,
                                      None if w_min is None else [w_min], None if w_max is None else [w_max],
-                                     device)[0]
+                                     device, route)[0]
 
 
 def halda_solve_budget(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent,
                        max_moved_layers: int, kv_bits: str = "8bit", w_min: Optional[Sequence[int]] = None,
-                       w_max: Optional[Sequence[int]] = None, device: int = 0) -> HALDAResult:
+                       w_max: Optional[Sequence[int]] = None, device: int = 0, route: str = "wave") -> HALDAResult:
     """The best plan at the incumbent's k that moves at most max_moved_layers layers in total (the frontier's
     last point); RuntimeError, as halda_solve raises it, when no plan lies within the budget and the bounds."""
-    r = halda_move_frontier(devs, model, incumbent, max_moved_layers, kv_bits, w_min, w_max, device)[-1].plan
+    r = halda_move_frontier(devs, model, incumbent, max_moved_layers, kv_bits, w_min, w_max, device, route)[-1].plan
     if r is None:
         raise RuntimeError("No feasible MILP found within the move budget.")
     return r

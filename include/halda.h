@@ -573,7 +573,8 @@ int halda_solve_fleets_boxed_host(void *ctx, const halda_model *model, const hal
  *
  * Gate, from the shapes alone: every fleet has 1 .. 64 devices, 0 <= max_p <= 63, and
  * halda_budget_lds_bytes(max_devices, max_p, k) is at most 160 KiB. Outside it the call returns HALDA_E_ARG
- * and launches nothing: there is no fallback. One launch of halda_sweep_budget_kernel (one wave per fleet;
+ * and launches nothing: this entry has no fallback (wider fleets and larger budgets: halda_wide.h's entry).
+ * One launch of halda_sweep_budget_kernel (one wave per fleet;
  * no context scratch, nothing shared between waves, so launches on different streams need no ordering). */
 typedef struct halda_budget {
     const int32_t *w0;            /* [dev_off[n_fleets]] the incumbents' layer counts, device layout */

@@ -14,6 +14,12 @@ The GPU work is one child process under a time limit; the parent prints one JSON
 writes it to a file.
 
     python tools/budget_ab.py --out profiles/budget_ab.json
+
+--wide times the workgroup route instead (halda_solve_fleets_budget_wide, halda_sweep_budget_wide_kernel) in the
+same way: beside the wave kernel on a shape both admit (4,096 x 16, P = 4, k = 1 and k = 2, the two launches'
+outputs compared bit for bit), and alone on one only it admits (64 x 16, P = 60, k = 1).
+
+    python tools/budget_ab.py --wide --out profiles/budget_wide_ab.json
 """
 
 from __future__ import annotations
@@ -33,9 +39,12 @@ SHAPES = (("a_4096x16_k1_P4", 4096, 16, 1, 4), ("b_4096x16_k1_P8", 4096, 16, 1, 
           ("c_4096x16_k2_P4", 4096, 16, 2, 4), ("d_4096x16_k2_P8", 4096, 16, 2, 8),
           ("e_4096x64_k1_P8", 4096, 64, 1, 8))
 LEGS = ("budget", "box")
+WIDE_SHAPES = (("a_4096x16_k1_P4", 4096, 16, 1, 4, ("budget", "wide")),
+               ("c_4096x16_k2_P4", 4096, 16, 2, 4, ("budget", "wide")),
+               ("w_64x16_k1_P60", 64, 16, 1, 60, ("wide",)))
 
 
-def child() -> None:
+def child(wide: bool) -> None:
     sys.path.insert(0, str(REPO))
     import numpy as np
     import torch
@@ -67,7 +76,7 @@ def child() -> None:
         return t.perturbed(np.random.default_rng(seed))
 
     tables = {}
-    for name, nf, M, k, P in SHAPES:
+    for name, nf, M, k, P, legs in (WIDE_SHAPES if wide else tuple(s + (LEGS,) for s in SHAPES)):
         if (nf, M) not in tables:
             tables[(nf, M)] = big_table(nf, M, 1000 + M)
         table = tables[(nf, M)]
@@ -100,9 +109,10 @@ def child() -> None:
                 torch.cuda.synchronize(dev)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                if kind == "budget":
-                    rc = lib.halda_solve_fleets_budget(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), k, ctypes.byref(bgc),
-                                                       ctypes.byref(frc), ctypes.c_void_p(stream.cuda_stream))
+                if kind in ("budget", "wide"):
+                    fn = lib.halda_solve_fleets_budget if kind == "budget" else lib.halda_solve_fleets_budget_wide
+                    rc = fn(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), k, ctypes.byref(bgc), ctypes.byref(frc),
+                            ctypes.c_void_p(stream.cuda_stream))
                 else:
                     rc = lib.halda_solve_fleets_bounded(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, 1,
                                                         ctypes.byref(bc), ctypes.byref(r),
@@ -116,16 +126,34 @@ def child() -> None:
             return statistics.median(ts)
 
         bd.set_bounds_path(ctx, 3)
-        rounds = {kd: [] for kd in LEGS}
+        rounds = {kd: [] for kd in legs}
+        snap = {}
         for _ in range(ROUNDS):  # alternate the legs
-            for kind in LEGS:
+            for kind in legs:
                 rounds[kind].append(leg(kind) * 1e3)
+                snap[kind] = [t.cpu().numpy().copy() for t in fo]  # the frontier the leg's last call wrote
         route = bd.last_bounds_route(ctx)
         bd.set_bounds_path(ctx, 0)
-        med = {kd: statistics.median(rounds[kd]) for kd in LEGS}
+        med = {kd: statistics.median(rounds[kd]) for kd in legs}
         st = fo[0].cpu().numpy().reshape(nf, P1)
         obj = fo[1].cpu().numpy().reshape(nf, P1)
         mv = fo[2].cpu().numpy().reshape(nf, P1)
+        if wide:
+            lds, glob = bg.budget_wide_bytes(M, P, k)
+            out[name] = {"workload": f"{nf} fleets x {M} devices, k = {k}, P = {P} ({P1} points per fleet)",
+                         "wide_lds_bytes_per_workgroup": lds, "wide_workspace_bytes_per_workgroup": glob,
+                         "points_optimal": int((st == 0).sum()), "points": int(st.size),
+                         "frontier_non_increasing": bool((np.diff(obj, axis=1) <= 0).all()),
+                         "median_moved_layers_at_P": float(np.median(mv[:, P])),
+                         "wide_us_per_fleet": med["wide"] / nf,
+                         **{f"{kd}_event_us": med[kd] for kd in legs}, **{f"{kd}_rounds_us": rounds[kd] for kd in legs}}
+            if "budget" in legs:
+                out[name]["wave_lds_bytes_per_wave"] = bg.budget_lds_bytes(M, P, k)
+                out[name]["wide_over_wave"] = med["wide"] / med["budget"]
+                out[name]["wide_equals_wave_bit_for_bit"] = all(
+                    np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(snap["wide"], snap["budget"]))
+            print(name, json.dumps(out[name]), file=sys.stderr, flush=True)
+            continue
         box_obj = o[1].cpu().numpy()
         ok = (st[:, P] == 0) & (o[0].cpu().numpy() > 0)
         out[name] = {"workload": f"{nf} fleets x {M} devices, k = {k}, P = {P} ({P1} points per fleet)",
@@ -147,13 +175,14 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", help="also write the JSON line to this file")
     ap.add_argument("--timeout", type=float, default=400.0, help="time limit of the GPU child process, seconds")
+    ap.add_argument("--wide", action="store_true", help="time the workgroup route (see above)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        child()
+        child(args.wide)
         return 0
-    p = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child"], capture_output=True, text=True,
-                       timeout=args.timeout)
+    p = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child"] + (["--wide"] if args.wide else []),
+                       capture_output=True, text=True, timeout=args.timeout)
     sys.stderr.write(p.stderr)
     if p.returncode != 0:
         return p.returncode
