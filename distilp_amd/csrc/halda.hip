@@ -1819,6 +1819,49 @@ int launch_frontier(Ctx *c, void (*kernel)(SweepArgs, Args), const halda_model &
     HIP_TRY(hipGetLastError());
     return HALDA_OK;
 }
+
+// The launch of a workgroup frontier kernel (halda_solve_fleets_budget_wide, halda_solve_change_wide): one
+// 256-thread workgroup per fleet / item with sl.lds bytes of LDS and a slice of sl.global bytes of the context's
+// global tables. The grid has the shape of the sweep's global-table launch: the resident workgroups, the fleets,
+// the workspace.
+template <class Args>
+int launch_wide(Ctx *c, void (*kernel)(SweepArgs, Args), const halda_model &model, const halda_fleets &view,
+                int32_t k, const BudgetWideSlice &sl, const Args &J, void *stream) {
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    SweepArgs A = {};
+    static_cast<halda_model &>(A.Mo) = model;
+    A.Mo.bvo = model_bvo(model);
+    A.F = view;
+    A.ks[0] = k;
+    A.Ws[0] = model.L / k;
+    A.n_k = 1;
+    A.mmax = view.max_devices;
+    A.uM = view.min_devices == view.max_devices ? view.max_devices : 0;
+    A.xstride = 7 * int64_t(view.max_devices) + 1;
+    A.gstride = (sl.global + 255) & ~int64_t(255);
+    const void *fn = reinterpret_cast<const void *>(kernel);
+    HIP_TRY(Ctx::ensure_lds(fn, sl.lds));
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kWideThreads, size_t(sl.lds)));
+    const unsigned grid = unsigned(std::max<int64_t>(
+        1, std::min<int64_t>({int64_t(c->cus) * std::max(1, per_cu), int64_t(view.n_fleets),
+                              kGlobalTableBudget / A.gstride})));
+    const size_t gneed = size_t(A.gstride) * size_t(grid);
+    if (gneed > c->gtab_bytes) {
+        if (c->gtab) HIP_TRY(hipFree(c->gtab));
+        c->gtab = nullptr;
+        c->gtab_bytes = 0;
+        HIP_TRY(hipMalloc(&c->gtab, gneed));
+        c->gtab_bytes = gneed;
+    }
+    // the global tables are per context: this launch runs after their previous user on another stream
+    if (const int rc = order_after_previous(c, s)) return rc;
+    A.gtab = static_cast<unsigned char *>(c->gtab);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWideThreads), size_t(sl.lds), s, A, J);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3342,45 +3385,10 @@ int halda_solve_fleets_budget_wide(void *ctx, const halda_model *model, const ha
     if (F.n_fleets <= 0) return HALDA_OK;
     if (frontier->n_devices < F.n_fleets)
         return fail(HALDA_E_ARG, "halda_solve_fleets_budget_wide: halda_frontier.n_devices is not dev_off[n_fleets]");
-    Ctx *c = static_cast<Ctx *>(ctx);
-    hipStream_t s = nullptr;
-    if (const int rc = enter(c, stream, &s)) return rc;
     const BudgetArgs Bg{budget->w0,       budget->w_min,   budget->w_max,   budget->max_p, frontier->n_devices,
                         frontier->status, frontier->obj,   frontier->moved, frontier->w,   frontier->n};
-    const BudgetWideSlice sl = budget_wide_slice(F.max_devices, budget->max_p, k > 1);
-    SweepArgs A = {};
-    static_cast<halda_model &>(A.Mo) = *model;
-    A.Mo.bvo = model_bvo(*model);
-    A.F = F;
-    A.ks[0] = k;
-    A.Ws[0] = model->L / k;
-    A.n_k = 1;
-    A.mmax = F.max_devices;
-    A.uM = F.min_devices == F.max_devices ? F.max_devices : 0;
-    A.xstride = 7 * int64_t(F.max_devices) + 1;
-    A.gstride = (sl.global + 255) & ~int64_t(255);
-    // the grid, the shape of the sweep's global-table launch: the resident workgroups, the fleets, the workspace
-    const void *fn = reinterpret_cast<const void *>(halda_sweep_budget_wide_kernel);
-    HIP_TRY(Ctx::ensure_lds(fn, sl.lds));
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kWideThreads, size_t(sl.lds)));
-    const unsigned grid = unsigned(std::max<int64_t>(
-        1, std::min<int64_t>({int64_t(c->cus) * std::max(1, per_cu), int64_t(F.n_fleets),
-                              kGlobalTableBudget / A.gstride})));
-    const size_t gneed = size_t(A.gstride) * size_t(grid);
-    if (gneed > c->gtab_bytes) {
-        if (c->gtab) HIP_TRY(hipFree(c->gtab));
-        c->gtab = nullptr;
-        c->gtab_bytes = 0;
-        HIP_TRY(hipMalloc(&c->gtab, gneed));
-        c->gtab_bytes = gneed;
-    }
-    // the global tables are per context: this launch runs after their previous user on another stream
-    if (const int rc = order_after_previous(c, s)) return rc;
-    A.gtab = static_cast<unsigned char *>(c->gtab);
-    hipLaunchKernelGGL(halda_sweep_budget_wide_kernel, dim3(grid), dim3(kWideThreads), size_t(sl.lds), s, A, Bg);
-    HIP_TRY(hipGetLastError());
-    return HALDA_OK;
+    return launch_wide(static_cast<Ctx *>(ctx), halda_sweep_budget_wide_kernel, *model, F, k,
+                       budget_wide_slice(F.max_devices, budget->max_p, k > 1), Bg, stream);
 }
 
 int halda_solve_fleets_budget_wide_host(void *ctx, const halda_model *model, const halda_fleets *fh, int32_t k,
@@ -3451,9 +3459,16 @@ int halda_solve_change(void *ctx, const halda_model *model, const halda_fleets *
                            change_slice(I.max_devices, change->max_p, change->max_deficit, k > 1).total, Cg, stream);
 }
 
-int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fleets *th, const halda_subfleets *ih,
-                            int32_t k, const halda_change *change, halda_change_frontier *fr_h) {
-    const char *who = "halda_solve_change_host";
+// The _host form of a change entry (`solve`, gated by `check`): the table, the items, the incumbent triple and the
+// frontier staged through the context's scratch, one copy each way.
+using ChangeCheck = int (*)(void *, const halda_model *, const halda_fleets *, const halda_subfleets *, int32_t,
+                            const halda_change *, const halda_change_frontier *, bool, const char *);
+using ChangeSolve = int (*)(void *, const halda_model *, const halda_fleets *, const halda_subfleets *, int32_t,
+                            const halda_change *, halda_change_frontier *, void *);
+
+static int change_host(void *ctx, const halda_model *model, const halda_fleets *th, const halda_subfleets *ih,
+                       int32_t k, const halda_change *change, halda_change_frontier *fr_h, const char *who,
+                       ChangeCheck check, ChangeSolve solve) {
     if (!ctx || !model || !th || !ih || !change || !fr_h)
         return fail(HALDA_E_ARG, std::string(who) + ": NULL ctx/model/table/items/change/frontier");
     Ctx *c = static_cast<Ctx *>(ctx);
@@ -3472,7 +3487,7 @@ int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fle
     halda_subfleets di = *ih;
     di.min_devices = int32_t(std::min<int64_t>(lmin, INT32_MAX));
     di.max_devices = int32_t(std::min<int64_t>(lmax, INT32_MAX));
-    rc = check_change_args(ctx, model, th, &di, k, change, fr_h, true, who);
+    rc = check(ctx, model, th, &di, k, change, fr_h, true, who);
     if (rc != HALDA_OK) return rc;
     // the incumbents: every w0_i >= 0 and 0 <= D <= max_deficit (-1: the items' largest D is taken)
     int64_t dtop = 0;
@@ -3486,7 +3501,7 @@ int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fle
     if (dc.max_deficit < 0) {
         if (dtop > kChangeMaxE) return fail(HALDA_E_ARG, std::string(who) + ": 2 max_p + max_deficit must be at most 254");
         dc.max_deficit = int32_t(dtop);
-        rc = check_change_args(ctx, model, th, &di, k, &dc, fr_h, true, who);
+        rc = check(ctx, model, th, &di, k, &dc, fr_h, true, who);
         if (rc != HALDA_OK) return rc;
     }
     const int64_t tot = ih->sub_off[n];
@@ -3509,11 +3524,108 @@ int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fle
     dc.w_min = B.at(base, 1);
     dc.w_max = B.at(base, 2);
     halda_change_frontier r = stage::bind_change(base, R, tot);
-    rc = halda_solve_change(ctx, model, &d, &di, k, &dc, &r, s);
+    rc = solve(ctx, model, &d, &di, k, &dc, &r, s);
     if (rc == HALDA_OK) rc = download(stage::change_copies(R, *fr_h), base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
+}
+
+int halda_solve_change_host(void *ctx, const halda_model *model, const halda_fleets *th, const halda_subfleets *ih,
+                            int32_t k, const halda_change *change, halda_change_frontier *fr_h) {
+    return change_host(ctx, model, th, ih, k, change, fr_h, "halda_solve_change_host", check_change_args,
+                       halda_solve_change);
+}
+
+// ---------------------------------------------------------------- a changed fleet beyond one wave
+// halda_solve_change_wide: halda_sweep_change_wide_kernel, one 256-thread workgroup per item; the gate is lists of
+// 1 .. 256 devices, one k, max_p <= 127, 2 max_p + max_deficit <= 254, the LDS slice within the LDS budget and one
+// workgroup's workspace slice within the global-table budget. halda_subfleets, halda_change and
+// halda_change_frontier are the wave entry's.
+int halda_change_wide_bytes(int32_t max_devices, int32_t max_p, int32_t max_deficit, int32_t k, int64_t *lds,
+                            int64_t *global) {
+    if (max_devices < 1 || max_p < 0 || max_deficit < 0 || k < 1 || !lds || !global)
+        return fail(HALDA_E_ARG, "halda_change_wide_bytes: max_devices < 1, max_p < 0, max_deficit < 0, k < 1 or a "
+                                 "NULL result");
+    if (max_devices > 4096 || max_p > 4096 || max_deficit > 65536) {  // far outside the gate; no overflow below
+        *lds = *global = INT64_MAX;
+        return HALDA_OK;
+    }
+    const BudgetWideSlice sl = change_wide_slice(max_devices, max_p, max_deficit, k > 1);
+    *lds = sl.lds;
+    *global = sl.global;
+    return HALDA_OK;
+}
+
+static int check_change_wide_args(void *ctx, const halda_model *model, const halda_fleets *table,
+                                  const halda_subfleets *items, int32_t k, const halda_change *change,
+                                  const halda_change_frontier *fr, bool host, const char *who_c) {
+    const std::string who = who_c;
+    if (!ctx || !model || !table || !items || !change || !fr)
+        return fail(HALDA_E_ARG, who + ": NULL ctx/model/table/items/change/frontier");
+    const halda_subfleets &I = *items;
+    if (I.n_items <= 0) return HALDA_OK;
+    if (!I.parent || !I.sub_off || !I.sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (table->n_fleets <= 0) return fail(HALDA_E_ARG, who + ": the table has no fleets");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    if (k < 1) return fail(HALDA_E_ARG, who + ": k must be >= 1");
+    if (!change->w0) return fail(HALDA_E_ARG, who + ": halda_change.w0 is NULL");
+    if (!(fr->status && fr->obj && fr->loaded && fr->released && fr->w && fr->n))
+        return fail(HALDA_E_ARG, who + ": halda_change_frontier has a NULL array");
+    if (I.min_devices < 1 || I.max_devices < I.min_devices || I.max_devices > kWideMaxM)
+        return fail(HALDA_E_ARG, who + ": every list must have 1 .. " + std::to_string(kWideMaxM) + " devices");
+    if (change->max_p < 0 || change->max_p > kWideMaxP)
+        return fail(HALDA_E_ARG, who + ": max_p must be in 0 .. " + std::to_string(kWideMaxP));
+    if (change->max_deficit < (host ? -1 : 0)) return fail(HALDA_E_ARG, who + ": max_deficit must be >= 0");
+    const int dmax = std::max(change->max_deficit, 0);
+    if (2 * int64_t(change->max_p) + dmax > kChangeMaxE)
+        return fail(HALDA_E_ARG, who + ": 2 max_p + max_deficit must be at most 254");
+    const BudgetWideSlice sl = change_wide_slice(I.max_devices, change->max_p, dmax, k > 1);
+    if (const int rc = check_frontier_lds(sl.lds, who)) return rc;
+    if (sl.global > kGlobalTableBudget)
+        return fail(HALDA_E_ARG, who + ": the workspace slice of " + std::to_string(sl.global) +
+                                     " B exceeds the global-table budget of " + std::to_string(kGlobalTableBudget) +
+                                     " B");
+    return HALDA_OK;
+}
+
+int halda_solve_change_wide(void *ctx, const halda_model *model, const halda_fleets *table,
+                            const halda_subfleets *items, int32_t k, const halda_change *change,
+                            halda_change_frontier *frontier, void *stream) {
+    const int rc = check_change_wide_args(ctx, model, table, items, k, change, frontier, false,
+                                          "halda_solve_change_wide");
+    if (rc != HALDA_OK) return rc;
+    const halda_subfleets &I = *items;
+    if (I.n_items <= 0) return HALDA_OK;
+    if (frontier->n_devices < I.n_items)
+        return fail(HALDA_E_ARG, "halda_solve_change_wide: halda_change_frontier.n_devices is not sub_off[n_items]");
+    halda_fleets view = *table;  // the parent table under the items' count and length summary
+    view.n_fleets = I.n_items;
+    view.min_devices = I.min_devices;
+    view.max_devices = I.max_devices;
+    const ChangeArgs Cg{SubArgs{I.parent, I.sub_off, I.sub_idx},
+                        change->w0,
+                        change->w_min,
+                        change->w_max,
+                        change->max_p,
+                        change->max_deficit,
+                        frontier->n_devices,
+                        frontier->status,
+                        frontier->obj,
+                        frontier->loaded,
+                        frontier->released,
+                        frontier->w,
+                        frontier->n};
+    return launch_wide(static_cast<Ctx *>(ctx), halda_sweep_change_wide_kernel, *model, view, k,
+                       change_wide_slice(I.max_devices, change->max_p, change->max_deficit, k > 1), Cg, stream);
+}
+
+int halda_solve_change_wide_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                                 const halda_subfleets *ih, int32_t k, const halda_change *change,
+                                 halda_change_frontier *fr_h) {
+    return change_host(ctx, model, th, ih, k, change, fr_h, "halda_solve_change_wide_host", check_change_wide_args,
+                       halda_solve_change_wide);
 }
 
 // ---------------------------------------------------------------- scale-in / scale-out

@@ -2807,11 +2807,12 @@ struct BudgetWideSlice {
     int S, RS;
 };
 
-__host__ __device__ inline BudgetWideSlice budget_wide_slice(int mmax, int P, bool kc) {
+// The slice of a launch whose rows hold RS doubles and whose value plane holds S states.
+__host__ __device__ inline BudgetWideSlice wide_slice(int mmax, int P, int RS, int S, bool kc) {
     BudgetWideSlice s;
     const int64_t P1 = P + 1;
-    s.RS = 2 * P + 1;
-    s.S = int(P1 * P1);
+    s.RS = RS;
+    s.S = S;
     int64_t o = 0;
     s.V = o;     o = align16(o + 2 * int64_t(s.S) * 8);
     s.rowG = o;  o = align16(o + 2 * int64_t(s.RS) * 8);
@@ -2831,6 +2832,17 @@ __host__ __device__ inline BudgetWideSlice budget_wide_slice(int mmax, int P, bo
     s.nplan = o; o = align16(o + P1 * mmax * 4);
     s.global = o;
     return s;
+}
+
+// The budget kernel's: rows of 2 P + 1 entries, S = (P + 1)^2 states.
+__host__ __device__ inline BudgetWideSlice budget_wide_slice(int mmax, int P, bool kc) {
+    return wide_slice(mmax, P, 2 * P + 1, int(int64_t(P + 1) * (P + 1)), kc);
+}
+
+// The change kernel's (halda_sweep_change_wide_kernel): change_slice's rows of (2 P + Dmax + 1) | 1 entries and
+// S = (P + 1)(Dmax + P + 1) states.
+__host__ __device__ inline BudgetWideSlice change_wide_slice(int mmax, int P, int Dmax, bool kc) {
+    return wide_slice(mmax, P, (2 * P + Dmax + 1) | 1, (P + 1) * (Dmax + P + 1), kc);
 }
 
 struct WideCtx {
@@ -2954,10 +2966,10 @@ __device__ inline const double *wide_dp(const WideCtx &c, const ChangeMap &m, in
     return cur;
 }
 
-// The plan of point p (thread p) with a finite final value, from state (p, p) after the last device back to
+// The plan of point p (thread p) with a finite final value, from state (p, D + p) after the last device back to
 // (0, 0) through the workspace's arg-min planes (frontier_backtrack's walk).
 __device__ inline void wide_backtrack(const WideCtx &c, const ChangeMap &m, int M, int p) {
-    int r = p, l = p;
+    int r = p, l = m.D + p;
     for (int i = M - 1; i >= 0; --i) {
         const int e = c.arg[int64_t(i) * c.S + m.at(r, l)];
         c.plan[int64_t(p) * c.mmax + i] = uint8_t(e);
@@ -3193,6 +3205,272 @@ __global__ __launch_bounds__(kWideThreads) void halda_sweep_budget_wide_kernel(S
     WideRed R = {smem + sl.red, 0, tid >> 6, tid & 63};
     const int nf = A.F.n_fleets;
     for (int64_t f = blockIdx.x; f < nf; f += gridDim.x) budget_wide_item(A, Bg, int(f), c, R, tid);
+}
+
+// ---------------------------------------------------------------- a changed fleet beyond one wave
+// halda_sweep_change_wide_kernel (halda_solve_change_wide): frontier_item<ChangeJob>'s problem, status ladder,
+// window, R1, tie rules and pricing on the budget workgroup kernel's split, for what the wave kernel's shape leaves
+// out: lists of up to 256 devices and max_p up to 127 wherever two planes of (P + 1)(Dmax + P + 1) doubles fit the
+// LDS. The item's plane is ChangeMap{P, D + P + 1, D} of its own deficit D, its rows hold R1 <= 2 P + D + 1 <= 255
+// entries, and wide_dp / wide_backtrack run on them as they stand. What this body adds to budget_wide_item is the
+// gather through the index list, w0_i = 0 joiners, the deficit, and what a point reports.
+
+// fleet_offsets_tree over a gathered list: listed device i is device base + idx[i] of the parent table; the sums
+// run in list order and the head is the first listed HALDA_DEV_HEAD device, else the first listed -- the constants
+// fleet_offsets_tree gives the materialised list.
+__device__ inline void fleet_offsets_tree_list(const halda_model &Mo, const halda_fleets &F, int64_t base,
+                                               const int32_t *idx, int M, int lane, double &tsum, double &xsum,
+                                               double &kappa) {
+    double t = 0.0, x = 0.0, tail = 0.0;
+    int hi = 0x7fffffff;
+    for (int i = lane; i < M; i += 64) {
+        const DevFields f = load_fields(F, base + idx[i]);
+        t += f.tcomm;
+        x += xi_term(f);
+        tail += tail_term(f);
+        if (f.flags & HALDA_DEV_HEAD) hi = min(hi, i);
+    }
+    tsum = wave_sum_f64(t);
+    xsum = wave_sum_f64(x);
+    tail = wave_sum_f64(tail);
+    hi = wave_imin(hi);
+    const int64_t h = base + idx[hi == 0x7fffffff ? 0 : hi];
+    kappa = kappa_head(Mo, F.flags[h], F.scpu_b1[h], F.T_cpu[h], F.s_disk[h]) + tail;
+}
+
+// One item. A list of at most 64 devices lies lane = listed device in EVERY wave (each prices its points as
+// frontier_item does); wave 0 builds its rows. A longer one lies thread = listed device: thread j gathers the
+// j-th listed device's fields from the parent table, wave q builds the rows of listed devices 64 q .. 64 q + 63,
+// and a wave prices a point in eval_plan_wide's order over the gathered list. Either way the raw obj of an OPTIMAL
+// point is halda_eval_plans' of the returned plan on the materialised list.
+__device__ inline void change_wide_item(const SweepArgs &A, const ChangeArgs &J, int it, const WideCtx &c, WideRed &R,
+                                        int tid) {
+    const int lane = tid & 63, q = tid >> 6;
+    const Wave sg(lane);
+    const int P = J.P, P1 = P + 1;
+    const int k = A.ks[0], W = A.Ws[0];
+    // the item's extent, parent and the parent's first device: uniform reads through the scalar cache
+    const int64_t so = sload_i64(J.S.sub_off + it);
+    const int M = A.uM > 0 ? A.uM : int(sload_i64(J.S.sub_off + it + 1) - so);
+    const int64_t base = sload_i64(A.F.dev_off + sload_i32(J.S.parent + it));
+    const int32_t *idx = J.S.sub_idx + so;
+    const bool narrow = M <= 64;
+    const int dev = narrow ? lane : tid;  // the listed device whose record the thread holds
+    const bool act = dev < M;
+    const bool own = tid < M;             // ... and whose rows, sums and plane entries are this thread's
+    const bool pt = tid < P1;
+    const int64_t o0 = so + (act ? dev : 0);
+    const int wmn = J.w_min ? J.w_min[o0] : 0;
+    const int wmx = J.w_max ? J.w_max[o0] : 0x7fffffff;
+    const int w0 = min(max(J.w0[o0], -kBoundCap), kBoundCap);
+    const DevFields mf = load_fields(A.F, base + J.S.sub_idx[o0]);
+    BoundRec me = {};
+    int bad = 0;
+    static_cast<FieldRec &>(me) = field_rec(A.Mo, mf, bad);
+    double tsum = 0.0, xsum = 0.0, kappa = 0.0;
+    if (narrow) fleet_offsets_regs<Wave, false>(A.Mo, mf, M, sg, tsum, xsum, kappa);
+    else fleet_offsets_tree_list(A.Mo, A.F, base, idx, M, lane, tsum, xsum, kappa);
+    bad = R.any(sg, own && bad != 0) ? 1 : 0;
+    const int lo = min(max(1, wmn), kBoundCap);
+    const int64_t sumlo = R.sum(sg, own ? lo : 0);
+    const int64_t sumw0 = R.sum(sg, own ? w0 : 0);
+    // the host entry rejects it before the launch; D is 0 where the incumbent is rejected
+    const bool w0bad = R.any(sg, own && w0 < 0) || sumw0 > W || W - sumw0 > J.Dmax;
+    const int D = w0bad ? 0 : int(W - sumw0);
+    // the window: a device gives up at most P layers and takes at most D + P
+    const int wlo = max(lo, w0 - P), whi = min(min(W, wmx), w0 + D + P);
+    const int64_t sumwlo = R.sum(sg, own ? min(wlo, kBoundCap) : 0);
+    constexpr int kOpen = 1000;
+    int st = kOpen;
+    if (!(W < 1000000)) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumlo > W) st = HALDA_STATUS_INFEASIBLE;
+    else if (bad || w0bad) st = HALDA_STATUS_UNSUPPORTED;
+    else if (sumwlo > W) st = HALDA_STATUS_INFEASIBLE;  // the window cannot reach the box
+    const int64_t fo = int64_t(it) * P1;
+    if (st != kOpen) {
+        if (pt) {
+            J.status[fo + tid] = st;
+            J.obj[fo + tid] = kInf;
+            J.loaded[fo + tid] = 0;
+            J.released[fo + tid] = 0;
+        }
+        if (own)
+            for (int p = 0; p < P1; ++p) {
+                J.w[int64_t(p) * J.nd + so + tid] = 0;
+                J.n[int64_t(p) * J.nd + so + tid] = 0;
+            }
+        return;
+    }
+    opaque_rec(me);
+    const double kc = double(k - 1);
+    me.W = W;
+    me.wlo = wlo;
+    me.whi = whi;
+    if (own) c.off[tid] = wlo - w0;
+    const int R1 = min(int(W - sumwlo), 2 * P + D) + 1;
+    const ChangeMap m = {P, D + P1, D};
+    {
+        // the wave's listed devices as one table_pass of their own: rows at their places in the workspace
+        Inst I = {};
+        I.inst = it;
+        I.M = narrow ? (q == 0 ? M : 0) : min(max(M - 64 * q, 0), 64);
+        I.W = W;
+        I.Wd = double(W);
+        I.kc = kc;
+        I.iC = 7 * M;
+        I.R1 = R1;
+        I.RS = c.RS;
+        WaveCtx w = {};
+        w.G = c.G + int64_t(64 * q) * c.RS;
+        w.H = kc > 0.0 ? c.H + int64_t(64 * q) * c.RS : nullptr;
+        if (I.M > 0) table_pass<64>(bound_src(&me), w, I, lane);
+    }
+    __syncthreads();
+    // best[p] (thread p): the least (k - 1) T + F^T_M[final state of p] and the T that gave it
+    double best = kInf, bT = kInf;
+    if (kc == 0.0) {
+        const double *F = wide_dp<true>(c, m, M, R1, 0.0, kInf, tid);
+        if (pt) best = F[m.final(tid)];
+        if (pt && best < kInf) wide_backtrack(c, m, M, tid);
+    } else {
+        const double *F = wide_dp<false>(c, m, M, R1, 0.0, kInf, tid);
+        const double sinf = pt ? F[m.final(tid)] : kInf;
+        // the first threshold that leaves every device an entry: max_i min_e H_i[e]
+        double hmin = kInf;
+        if (own)
+            for (int e = 0; e < R1; ++e) hmin = fmin(hmin, c.H[int64_t(tid) * c.RS + e]);
+        double T = R.max_f64(sg, own ? hmin : 0.0);
+        while (T < kInf) {
+            // point p is closed once (k - 1) T + S_inf[p] >= best[p]; the scan stops when every point is
+            if (!R.any(sg, pt && !(kc * T + sinf >= best))) break;
+            F = wide_dp<false>(c, m, M, R1, kc, T, tid);
+            if (pt) {
+                const double v = kc * T + F[m.final(tid)];
+                if (v < best) {  // strict: the earliest T wins
+                    best = v;
+                    bT = T;
+                }
+            }
+            double nx = kInf;  // the next distinct finite H above T
+            for (int t = tid; t < M * R1; t += kWideThreads) {
+                const int i = t / R1, e = t - i * R1;
+                const double h = c.H[int64_t(i) * c.RS + e];
+                if (h > T) nx = fmin(nx, h);
+            }
+            T = R.min_f64(sg, nx);
+        }
+        // the arg-min planes of each distinct winning T, once, for the points it won
+        bool left = pt && best < kInf;
+        while (R.any(sg, left)) {
+            const double Tw = R.min_f64(sg, left ? bT : kInf);
+            wide_dp<true>(c, m, M, R1, kc, Tw, tid);
+            if (left && bT == Tw) {
+                wide_backtrack(c, m, M, tid);
+                left = false;
+            }
+        }
+    }
+    if (pt) c.best[tid] = best;
+    __syncthreads();
+    // price every exact-p plan, the waves taking the points round-robin
+    for (int p = q; p < P1; p += kWideWaves) {
+        double obj = kInf;
+        int cnt = 0;
+        if (c.best[p] < kInf) {
+            const uint8_t *pl = c.plan + int64_t(p) * c.mmax;
+            int *np = c.nplan + int64_t(p) * c.mmax;
+            double gsum, hmax;
+            if (narrow) {
+                double gd = 0.0, H = 0.0;
+                int wl = 0, n = 0;
+                if (act) {
+                    wl = wlo + pl[lane];
+                    double Pc, Qc;
+                    int sl[4] = {0, 0, 0, 0};
+                    split_full(me, wl, gd, n, sl);
+                    dev_cycle(me, wl, n, sl, Pc, Qc);
+                    H = fmax(0.0, Qc >= Pc ? 0.5 * (Pc + Qc) : Pc);
+                    np[lane] = n;
+                }
+                hmax = sg.max_f64(act ? H : 0.0);
+                gsum = sg.sum_f64(act ? gd : 0.0);
+                cnt = sg.sum_i(act ? max(0, w0 - wl) : 0);
+            } else {
+                double gs = 0.0, hm = 0.0;
+                int cn = 0;
+                for (int i = lane; i < M; i += 64) {
+                    BoundRec ri = {};
+                    int bi = 0;
+                    static_cast<FieldRec &>(ri) = field_rec(A.Mo, load_fields(A.F, base + idx[i]), bi);
+                    const int w0i = min(max(J.w0[so + i], -kBoundCap), kBoundCap);
+                    ri.W = W;
+                    ri.wlo = w0i + c.off[i];
+                    ri.whi = W;
+                    const int wl = ri.wlo + pl[i];
+                    double gd = 0.0, Pc, Qc;
+                    int n = 0, sl[4] = {0, 0, 0, 0};
+                    split_full(ri, wl, gd, n, sl);
+                    dev_cycle(ri, wl, n, sl, Pc, Qc);
+                    np[i] = n;
+                    gs += gd;
+                    hm = fmax(hm, fmax(0.0, Qc >= Pc ? 0.5 * (Pc + Qc) : Pc));
+                    cn += max(0, w0i - wl);
+                }
+                hmax = sg.max_f64(hm);
+                gsum = sg.sum_f64(gs);
+                cnt = sg.sum_i(cn);
+            }
+            obj = gsum + kc * hmax;
+            obj = obj + tsum;
+            obj = obj + xsum;
+            obj = obj + kappa;
+        }
+        if (lane == 0) {
+            c.objv[p] = obj;
+            c.cnt[p] = cnt;
+        }
+    }
+    __syncthreads();
+    // point p: the best exact point p' <= p, the fewest layers released among equal objectives (strict "<",
+    // ascending)
+    if (pt) {
+        double run = kInf;
+        int src = -1, runcnt = 0;
+        for (int pp = 0; pp <= tid; ++pp) {
+            const double o = c.objv[pp];
+            if (o < run) {
+                run = o;
+                src = pp;
+                runcnt = c.cnt[pp];
+            }
+        }
+        J.status[fo + tid] = src >= 0 ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+        J.obj[fo + tid] = run;
+        J.loaded[fo + tid] = src >= 0 ? D + runcnt : 0;
+        J.released[fo + tid] = runcnt;
+        c.src[tid] = src;
+    }
+    __syncthreads();
+    if (own)
+        for (int p = 0; p < P1; ++p) {
+            const int sp = c.src[p];
+            J.w[int64_t(p) * J.nd + so + tid] = sp >= 0 ? wlo + c.plan[int64_t(sp) * c.mmax + tid] : 0;
+            J.n[int64_t(p) * J.nd + so + tid] = sp >= 0 ? c.nplan[int64_t(sp) * c.mmax + tid] : 0;
+        }
+    __syncthreads();  // the LDS and the workspace slice are rewritten by the workgroup's next item
+}
+
+// One 256-thread workgroup per item on a persistent grid (workgroup b takes items b, b + grid, ...), its LDS and
+// its workspace slice (A.gtab + b A.gstride) laid out by change_wide_slice of the launch's shape. Every barrier is
+// reached by every thread; no spin-wait, no atomics, nothing shared between workgroups.
+__global__ __launch_bounds__(kWideThreads) void halda_sweep_change_wide_kernel(SweepArgs A, ChangeArgs Cg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x;
+    const BudgetWideSlice sl = change_wide_slice(A.mmax, Cg.P, Cg.Dmax, A.ks[0] > 1);
+    const WideCtx c = wide_ctx(smem, A.gtab + int64_t(blockIdx.x) * A.gstride, sl, Cg.P, A.mmax);
+    WideRed R = {smem + sl.red, 0, tid >> 6, tid & 63};
+    const int n = A.F.n_fleets;
+    for (int64_t it = blockIdx.x; it < n; it += gridDim.x) change_wide_item(A, Cg, int(it), c, R, tid);
 }
 
 // ---------------------------------------------------------------- scale-in / scale-out (halda_solve_change_subsets)

@@ -205,9 +205,12 @@ BOXES_PROTOTYPES = {
     **_knob("boxes"),
 }
 
-# include/halda_wide.h, the companion header of the move budget's workgroup route: it adds no struct (the entries
-# take halda_budget and halda_frontier); its prototypes are applied by load_library with the others
+# include/halda_wide.h, the companion header of the move budget's and the change frontier's workgroup routes: it
+# adds no struct (the entries take halda.h's); its prototypes are applied by load_library with the others
 WIDE_PROTOTYPES = {
     **_with_host("halda_solve_fleets_budget_wide", *_table, c_int32, POINTER(HaldaBudgetC), POINTER(HaldaFrontierC)),
     "halda_budget_wide_bytes": (c_int, [c_int32] * 3 + [POINTER(c_int64)] * 2),
+    **_with_host("halda_solve_change_wide", *_table, _items, c_int32, POINTER(HaldaChangeC),
+                 POINTER(HaldaChangeFrontierC)),
+    "halda_change_wide_bytes": (c_int, [c_int32] * 4 + [POINTER(c_int64)] * 2),
 }

@@ -30,7 +30,7 @@ from ..common import DeviceProfile, ModelProfile
 from ._abi import HaldaChangeC, HaldaChangeFrontierC, HaldaSubfleetsC
 from ._libhalda import STATUS_OPTIMAL, get_context, ptr
 from .bounds import INT32_MAX, check_bounds
-from .budget import check_incumbent, distinct_plans, frontier_lds_bytes, host_frontier
+from .budget import GLOBAL_BUDGET, ROUTES, _align16, check_incumbent, distinct_plans, frontier_lds_bytes, host_frontier
 from .coefficients import HALDAResult, assign_sets
 from .fleets import FleetTable, _host_struct, fleet_table, model_struct
 from .fleets import _bind as _bind_change  # noqa: F401 -- the identity, for callers from before load_library bound all
@@ -42,6 +42,8 @@ LDS_BUDGET = 160 * 1024  # csrc/halda.hip kLdsBudget
 MAX_P = 63               # one lane per frontier point
 MAX_DEVICES = 64         # one lane per listed device
 MAX_ENTRY = 254          # 2 P + max_deficit: a table index is one byte, 255 marks an unreached state
+WIDE_MAX_P = 127         # route "wide": one thread per frontier point, an arg-min byte per entry
+WIDE_MAX_DEVICES = 256   # route "wide": one thread per listed device of a 256-thread workgroup
 
 Lost = Union[int, Sequence[int]]
 
@@ -54,7 +56,8 @@ def change_lds_bytes(max_devices: int, max_p: int, max_deficit: int, k: int) -> 
 
 
 def check_gate(max_devices: int, min_devices: int, max_p: int, max_deficit: int, k: int) -> None:
-    """The launch's gate, from the shapes alone: ValueError outside it (there is no other route)."""
+    """The wave launch's gate, from the shapes alone: ValueError outside it (route "wave" has no fallback; the
+    shapes beyond it are route "wide"'s, check_gate_wide)."""
     if min_devices < 1 or max_devices > MAX_DEVICES:
         raise ValueError(f"a change frontier needs lists of 1 .. {MAX_DEVICES} devices, got {min_devices} .. "
                          f"{max_devices}")
@@ -68,6 +71,66 @@ def check_gate(max_devices: int, min_devices: int, max_p: int, max_deficit: int,
     if need > LDS_BUDGET:
         raise ValueError(f"{max_p} released layers with a deficit of {max_deficit} on lists of up to {max_devices} "
                          f"devices need {need} B of LDS per item, beyond the {LDS_BUDGET} B budget: lower max_released")
+
+
+def change_wide_bytes(max_devices: int, max_p: int, max_deficit: int, k: int):
+    """(lds, global) of one workgroup of halda_sweep_change_wide_kernel (csrc/halda_sweep.hpp change_wide_slice,
+    the figures halda_change_wide_bytes returns), with RS = (2 P + Dmax + 1) | 1 and S = (P + 1)(Dmax + P + 1).
+    LDS: two value planes of S doubles, two row buffers of RS doubles per table (G, and H for k > 1), per device
+    wlo - w0, the reduction slots, per point best, obj, released and source. Workspace: G and H as max_devices
+    rows of RS doubles, one arg-min byte per (device, state), the plan rows and their n."""
+    M, P1, D, kc = int(max_devices), int(max_p) + 1, int(max_deficit), k > 1
+    RS, S = (2 * P1 + D - 1) | 1, P1 * (D + P1)
+    o = _align16(2 * S * 8)
+    o = _align16(o + 2 * RS * 8)
+    o = _align16(o + (2 * RS * 8 if kc else 0))
+    o = _align16(o + M * 4)
+    o = _align16(o + 2 * 4 * 8)
+    o = _align16(o + P1 * 8)
+    o = _align16(o + P1 * 8)
+    o = _align16(o + P1 * 4)
+    lds = _align16(o + P1 * 4)
+    g = _align16(M * RS * 8)
+    g = _align16(g + (M * RS * 8 if kc else 0))
+    g = _align16(g + M * S)
+    g = _align16(g + P1 * M)
+    return lds, _align16(g + P1 * M * 4)
+
+
+def check_gate_wide(max_devices: int, min_devices: int, max_p: int, max_deficit: int, k: int) -> None:
+    """The gate of route "wide", from the shapes alone: ValueError outside it."""
+    if min_devices < 1 or max_devices > WIDE_MAX_DEVICES:
+        raise ValueError(f"a change frontier on route 'wide' needs lists of 1 .. {WIDE_MAX_DEVICES} devices, got "
+                         f"{min_devices} .. {max_devices}")
+    if max_p < 0 or max_p > WIDE_MAX_P:
+        raise ValueError(f"max_released = {max_p} exceeds {WIDE_MAX_P} on route 'wide'" if max_p > WIDE_MAX_P
+                         else "max_released must be >= 0")
+    if max_deficit < 0:
+        raise ValueError("max_deficit must be >= 0")
+    if 2 * max_p + max_deficit > MAX_ENTRY:
+        raise ValueError(f"2 * max_released + deficit = {2 * max_p + max_deficit} exceeds {MAX_ENTRY}")
+    lds, glob = change_wide_bytes(max_devices, max_p, max_deficit, k)
+    if lds > LDS_BUDGET:
+        raise ValueError(f"{max_p} released layers with a deficit of {max_deficit} need {lds} B of LDS per item on "
+                         f"route 'wide', beyond the {LDS_BUDGET} B budget: lower max_released")
+    if glob > GLOBAL_BUDGET:
+        raise ValueError(f"{max_p} released layers with a deficit of {max_deficit} on lists of up to {max_devices} "
+                         f"devices need {glob} B of workspace per item, beyond the {GLOBAL_BUDGET} B budget")
+
+
+def pick_route(route: str, max_devices: int, min_devices: int, max_p: int, max_deficit: int, k: int) -> str:
+    """"wave" or "wide" for a call of these shapes, its gate checked (ValueError outside it). "auto": the wave
+    kernel wherever check_gate admits the call, the workgroup kernel elsewhere."""
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
+    if route == "auto":
+        try:
+            check_gate(max_devices, min_devices, max_p, max_deficit, k)
+            return "wave"
+        except ValueError:
+            route = "wide"
+    (check_gate if route == "wave" else check_gate_wide)(max_devices, min_devices, max_p, max_deficit, k)
+    return route
 
 
 def check_released(max_released) -> int:
@@ -131,8 +194,9 @@ class ChangeSolve:
 
 def solve_change_table(table: FleetTable, model: ModelProfile, k: int, items, w0: np.ndarray, max_p: int,
                        kv_factor: float, w_min: Optional[np.ndarray] = None, w_max: Optional[np.ndarray] = None,
-                       max_deficit: Optional[int] = None, device: int = 0) -> ChangeSolve:
-    """One halda_solve_change_host call on a packed parent table. `items` is (parent, sub_off, sub_idx) as
+                       max_deficit: Optional[int] = None, device: int = 0, route: str = "wave") -> ChangeSolve:
+    """One halda_solve_change_host call on a packed parent table, or on route "wide" (and on "auto" outside the
+    wave kernel's gate) one halda_solve_change_wide_host call. `items` is (parent, sub_off, sub_idx) as
     subfleets.pack_items returns them; w0 / w_min / w_max are int32 arrays laid out by sub_off. max_deficit
     None: the items' largest deficit. ValueError before any GPU work for a bad w0 or a shape outside the gate."""
     parent, sub_off, sub_idx = items
@@ -141,7 +205,8 @@ def solve_change_table(table: FleetTable, model: ModelProfile, k: int, items, w0
         raise ValueError(f"k = {k} must be positive")
     top = check_w0(sub_off, w0, int(model.L) // int(k), max_deficit)
     dmax = top if max_deficit is None else int(max_deficit)
-    check_gate(int(lens.max()), int(lens.min()), int(max_p), dmax, int(k))
+    route = pick_route(route, int(lens.max()), int(lens.min()), int(max_p), dmax, int(k))
+    entry = "halda_solve_change_host" if route == "wave" else "halda_solve_change_wide_host"
     ctx = get_context(device)
     n, tot, P1 = len(parent), int(sub_off[-1]), int(max_p) + 1
     out = ChangeSolve(status=np.zeros((n, P1), np.int32), obj=np.zeros((n, P1)), loaded=np.zeros((n, P1), np.int32),
@@ -158,7 +223,7 @@ def solve_change_table(table: FleetTable, model: ModelProfile, k: int, items, w0
     ch = HaldaChangeC(ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(max_p), dmax)
     fr = HaldaChangeFrontierC(tot, *(ptr(getattr(out, f)) for f in ("status", "obj", "loaded", "released", "w", "n")))
     m = model_struct(model, kv_factor)
-    ctx.call("halda_solve_change_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it), int(k),
+    ctx.call(entry, ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it), int(k),
              ctypes.byref(ch), ctypes.byref(fr))
     del keep
     return out
@@ -178,14 +243,18 @@ def halda_change_frontiers(fleets: Sequence[Sequence[DeviceProfile]], model: Mod
                            max_released: int, kv_bits: str = "8bit",
                            w_min: Optional[Sequence[Optional[Sequence[int]]]] = None,
                            w_max: Optional[Sequence[Optional[Sequence[int]]]] = None,
-                           device: int = 0) -> List[List[ChangePoint]]:
+                           device: int = 0, route: str = "wave") -> List[List[ChangePoint]]:
     """Per item (parent fleet, index list) the change frontier around w0s[i] (the layers its listed devices
     hold, in list order; zeros allowed): one ChangePoint per p = 0 .. max_released. ONE packed parent table and
     ONE kernel call for every item; one halda_solve_subfleets call gives the lists' free optima at k (for
     `regret`), and one evaluation call prices every distinct returned plan on its materialised list, so a
     point's obj_value is halda_evaluate_plan's of its plan bit for bit. w_min / w_max: per item a list of bounds
     in list order or None. ValueError / IndexError before any GPU work for malformed items, a bad w0 (a negative
-    entry, a sum above L // k), a bad budget, or a shape outside the launch's gate."""
+    entry, a sum above L // k), a bad budget, or a shape outside the launch's gate. route: "wave" (the default) is
+    halda_solve_change and its gate (lists of at most 64 devices, max_released <= 63, the LDS slice); "wide" the
+    workgroup kernel (halda_solve_change_wide: lists of up to 256 devices, max_released <= 127 and two planes of
+    (P + 1)(D + P + 1) doubles within the LDS, check_gate_wide); "auto" the wave kernel where its gate admits the
+    call and the workgroup kernel elsewhere. Where both admit a call their frontiers are equal."""
     kv_factor = kv_bits_to_factor(kv_bits)
     fleets = [list(d) for d in fleets]
     items = [(int(f), [int(j) for j in s]) for f, s in items]
@@ -213,10 +282,10 @@ def halda_change_frontiers(fleets: Sequence[Sequence[DeviceProfile]], model: Mod
     if len(w0) and (int(w0.max()) > INT32_MAX or int(w0.min()) < -INT32_MAX):
         raise ValueError("w0: an entry does not fit 32 bits")
     top = check_w0(packed[1], w0, int(model.L) // k)
-    check_gate(int(lens.max()), int(lens.min()), P, top, k)
+    pick_route(route, int(lens.max()), int(lens.min()), P, top, k)
     table = fleet_table(fleets, model)
     res = solve_change_table(table, model, k, packed, w0.astype(np.int32), P, kv_factor,
-                             _flat_lists((los, lens), 0), _flat_lists((his, lens), INT32_MAX), top, device)
+                             _flat_lists((los, lens), 0), _flat_lists((his, lens), INT32_MAX), top, device, route)
     raw = []  # per item [(w, n, loaded, released) or None per point]
     for i in range(len(items)):
         a, b = int(packed[1][i]), int(packed[1][i + 1])
@@ -247,12 +316,15 @@ def halda_change_frontiers(fleets: Sequence[Sequence[DeviceProfile]], model: Mod
 
 def halda_change_frontier(devs: Sequence[DeviceProfile], model: ModelProfile, k: int, w0: Sequence[int],
                           max_released: int, kv_bits: str = "8bit", w_min: Optional[Sequence[int]] = None,
-                          w_max: Optional[Sequence[int]] = None, device: int = 0) -> List[ChangePoint]:
+                          w_max: Optional[Sequence[int]] = None, device: int = 0,
+                          route: str = "wave") -> List[ChangePoint]:
     """The change frontier of one fleet AFTER the change: `devs` are the devices there are now, w0 the layers
-    each holds (0 for a device that just joined; sum w0 <= L // k, the rest being orphaned layers)."""
+    each holds (0 for a device that just joined; sum w0 <= L // k, the rest being orphaned layers). route: as in
+    halda_change_frontiers."""
     devs = list(devs)
     return halda_change_frontiers([devs], model, [(0, list(range(len(devs))))], k, [list(w0)], max_released, kv_bits,
-                                  None if w_min is None else [w_min], None if w_max is None else [w_max], device)[0]
+                                  None if w_min is None else [w_min], None if w_max is None else [w_max], device,
+                                  route)[0]
 
 
 def _lost_lists(M: int, lost) -> List[List[int]]:
@@ -283,11 +355,12 @@ def _sub(a: Optional[Sequence[int]], keep: Sequence[int]):
 def halda_failover_frontiers(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent,
                              max_released: int, lost: Optional[Sequence[Lost]] = None, kv_bits: str = "8bit",
                              w_min: Optional[Sequence[int]] = None, w_max: Optional[Sequence[int]] = None,
-                             device: int = 0) -> List[List[ChangePoint]]:
+                             device: int = 0, route: str = "wave") -> List[List[ChangePoint]]:
     """The N-1 contingency table of a running plan: one change frontier per entry of `lost` (a device index or
     a tuple of them; default: every single device), for the fleet without those devices, the survivors holding
     the incumbent's layers. The fleet is packed ONCE and every entry is solved in ONE kernel call. Plans are
-    indexed within the survivors' list (the fleet's order); w_min / w_max are per device of `devs`."""
+    indexed within the survivors' list (the fleet's order); w_min / w_max are per device of `devs`. route: as in
+    halda_change_frontiers ("wide" or "auto" for a fleet of more than 65 devices)."""
     devs = list(devs)
     M = len(devs)
     P = check_released(max_released)
@@ -299,17 +372,18 @@ def halda_failover_frontiers(devs: Sequence[DeviceProfile], model: ModelProfile,
     keeps = [[j for j in range(M) if j not in set(g)] for g in gone]
     return halda_change_frontiers([devs], model, [(0, s) for s in keeps], k, [[w[j] for j in s] for s in keeps], P,
                                   kv_bits, None if w_min is None else [_sub(w_min, s) for s in keeps],
-                                  None if w_max is None else [_sub(w_max, s) for s in keeps], device)
+                                  None if w_max is None else [_sub(w_max, s) for s in keeps], device, route)
 
 
 def halda_join_frontiers(devs: Sequence[DeviceProfile], pool: Sequence[DeviceProfile], model: ModelProfile,
                          incumbent: Incumbent, max_released: int, kv_bits: str = "8bit",
                          w_min: Optional[Sequence[int]] = None, w_max: Optional[Sequence[int]] = None,
-                         device: int = 0) -> List[List[ChangePoint]]:
+                         device: int = 0, route: str = "wave") -> List[List[ChangePoint]]:
     """One change frontier per device of `pool` that joins the running fleet: the list is `devs` followed by
     that device, which holds nothing (w0 = 0) and must receive at least one layer, so point 0 has no plan. The
     parent is the fleet plus the pool, packed once; one kernel call. w_min / w_max are per device of `devs` (the
-    joiner is unbounded)."""
+    joiner is unbounded). route: as in halda_change_frontiers ("wide" or "auto" for a fleet of more than 63
+    devices)."""
     devs, pool = list(devs), list(pool)
     M = len(devs)
     P = check_released(max_released)
@@ -321,15 +395,16 @@ def halda_join_frontiers(devs: Sequence[DeviceProfile], pool: Sequence[DevicePro
     return halda_change_frontiers([devs + pool], model, [(0, list(range(M)) + [M + j]) for j in range(n)], k,
                                   [list(w) + [0]] * n, P, kv_bits,
                                   None if w_min is None else [list(w_min) + [1]] * n,
-                                  None if w_max is None else [list(w_max) + [INT32_MAX]] * n, device)
+                                  None if w_max is None else [list(w_max) + [INT32_MAX]] * n, device, route)
 
 
 def halda_failover_plan(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent, lost: Lost,
-                        max_released: int, kv_bits: str = "8bit", device: int = 0) -> HALDAResult:
+                        max_released: int, kv_bits: str = "8bit", device: int = 0, route: str = "wave") -> HALDAResult:
     """The plan to move to when `lost` (a device index or a tuple of them) drops out and at most max_released
     layers may be taken off the survivors: the frontier's last point. RuntimeError, as halda_solve raises it,
-    when there is none."""
-    r = halda_failover_frontiers(devs, model, incumbent, max_released, [lost], kv_bits, device=device)[0][-1].plan
+    when there is none. route: as in halda_change_frontiers."""
+    r = halda_failover_frontiers(devs, model, incumbent, max_released, [lost], kv_bits, device=device,
+                                 route=route)[0][-1].plan
     if r is None:
         raise RuntimeError("No feasible MILP found within the released-layer budget.")
     return r

@@ -13,6 +13,14 @@ The GPU work is one child process under a time limit; the parent prints one JSON
 writes it to a file.
 
     python tools/change_ab.py --out profiles/change_ab.json
+
+--wide times the workgroup route instead (halda_solve_change_wide, halda_sweep_change_wide_kernel) in the same
+way: beside the wave kernel on shapes both admit (64 x 16, P = 4, k = 1 and k = 2, the two launches' outputs
+compared bit for bit), and alone on two only it admits: the leave-one-out of one 256-device fleet on a 320-layer
+model at P = 4, and at P = 72 the 4-device fleet synth_fleet(0, 4) without device 1, the survivors holding the
+optimum of synth_fleet(100, 4) (a stale incumbent whose free optimum releases 72 layers).
+
+    python tools/change_ab.py --wide --out profiles/change_wide_ab.json
 """
 
 from __future__ import annotations
@@ -30,9 +38,14 @@ WARM, REPS, ROUNDS = 2, 7, 3
 SHAPES = (("a_64x16_k1_P4", 64, 16, 1, 4), ("b_64x16_k1_P8", 64, 16, 1, 8), ("c_64x16_k2_P4", 64, 16, 2, 4),
           ("d_64x16_k2_P8", 64, 16, 2, 8), ("e_64x64_k1_P4", 64, 64, 1, 4))
 LEGS = ("change", "resolve")
+# name, fleets, devices, k, P, legs, model depth, stale: (seed of the fleet, seed of the incumbent's fleet, lost)
+WIDE_SHAPES = (("a_64x16_k1_P4", 64, 16, 1, 4, ("change", "wide"), 80, None),
+               ("c_64x16_k2_P4", 64, 16, 2, 4, ("change", "wide"), 80, None),
+               ("w_1x256_k1_P4", 1, 256, 1, 4, ("wide",), 320, None),
+               ("s_1x4_stale_k1_P72", 1, 4, 1, 72, ("wide",), 80, (0, 100, 1)))
 
 
-def child() -> None:
+def child(wide: bool) -> None:
     sys.path.insert(0, str(REPO))
     import numpy as np
     import torch
@@ -46,7 +59,7 @@ def child() -> None:
     from distilp_amd.solver.subfleets import HaldaSubfleetsC, last_subfleets_route, leave_one_out_items
     from distilp_amd.synth import load_model_dict, synth_fleet
 
-    model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
+    model80 = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
     lib = ctx.lib
@@ -54,19 +67,27 @@ def child() -> None:
     out = {"gpu": torch.cuda.get_device_name(0), "reps": REPS, "rounds": ROUNDS}
     fields = ("os_class", "flags") + F64_FIELDS + BYTE_FIELDS
     tables = {}
-    for name, nf, M, k, P in SHAPES:
-        if (nf, M) not in tables:
-            tables[(nf, M)] = fleet_table([[DeviceProfile.model_validate(d) for d in synth_fleet(1000 + M + s, M)]
-                                           for s in range(nf)], model)
-        table = tables[(nf, M)]
-        inc = solve_table(table, model, [k], 0.5)
+    def seeded(seed, nf, M, model):
+        return fleet_table([[DeviceProfile.model_validate(d) for d in synth_fleet(seed + s, M)] for s in range(nf)],
+                           model)
+
+    for name, nf, M, k, P, legs, L, stale in (WIDE_SHAPES if wide else tuple(s + (LEGS, 80, None) for s in SHAPES)):
+        model = model80.model_copy(update={"L": L})
+        if (nf, M, L, stale) not in tables:
+            tables[(nf, M, L, stale)] = seeded(stale[0] if stale else 1000 + M, nf, M, model)
+        table = tables[(nf, M, L, stale)]
+        inc = solve_table(seeded(stale[1], nf, M, model) if stale else table, model, [k], 0.5)
         assert (inc.best_k == k).all()
         parent, sub_off, sub_idx = leave_one_out_items(table.sizes())
+        if stale:  # the one list without device `lost`
+            j = stale[2]
+            parent, sub_idx = parent[j:j + 1], sub_idx[int(sub_off[j]):int(sub_off[j + 1])]
+            sub_off = np.asarray([0, len(sub_idx)], np.int64)
         n, tot, P1 = len(parent), int(sub_off[-1]), P + 1
         g = np.repeat(table.dev_off[parent.astype(np.int64)], np.diff(sub_off)) + sub_idx
         w0 = inc.w[g].astype(np.int32)
         top = ch.check_w0(sub_off, w0, int(model.L) // k)
-        ch.check_gate(M - 1, M - 1, P, top, k)
+        (ch.check_gate if "change" in legs else ch.check_gate_wide)(M - 1, M - 1, P, top, k)
         arrs = {f: torch.from_numpy(np.ascontiguousarray(getattr(table, f))).to(dev) for f in ("dev_off",) + fields}
         fs = _fleets_struct(table, lambda f: arrs[f].data_ptr())
         i32, f64 = torch.int32, torch.float64
@@ -91,10 +112,10 @@ def child() -> None:
                 torch.cuda.synchronize(dev)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                if kind == "change":
-                    rc = lib.halda_solve_change(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(itc), k,
-                                                ctypes.byref(chc), ctypes.byref(frc),
-                                                ctypes.c_void_p(stream.cuda_stream))
+                if kind in ("change", "wide"):
+                    fn = lib.halda_solve_change if kind == "change" else lib.halda_solve_change_wide
+                    rc = fn(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(itc), k, ctypes.byref(chc),
+                            ctypes.byref(frc), ctypes.c_void_p(stream.cuda_stream))
                 else:
                     rc = lib.halda_solve_subfleets(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(itc),
                                                    karr.ctypes.data, 1, ctypes.byref(r),
@@ -107,14 +128,35 @@ def child() -> None:
                     ts.append(e0.elapsed_time(e1))
             return statistics.median(ts)
 
-        rounds = {kd: [] for kd in LEGS}
+        rounds = {kd: [] for kd in legs}
+        snap = {}
         for _ in range(ROUNDS):  # alternate the legs
-            for kind in LEGS:
+            for kind in legs:
                 rounds[kind].append(leg(kind) * 1e3)
-        med = {kd: statistics.median(rounds[kd]) for kd in LEGS}
+                snap[kind] = [t.cpu().numpy().copy() for t in fo]  # the frontier the leg's last call wrote
+        med = {kd: statistics.median(rounds[kd]) for kd in legs}
         st = fo[0].cpu().numpy().reshape(n, P1)
         obj = fo[1].cpu().numpy().reshape(n, P1)
         rel = fo[3].cpu().numpy().reshape(n, P1)
+        if wide:
+            lds, glob = ch.change_wide_bytes(M - 1, P, top, k)
+            out[name] = {"workload": f"{nf} fleets x {M} devices on {L} layers: {n} lists of {M - 1}, k = {k}, "
+                                     f"P = {P} ({P1} points per list)",
+                         "max_deficit": top, "wide_lds_bytes_per_workgroup": lds,
+                         "wide_workspace_bytes_per_workgroup": glob,
+                         "points_optimal": int((st == 0).sum()), "points": int(st.size),
+                         "frontier_non_increasing": bool((obj[:, 1:] <= obj[:, :-1]).all()),
+                         "lists_that_release_at_P": int((rel[:, P] > 0).sum()),
+                         "most_released_at_P": int(rel[:, P].max()),
+                         "wide_us_per_list": med["wide"] / n,
+                         **{f"{kd}_event_us": med[kd] for kd in legs}, **{f"{kd}_rounds_us": rounds[kd] for kd in legs}}
+            if "change" in legs:
+                out[name]["wave_lds_bytes_per_wave"] = ch.change_lds_bytes(M - 1, P, top, k)
+                out[name]["wide_over_wave"] = med["wide"] / med["change"]
+                out[name]["wide_equals_wave_bit_for_bit"] = all(
+                    np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(snap["wide"], snap["change"]))
+            print(name, json.dumps(out[name]), file=sys.stderr, flush=True)
+            continue
         free_obj = o[1].cpu().numpy()
         ok = (st[:, P] == 0) & (o[0].cpu().numpy() > 0)
         out[name] = {"workload": f"{nf} fleets x {M} devices: {n} leave-one-out lists of {M - 1}, k = {k}, P = {P} "
@@ -139,13 +181,14 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", help="also write the JSON line to this file")
     ap.add_argument("--timeout", type=float, default=400.0, help="time limit of the GPU child process, seconds")
+    ap.add_argument("--wide", action="store_true", help="time the workgroup route (see above)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        child()
+        child(args.wide)
         return 0
-    p = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child"], capture_output=True, text=True,
-                       timeout=args.timeout)
+    p = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child"] + (["--wide"] if args.wide else []),
+                       capture_output=True, text=True, timeout=args.timeout)
     sys.stderr.write(p.stderr)
     if p.returncode != 0:
         return p.returncode
