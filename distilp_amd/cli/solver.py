@@ -33,6 +33,8 @@ one line per (d, p): `scale-in d, p: dropped=[names], loaded=..., released=..., 
 --failover P (with --evaluate-solution) prints, after those, one line per device: the best plan of the fleet
 without it at that plan's k that takes at most P layers off the survivors (halda_failover_frontiers' last
 point), `lose NAME: p=..., loaded=..., released=..., obj=..., regret=...`, or `lose NAME: infeasible`.
+--route {wave,wide,auto} (default wave) picks the GPU route of --select-devices, --scale-in, --failover and
+--move-frontier: wide serves fleets of up to 256 devices, auto takes wave wherever its gate admits the call.
 --cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
 halda_solve_bounded) and prints the usual output for that solve. Without these flags the output is unchanged.
 """
@@ -159,13 +161,14 @@ def within_line(devices: List[DeviceProfile], model: ModelProfile, plan, max_mov
     return line
 
 
-def frontier_lines(devices: List[DeviceProfile], model: ModelProfile, plan, budget: int) -> List[str]:
+def frontier_lines(devices: List[DeviceProfile], model: ModelProfile, plan, budget: int,
+                   route: str = "wave") -> List[str]:
     """--move-frontier B: one line per point of halda_move_frontier around the incumbent (kv_bits "4bit" like
     the solve above)."""
     from ..solver.budget import halda_move_frontier
 
     out = []
-    for p, pt in enumerate(halda_move_frontier(devices, model, plan, budget, kv_bits="4bit")):
+    for p, pt in enumerate(halda_move_frontier(devices, model, plan, budget, kv_bits="4bit", route=route)):
         if pt.plan is None:
             out.append(f"frontier {p}: infeasible")
         else:
@@ -189,13 +192,15 @@ def reload_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_se
     return out
 
 
-def failover_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_released: int) -> List[str]:
+def failover_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_released: int,
+                   route: str = "wave") -> List[str]:
     """--failover P: per device, the last point of its halda_failover_frontiers entry -- the best plan of the
     fleet without it that takes at most P layers off the survivors (kv_bits "4bit" like the solve above)."""
     from ..solver.change import halda_failover_frontiers
 
     out = []
-    for dev, fr in zip(devices, halda_failover_frontiers(devices, model, plan, max_released, kv_bits="4bit")):
+    for dev, fr in zip(devices, halda_failover_frontiers(devices, model, plan, max_released, kv_bits="4bit",
+                                                     route=route)):
         pt = fr[-1]
         if pt.plan is None:
             out.append(f"lose {dev.name}: infeasible")
@@ -221,12 +226,12 @@ def pick_indices(devices: List[DeviceProfile], picks: Sequence[str]) -> List[int
 
 
 def select_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: float, max_drop: Optional[int],
-                 keep: Sequence[int]) -> List[str]:
+                 keep: Sequence[int], route: str = "wave") -> List[str]:
     """--select-devices [D] [--keep ...]: one line per point of halda_subset_frontier, then the selection (the
     strict prefix-minimum over d), device names in the fleet's order (kv_bits "4bit" like the solve above)."""
     from ..solver.subsets import halda_subset_frontier, select_point
 
-    pts = halda_subset_frontier(devices, model, max_drop, keep or None, mip_gap=mip_gap, kv_bits="4bit")
+    pts = halda_subset_frontier(devices, model, max_drop, keep or None, mip_gap=mip_gap, kv_bits="4bit", route=route)
     out = []
     for d, pt in enumerate(pts):
         if pt.result is None:
@@ -257,14 +262,14 @@ def cpu_only_n_max(devices: List[DeviceProfile], picks: Sequence[str]) -> List[i
 
 
 def scale_in_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_drop: int, max_released: int,
-                   keep: List[int]) -> List[str]:
+                   keep: List[int], route: str = "wave") -> List[str]:
     """--scale-in D --failover P: one line per (d, p), d = 0 .. D devices handed back and at most p layers taken
     off the others -- the cells of halda_scale_in_frontier (kv_bits "4bit" like the solve above)."""
     from ..solver.scale import halda_scale_in_frontier
 
     out = []
     for d, row in enumerate(halda_scale_in_frontier(devices, model, plan, max_drop, max_released, keep=keep or None,
-                                                    kv_bits="4bit")):
+                                                    kv_bits="4bit", route=route)):
         for p, cell in enumerate(row):
             pt = cell.point
             if pt.plan is None:
@@ -323,6 +328,10 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--select-devices", nargs="?", type=int, const=-1, default=None, metavar="D",
                    help="After the solution, print the best sub-fleet with exactly d devices left out for every "
                         "d up to D (default: every subset), and the selection over them")
+    o.add_argument("--route", choices=("wave", "wide", "auto"), default="wave",
+                   help="With --select-devices, --scale-in, --failover or --move-frontier: the GPU route -- wave "
+                        "(default: fleets of up to 64 devices), wide (up to 256 devices) or auto (wave where its gate "
+                        "admits the call)")
     o.add_argument("--keep", nargs="+", metavar="NAME_OR_INDEX", default=[],
                    help="With --select-devices or --scale-in: devices (name or 0-based index) that may not be left "
                         "out")
@@ -435,7 +444,7 @@ def main(argv=None) -> int:
         try:
             lines = select_lines(devices, model, args.mip_gap,
                                  None if args.select_devices == -1 else args.select_devices,
-                                 pick_indices(devices, args.keep))
+                                 pick_indices(devices, args.keep), args.route)
         except (ValueError, IndexError) as e:
             print(f"error: --select-devices: {e}", file=sys.stderr)
             return 2
@@ -451,7 +460,7 @@ def main(argv=None) -> int:
                 print(within_line(devices, model, incumbent, args.max_move, args.max_move_n))
         if args.move_frontier is not None:
             try:
-                lines = frontier_lines(devices, model, incumbent, args.move_frontier)
+                lines = frontier_lines(devices, model, incumbent, args.move_frontier, args.route)
             except ValueError as e:
                 print(f"error: --move-frontier: {e}", file=sys.stderr)
                 return 2
@@ -468,7 +477,7 @@ def main(argv=None) -> int:
                 print(line)
         if args.failover is not None:
             try:
-                lines = failover_lines(devices, model, incumbent, args.failover)
+                lines = failover_lines(devices, model, incumbent, args.failover, args.route)
             except ValueError as e:
                 print(f"error: --failover: {e}", file=sys.stderr)
                 return 2
@@ -477,7 +486,7 @@ def main(argv=None) -> int:
         if args.scale_in is not None:
             try:
                 lines = scale_in_lines(devices, model, incumbent, args.scale_in, args.failover,
-                                       pick_indices(devices, args.keep))
+                                       pick_indices(devices, args.keep), args.route)
             except (ValueError, IndexError) as e:
                 print(f"error: --scale-in: {e}", file=sys.stderr)
                 return 2

@@ -58,6 +58,7 @@ bool in_host_block(const void *p, size_t bytes) {
 #include "halda_prims.hpp"
 #include "halda_solve.hpp"
 #include "halda_sweep.hpp"
+#include "halda_rank.hpp"
 
 // ------------------------------------------------------------------ host side
 thread_local std::string g_err;
@@ -3979,6 +3980,509 @@ int halda_solve_change_subsets_host(void *ctx, const halda_model *model, const h
     halda_change_subset_frontier r = stage::bind_change_subsets(base, R);
     rc = solve_change_subsets(ctx, model, &d, k, &dc, &r, Q, s);
     if (rc == HALDA_OK) rc = download(stage::change_subsets_copies(R, *fh), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- selection and scale-in beyond one wave
+// halda_solve_subsets_wide / halda_solve_change_subsets_wide (halda_rank.hpp): the candidates, groups and chunks
+// of the two entries above, a candidate carried as its rank. The host lays out one RankFleet per (d, fleet) and
+// uploads it with the table of binomials; no combo list exists. Everything lives in the context's grow-only
+// sel_buf, so the calls run after the previous user of the context's shared scratch on another stream
+// (order_after_previous).
+constexpr int64_t kRankLdsCap = 48 * 1024;  // the LDS rows of a launch: d (qmax + 1) entries
+
+// C(n, j), n <= 256, j <= 63, saturated at kRankSat, row j at j * kRankTableW.
+static const std::vector<uint32_t> &rank_table() {
+    static const std::vector<uint32_t> T = [] {
+        std::vector<uint32_t> t(size_t(kRankMaxD + 1) * kRankTableW, 0);
+        for (int n = 0; n <= kRankMaxM; ++n) t[n] = 1;
+        for (int j = 1; j <= kRankMaxD; ++j)
+            for (int n = j; n <= kRankMaxM; ++n)
+                t[size_t(j) * kRankTableW + n] = uint32_t(std::min<uint64_t>(
+                    kRankSat, uint64_t(t[size_t(j - 1) * kRankTableW + n - 1]) + t[size_t(j) * kRankTableW + n - 1]));
+        return t;
+    }();
+    return T;
+}
+
+// The gate's findings: per fleet its droppable devices, their count, the most it may drop within the range and its
+// size; the most droppable devices of a fleet; for scale-in, per d of the range the largest deficit and the longest
+// list of the fleets that admit it (-1 / 0: none).
+struct RankGate {
+    std::vector<std::array<uint64_t, 4>> drop;
+    std::vector<int> qs, Df, sizes;
+    int qmax = 0;
+    std::vector<int64_t> dtop;
+    std::vector<int> ltop;
+};
+
+// The shapes' part of the gate: sizes, keep bits, the d range d0 .. d1, the candidate count per fleet.
+static int rank_shape_gate(const std::string &who, int nf, const int64_t *sizes, const uint64_t *keep, int d0, int d1,
+                           RankGate &Q) {
+    if (d0 < 0 || d1 < d0 || d1 > kRankMaxD)
+        return fail(HALDA_E_ARG, who + ": needs 0 <= min_drop <= max_drop <= 63");
+    Q.drop.assign(size_t(nf), {});
+    Q.qs.assign(nf, 0);
+    Q.Df.assign(nf, 0);
+    Q.sizes.assign(nf, 0);
+    Q.qmax = 0;
+    bool any = false;
+    for (int f = 0; f < nf; ++f) {
+        if (sizes[f] < 1 || sizes[f] > kRankMaxM)
+            return fail(HALDA_E_ARG, who + ": fleet " + std::to_string(f) + " has " + std::to_string(sizes[f]) +
+                                         " devices (1..256)");
+        const int M = Q.sizes[f] = int(sizes[f]);
+        int q = 0;
+        for (int w = 0; w < 4; ++w) {
+            const int lo = 64 * w, bits = std::max(0, std::min(64, M - lo));
+            const uint64_t all = bits == 64 ? ~uint64_t(0) : (uint64_t(1) << bits) - 1, km = keep ? keep[4 * f + w] : 0;
+            if (km & ~all)
+                return fail(HALDA_E_ARG, who + ": keep_mask of fleet " + std::to_string(f) + " names a device past " +
+                                             std::to_string(M));
+            Q.drop[f][w] = all & ~km;
+            q += __builtin_popcountll(Q.drop[f][w]);
+        }
+        Q.qs[f] = q;
+        Q.qmax = std::max(Q.qmax, q);
+        Q.Df[f] = std::min({d1, q, M - 1});
+        int64_t cnt = 0;
+        for (int d = d0; d <= Q.Df[f]; ++d) {
+            any = true;
+            cnt += std::min<int64_t>(binom_sat(q, d), int64_t(HALDA_SUBSETS_MAX) + 1);
+            if (cnt > HALDA_SUBSETS_MAX)
+                return fail(HALDA_E_ARG, who + ": fleet " + std::to_string(f) + " has more than " +
+                                             std::to_string(HALDA_SUBSETS_MAX) + " candidates");
+        }
+    }
+    if (!any) return fail(HALDA_E_ARG, who + ": min_drop " + std::to_string(d0) + " is beyond min(q, M - 1) of every fleet");
+    return HALDA_OK;
+}
+
+// The records of one d (compact item and list prefixes over the fleets) and its launches: chunks cut at
+// candidate boundaries, each of at most `cap` units where a candidate of `len` listed devices costs
+// per_item + len * per_dev, and of at most max_n candidates; one candidate at the least. Returns the d's candidates.
+static int64_t rank_plan_d(const RankGate &Q, int d, int64_t cap, int64_t max_n, int64_t per_item, int64_t per_dev,
+                           RankFleet *R, std::vector<SubsetLaunch> &launches) {
+    const int nf = int(Q.sizes.size());
+    int64_t items = 0, devs = 0;
+    for (int f = 0; f < nf; ++f) {
+        RankFleet &r = R[f];
+        r = RankFleet{};
+        for (int w = 0; w < 4; ++w) r.drop[w] = Q.drop[f][w];
+        r.M = Q.sizes[f];
+        r.q = Q.qs[f];
+        r.cnt = d <= Q.Df[f] ? int32_t(binom_sat(Q.qs[f], d)) : 0;
+        r.item_off = items;
+        r.list_off = devs;
+        items += r.cnt;
+        devs += int64_t(r.cnt) * (Q.sizes[f] - d);
+    }
+    int f = 0;
+    int64_t a = 0;
+    while (a < items) {
+        SubsetLaunch L{d, false, a, 0, 0, 0, kRankMaxM, 0};
+        while (R[f].cnt == 0 || R[f].item_off + R[f].cnt <= a) ++f;
+        L.l0 = R[f].list_off + (a - R[f].item_off) * (Q.sizes[f] - d);
+        int64_t b = a, used = 0;
+        for (int g = f; g < nf && b < items; ++g) {
+            if (R[g].cnt == 0) continue;
+            const int len = Q.sizes[g] - d;
+            const int64_t left = R[g].item_off + R[g].cnt - b, each = per_item + len * per_dev;
+            int64_t take = std::min<int64_t>(left, (cap - used) / each);
+            if (take <= 0 && L.n == 0) take = 1;
+            take = std::min<int64_t>(take, max_n - L.n);
+            if (take <= 0) break;
+            L.n += take;
+            L.nd += take * len;
+            used += take * each;
+            L.lmin = std::min(L.lmin, len);
+            L.lmax = std::max(L.lmax, len);
+            b += take;
+            if (take < left) break;
+        }
+        launches.push_back(L);
+        a = b;
+    }
+    return items;
+}
+
+static RankArgs rank_args(const char *base, size_t o_rec, size_t o_tab, const SubsetLaunch &L, int row, int nf, int qmax) {
+    RankArgs U = {};
+    U.fl = reinterpret_cast<const RankFleet *>(base + o_rec) + size_t(row) * nf;
+    U.binom = reinterpret_cast<const uint32_t *>(base + o_tab);
+    U.i0 = L.i0;
+    U.l0 = L.l0;
+    U.n = int32_t(L.n);
+    U.n_fleets = nf;
+    U.d = L.d;
+    U.qmax = qmax;
+    return U;
+}
+
+// sizes: every fleet's device count (host)
+static int solve_subsets_wide(void *ctx, const halda_model *model, const halda_fleets *table, const int64_t *sizes,
+                              const halda_subsets_wide *sw, const int32_t *ks, int32_t n_k,
+                              halda_subset_frontier_wide *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const std::string who = "halda_solve_subsets_wide";
+    const int nf = table->n_fleets, D = sw->max_drop;
+    if (!frontier->status || !frontier->obj || !frontier->best_k || (D > 0 && !frontier->dropped))
+        return fail(HALDA_E_ARG, "halda_subset_frontier_wide: NULL");
+    if (D < 0 || D > kRankMaxD) return fail(HALDA_E_ARG, who + ": max_drop must be in 0..63");
+    if (n_k <= 0 || n_k > 1024) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    for (int j = 0; j < n_k; ++j)
+        if (ks[j] < 1 || (j && ks[j] <= ks[j - 1])) return fail(HALDA_E_ARG, "ks must be ascending, unique, > 0");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    RankGate Q;
+    if (const int rc = rank_shape_gate(who, nf, sizes, sw->keep_mask, 0, D, Q)) return rc;
+    if (D > *std::max_element(Q.Df.begin(), Q.Df.end()))
+        return fail(HALDA_E_ARG, who + ": max_drop " + std::to_string(D) + " is beyond min(q, M - 1) of every fleet");
+    if (4 * int64_t(D) * (Q.qmax + 1) > kRankLdsCap) return fail(HALDA_E_ARG, who + ": the rows of the binomial table exceed LDS");
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    std::vector<RankFleet> recs(size_t(D + 1) * nf);
+    std::vector<SubsetLaunch> launches;
+    for (int d = 0; d <= D; ++d)
+        rank_plan_d(Q, d, kSubsetsChunkDevices, INT32_MAX / 2, 0, 1, recs.data() + size_t(d) * nf, launches);
+    int64_t max_items = 0, max_dev = 0;
+    for (const SubsetLaunch &L : launches) {
+        max_items = std::max(max_items, L.n);
+        max_dev = std::max(max_dev, L.nd);
+    }
+    const std::vector<uint32_t> &tab = rank_table();
+    stage::Bump lay;
+    const size_t o_tab = lay.take(4 * tab.size()), o_rec = lay.take(sizeof(RankFleet) * recs.size()),
+                 o_obj = lay.take(8 * size_t(max_items)), o_bk = lay.take(4 * size_t(max_items)),
+                 o_par = lay.take(4 * size_t(max_items)), o_soff = lay.take(8 * size_t(max_items + 1)),
+                 o_sidx = lay.take(4 * size_t(max_dev)), o_w = lay.take(4 * size_t(max_dev)),
+                 o_n = lay.take(4 * size_t(max_dev));
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sel_buf, &c->sel_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
+    }
+    char *base = reinterpret_cast<char *>(c->sel_buf);
+    // (the table is static and the records are staged before the call returns)
+    HIP_TRY(hipMemcpyAsync(base + o_tab, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_rec, recs.data(), sizeof(RankFleet) * recs.size(), hipMemcpyHostToDevice, s));
+    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+    halda_fleet_result out = {};
+    out.best_k = i32(o_bk);
+    out.obj_value = reinterpret_cast<double *>(base + o_obj);
+    out.w = i32(o_w);
+    out.n = i32(o_n);
+    const ChangeSubsetsItems O{i32(o_par), reinterpret_cast<int64_t *>(base + o_soff), i32(o_sidx), nullptr, nullptr,
+                               nullptr};
+    const RankFrontier FR{frontier->status, frontier->obj, frontier->dropped, frontier->best_k};
+    c->fleet_timed = false;
+    for (const SubsetLaunch &L : launches) {
+        const RankArgs U = rank_args(base, o_rec, o_tab, L, L.d, nf, Q.qmax);
+        const size_t lds = 4 * size_t(L.d) * size_t(Q.qmax + 1);
+        hipLaunchKernelGGL(halda_rank_index_kernel, dim3(unsigned((L.n + 3) / 4)), dim3(256), lds, s, U, O);
+        HIP_TRY(hipGetLastError());
+        halda_subfleets I;
+        I.n_items = int32_t(L.n);
+        I.min_devices = L.lmin;
+        I.max_devices = L.lmax;
+        I.parent = O.parent;
+        I.sub_off = O.sub_off;
+        I.sub_idx = O.sub_idx;
+        // the sub-fleet entry's expansion route, unedited, on the items just written
+        const lrec::PathOverride expand(c->knob[lrec::kSubfleets], 1, /*keep_route=*/true);
+        const int rc = solve_subfleets(ctx, model, table, &I, ks, n_k, &out, s, L.nd);
+        if (rc != HALDA_OK) return rc;
+        hipLaunchKernelGGL(halda_rank_pick_kernel, dim3(unsigned(nf)), dim3(256), lds, s, U,
+                           static_cast<const double *>(out.obj_value), static_cast<const int32_t *>(out.best_k), FR,
+                           D + 1, D);
+        HIP_TRY(hipGetLastError());
+    }
+    return HALDA_OK;
+}
+
+// The fleets' sizes of a device table, clamped to 0 .. 257 (one read-back unless every fleet has one size).
+static int rank_sizes(Ctx *c, const halda_fleets *fleets, void *stream, std::vector<int64_t> &sizes,
+                      std::vector<int64_t> *off_out) {
+    const int64_t nf = fleets->n_fleets;
+    sizes.assign(size_t(nf), fleets->max_devices);
+    if (fleets->min_devices == fleets->max_devices && !off_out) return HALDA_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    std::vector<int64_t> off(size_t(nf) + 1);
+    HIP_TRY(hipMemcpyAsync(off.data(), fleets->dev_off, 8 * (nf + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t f = 0; f < nf; ++f) sizes[f] = std::max<int64_t>(0, std::min<int64_t>(off[f + 1] - off[f], 257));
+    if (off_out) *off_out = std::move(off);
+    return HALDA_OK;
+}
+
+int halda_solve_subsets_wide(void *ctx, const halda_model *model, const halda_fleets *fleets,
+                             const halda_subsets_wide *subsets, const int32_t *ks, int32_t n_k,
+                             halda_subset_frontier_wide *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fleets || !subsets || !ks || !frontier)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/ks/frontier");
+    if (fleets->n_fleets <= 0) return HALDA_OK;
+    if (!fleets->dev_off) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    std::vector<int64_t> sizes;
+    if (const int rc = rank_sizes(c, fleets, stream, sizes, nullptr)) return rc;
+    return solve_subsets_wide(ctx, model, fleets, sizes.data(), subsets, ks, n_k, frontier, stream);
+}
+
+int halda_solve_subsets_wide_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                                  const halda_subsets_wide *subsets, const int32_t *ks, int32_t n_k,
+                                  halda_subset_frontier_wide *fh) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !subsets || !ks || !fh)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/ks/frontier");
+    if (th->n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    const int D = subsets->max_drop;
+    if (D < 0 || D > kRankMaxD) return fail(HALDA_E_ARG, "halda_solve_subsets_wide_host: max_drop must be in 0..63");
+    if (!fh->status || !fh->obj || !fh->best_k || (D > 0 && !fh->dropped))
+        return fail(HALDA_E_ARG, "halda_subset_frontier_wide: NULL");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf];
+    if (th->dev_off[0] != 0 || nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    std::vector<int64_t> sizes(size_t(nf), 0);
+    for (int64_t f = 0; f < nf; ++f)
+        sizes[f] = std::max<int64_t>(0, std::min<int64_t>(th->dev_off[f + 1] - th->dev_off[f], 257));
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const stage::RankSubsetSlots R = stage::lay_rank_subsets(lay, size_t(nf) * size_t(D + 1), size_t(D));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    halda_subset_frontier_wide fd = stage::bind_rank_subsets(base, R);
+    rc = solve_subsets_wide(ctx, model, &d, sizes.data(), subsets, ks, n_k, &fd, s);
+    if (rc == HALDA_OK) rc = download(stage::rank_subsets_copies(R, *fh), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+int64_t halda_change_subsets_wide_launch_bytes(int32_t len, int32_t max_p, int32_t max_deficit, int32_t k,
+                                               int64_t n_items) {
+    if (len < 1 || max_p < 0 || max_deficit < 0 || k < 1 || n_items < 0) return -1;
+    if (len > 4096 || max_p > 4096 || max_deficit > 65536) return INT64_MAX;  // far outside the gate
+    const int64_t g = (change_wide_slice(len, max_p, max_deficit, k > 1).global + 255) & ~int64_t(255);
+    return kChangeSubsetsFixedBytes + n_items * (change_subsets_item_bytes(len, max_p + 1) + g);
+}
+
+// The gate of halda_solve_change_subsets_wide, from the shapes and w0 alone: no GPU work. off / w0_h: the table's
+// dev_off and the call's w0 in HOST memory.
+static int change_rank_gate(const halda_model *model, const halda_fleets *table, const int64_t *off,
+                            const int32_t *w0_h, int32_t k, const halda_change_subsets_wide *cs,
+                            const halda_change_subset_frontier_wide *fr, RankGate &Q) {
+    const std::string who = "halda_solve_change_subsets_wide";
+    const int nf = table->n_fleets, d0 = cs->min_drop, d1 = cs->max_drop, P = cs->max_p;
+    if (!fr->status || !fr->obj || !fr->loaded || !fr->released || !fr->w || !fr->n || (d1 > 0 && !fr->dropped))
+        return fail(HALDA_E_ARG, "halda_change_subset_frontier_wide has a NULL array");
+    if (!cs->w0) return fail(HALDA_E_ARG, "halda_change_subsets_wide.w0 is NULL");
+    if (P < 0 || P > kWideMaxP) return fail(HALDA_E_ARG, who + ": max_p must be in 0 .. " + std::to_string(kWideMaxP));
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    if (k < 1) return fail(HALDA_E_ARG, who + ": k must be >= 1");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    std::vector<int64_t> sizes(size_t(nf), 0);
+    for (int f = 0; f < nf; ++f) sizes[f] = std::max<int64_t>(0, std::min<int64_t>(off[f + 1] - off[f], 257));
+    if (const int rc = rank_shape_gate(who, nf, sizes.data(), cs->keep_mask, d0, d1, Q)) return rc;
+    if (4 * int64_t(d1) * (Q.qmax + 1) > kRankLdsCap) return fail(HALDA_E_ARG, who + ": the rows of the binomial table exceed LDS");
+    const int64_t W = model->L / k;
+    const int D1 = d1 - d0 + 1;
+    Q.dtop.assign(size_t(D1), -1);
+    Q.ltop.assign(size_t(D1), 0);
+    for (int f = 0; f < nf; ++f) {
+        const int M = Q.sizes[f];
+        int64_t sum = 0;
+        std::vector<int64_t> can;
+        for (int i = 0; i < M; ++i) {
+            const int64_t v = w0_h[off[f] + i];
+            if (v < 0) return fail(HALDA_E_ARG, who + ": fleet " + std::to_string(f) + ": every w0_i must be >= 0");
+            sum += v;
+            if ((Q.drop[f][i >> 6] >> (i & 63)) & 1) can.push_back(v);
+        }
+        if (sum > W)
+            return fail(HALDA_E_ARG, who + ": fleet " + std::to_string(f) + ": w0 sums to " + std::to_string(sum) +
+                                         ", above L / k = " + std::to_string(W));
+        std::sort(can.begin(), can.end(), std::greater<int64_t>());
+        int64_t Dd = W - sum;
+        for (int d = 0; d <= Q.Df[f]; ++d) {
+            if (d) Dd += can[d - 1];
+            if (d < d0) continue;
+            Q.dtop[d - d0] = std::max(Q.dtop[d - d0], Dd);
+            Q.ltop[d - d0] = std::max(Q.ltop[d - d0], M - d);
+        }
+    }
+    for (int j = 0; j < D1; ++j) {
+        if (Q.dtop[j] < 0) continue;
+        const std::string at = who + ": d = " + std::to_string(d0 + j);
+        if (2 * int64_t(P) + Q.dtop[j] > kChangeMaxE)
+            return fail(HALDA_E_ARG, at + ": 2 max_p + deficit = " + std::to_string(2 * int64_t(P) + Q.dtop[j]) +
+                                         " must be at most 254");
+        const BudgetWideSlice sl = change_wide_slice(Q.ltop[j], P, int32_t(Q.dtop[j]), k > 1);
+        if (const int rc = check_frontier_lds(sl.lds, at)) return rc;
+        if (sl.global > kGlobalTableBudget)
+            return fail(HALDA_E_ARG, at + ": the workspace slice of " + std::to_string(sl.global) +
+                                         " B exceeds the global-table budget");
+    }
+    return HALDA_OK;
+}
+
+// table, cs->w0 / w_min / w_max and fr hold device arrays; Q: the call's gate, passed
+static int solve_change_subsets_wide(void *ctx, const halda_model *model, const halda_fleets *table, int32_t k,
+                                     const halda_change_subsets_wide *cs, halda_change_subset_frontier_wide *fr,
+                                     const RankGate &Q, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int nf = table->n_fleets, d0 = cs->min_drop, d1 = cs->max_drop, P = cs->max_p;
+    const int D1 = d1 - d0 + 1, P1 = P + 1;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    const int64_t cap = (c->scale_chunk > 0 ? c->scale_chunk : kChangeSubsetsChunkBytes) - kChangeSubsetsFixedBytes;
+    std::vector<RankFleet> recs(size_t(D1) * nf);
+    std::vector<SubsetLaunch> launches;
+    for (int d = d0; d <= d1; ++d) {
+        int64_t g = 0;  // one workspace slice per candidate, at this d's gate shape
+        if (Q.dtop[d - d0] >= 0)
+            g = (change_wide_slice(Q.ltop[d - d0], P, int32_t(Q.dtop[d - d0]), k > 1).global + 255) & ~int64_t(255);
+        const int64_t items =
+            rank_plan_d(Q, d, cap, (INT32_MAX / 2) / P1, change_subsets_item_bytes(0, P1) + g,
+                        change_subsets_item_bytes(1, P1) - change_subsets_item_bytes(0, P1),
+                        recs.data() + size_t(d - d0) * nf, launches);
+        // no fleet admits this d: the pick alone, which writes the empty cells
+        if (items == 0) launches.push_back(SubsetLaunch{d, false, 0, 0, 0, 0, 0, 0});
+    }
+    int64_t max_items = 0, max_dev = 0;
+    for (const SubsetLaunch &L : launches) {
+        max_items = std::max(max_items, L.n);
+        max_dev = std::max(max_dev, L.nd);
+    }
+    const std::vector<uint32_t> &tab = rank_table();
+    stage::Bump lay;
+    const size_t pts = size_t(max_items) * P1, pl = size_t(max_dev) * P1;
+    const size_t o_tab = lay.take(4 * tab.size()), o_rec = lay.take(sizeof(RankFleet) * recs.size()),
+                 o_par = lay.take(4 * size_t(max_items)), o_soff = lay.take(8 * size_t(max_items + 1)),
+                 o_sidx = lay.take(4 * size_t(max_dev)), o_w0 = lay.take(4 * size_t(max_dev)),
+                 o_lo = lay.take(4 * size_t(max_dev)), o_hi = lay.take(4 * size_t(max_dev)), o_st = lay.take(4 * pts),
+                 o_obj = lay.take(8 * pts), o_ld = lay.take(4 * pts), o_rl = lay.take(4 * pts), o_w = lay.take(4 * pl),
+                 o_n = lay.take(4 * pl);
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sel_buf, &c->sel_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
+    }
+    char *base = reinterpret_cast<char *>(c->sel_buf);
+    HIP_TRY(hipMemcpyAsync(base + o_tab, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_rec, recs.data(), sizeof(RankFleet) * recs.size(), hipMemcpyHostToDevice, s));
+    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+    const ChangeSubsetsSrc G{table->dev_off, cs->w0, cs->w_min, cs->w_max};
+    const ChangeSubsetsItems O{i32(o_par), reinterpret_cast<int64_t *>(base + o_soff), i32(o_sidx), i32(o_w0), i32(o_lo),
+                               i32(o_hi)};
+    const ChangeRankGrid GR{fr->status, fr->obj, fr->dropped, fr->loaded, fr->released, fr->w, fr->n};
+    for (const SubsetLaunch &L : launches) {
+        const RankArgs U = rank_args(base, o_rec, o_tab, L, L.d - d0, nf, Q.qmax);
+        const size_t lds = 4 * size_t(L.d) * size_t(Q.qmax + 1);
+        if (L.n > 0) {
+            hipLaunchKernelGGL(halda_change_rank_index_kernel, dim3(unsigned((L.n + 3) / 4)), dim3(256), lds, s, U, G, O);
+            HIP_TRY(hipGetLastError());
+            // halda_solve_change_wide, unedited, on the items just written
+            halda_subfleets I;
+            I.n_items = int32_t(L.n);
+            I.min_devices = L.lmin;
+            I.max_devices = L.lmax;
+            I.parent = O.parent;
+            I.sub_off = O.sub_off;
+            I.sub_idx = O.sub_idx;
+            const halda_change ch{O.w0, cs->w_min ? O.w_min : nullptr, cs->w_max ? O.w_max : nullptr, P,
+                                  int32_t(Q.dtop[L.d - d0])};
+            halda_change_frontier cf;
+            cf.n_devices = L.nd;
+            cf.status = i32(o_st);
+            cf.obj = reinterpret_cast<double *>(base + o_obj);
+            cf.loaded = i32(o_ld);
+            cf.released = i32(o_rl);
+            cf.w = i32(o_w);
+            cf.n = i32(o_n);
+            const int rc = halda_solve_change_wide(ctx, model, table, &I, k, &ch, &cf, s);
+            if (rc != HALDA_OK) return rc;
+        }
+        const ChangeSubsetsChunk C{reinterpret_cast<const double *>(base + o_obj), i32(o_ld), i32(o_rl), i32(o_w), i32(o_n),
+                                   L.nd, P1, D1, d0};
+        hipLaunchKernelGGL(halda_change_rank_pick_kernel, dim3(unsigned(nf)), dim3(256), lds, s, U, C, GR, d1);
+        HIP_TRY(hipGetLastError());
+    }
+    return HALDA_OK;
+}
+
+int halda_solve_change_subsets_wide(void *ctx, const halda_model *model, const halda_fleets *fleets, int32_t k,
+                                    const halda_change_subsets_wide *subsets,
+                                    halda_change_subset_frontier_wide *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fleets || !subsets || !frontier)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/frontier");
+    const int64_t nf = fleets->n_fleets;
+    if (nf <= 0) return HALDA_OK;
+    if (!fleets->dev_off) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!subsets->w0) return fail(HALDA_E_ARG, "halda_change_subsets_wide.w0 is NULL");
+    // the gate reads dev_off and w0: both come back once
+    std::vector<int64_t> sizes, off;
+    if (const int rc = rank_sizes(c, fleets, stream, sizes, &off)) return rc;
+    if (off[0] != 0) return fail(HALDA_E_ARG, "halda_solve_change_subsets_wide: dev_off[0] must be 0");
+    for (int64_t f = 0; f < nf; ++f)
+        if (off[f + 1] - off[f] < 1 || off[f + 1] - off[f] > kRankMaxM)
+            return fail(HALDA_E_ARG, "halda_solve_change_subsets_wide: fleet " + std::to_string(f) + " has " +
+                                         std::to_string(off[f + 1] - off[f]) + " devices (1..256)");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    std::vector<int32_t> w0(static_cast<size_t>(off[nf]), 0);
+    HIP_TRY(hipMemcpyAsync(w0.data(), subsets->w0, 4 * size_t(off[nf]), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    RankGate Q;
+    const int rc = change_rank_gate(model, fleets, off.data(), w0.data(), k, subsets, frontier, Q);
+    if (rc != HALDA_OK) return rc;
+    return solve_change_subsets_wide(ctx, model, fleets, k, subsets, frontier, Q, stream);
+}
+
+int halda_solve_change_subsets_wide_host(void *ctx, const halda_model *model, const halda_fleets *th, int32_t k,
+                                         const halda_change_subsets_wide *subsets,
+                                         halda_change_subset_frontier_wide *fh) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !subsets || !fh) return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/frontier");
+    if (th->n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!subsets->w0) return fail(HALDA_E_ARG, "halda_change_subsets_wide.w0 is NULL");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf];
+    if (th->dev_off[0] != 0 || nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    for (int64_t f = 0; f < nf; ++f)
+        if (th->dev_off[f + 1] - th->dev_off[f] < 1 || th->dev_off[f + 1] - th->dev_off[f] > kRankMaxM)
+            return fail(HALDA_E_ARG, "halda_solve_change_subsets_wide_host: fleet " + std::to_string(f) + " has " +
+                                         std::to_string(th->dev_off[f + 1] - th->dev_off[f]) + " devices (1..256)");
+    RankGate Q;
+    int rc = change_rank_gate(model, th, th->dev_off, subsets->w0, k, subsets, fh, Q);
+    if (rc != HALDA_OK) return rc;
+    const size_t pts = size_t(nf) * size_t(subsets->max_drop - subsets->min_drop + 1) * size_t(subsets->max_p + 1);
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const stage::TripleLayout B = stage::lay_triple(lay, subsets->w0, subsets->w_min, subsets->w_max, nd);
+    const stage::ChangeRankSlots R = stage::lay_change_rank(lay, pts, size_t(subsets->max_drop));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    if (rc == HALDA_OK) rc = upload(base, B, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    halda_change_subsets_wide dc = *subsets;
+    dc.w0 = B.at(base, 0);
+    dc.w_min = B.at(base, 1);
+    dc.w_max = B.at(base, 2);
+    halda_change_subset_frontier_wide r = stage::bind_change_rank(base, R);
+    rc = solve_change_subsets_wide(ctx, model, &d, k, &dc, &r, Q, s);
+    if (rc == HALDA_OK) rc = download(stage::change_rank_copies(R, *fh), base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;

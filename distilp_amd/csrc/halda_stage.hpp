@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "halda.h"
+#include "halda_wide.h"
 
 namespace stage {
 
@@ -337,6 +338,80 @@ inline std::array<Copy, 7> change_subsets_copies(const ChangeSubsetSlots &s, con
              {h.released, s.released, 4 * s.pts},
              {h.w, s.w, 4 * 64 * s.pts},
              {h.n, s.n, 4 * 64 * s.pts}}};
+}
+
+// The frontiers of the rank routes (halda_wide.h) in a staging buffer. Selection: status, obj and best_k over
+// pts = n_fleets x (max_drop + 1) points and dcap = max_drop dropped indices per point. Scale-in: the four
+// per-cell arrays over pts = n_fleets x D1 x (max_p + 1) cells, dcap indices and two plans of 256 entries per cell.
+struct RankSubsetSlots {
+    size_t pts, dcap;
+    size_t status, obj, dropped, best_k;
+};
+
+inline RankSubsetSlots lay_rank_subsets(Bump &b, size_t pts, size_t dcap) {
+    RankSubsetSlots s{pts, dcap, 0, 0, 0, 0};
+    s.status = b.take(4 * pts);
+    s.obj = b.take(8 * pts);
+    s.dropped = b.take(4 * pts * dcap);
+    s.best_k = b.take(4 * pts);
+    return s;
+}
+
+inline halda_subset_frontier_wide bind_rank_subsets(char *base, const RankSubsetSlots &s) {
+    halda_subset_frontier_wide r;
+    r.status = reinterpret_cast<int32_t *>(base + s.status);
+    r.obj = reinterpret_cast<double *>(base + s.obj);
+    r.dropped = reinterpret_cast<int32_t *>(base + s.dropped);
+    r.best_k = reinterpret_cast<int32_t *>(base + s.best_k);
+    return r;
+}
+
+inline std::array<Copy, 4> rank_subsets_copies(const RankSubsetSlots &s, const halda_subset_frontier_wide &h) {
+    return {{{h.status, s.status, 4 * s.pts},
+             {h.obj, s.obj, 8 * s.pts},
+             {h.dropped, s.dropped, 4 * s.pts * s.dcap},
+             {h.best_k, s.best_k, 4 * s.pts}}};
+}
+
+constexpr size_t kRankPlan = 256;  // plan entries per cell of halda_change_subset_frontier_wide
+
+struct ChangeRankSlots {
+    size_t pts, dcap;
+    size_t status, obj, dropped, loaded, released, w, n;
+};
+
+inline ChangeRankSlots lay_change_rank(Bump &b, size_t pts, size_t dcap) {
+    ChangeRankSlots s{pts, dcap, 0, 0, 0, 0, 0, 0, 0};
+    s.status = b.take(4 * pts);
+    s.obj = b.take(8 * pts);
+    s.dropped = b.take(4 * pts * dcap);
+    s.loaded = b.take(4 * pts);
+    s.released = b.take(4 * pts);
+    s.w = b.take(4 * kRankPlan * pts);
+    s.n = b.take(4 * kRankPlan * pts);
+    return s;
+}
+
+inline halda_change_subset_frontier_wide bind_change_rank(char *base, const ChangeRankSlots &s) {
+    halda_change_subset_frontier_wide r;
+    r.status = reinterpret_cast<int32_t *>(base + s.status);
+    r.obj = reinterpret_cast<double *>(base + s.obj);
+    r.dropped = reinterpret_cast<int32_t *>(base + s.dropped);
+    r.loaded = reinterpret_cast<int32_t *>(base + s.loaded);
+    r.released = reinterpret_cast<int32_t *>(base + s.released);
+    r.w = reinterpret_cast<int32_t *>(base + s.w);
+    r.n = reinterpret_cast<int32_t *>(base + s.n);
+    return r;
+}
+
+inline std::array<Copy, 7> change_rank_copies(const ChangeRankSlots &s, const halda_change_subset_frontier_wide &h) {
+    return {{{h.status, s.status, 4 * s.pts},
+             {h.obj, s.obj, 8 * s.pts},
+             {h.dropped, s.dropped, 4 * s.pts * s.dcap},
+             {h.loaded, s.loaded, 4 * s.pts},
+             {h.released, s.released, 4 * s.pts},
+             {h.w, s.w, 4 * kRankPlan * s.pts},
+             {h.n, s.n, 4 * kRankPlan * s.pts}}};
 }
 
 }  // namespace stage

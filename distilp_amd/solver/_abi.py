@@ -205,12 +205,38 @@ BOXES_PROTOTYPES = {
     **_knob("boxes"),
 }
 
-# include/halda_wide.h, the companion header of the move budget's and the change frontier's workgroup routes: it
-# adds no struct (the entries take halda.h's); its prototypes are applied by load_library with the others
+# include/halda_wide.h, the companion header of the workgroup routes of the move budget and the change frontier
+# (which take halda.h's structs) and of the rank routes of selection and scale-in / scale-out, whose structs
+# follow; its prototypes are applied by load_library with the others
+class HaldaSubsetsWideC(ctypes.Structure):
+    _fields_ = [("max_drop", c_int32)] + _ptrs("keep_mask")
+
+
+class HaldaSubsetFrontierWideC(ctypes.Structure):
+    _fields_ = _ptrs("status", "obj", "dropped", "best_k")
+
+
+class HaldaChangeSubsetsWideC(ctypes.Structure):
+    _fields_ = (_ptrs("w0", "w_min", "w_max") + [("min_drop", c_int32), ("max_drop", c_int32), ("max_p", c_int32)]
+                + _ptrs("keep_mask"))
+
+
+class HaldaChangeSubsetFrontierWideC(ctypes.Structure):
+    _fields_ = _ptrs("status", "obj", "dropped", "loaded", "released", "w", "n")
+
+
+WIDE_STRUCTS = {HaldaSubsetsWideC: "halda_subsets_wide", HaldaSubsetFrontierWideC: "halda_subset_frontier_wide",
+                HaldaChangeSubsetsWideC: "halda_change_subsets_wide",
+                HaldaChangeSubsetFrontierWideC: "halda_change_subset_frontier_wide"}
 WIDE_PROTOTYPES = {
     **_with_host("halda_solve_fleets_budget_wide", *_table, c_int32, POINTER(HaldaBudgetC), POINTER(HaldaFrontierC)),
     "halda_budget_wide_bytes": (c_int, [c_int32] * 3 + [POINTER(c_int64)] * 2),
     **_with_host("halda_solve_change_wide", *_table, _items, c_int32, POINTER(HaldaChangeC),
                  POINTER(HaldaChangeFrontierC)),
     "halda_change_wide_bytes": (c_int, [c_int32] * 4 + [POINTER(c_int64)] * 2),
+    **_with_host("halda_solve_subsets_wide", *_table, POINTER(HaldaSubsetsWideC), *_ks,
+                 POINTER(HaldaSubsetFrontierWideC)),
+    **_with_host("halda_solve_change_subsets_wide", *_table, c_int32, POINTER(HaldaChangeSubsetsWideC),
+                 POINTER(HaldaChangeSubsetFrontierWideC)),
+    "halda_change_subsets_wide_launch_bytes": (c_int64, [c_int32] * 4 + [c_int64]),
 }

@@ -19,6 +19,12 @@ list (its point p, which the budget also admits).
 Scale-out is the same call on `devs + pool`: every device of `devs` is kept, the pool holds nothing (w0 = 0), and
 "add a of the q pool devices" is d = q - a. The tie order is therefore the DROPPED-list order: among equal
 objectives the candidate whose left-out pool indices come first wins, so for a = 1 a tie goes to the LAST pool device.
+
+route="wide" (libhalda `halda_solve_change_subsets_wide`) serves fleets (fleet plus pool) of up to 256 devices: the
+candidates are carried as ranks and unranked on the GPU (csrc/halda_rank.hpp), every (d, chunk) runs the workgroup
+change kernel, the gate per d is `change.check_gate_wide`'s, and the follow-up is `halda_change_frontiers(...,
+route="wide")`. route="wave" is the default and is the call described above, untouched; route="auto" takes it
+wherever its gate admits the call.
 """
 
 from __future__ import annotations
@@ -32,17 +38,20 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._abi import HaldaChangeSubsetFrontierC, HaldaChangeSubsetsC
+from ._abi import (HaldaChangeSubsetFrontierC, HaldaChangeSubsetFrontierWideC, HaldaChangeSubsetsC,
+                   HaldaChangeSubsetsWideC)
 from ._libhalda import STATUS_OPTIMAL, get_context, ptr
 from .bounds import INT32_MAX
 from .budget import check_incumbent
-from .change import ChangePoint, check_gate, check_released, halda_change_frontiers
+from .change import (ChangePoint, change_wide_bytes, check_gate, check_gate_wide, check_released,
+                     halda_change_frontiers)
 from .coefficients import HALDAResult
 from .fleets import _host_struct, fleet_table, model_struct
 from .fleets import _bind as _bind_scale  # noqa: F401 -- the identity, for callers from before load_library bound all
 from .lower import kv_bits_to_factor
 from .plans import Incumbent
-from .subsets import MAX_DEVICES, SUBSETS_MAX, candidate_lists, droppable
+from .subsets import (MAX_DEVICES, ROUTES, SUBSETS_MAX, WIDE_MAX_DEVICES, candidate_lists, droppable, droppable_wide,
+                      keep_words)
 
 CHUNK_BYTES = 256 << 20  # csrc/halda.hip kChangeSubsetsChunkBytes: the scratch cap of one launch
 FIXED_BYTES = 4096       # kChangeSubsetsFixedBytes
@@ -63,6 +72,13 @@ def launch_bytes(length: int, max_p: int, n_items: int) -> int:
     two planes per listed device; 4096 fixed."""
     P1 = int(max_p) + 1
     return FIXED_BYTES + int(n_items) * (12 + 20 * P1 + int(length) * (16 + 8 * P1))
+
+
+def launch_bytes_wide(length: int, max_p: int, deficit: int, k: int, n_items: int) -> int:
+    """halda_change_subsets_wide_launch_bytes: launch_bytes plus, per candidate, one workspace slice of the
+    workgroup change kernel (change_wide_bytes' second figure, 256-byte aligned)."""
+    g = (change_wide_bytes(length, max_p, deficit, k)[1] + 255) & ~255
+    return launch_bytes(length, max_p, n_items) + int(n_items) * g
 
 
 def max_deficit(w0: Sequence[int], slots: Sequence[int], d: int, W: int) -> int:
@@ -94,15 +110,18 @@ def check_drops(min_drop, max_drop) -> Tuple[int, int]:
 
 
 def check_scale_gate(sizes: Sequence[int], slots: Sequence[Sequence[int]], w0s: Sequence[Sequence[int]], W: int, k: int,
-                     min_drop: int, max_drop: int, max_p: int) -> List[Optional[int]]:
+                     min_drop: int, max_drop: int, max_p: int, wide: bool = False) -> List[Optional[int]]:
     """The call's gate, from the shapes and w0 alone (what halda_solve_change_subsets refuses with HALDA_E_ARG):
-    ValueError outside it. Returns, per d of the range, that d's largest deficit (None: no fleet admits d)."""
+    ValueError outside it. Returns, per d of the range, that d's largest deficit (None: no fleet admits d).
+    wide: the gate of halda_solve_change_subsets_wide -- fleets of up to 256 devices and, per d,
+    change.check_gate_wide in place of check_gate."""
+    top_m = WIDE_MAX_DEVICES if wide else MAX_DEVICES
     tops: List[Optional[int]] = [None] * (max_drop - min_drop + 1)
-    lens = [[0, MAX_DEVICES] for _ in tops]
+    lens = [[0, top_m] for _ in tops]
     any_d = False
     for f, (M, sl, w0) in enumerate(zip(sizes, slots, w0s)):
-        if M < 1 or M > MAX_DEVICES:
-            raise ValueError(f"scale-in needs fleets of 1 .. {MAX_DEVICES} devices, fleet {f} has {M}")
+        if M < 1 or M > top_m:
+            raise ValueError(f"scale-in needs fleets of 1 .. {top_m} devices, fleet {f} has {M}")
         if len(w0) != M:
             raise ValueError(f"fleet {f}: w0 of {len(w0)} entries for {M} devices")
         if any(int(v) < 0 for v in w0):
@@ -125,15 +144,32 @@ def check_scale_gate(sizes: Sequence[int], slots: Sequence[Sequence[int]], w0s: 
         raise ValueError(f"min_drop = {min_drop} is beyond min(droppable devices, M - 1) of every fleet")
     for j, top in enumerate(tops):
         if top is not None:
-            check_gate(lens[j][0], lens[j][1], max_p, top, k)
+            (check_gate_wide if wide else check_gate)(lens[j][0], lens[j][1], max_p, top, k)
     return tops
+
+
+def pick_scale_route(route: str, sizes, slots, w0s, W: int, k: int, min_drop: int, max_drop: int, max_p: int) -> str:
+    """"wave" or "wide" for a call of these shapes, its gate checked (ValueError outside it). "auto": the wave
+    route wherever check_scale_gate admits the call, the wide route elsewhere."""
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
+    if route == "auto":
+        try:
+            check_scale_gate(sizes, slots, w0s, W, k, min_drop, max_drop, max_p)
+            return "wave"
+        except ValueError:
+            route = "wide"
+    check_scale_gate(sizes, slots, w0s, W, k, min_drop, max_drop, max_p, wide=route == "wide")
+    return route
 
 
 # ---------------------------------------------------------------- the C call
 @dataclass
 class ScaleSolve:
     """halda_solve_change_subsets' grid: status / obj / dropped_mask / loaded / released [n_fleets, D1, P + 1] and
-    w / n [n_fleets, D1, P + 1, 64] by PARENT device. obj is the GPU-formed objective."""
+    w / n [n_fleets, D1, P + 1, 64] by PARENT device. obj is the GPU-formed objective. From
+    halda_solve_change_subsets_wide: dropped_mask is None, `dropped` holds the winners' device indices, int32
+    [n_fleets, D1, P + 1, max_drop], -1 padded, and w / n are 256 wide."""
 
     status: np.ndarray
     obj: np.ndarray
@@ -146,19 +182,35 @@ class ScaleSolve:
     min_drop: int
     max_drop: int
     max_p: int
+    dropped: Optional[np.ndarray] = None
+
+    def gone(self, f: int, j: int, p: int) -> List[int]:
+        """The devices cell (f, j, p) drops, ascending, from either form."""
+        if self.dropped is not None:
+            return [int(i) for i in self.dropped[f, j, p] if i >= 0]
+        m = int(self.dropped_mask[f, j, p])
+        return [i for i in range(64) if (m >> i) & 1]
 
 
 def solve_change_subsets_table(table, model: ModelProfile, k: int, w0: np.ndarray, min_drop: int, max_drop: int,
                                max_p: int, kv_factor: float, keep_masks: Optional[np.ndarray] = None,
                                w_min: Optional[np.ndarray] = None, w_max: Optional[np.ndarray] = None,
-                               device: int = 0) -> ScaleSolve:
+                               device: int = 0, route: str = "wave") -> ScaleSolve:
     """One halda_solve_change_subsets_host call on a packed table; w0 / w_min / w_max are int32 arrays per device
     of the table (laid out by dev_off), keep_masks uint64 per fleet or None. RuntimeError (HALDA_E_ARG) for a
-    call outside the gate."""
+    call outside the gate. route "wide": one halda_solve_change_subsets_wide_host call, keep_masks [n_fleets, 4]
+    (subsets.keep_words); "auto": the wave call where every fleet has at most 64 devices and max_p <= 63."""
     ctx = get_context(device)
     nf, D1, P1 = table.n_fleets, int(max_drop) - int(min_drop) + 1, int(max_p) + 1
     if D1 < 1 or P1 < 1:
         raise ValueError("needs min_drop <= max_drop and max_p >= 0")
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
+    if route == "auto":
+        route = "wave" if int(np.diff(table.dev_off[:nf + 1]).max()) <= MAX_DEVICES and max_p <= 63 else "wide"
+    if route == "wide":
+        return _solve_change_subsets_wide(ctx, table, model, k, w0, min_drop, max_drop, max_p, kv_factor, keep_masks,
+                                          w_min, w_max)
     out = ScaleSolve(status=np.zeros((nf, D1, P1), np.int32), obj=np.zeros((nf, D1, P1)),
                      dropped_mask=np.zeros((nf, D1, P1), np.uint64), loaded=np.zeros((nf, D1, P1), np.int32),
                      released=np.zeros((nf, D1, P1), np.int32), w=np.zeros((nf, D1, P1, 64), np.int32),
@@ -177,6 +229,33 @@ def solve_change_subsets_table(table, model: ModelProfile, k: int, w0: np.ndarra
     m = model_struct(model, kv_factor)
     ctx.call("halda_solve_change_subsets_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k), ctypes.byref(sub),
              ctypes.byref(fr))
+    del hold
+    return out
+
+
+def _solve_change_subsets_wide(ctx, table, model, k, w0, min_drop, max_drop, max_p, kv_factor, keep_masks, w_min,
+                               w_max) -> ScaleSolve:
+    nf, D1, P1, dc = table.n_fleets, int(max_drop) - int(min_drop) + 1, int(max_p) + 1, int(max_drop)
+    cell = (nf, D1, P1)
+    out = ScaleSolve(status=np.zeros(cell, np.int32), obj=np.zeros(cell), dropped_mask=None,
+                     loaded=np.zeros(cell, np.int32), released=np.zeros(cell, np.int32),
+                     w=np.zeros(cell + (WIDE_MAX_DEVICES,), np.int32), n=np.zeros(cell + (WIDE_MAX_DEVICES,), np.int32),
+                     k=int(k), min_drop=int(min_drop), max_drop=int(max_drop), max_p=int(max_p),
+                     dropped=np.full(cell + (dc,), -1, np.int32))
+    fs, hold = _host_struct(table)
+    nd = int(table.dev_off[nf])
+    arrs = [None if a is None else np.ascontiguousarray(a, np.int32) for a in (w0, w_min, w_max)]
+    for a in arrs:
+        if a is not None and len(a) != nd:
+            raise ValueError(f"an array of {len(a)} entries for a table of {nd} devices")
+    km = None if keep_masks is None else np.ascontiguousarray(keep_masks, np.uint64).reshape(nf, 4)
+    sub = HaldaChangeSubsetsWideC(ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), int(min_drop), int(max_drop), int(max_p),
+                                  ptr(km))
+    fr = HaldaChangeSubsetFrontierWideC(ptr(out.status), ptr(out.obj), ptr(out.dropped) if dc else None,
+                                        ptr(out.loaded), ptr(out.released), ptr(out.w), ptr(out.n))
+    m = model_struct(model, kv_factor)
+    ctx.call("halda_solve_change_subsets_wide_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), int(k),
+             ctypes.byref(sub), ctypes.byref(fr))
     del hold
     return out
 
@@ -236,16 +315,18 @@ def _mask(idx: Iterable[int]) -> int:
     return sum(1 << int(i) for i in idx)
 
 
-def _scale_core(fleets, model, ks, w0s, slots, min_drop, max_drop, P, kv_bits, los, his, device, solve_lists):
+def _scale_core(fleets, model, ks, w0s, slots, min_drop, max_drop, P, kv_bits, los, his, device, solve_lists,
+                route="wave"):
     """Per fleet [d - min_drop][p] of (dropped, kept, ChangePoint) or None. ks / w0s / slots / los / his per fleet
-    (los / his: per-device bound lists or None)."""
+    (los / his: per-device bound lists or None). route: per incumbent k, pick_scale_route's."""
     L = int(model.L)
     sizes = [len(d) for d in fleets]
     D1 = max_drop - min_drop + 1
+    routes = {}
     for k in sorted(set(ks)):
         grp = [f for f in range(len(fleets)) if ks[f] == k]
-        check_scale_gate([sizes[f] for f in grp], [slots[f] for f in grp], [w0s[f] for f in grp], L // k, k, min_drop,
-                         max_drop, P)
+        routes[k] = pick_scale_route(route, [sizes[f] for f in grp], [slots[f] for f in grp], [w0s[f] for f in grp],
+                                     L // k, k, min_drop, max_drop, P)
     out: List[Optional[list]] = [None] * len(fleets)
     if solve_lists is not None:
         for f in range(len(fleets)):
@@ -264,9 +345,12 @@ def _scale_core(fleets, model, ks, w0s, slots, min_drop, max_drop, P, kv_bits, l
         bound = lambda bs, fill: None if all(bs[f] is None for f in grp) else np.concatenate(  # noqa: E731
             [np.full(sizes[f], fill, np.int32) if bs[f] is None else
              np.clip(np.asarray(bs[f], np.int64), -INT32_MAX, INT32_MAX).astype(np.int32) for f in grp])
-        masks = np.asarray([_mask(i for i in range(sizes[f]) if i not in set(slots[f])) for f in grp], np.uint64)
+        if routes[k] == "wide":
+            masks = np.asarray([keep_words(sizes[f], slots[f]) for f in grp], np.uint64)
+        else:
+            masks = np.asarray([_mask(i for i in range(sizes[f]) if i not in set(slots[f])) for f in grp], np.uint64)
         res = solve_change_subsets_table(table, model, k, w0, min_drop, max_drop, P, kv_factor, masks, bound(los, 0),
-                                         bound(his, INT32_MAX), device)
+                                         bound(his, INT32_MAX), device, routes[k])
         rows = {f: [] for f in grp}
         for j in range(D1):
             # the distinct winning lists of this d, one follow-up call
@@ -277,8 +361,8 @@ def _scale_core(fleets, model, ks, w0s, slots, min_drop, max_drop, P, kv_bits, l
                     if int(res.status[g, j, p]) != STATUS_OPTIMAL:
                         pk.append(None)
                         continue
-                    m = int(res.dropped_mask[g, j, p])
-                    kept = tuple(i for i in range(sizes[f]) if not (m >> i) & 1)
+                    gone = set(res.gone(g, j, p))
+                    kept = tuple(i for i in range(sizes[f]) if i not in gone)
                     pk.append(kept)
                     if (g, kept) not in at:
                         at[(g, kept)] = len(items)
@@ -289,7 +373,8 @@ def _scale_core(fleets, model, ks, w0s, slots, min_drop, max_drop, P, kv_bits, l
                 kv_bits, None if all(los[f] is None for f in grp) else
                 [None if los[grp[g]] is None else [los[grp[g]][i] for i in s] for g, s in items],
                 None if all(his[f] is None for f in grp) else
-                [None if his[grp[g]] is None else [his[grp[g]][i] for i in s] for g, s in items], device) if items else []
+                [None if his[grp[g]] is None else [his[grp[g]][i] for i in s] for g, s in items], device,
+                routes[k]) if items else []
             for g, f in enumerate(grp):
                 of = {s: frs[i] for (gg, s), i in at.items() if gg == g}
                 rows[f].append((_row(P, picks[f], of.__getitem__), of))
@@ -332,7 +417,8 @@ def halda_scale_in_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], mod
                                   keep: Optional[Sequence[Optional[Iterable[int]]]] = None, min_drop: int = 0,
                                   kv_bits: str = "8bit", w_min: Optional[Sequence[Optional[Sequence[int]]]] = None,
                                   w_max: Optional[Sequence[Optional[Sequence[int]]]] = None, device: int = 0,
-                                  _solve_lists: Optional[SolveLists] = None) -> List[List[List[ScalePoint]]]:
+                                  _solve_lists: Optional[SolveLists] = None,
+                                  route: str = "wave") -> List[List[List[ScalePoint]]]:
     """Per fleet its scale-in frontier [d - min_drop][p], d = min_drop .. max_drop, p = 0 .. max_released: the best
     way to hand back exactly d of the droppable devices (all but `keep[f]`) while taking at most p layers off the
     others, which hold `incumbents[f]`'s layers. One packed table and one C call per distinct incumbent k (fleets of
@@ -341,8 +427,12 @@ def halda_scale_in_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], mod
     ValueError / IndexError before any GPU work for a bad incumbent, budget, keep index, d range, more than 2^20
     candidates in a fleet, more than 64 devices, or a d whose list length and largest deficit fall outside the
     change kernel's gate. `_solve_lists(f, lists)` (tests): the change frontiers (max_released + 1 ChangePoints
-    each) of index lists of fleet f, in place of the GPU."""
+    each) of index lists of fleet f, in place of the GPU. route: "wave" (default) is this call; "wide" takes fleets
+    of up to 256 devices and max_released up to 127 under change.check_gate_wide per d (a keep index out of range is
+    a ValueError there); "auto" is "wave" wherever its gate admits the call."""
     fleets = [list(d) for d in fleets]
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
     P = check_released(max_released)
     min_drop, max_drop = check_drops(min_drop, max_drop)
     if len(incumbents) != len(fleets):
@@ -354,15 +444,17 @@ def halda_scale_in_frontier_batch(fleets: Sequence[Sequence[DeviceProfile]], mod
     for f, devs in enumerate(fleets):
         if not devs:
             raise IndexError("list index out of range")  # the reference's kappa on an empty fleet
-        if len(devs) > MAX_DEVICES:
-            raise ValueError(f"scale-in needs fleets of at most {MAX_DEVICES} devices, fleet {f} has {len(devs)}")
+        if len(devs) > (MAX_DEVICES if route == "wave" else WIDE_MAX_DEVICES):
+            raise ValueError(f"scale-in needs fleets of at most {MAX_DEVICES if route == 'wave' else WIDE_MAX_DEVICES} "
+                             f"devices, fleet {f} has {len(devs)}")
         k, w, _ = check_incumbent(incumbents[f], len(devs), int(model.L))
         ks.append(k)
         w0s.append(w)
-        slots.append(droppable(len(devs), None if keep is None else keep[f]))
+        slots.append((droppable if route == "wave" else droppable_wide)(len(devs), None if keep is None else keep[f]))
     if not fleets:
         return []
-    rows = _scale_core(fleets, model, ks, w0s, slots, min_drop, max_drop, P, kv_bits, los, his, device, _solve_lists)
+    rows = _scale_core(fleets, model, ks, w0s, slots, min_drop, max_drop, P, kv_bits, los, his, device, _solve_lists,
+                       route)
     return [_points(len(fleets[f]), rows[f]) for f in range(len(fleets))]
 
 
@@ -370,27 +462,28 @@ def halda_scale_in_frontier(devs: Sequence[DeviceProfile], model: ModelProfile, 
                             max_released: int, keep: Optional[Iterable[int]] = None, min_drop: int = 0,
                             kv_bits: str = "8bit", w_min: Optional[Sequence[int]] = None,
                             w_max: Optional[Sequence[int]] = None, device: int = 0,
-                            _solve_lists: Optional[Callable[[List[List[int]]], List[List[ChangePoint]]]] = None
-                            ) -> List[List[ScalePoint]]:
+                            _solve_lists: Optional[Callable[[List[List[int]]], List[List[ChangePoint]]]] = None,
+                            route: str = "wave") -> List[List[ScalePoint]]:
     """The scale-in frontier of one fleet, [d - min_drop][p] of ScalePoint: cell (d, p) names the d devices to
     hand back and the plan to move to when at most p layers may be taken off the others. Its `point` equals
     `halda_failover_frontiers(devs, model, incumbent, max_released, lost=[dropped])[0][p]` bit for bit; row 0 is
-    `halda_change_frontier` of the whole fleet. Errors as halda_scale_in_frontier_batch."""
+    `halda_change_frontier` of the whole fleet. Errors and route as halda_scale_in_frontier_batch (on route "wide"
+    the equality holds with `halda_failover_frontiers(..., route="wide")`)."""
     hook = None if _solve_lists is None else (lambda f, ls: _solve_lists(ls))
     return halda_scale_in_frontier_batch([list(devs)], model, [incumbent], max_drop, max_released,
                                          None if keep is None else [keep], min_drop, kv_bits,
                                          None if w_min is None else [w_min], None if w_max is None else [w_max], device,
-                                         hook)[0]
+                                         hook, route)[0]
 
 
 def halda_scale_in(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent, drop: int,
                    max_released: int, keep: Optional[Iterable[int]] = None, kv_bits: str = "8bit", device: int = 0,
-                   _solve_lists=None) -> Tuple[List[int], HALDAResult]:
+                   _solve_lists=None, route: str = "wave") -> Tuple[List[int], HALDAResult]:
     """Which `drop` devices to hand back, and the plan to move to (indexed within the kept devices), when at most
     max_released layers may be taken off the others: the last point of row `drop`. RuntimeError when there is
     none."""
     pt = halda_scale_in_frontier(devs, model, incumbent, drop, max_released, keep, drop, kv_bits, device=device,
-                                 _solve_lists=_solve_lists)[0][-1]
+                                 _solve_lists=_solve_lists, route=route)[0][-1]
     if pt.point.plan is None:
         raise RuntimeError("No feasible MILP found within the released-layer budget for any choice of devices.")
     return list(pt.dropped), pt.point.plan
@@ -398,26 +491,30 @@ def halda_scale_in(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent
 
 def halda_scale_out_frontier(devs: Sequence[DeviceProfile], pool: Sequence[DeviceProfile], model: ModelProfile,
                              incumbent: Incumbent, max_add: int, max_released: int, kv_bits: str = "8bit",
-                             device: int = 0, _solve_lists=None) -> List[List[ScalePoint]]:
+                             device: int = 0, _solve_lists=None, route: str = "wave") -> List[List[ScalePoint]]:
     """The scale-out frontier [a][p], a = 0 .. max_add: the best a devices of `pool` to add to the running fleet when
     at most p layers may be taken off its devices; `added` holds their pool indices, `kept` / `dropped` index
     devs + pool, and the plan is indexed within `kept`. A joiner holds nothing and must receive a layer, so with a
     full incumbent point 0 of every row a >= 1 has no plan. Row 1 is the per-p best of `halda_join_frontiers`.
     Ties: the candidate order is that of the LEFT-OUT pool indices (ascending lists, lexicographic), so among equal
-    objectives the later pool devices are added. ValueError for max_add outside 0 .. len(pool)."""
+    objectives the later pool devices are added. ValueError for max_add outside 0 .. len(pool). route: as in
+    halda_scale_in_frontier_batch, on fleet plus pool."""
     devs, pool = list(devs), list(pool)
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
     M, q = len(devs), len(pool)
     P = check_released(max_released)
     if isinstance(max_add, bool) or not isinstance(max_add, numbers.Integral) or not 0 <= max_add <= q:
         raise ValueError(f"max_add = {max_add!r} must be an integer in 0 .. {q} (the pool)")
     if not devs:
         raise IndexError("list index out of range")
-    if M + q > MAX_DEVICES:
-        raise ValueError(f"scale-out needs at most {MAX_DEVICES} devices in fleet and pool, got {M + q}")
+    if M + q > (MAX_DEVICES if route == "wave" else WIDE_MAX_DEVICES):
+        raise ValueError(f"scale-out needs at most {MAX_DEVICES if route == 'wave' else WIDE_MAX_DEVICES} devices in "
+                         f"fleet and pool, got {M + q}")
     k, w, _ = check_incumbent(incumbent, M, int(model.L))
     min_drop, max_drop = check_drops(q - int(max_add), q)
     hook = None if _solve_lists is None else (lambda f, ls: _solve_lists(ls))
     rows = _scale_core([devs + pool], model, [k], [list(w) + [0] * q], [list(range(M, M + q))], min_drop, max_drop, P,
-                       kv_bits, [None], [None], device, hook)[0]
+                       kv_bits, [None], [None], device, hook, route)[0]
     pts = _points(M + q, rows, lambda kept: [i - M for i in kept if i >= M])
     return pts[::-1]  # row a is d = q - a

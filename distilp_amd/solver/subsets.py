@@ -13,6 +13,11 @@ crosses PCIe. The device orders candidates by the objective it forms; each winne
 built by ONE follow-up `halda_solve_subfleets` call over the winning lists, so a point's `result` is that
 entry's, bit for bit, and the selection takes the running minimum over d again on these host-formed
 obj_values (as budget.py does for its frontier).
+
+route="wide" (libhalda `halda_solve_subsets_wide`) serves fleets of up to 256 devices: a candidate is carried as
+its RANK in the enumeration order and unranked on the GPU (csrc/halda_rank.hpp; `unrank` below is its host
+mirror), the winners come back as dropped-index lists, and nothing else changes. route="wave" is the default and
+is the call described above, untouched; route="auto" takes it wherever every fleet has at most 64 devices.
 """
 
 from __future__ import annotations
@@ -27,7 +32,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._abi import HaldaSubsetFrontierC, HaldaSubsetsC
+from ._abi import HaldaSubsetFrontierC, HaldaSubsetFrontierWideC, HaldaSubsetsC, HaldaSubsetsWideC
 from ._libhalda import STATUS_OPTIMAL, get_context, last_route, ptr, set_path
 from .coefficients import HALDAResult
 from .fleets import DEV_HEAD, _host_struct, fleet_table, model_struct
@@ -38,6 +43,10 @@ from .subfleets import check_item_heads, halda_solve_subfleets
 
 MAX_DEVICES = 64  # a candidate is a 64-bit mask; lane = device in the fused kernel
 SUBSETS_MAX = 1 << 20  # include/halda.h HALDA_SUBSETS_MAX: candidates per fleet
+ROUTES = ("wave", "wide", "auto")
+WIDE_MAX_DEVICES = 256  # route "wide": a candidate is a rank; one wave covers the parent devices in four passes
+MAX_DROP = 63
+RANK_SAT = (1 << 20) + 1  # csrc/halda_rank.hpp kRankSat: the binomial table's "more than 2^20"
 
 SolveLists = Callable[[List[List[int]]], List[Optional[HALDAResult]]]
 
@@ -63,6 +72,76 @@ def combo_list(q: int, d: int) -> List[int]:
     """The combos of d of q slots in enumeration order (bit r: slot r dropped): ascending index lists,
     lexicographic -- the list the library uploads per (q, d)."""
     return [sum(1 << r for r in c) for c in itertools.combinations(range(q), d)]
+
+
+def binom_table(n_max: int = WIDE_MAX_DEVICES, j_max: int = MAX_DROP) -> List[List[int]]:
+    """T[j][n] = min(C(n, j), 2^20 + 1): the table the rank kernels read (csrc/halda.hip rank_table), built by
+    Pascal's rule with a saturating sum."""
+    T = [[1] * (n_max + 1)] + [[0] * (n_max + 1) for _ in range(j_max)]
+    for j in range(1, j_max + 1):
+        for n in range(j, n_max + 1):
+            T[j][n] = min(RANK_SAT, T[j - 1][n - 1] + T[j][n - 1])
+    return T
+
+
+_BINOM: List[List[int]] = []
+
+
+def unrank(q: int, d: int, r: int) -> List[int]:
+    """The r-th of the C(q, d) ascending d-lists of q slots in lexicographic order: the host mirror of
+    csrc/halda_rank.hpp rank_unrank, step for step -- per position the largest c whose "lists that begin below
+    start + c", C(qp, dd) - C(qp - c, dd), is at most the rank left, found 64 candidates c at a time on the
+    saturated table. ValueError outside 0 <= d <= min(q, 63), q <= 256, 0 <= r < C(q, d) <= 2^20."""
+    if not 0 <= d <= min(q, MAX_DROP) or q > WIDE_MAX_DEVICES or math.comb(q, d) > SUBSETS_MAX or not 0 <= r < math.comb(q, d):
+        raise ValueError(f"unrank: (q, d, r) = ({q}, {d}, {r}) is outside the rank scheme")
+    if not _BINOM:
+        _BINOM.extend(binom_table())
+    out, start = [], 0
+    for j in range(d):
+        dd, qp = d - j, q - start
+        row, top, c = _BINOM[dd], _BINOM[dd][qp], 0
+        for step in range(4):
+            t = sum(1 for lane in range(64)
+                    if step * 64 + lane + 1 <= qp - dd and top - row[qp - (step * 64 + lane + 1)] <= r)
+            c += t
+            if t < 64:
+                break
+        r -= top - row[qp - c]
+        out.append(start + c)
+        start += c + 1
+    return out
+
+
+def keep_words(M: int, slots: Sequence[int]) -> List[int]:
+    """halda_subsets_wide.keep_mask of one fleet: four 64-bit words, bit i & 63 of word i >> 6 set for every
+    device that is NOT in `slots`."""
+    can, w = set(slots), [0, 0, 0, 0]
+    for i in range(M):
+        if i not in can:
+            w[i >> 6] |= 1 << (i & 63)
+    return w
+
+
+def pick_route(route: str, sizes: Sequence[int]) -> str:
+    """"wave" or "wide" for fleets of these sizes. "auto": the wave route where every fleet has at most 64
+    devices. ValueError for an unknown route or, on the wide route, a fleet of more than 256 devices."""
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
+    if route == "auto":
+        route = "wave" if all(m <= MAX_DEVICES for m in sizes) else "wide"
+    if route == "wide":
+        for f, m in enumerate(sizes):
+            if m > WIDE_MAX_DEVICES:
+                raise ValueError(f"route 'wide' needs fleets of at most {WIDE_MAX_DEVICES} devices, fleet {f} has {m}")
+    return route
+
+
+def droppable_wide(M: int, keep: Optional[Iterable[int]]) -> List[int]:
+    """`droppable` under the wide route's gate: a keep index at or past M is a ValueError."""
+    try:
+        return droppable(M, keep)
+    except IndexError as e:
+        raise ValueError(str(e)) from None
 
 
 def droppable(M: int, keep: Optional[Iterable[int]]) -> List[int]:
@@ -153,12 +232,26 @@ def _frontier_by_lists(M: int, slots: Sequence[int], D: int, solve: SolveLists) 
 
 
 def solve_subsets_table(table, model: ModelProfile, pos: List[int], kv_factor: float, max_drop: int,
-                        keep_masks: Optional[np.ndarray], device: int = 0):
+                        keep_masks: Optional[np.ndarray], device: int = 0, route: str = "wave"):
     """One halda_solve_subsets_host call on a packed table: (status, obj, dropped_mask, best_k), each
-    [n_fleets, max_drop + 1]. obj is the GPU-formed objective."""
+    [n_fleets, max_drop + 1]. obj is the GPU-formed objective. On route "wide" (and on "auto" with a fleet of
+    more than 64 devices) one halda_solve_subsets_wide_host call: keep_masks is [n_fleets, 4] (keep_words), and
+    in place of the masks comes `dropped`, int32 [n_fleets, max_drop + 1, max_drop], -1 padded."""
     ctx = get_context(device)
     nf, P1 = table.n_fleets, int(max_drop) + 1
     status, obj = np.zeros((nf, P1), np.int32), np.zeros((nf, P1))
+    if pick_route(route, np.diff(np.asarray(table.dev_off[:nf + 1], np.int64)).tolist()) == "wide":
+        gone, best_k = np.full((nf, P1, int(max_drop)), -1, np.int32), np.zeros((nf, P1), np.int32)
+        fs, hold = _host_struct(table)
+        km = None if keep_masks is None else np.ascontiguousarray(keep_masks, np.uint64).reshape(nf, 4)
+        sub = HaldaSubsetsWideC(int(max_drop), ptr(km))
+        fr = HaldaSubsetFrontierWideC(ptr(status), ptr(obj), ptr(gone) if max_drop else None, ptr(best_k))
+        karr = np.asarray(pos, np.int32)
+        m = model_struct(model, kv_factor)
+        ctx.call("halda_solve_subsets_wide_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(sub),
+                 karr.ctypes.data, len(pos), ctypes.byref(fr))
+        del hold
+        return status, obj, gone, best_k
     mask, best_k = np.zeros((nf, P1), np.uint64), np.zeros((nf, P1), np.int32)
     fs, hold = _host_struct(table)
     km = None if keep_masks is None else np.ascontiguousarray(keep_masks, np.uint64)
@@ -182,6 +275,7 @@ def halda_subset_frontier_batch(
     kv_bits: str = "8bit",
     device: int = 0,
     _solve_lists: Optional[Callable[[int, List[List[int]]], List[Optional[HALDAResult]]]] = None,
+    route: str = "wave",
 ) -> List[List[SubsetPoint]]:
     """Per fleet its selection frontier: one SubsetPoint per d = 0 .. min(max_drop, q, M - 1), q the fleet's
     droppable devices (max_drop None: every d the fleet admits -- with nothing kept, every non-empty
@@ -190,22 +284,25 @@ def halda_subset_frontier_batch(
     or None. ValueError before any GPU work for a fleet of more than 64 devices, a max_drop that is negative,
     non-integer or beyond what every fleet admits, or more than 2^20 candidates in a fleet; IndexError for a
     keep index out of range or an empty fleet. `_solve_lists(f, lists)` (tests): the solve of index lists of
-    fleet f, in place of the GPU."""
+    fleet f, in place of the GPU. route: "wave" (default) is this call; "wide" takes fleets of up to 256 devices
+    (ValueError beyond, for max_drop above 63 and for a keep index out of range); "auto" is "wave" where every
+    fleet has at most 64 devices and "wide" elsewhere."""
     fleets = [list(d) for d in fleets]
+    route = pick_route(route, [len(d) for d in fleets])
     if keep is not None and len(keep) != len(fleets):
         raise ValueError(f"{len(keep)} keep entries for {len(fleets)} fleets")
     slots, lim = [], []
     for f, devs in enumerate(fleets):
         if not devs:
             raise IndexError("list index out of range")  # the reference's kappa on an empty fleet
-        if len(devs) > MAX_DEVICES:
+        if route == "wave" and len(devs) > MAX_DEVICES:
             raise ValueError(f"exact selection needs fleets of at most {MAX_DEVICES} devices, fleet {f} has "
                              f"{len(devs)}")
-        slots.append(droppable(len(devs), None if keep is None else keep[f]))
+        slots.append((droppable if route == "wave" else droppable_wide)(len(devs), None if keep is None else keep[f]))
         lim.append(min(len(slots[f]), len(devs) - 1))
     if not fleets:
         return []
-    D = check_max_drop(max_drop, max(lim))
+    D = check_max_drop(max_drop, max(lim) if route == "wave" else min(max(lim), MAX_DROP))
     Df = [min(D, x) for x in lim]
     for f in range(len(fleets)):
         check_count(len(slots[f]), Df[f])
@@ -228,16 +325,22 @@ def halda_subset_frontier_batch(
     check_item_heads(fleets, table, np.asarray(par, np.int64), np.asarray(hd, np.int64), model)
     masks = None
     if keep is not None and any(len(slots[f]) < len(fleets[f]) for f in range(len(fleets))):
-        masks = np.asarray([sum(1 << i for i in range(len(fleets[f])) if i not in set(slots[f]))
-                            for f in range(len(fleets))], np.uint64)
-    status, _, dmask, _ = solve_subsets_table(table, model, pos, kv_factor, D, masks, device)
+        if route == "wide":
+            masks = np.asarray([keep_words(len(fleets[f]), slots[f]) for f in range(len(fleets))], np.uint64)
+        else:
+            masks = np.asarray([sum(1 << i for i in range(len(fleets[f])) if i not in set(slots[f]))
+                                for f in range(len(fleets))], np.uint64)
+    status, _, dmask, _ = solve_subsets_table(table, model, pos, kv_factor, D, masks, device, route)
     items, at = [], {}
     for f in range(len(fleets)):
         for d in range(Df[f] + 1):
             if int(status[f, d]) == STATUS_OPTIMAL:
-                m = int(dmask[f, d])
+                if route == "wide":
+                    gone = {int(i) for i in dmask[f, d, :d]}
+                else:
+                    gone = {i for i in range(len(fleets[f])) if (int(dmask[f, d]) >> i) & 1}
                 at[(f, d)] = len(items)
-                items.append((f, [i for i in range(len(fleets[f])) if not (m >> i) & 1]))
+                items.append((f, [i for i in range(len(fleets[f])) if i not in gone]))
     res = halda_solve_subfleets(fleets, model, items, k_candidates, mip_gap, kv_bits, device) if items else []
     out = []
     for f in range(len(fleets)):
@@ -265,20 +368,21 @@ def halda_subset_frontier(
     kv_bits: str = "8bit",
     device: int = 0,
     _solve_lists: Optional[SolveLists] = None,
+    route: str = "wave",
 ) -> List[SubsetPoint]:
     """The selection frontier of one fleet: point d is the best sub-fleet with exactly d of the droppable
     devices (all but `keep`) left out, d = 0 .. max_drop (None: min(q, M - 1), every candidate there is).
     Point 0 is the full fleet. Each point's `result` equals
     `halda_solve_subfleets([devs], model, [(0, kept)])[0]` bit for bit. ValueError for max_drop beyond
-    min(q, M - 1); otherwise the errors of halda_subset_frontier_batch."""
+    min(q, M - 1); otherwise the errors of halda_subset_frontier_batch. route: as there."""
     devs = list(devs)
     if not devs:
         raise IndexError("list index out of range")
-    if len(devs) <= MAX_DEVICES:
+    if pick_route(route, [len(devs)]) == "wave" and len(devs) <= MAX_DEVICES:
         check_max_drop(max_drop, min(len(droppable(len(devs), keep)), len(devs) - 1))
     hook = None if _solve_lists is None else (lambda f, ls: _solve_lists(ls))
     return halda_subset_frontier_batch([devs], model, max_drop, None if keep is None else [keep], k_candidates,
-                                       mip_gap, kv_bits, device, hook)[0]
+                                       mip_gap, kv_bits, device, hook, route)[0]
 
 
 def select_point(points: Sequence[SubsetPoint]) -> Optional[SubsetPoint]:
@@ -301,13 +405,14 @@ def halda_select_devices_exact(
     kv_bits: str = "8bit",
     device: int = 0,
     _solve_lists: Optional[SolveLists] = None,
+    route: str = "wave",
 ) -> Tuple[List[int], HALDAResult]:
     """Which devices to use: the optimum over every sub-fleet that leaves out at most max_drop of the
     droppable devices (None: over all of them), not halda_select_devices' greedy walk. Returns (kept
     indices into `devs`, ascending; the HALDAResult of that sub-fleet, indexed within the kept list).
-    RuntimeError when no sub-fleet is feasible."""
+    RuntimeError when no sub-fleet is feasible. route: as in halda_subset_frontier_batch."""
     best = select_point(halda_subset_frontier(devs, model, max_drop, keep, k_candidates, mip_gap, kv_bits, device,
-                                              _solve_lists))
+                                              _solve_lists, route))
     if best is None:
         raise RuntimeError("No feasible MILP found for any k this round.")
     return list(best.kept), best.result
