@@ -18,6 +18,8 @@ from distilp_amd.solver import (ScalePoint, halda_scale_in, halda_scale_in_front
                                 halda_scale_in_frontier_batch, halda_scale_out_frontier)
 from distilp_amd.solver import (ReloadPoint, halda_reload_frontier, halda_solve_boxes,  # noqa: F401
                                 halda_solve_boxes_batch, reload_caps)
+from distilp_amd.solver import (PartitionPoint, halda_partition, halda_partition_frontier,  # noqa: F401
+                                halda_partition_frontier_batch)
 
 __all__ = ["halda_solve", "HALDAResult"]
 

@@ -245,6 +245,22 @@ def select_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: flo
     return out
 
 
+def replica_lines(devices: List[DeviceProfile], model: ModelProfile, replicas: int, criterion: str) -> List[str]:
+    """--replicas R [--criterion max|sum]: one line per point of halda_partition_frontier, r = 1 .. R, device
+    names in the fleet's order (kv_bits "4bit" like the solve above)."""
+    from ..solver.partition import halda_partition_frontier
+
+    out = []
+    for r, pt in enumerate(halda_partition_frontier(devices, model, replicas, criterion, kv_bits="4bit"), 1):
+        if pt.groups is None:
+            out.append(f"replicas {r}: infeasible")
+            continue
+        names = ", ".join("[" + ", ".join(devices[i].name for i in g) + "]" for g in pt.groups)
+        out.append(f"replicas {r}: value={pt.value:.6f}, groups=[{names}], k=[{', '.join(str(x.k) for x in pt.results)}], "
+                   f"obj=[{', '.join(f'{x.obj_value:.6f}' for x in pt.results)}]")
+    return out
+
+
 def cpu_only_n_max(devices: List[DeviceProfile], picks: Sequence[str]) -> List[int]:
     """--cpu-only NAME_OR_INDEX ...: the n_max list with 0 on the picked devices (a device's name, else its
     0-based index in the fleet's order) and "no bound" elsewhere. ValueError for a pick that names no device."""
@@ -335,6 +351,12 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--keep", nargs="+", metavar="NAME_OR_INDEX", default=[],
                    help="With --select-devices or --scale-in: devices (name or 0-based index) that may not be left "
                         "out")
+    o.add_argument("--replicas", type=int, metavar="R",
+                   help="After the solution, print for every r up to R the best split of the fleet into r independent "
+                        "pipelines (at most 20 devices, R up to 8)")
+    o.add_argument("--criterion", choices=("max", "sum"), default="max",
+                   help="With --replicas: price a split by its slowest pipeline (max, default; the other pipelines are "
+                        "only held at or below it) or by the sum of its pipelines' objectives (sum)")
     g.add_argument("--cpu-only", nargs="+", metavar="NAME_OR_INDEX",
                    help="Solve without using the GPU of these devices (their name or 0-based index)")
     return p
@@ -447,6 +469,14 @@ def main(argv=None) -> int:
                                  pick_indices(devices, args.keep), args.route)
         except (ValueError, IndexError) as e:
             print(f"error: --select-devices: {e}", file=sys.stderr)
+            return 2
+        for line in lines:
+            print(line)
+    if args.replicas is not None:
+        try:
+            lines = replica_lines(devices, model, args.replicas, args.criterion)
+        except ValueError as e:
+            print(f"error: --replicas: {e}", file=sys.stderr)
             return 2
         for line in lines:
             print(line)

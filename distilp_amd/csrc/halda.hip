@@ -36,6 +36,7 @@
 #include "halda.h"
 #include "halda_boxes.h"
 #include "halda_wide.h"
+#include "halda_partition.h"
 #include "halda_launch.hpp"
 #include "halda_stage.hpp"
 
@@ -4814,6 +4815,265 @@ int halda_solve_batch(void *ctx, const halda_batch *in_h, halda_result *out_h) {
     HIP_TRY(down(out_h->dual_bound, o_db, 8 * n));
     HIP_TRY(down(out_h->gap, o_gap, 8 * n));
     HIP_TRY(down(out_h->nodes, o_nodes, 8 * n));
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- exact replica partitioning
+// halda_solve_partition (include/halda_partition.h): per fleet and r = 1 .. max_groups the best split of the
+// fleet into r groups, each priced by halda_solve_subfleets' value of its devices in ascending order.
+// Every mask of every fleet is an item (mask m of fleet f: item item_off[f] + m - 1). The items are solved in
+// launches of at most kSubsetsChunkDevices listed devices, cut at item boundaries: halda_partition_index_kernel
+// writes the launch's lists, the sub-fleet entry's expansion route, unedited, solves them straight into the
+// val and k planes. Then one halda_partition_level_kernel launch per level r = 2 .. R (the launch boundary is
+// the dependency between levels) and one halda_partition_trace_kernel. The planes -- val, k, two ping-pong
+// best planes, R - 1 arg planes -- and the launches' item arrays live in the context's grow-only sel_buf, so the
+// call runs after the previous user of the context's shared scratch on another stream (order_after_previous).
+constexpr int kPartMaxDevices = 20;  // 2^20 = HALDA_SUBSETS_MAX masks per fleet
+constexpr int kPartMaxGroups = 8;
+constexpr int kPartLdsDevices = 13;  // both planes of 2^13 doubles fill 128 KiB of LDS
+
+int64_t halda_partition_bytes(int32_t max_devices, int32_t max_groups) {
+    if (max_devices < 1 || max_devices > kPartMaxDevices || max_groups < 1 || max_groups > kPartMaxGroups) return -1;
+    // per mask: val (8), k (4), two best planes (16) and an arg entry (4) per level r = 2 .. max_groups
+    return (int64_t(1) << max_devices) * (28 + 4 * int64_t(max_groups - 1));
+}
+
+// The fewest and the most devices of the masks a .. b (1 <= a <= b).
+static void part_len_range(uint32_t a, uint32_t b, int *lmin, int *lmax) {
+    uint32_t x = b;
+    while ((x & (x - 1)) >= a && (x & (x - 1)) != 0) x &= x - 1;
+    *lmin = std::min(*lmin, __builtin_popcount(x));
+    x = a;
+    while ((x | (x + 1)) <= b) x |= x + 1;
+    *lmax = std::max(*lmax, __builtin_popcount(x));
+}
+
+extern "C++" {
+template <int Op, bool Lds>
+static int launch_partition_level(const PartArgs &P, const PartLevel &L, unsigned grid, size_t lds, hipStream_t s) {
+    if (lds) HIP_TRY(Ctx::ensure_lds(reinterpret_cast<const void *>(halda_partition_level_kernel<Op, Lds>), int64_t(lds)));
+    hipLaunchKernelGGL((halda_partition_level_kernel<Op, Lds>), dim3(grid), dim3(256), lds, s, P, L);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+}  // extern "C++"
+
+// sizes: every fleet's device count (host), capped at kPartMaxDevices + 1
+static int solve_partition(void *ctx, const halda_model *model, const halda_fleets *table, const int32_t *sizes,
+                           const halda_partition *partition, const int32_t *ks, int32_t n_k,
+                           halda_partition_frontier *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int nf = table->n_fleets, R = partition->max_groups, crit = partition->criterion;
+    if (!frontier->status || !frontier->value || !frontier->group_mask || !frontier->group_obj || !frontier->group_k)
+        return fail(HALDA_E_ARG, "halda_partition_frontier: NULL");
+    // the gate, from the shapes alone
+    if (R < 1 || R > kPartMaxGroups) return fail(HALDA_E_ARG, "halda_partition: max_groups must be in 1..8");
+    if (crit != kPartMax && crit != kPartSum) return fail(HALDA_E_ARG, "halda_partition: criterion must be 0 (max) or 1 (sum)");
+    if (n_k <= 0 || n_k > 1024) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    for (int j = 0; j < n_k; ++j)
+        if (ks[j] < 1 || (j && ks[j] <= ks[j - 1])) return fail(HALDA_E_ARG, "ks must be ascending, unique, > 0");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    std::vector<PartFleet> fl(static_cast<size_t>(nf));
+    int Mmax = 0;
+    int64_t items = 0, listed = 0;
+    for (int f = 0; f < nf; ++f) {
+        const int M = sizes[f];
+        if (M < 1 || M > kPartMaxDevices)
+            return fail(HALDA_E_ARG, "halda_solve_partition: fleet " + std::to_string(f) + " has " + std::to_string(M) +
+                                         " devices (1..20)");
+        fl[f] = PartFleet{items, listed, M, 0};
+        items += (int64_t(1) << M) - 1;
+        listed += int64_t(M) << (M - 1);
+        Mmax = std::max(Mmax, M);
+    }
+    if (R > Mmax)
+        return fail(HALDA_E_ARG, "halda_partition: max_groups " + std::to_string(R) + " is beyond the " +
+                                     std::to_string(Mmax) + " devices of the largest fleet");
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    // the listed devices in front of item g (g = items: all of them)
+    auto listed_before = [&](int64_t g) -> int64_t {
+        if (g >= items) return listed;
+        int f = nf - 1;
+        while (fl[f].item_off > g) --f;
+        return fl[f].list_off + part_bits_below(uint32_t(g - fl[f].item_off) + 1);
+    };
+    // launches of at most kSubsetsChunkDevices listed devices (an item lists at most 20: every launch has items)
+    struct Chunk { int64_t a, n, l0, nd; int lmin, lmax; };
+    std::vector<Chunk> chunks;
+    int64_t max_items = 0, max_dev = 0;
+    for (int64_t a = 0; a < items;) {
+        const int64_t l0 = listed_before(a);
+        int64_t lo = a + 1, hi = items;  // the largest b with listed_before(b) - l0 within the cap
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo + 1) / 2;
+            if (listed_before(mid) - l0 <= kSubsetsChunkDevices) lo = mid;
+            else hi = mid - 1;
+        }
+        Chunk ch{a, lo - a, l0, listed_before(lo) - l0, 64, 0};
+        for (int f = 0; f < nf; ++f) {
+            const int64_t b0 = std::max(a, fl[f].item_off), b1 = std::min(lo, fl[f].item_off + (int64_t(1) << fl[f].M) - 1);
+            if (b0 < b1) part_len_range(uint32_t(b0 - fl[f].item_off) + 1, uint32_t(b1 - fl[f].item_off), &ch.lmin, &ch.lmax);
+        }
+        chunks.push_back(ch);
+        max_items = std::max(max_items, ch.n);
+        max_dev = std::max(max_dev, ch.nd);
+        a = lo;
+    }
+    stage::Bump lay;
+    const size_t n8 = 8 * size_t(items), n4 = 4 * size_t(items);
+    const size_t o_fl = lay.take(sizeof(PartFleet) * fl.size()), o_val = lay.take(n8), o_k = lay.take(n4),
+                 o_b0 = lay.take(n8), o_b1 = lay.take(n8), o_arg = lay.take(n4 * size_t(R - 1)),
+                 o_pt = lay.take(8 * size_t(nf) * R), o_par = lay.take(4 * size_t(max_items)),
+                 o_soff = lay.take(8 * size_t(max_items + 1)), o_sidx = lay.take(4 * size_t(max_dev)),
+                 o_w = lay.take(4 * size_t(max_dev)), o_n = lay.take(4 * size_t(max_dev));
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sel_buf, &c->sel_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
+    }
+    char *base = reinterpret_cast<char *>(c->sel_buf);
+    // (pageable source: the copy is staged before the call returns)
+    HIP_TRY(hipMemcpyAsync(base + o_fl, fl.data(), sizeof(PartFleet) * fl.size(), hipMemcpyHostToDevice, s));
+    PartArgs P;
+    P.fl = reinterpret_cast<const PartFleet *>(base + o_fl);
+    P.n_items = items;
+    P.n_fleets = nf;
+    P.R = R;
+    double *val = reinterpret_cast<double *>(base + o_val);
+    int32_t *kpl = reinterpret_cast<int32_t *>(base + o_k);
+    c->fleet_timed = false;
+    for (const Chunk &ch : chunks) {
+        halda_subfleets I;
+        I.n_items = int32_t(ch.n);
+        I.min_devices = ch.lmin;
+        I.max_devices = ch.lmax;
+        I.parent = reinterpret_cast<const int32_t *>(base + o_par);
+        I.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
+        I.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
+        hipLaunchKernelGGL(halda_partition_index_kernel, dim3(unsigned((ch.n + 3) / 4)), dim3(256), 0, s, P, ch.a, ch.l0,
+                           int32_t(ch.n), reinterpret_cast<int32_t *>(base + o_par),
+                           reinterpret_cast<int64_t *>(base + o_soff), reinterpret_cast<int32_t *>(base + o_sidx));
+        HIP_TRY(hipGetLastError());
+        halda_fleet_result out = {};
+        out.best_k = kpl + ch.a;
+        out.obj_value = val + ch.a;
+        out.w = reinterpret_cast<int32_t *>(base + o_w);
+        out.n = reinterpret_cast<int32_t *>(base + o_n);
+        // the sub-fleet entry's expansion route, unedited, on the items just written
+        const lrec::PathOverride expand(c->knob[lrec::kSubfleets], 1, /*keep_route=*/true);
+        const int rc = solve_subfleets(ctx, model, table, &I, ks, n_k, &out, s, ch.nd);
+        if (rc != HALDA_OK) return rc;
+    }
+    // the levels: LDS source where both planes of the largest fleet fit 128 KiB
+    const bool lds = Mmax <= kPartLdsDevices;
+    const size_t lds_bytes = lds ? size_t(16) << Mmax : 0;
+    double *bp[2] = {reinterpret_cast<double *>(base + o_b0), reinterpret_cast<double *>(base + o_b1)};
+    for (int r = 2; r <= R; ++r) {
+        PartLevel L;
+        L.val = val;
+        L.prev = r == 2 ? val : bp[(r - 1) & 1];
+        L.best = bp[r & 1];
+        L.arg = reinterpret_cast<uint32_t *>(base + o_arg) + size_t(r - 2) * size_t(items);
+        L.pt = reinterpret_cast<double *>(base + o_pt);
+        L.r = r;
+        L.full_only = r == R;
+        // LDS: workgroups per fleet -- about 32 masks a workgroup, no more workgroups than fill the device
+        L.bpf = L.full_only ? 1 : int(std::max<int64_t>(1, std::min<int64_t>((int64_t(1) << Mmax) / 32, c->cus / nf)));
+        const int64_t waves = L.full_only ? nf : items;
+        const unsigned grid = lds ? unsigned(nf) * unsigned(L.bpf)
+                                  : unsigned(std::min<int64_t>((waves + 3) / 4, int64_t(c->cus) * 8));
+        int rc;
+        if (crit == kPartSum)
+            rc = lds ? launch_partition_level<kPartSum, true>(P, L, grid, lds_bytes, s)
+                     : launch_partition_level<kPartSum, false>(P, L, grid, 0, s);
+        else
+            rc = lds ? launch_partition_level<kPartMax, true>(P, L, grid, lds_bytes, s)
+                     : launch_partition_level<kPartMax, false>(P, L, grid, 0, s);
+        if (rc != HALDA_OK) return rc;
+    }
+    const PartFrontier O{frontier->status, frontier->value, frontier->group_mask, frontier->group_obj, frontier->group_k};
+    hipLaunchKernelGGL(halda_partition_trace_kernel, dim3(unsigned((nf * R + 255) / 256)), dim3(256), 0, s, P,
+                       static_cast<const double *>(val), static_cast<const int32_t *>(kpl),
+                       reinterpret_cast<const uint32_t *>(base + o_arg), reinterpret_cast<const double *>(base + o_pt), O);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+static int check_partition_args(const void *ctx, const halda_model *model, const halda_fleets *fleets,
+                                const halda_partition *partition, const int32_t *ks,
+                                const halda_partition_frontier *frontier) {
+    if (!ctx || !model || !fleets || !partition || !ks || !frontier)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/partition/ks/frontier");
+    return HALDA_OK;
+}
+
+int halda_solve_partition(void *ctx, const halda_model *model, const halda_fleets *fleets,
+                          const halda_partition *partition, const int32_t *ks, int32_t n_k,
+                          halda_partition_frontier *frontier, void *stream) {
+    if (const int rc = check_partition_args(ctx, model, fleets, partition, ks, frontier)) return rc;
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int64_t nf = fleets->n_fleets;
+    if (nf <= 0) return HALDA_OK;
+    if (!fleets->dev_off) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    const auto cap = [](int64_t m) { return int32_t(std::max<int64_t>(-1, std::min<int64_t>(m, kPartMaxDevices + 1))); };
+    std::vector<int32_t> sizes(size_t(nf), cap(fleets->max_devices));
+    if (fleets->min_devices != fleets->max_devices) {
+        HIP_TRY(hipSetDevice(c->device));
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+        std::vector<int64_t> off(size_t(nf) + 1);
+        HIP_TRY(hipMemcpyAsync(off.data(), fleets->dev_off, 8 * (nf + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int64_t f = 0; f < nf; ++f) sizes[f] = cap(off[f + 1] - off[f]);
+    }
+    return solve_partition(ctx, model, fleets, sizes.data(), partition, ks, n_k, frontier, stream);
+}
+
+int halda_solve_partition_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                               const halda_partition *partition, const int32_t *ks, int32_t n_k,
+                               halda_partition_frontier *fh) {
+    if (const int rc = check_partition_args(ctx, model, th, partition, ks, fh)) return rc;
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (th->n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!fh->status || !fh->value || !fh->group_mask || !fh->group_obj || !fh->group_k)
+        return fail(HALDA_E_ARG, "halda_partition_frontier: NULL");
+    if (partition->max_groups < 1 || partition->max_groups > kPartMaxGroups)
+        return fail(HALDA_E_ARG, "halda_partition: max_groups must be in 1..8");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    std::vector<int32_t> sizes(size_t(nf), 0);
+    for (int64_t f = 0; f < nf; ++f)
+        sizes[f] = int32_t(std::max<int64_t>(-1, std::min<int64_t>(th->dev_off[f + 1] - th->dev_off[f], kPartMaxDevices + 1)));
+    const size_t pts = size_t(nf) * size_t(partition->max_groups), slots = 8 * pts;
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const size_t o_st = lay.take(4 * pts), o_v = lay.take(8 * pts), o_gm = lay.take(4 * slots),
+                 o_go = lay.take(8 * slots), o_gk = lay.take(4 * slots);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    halda_partition_frontier fd;
+    fd.status = reinterpret_cast<int32_t *>(base + o_st);
+    fd.value = reinterpret_cast<double *>(base + o_v);
+    fd.group_mask = reinterpret_cast<uint32_t *>(base + o_gm);
+    fd.group_obj = reinterpret_cast<double *>(base + o_go);
+    fd.group_k = reinterpret_cast<int32_t *>(base + o_gk);
+    rc = solve_partition(ctx, model, &d, sizes.data(), partition, ks, n_k, &fd, s);
+    if (rc != HALDA_OK) return rc;
+    const std::array<stage::Copy, 5> back = {{{fh->status, o_st, 4 * pts},
+                                              {fh->value, o_v, 8 * pts},
+                                              {fh->group_mask, o_gm, 4 * slots},
+                                              {fh->group_obj, o_go, 8 * slots},
+                                              {fh->group_k, o_gk, 4 * slots}}};
+    rc = download(back, base, s);
+    if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;
 }

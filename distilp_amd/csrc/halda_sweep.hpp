@@ -4451,3 +4451,259 @@ __global__ __launch_bounds__(64) void halda_pick_kernel(halda_batch B, halda_res
         out.n[d0 + i] = n;
     }
 }
+
+// ---------------------------------------------------------------- exact replica partitioning
+// halda_solve_partition: a fleet of M <= 20 devices split into r = 1 .. R groups, each group a pipeline of its
+// own. A group is a device mask; val[mask] is what halda_solve_subfleets writes for the mask's devices in
+// ascending order. Every mask of every fleet is an item of the call -- mask m of fleet f is item
+// fl[f].item_off + m - 1 -- and every per-mask plane (val, k, best_r, arg_r) is indexed by item.
+// The functions of this section are compiled without the packed FP32 instructions (they use none: every value is
+// a double or an integer), whatever the translation unit's flags say.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HALDA_PART_FN __attribute__((target("no-packed-fp32-ops")))
+#else
+#define HALDA_PART_FN
+#endif
+
+struct PartFleet {
+    int64_t item_off;  // the fleet's first item (mask 1)
+    int64_t list_off;  // listed devices of every item in front of it
+    int32_t M;         // its devices
+    int32_t pad;
+};
+
+struct PartArgs {
+    const PartFleet *fl;  // [n_fleets]
+    int64_t n_items;      // sum over fleets of 2^M - 1
+    int32_t n_fleets, R;
+};
+
+constexpr int kPartMax = 0, kPartSum = 1;  // halda_partition.criterion
+
+// The listed devices of the masks below m: the set bits of 0 .. m - 1, bit by bit (m <= 2^20).
+HALDA_PART_FN __host__ __device__ inline int64_t part_bits_below(uint32_t m) {
+    int64_t t = 0;
+    for (int b = 0; b <= 20; ++b) {
+        const uint32_t blk = uint32_t(1) << b, rem = m & (2 * blk - 1);
+        t += int64_t(m >> (b + 1)) << b;
+        if (rem > blk) t += rem - blk;
+    }
+    return t;
+}
+
+// The fleet of item g: the last one whose item_off is <= g.
+HALDA_PART_FN __device__ inline int part_fleet_of(const PartArgs &P, int64_t g) {
+    int lo = 0, hi = P.n_fleets - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (P.fl[mid].item_off <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// halda_partition_index_kernel: one wave per item of the launch [i0, i0 + n) writes its mask's devices as an
+// item of halda_solve_subfleets (halda_subsets_index_kernel's job without combo lists: the mask is the
+// candidate). Lane b < 20 owns device b; l0 is the listed devices in front of item i0.
+__global__ HALDA_PART_FN __launch_bounds__(256) void halda_partition_index_kernel(PartArgs P, int64_t i0, int64_t l0, int32_t n,
+                                                                    int32_t *parent, int64_t *sub_off,
+                                                                    int32_t *sub_idx) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * 4 + int(threadIdx.x >> 6));
+    if (i >= n) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t g = i0 + i;
+    const int f = part_fleet_of(P, g);
+    const PartFleet pf = P.fl[f];
+    const uint32_t mask = uint32_t(g - pf.item_off) + 1;
+    const int64_t so = pf.list_off + part_bits_below(mask) - l0;
+    if (lane < pf.M && ((mask >> lane) & 1)) sub_idx[so + __builtin_popcount(mask & ((uint32_t(1) << lane) - 1))] = lane;
+    if (lane == 0) {
+        parent[i] = f;
+        sub_off[i] = so;
+        if (i == n - 1) sub_off[i + 1] = so + __builtin_popcount(mask);
+    }
+}
+
+// One level of the recurrence: best_r[S] = min over T, lowbit(S) in T, T a proper subset of S, of
+// op(val[T], best_{r-1}[S \ T]) on the pair (value, T), lexicographic.
+struct PartLevel {
+    const double *val, *prev;  // val and best_{r-1} (val itself at r = 2)
+    double *best;              // best_r
+    uint32_t *arg;             // arg_r: the winning T (0 where |S| < r)
+    double *pt;                // [n_fleets * R]: best_r of the full mask at f * R + r - 1
+    int32_t r;
+    int32_t full_only;         // the last level: the full mask of every fleet only
+    int32_t bpf;               // LDS source: workgroups per fleet
+};
+
+template <int Op>
+HALDA_PART_FN __device__ inline double part_op(double a, double b) {
+    if constexpr (Op == kPartSum) return a + b;
+    else return __builtin_fmax(a, b);
+}
+
+HALDA_PART_FN __device__ inline void part_min(double &v, uint32_t &t, double v2, uint32_t t2) {
+    if (v2 < v || (v2 == v && t2 < t)) {
+        v = v2;
+        t = t2;
+    }
+}
+
+// __shfl_xor of a double: the value of lane ^ s, as two 32-bit lane permutes.
+HALDA_PART_FN __device__ inline double part_shfl_xor(double v, int s, int lane) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const int a = (lane ^ s) << 2;
+    const uint32_t lo = uint32_t(__builtin_amdgcn_ds_bpermute(a, int(uint32_t(u))));
+    const uint32_t hi = uint32_t(__builtin_amdgcn_ds_bpermute(a, int(uint32_t(u >> 32))));
+    return __builtin_bit_cast(double, (uint64_t(hi) << 32) | lo);
+}
+
+// Where a wave reads val and best_{r-1} of its fleet from, by mask: the scratch planes, or the workgroup's
+// copy of them in LDS.
+struct PartGlobalSrc {
+    const double *v, *p;
+    int64_t o;  // item_off - 1
+    HALDA_PART_FN __device__ double val(uint32_t m) const { return v[o + m]; }
+    HALDA_PART_FN __device__ double prev(uint32_t m) const { return p[o + m]; }
+};
+
+struct PartLdsSrc {
+    const double *v, *p;  // [2^M] each, entry 0 unused
+    HALDA_PART_FN __device__ double val(uint32_t m) const { return v[m]; }
+    HALDA_PART_FN __device__ double prev(uint32_t m) const { return p[m]; }
+};
+
+// The wave's minimum for one S (wave-uniform, |S| >= 2). F = S without its lowest device; the top
+// h = min(6, |F|) bits of F are spread over the lanes (lane l < 2^h holds the bits of l in those positions),
+// and every lane walks all submasks x of the other bits of F: 2^(|F| - h) steps on every lane alike.
+template <int Op, class Src>
+HALDA_PART_FN __device__ inline void part_wave_min(const Src &src, uint32_t S, int lane, double *v_out, uint32_t *t_out) {
+    const uint32_t low = S & (0u - S), F = S ^ low;
+    const int q = __builtin_popcount(F), h = q < 6 ? q : 6;
+    uint32_t hi = 0, mine = 0, rest = F;
+    for (int j = h - 1; j >= 0; --j) {
+        const uint32_t b = 0x80000000u >> __builtin_clz(rest);
+        hi |= b;
+        rest ^= b;
+        if ((lane >> j) & 1) mine |= b;
+    }
+    const uint32_t lo = F ^ hi;
+    double v = kInf;
+    uint32_t t = 0xFFFFFFFFu;
+    if (lane < (1 << h)) {
+        uint32_t x = lo;
+        while (true) {
+            const uint32_t T = low | mine | x;
+            if (T != S) part_min(v, t, part_op<Op>(src.val(T), src.prev(S ^ T)), T);
+            if (x == 0) break;
+            x = (x - 1) & lo;
+        }
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double v2 = part_shfl_xor(v, s, lane);
+        const uint32_t t2 = uint32_t(__builtin_amdgcn_ds_bpermute((lane ^ s) << 2, int(t)));
+        part_min(v, t, v2, t2);
+    }
+    *v_out = v;
+    *t_out = t;
+}
+
+template <int Op, class Src>
+HALDA_PART_FN __device__ inline void part_one(const PartArgs &P, const PartLevel &L, const Src &src, int f, int M, int64_t o,
+                                uint32_t S, int lane) {
+    double v = kInf;
+    uint32_t t = 0;
+    if (__builtin_popcount(S) >= L.r) part_wave_min<Op>(src, S, lane, &v, &t);
+    if (lane == 0) {
+        L.best[o + S] = v;
+        L.arg[o + S] = t;
+        if (S == (uint32_t(1) << M) - 1) L.pt[int64_t(f) * P.R + L.r - 1] = v;
+    }
+}
+
+// halda_partition_level_kernel: level r of every fleet on a persistent grid, one wave per (fleet, S) at a
+// time. Lds: workgroup b serves fleet b / bpf; it copies the fleet's val and best_{r-1} into LDS once
+// (coalesced; the one barrier is reached by every thread), then its four waves walk the masks
+// 1 + 4 (b % bpf) + wave, stepping by 4 bpf. Otherwise the waves of the grid stride over the call's items
+// and read the planes in global memory. The level before is complete: it was the launch before.
+template <int Op, bool Lds>
+__global__ HALDA_PART_FN __launch_bounds__(256) void halda_partition_level_kernel(PartArgs P, PartLevel L) {
+    const int lane = int(threadIdx.x & 63);
+    const int wv = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+    if constexpr (Lds) {
+        extern __shared__ double part_lds[];
+        const int f = int(blockIdx.x) / L.bpf, j = int(blockIdx.x) - f * L.bpf;
+        const PartFleet pf = P.fl[f];
+        const uint32_t n = uint32_t(1) << pf.M;
+        const int64_t o = pf.item_off - 1;
+        double *lv = part_lds, *lp = part_lds + n;
+        for (uint32_t m = 1 + threadIdx.x; m < n; m += 256) {
+            lv[m] = L.val[o + m];
+            lp[m] = L.prev[o + m];
+        }
+        __syncthreads();
+        const PartLdsSrc src{lv, lp};
+        if (L.full_only) {
+            if (j == 0 && wv == 0) part_one<Op>(P, L, src, f, pf.M, o, n - 1, lane);
+        } else {
+            for (uint32_t S = 1 + 4 * uint32_t(j) + uint32_t(wv); S < n; S += 4 * uint32_t(L.bpf))
+                part_one<Op>(P, L, src, f, pf.M, o, S, lane);
+        }
+    } else {
+        const int64_t w0 = int64_t(blockIdx.x) * 4 + wv, nw = int64_t(gridDim.x) * 4;
+        if (L.full_only) {
+            for (int64_t f = w0; f < P.n_fleets; f += nw) {
+                const PartFleet pf = P.fl[f];
+                const PartGlobalSrc src{L.val, L.prev, pf.item_off - 1};
+                part_one<Op>(P, L, src, int(f), pf.M, src.o, (uint32_t(1) << pf.M) - 1, lane);
+            }
+        } else {
+            for (int64_t g = w0; g < P.n_items; g += nw) {
+                const int f = part_fleet_of(P, g);
+                const PartFleet pf = P.fl[f];
+                const PartGlobalSrc src{L.val, L.prev, pf.item_off - 1};
+                part_one<Op>(P, L, src, f, pf.M, src.o, uint32_t(g - pf.item_off) + 1, lane);
+            }
+        }
+    }
+}
+
+// halda_partition_trace_kernel: one thread per (fleet, r) walks arg_r, arg_{r-1}, ... from the full mask and
+// writes the point: group 0 holds device 0, group 1 the lowest device not in group 0, and so on; the last
+// group is what is left. arg holds the planes of r = 2 .. R, n_items entries each.
+struct PartFrontier {
+    int32_t *status;       // [n_fleets * R]
+    double *value;         // [n_fleets * R]
+    uint32_t *group_mask;  // [n_fleets * R * 8]
+    double *group_obj;     // [n_fleets * R * 8]
+    int32_t *group_k;      // [n_fleets * R * 8]
+};
+
+__global__ HALDA_PART_FN __launch_bounds__(256) void halda_partition_trace_kernel(PartArgs P, const double *val, const int32_t *k,
+                                                                    const uint32_t *arg, const double *pt,
+                                                                    PartFrontier O) {
+    const int i = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (i >= P.n_fleets * P.R) return;
+    const int f = i / P.R, r = i - f * P.R + 1;
+    const PartFleet pf = P.fl[f];
+    const int64_t o = pf.item_off - 1;
+    const uint32_t full = (uint32_t(1) << pf.M) - 1;
+    double v = kInf;
+    if (pf.M >= r) v = r == 1 ? val[o + full] : pt[i];
+    const bool ok = v < kInf;
+    O.status[i] = ok ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+    O.value[i] = ok ? v : kInf;
+    uint32_t S = full;
+    for (int g = 0; g < 8; ++g) {
+        uint32_t T = 0;
+        if (ok && g < r) {
+            const int level = r - g;  // the groups still to place
+            // (a finite point's T is a non-empty part of S; nothing is read for an S that ran empty)
+            T = !S ? 0 : level >= 2 ? arg[int64_t(level - 2) * P.n_items + o + S] & S : S;
+            S ^= T;
+        }
+        O.group_mask[int64_t(i) * 8 + g] = T;
+        O.group_obj[int64_t(i) * 8 + g] = T ? val[o + T] : kInf;
+        O.group_k[int64_t(i) * 8 + g] = T ? k[o + T] : 0;
+    }
+}

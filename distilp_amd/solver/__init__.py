@@ -11,6 +11,8 @@ from .change import (ChangePoint, halda_change_frontier, halda_change_frontiers,
 from .coefficients import HALDAResult, ILPResult
 from .fleets import halda_solve_fleets  # noqa: F401
 from .halda import halda_solve, halda_solve_batch  # noqa: F401
+from .partition import (PartitionPoint, halda_partition, halda_partition_frontier,  # noqa: F401
+                        halda_partition_frontier_batch)
 from .plans import (PlanEvaluation, Replacement, evaluate_plan_np, halda_evaluate_plan,  # noqa: F401
                     halda_evaluate_plans_batch, halda_replace_or_keep, halda_replace_or_keep_batch)
 from .scale import (ScalePoint, halda_scale_in, halda_scale_in_frontier, halda_scale_in_frontier_batch,  # noqa: F401
@@ -32,6 +34,7 @@ __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solv
            "halda_failover_frontiers", "halda_join_frontiers", "halda_failover_plan", "ChangePoint",
            "halda_scale_in_frontier", "halda_scale_in_frontier_batch", "halda_scale_in", "halda_scale_out_frontier",
            "ScalePoint", "halda_solve_boxes", "halda_solve_boxes_batch", "reload_caps", "halda_reload_frontier",
-           "ReloadPoint", "ILPResult"]
+           "ReloadPoint", "ILPResult", "halda_partition_frontier", "halda_partition_frontier_batch",
+           "halda_partition", "PartitionPoint"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

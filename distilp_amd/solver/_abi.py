@@ -1,6 +1,6 @@
 """The C ABI of libhalda (include/halda.h, and include/halda_boxes.h beside it) as ctypes declarations: every
 struct, in header order, and the prototype of every function. `_libhalda.load_library` applies PROTOTYPES,
-BOXES_PROTOTYPES and WIDE_PROTOTYPES (include/halda_wide.h) to the library it opens, so no call can reach a function with ctypes' default `int` arguments
+BOXES_PROTOTYPES, WIDE_PROTOTYPES (include/halda_wide.h) and PARTITION_PROTOTYPES (include/halda_partition.h) to the library it opens, so no call can reach a function with ctypes' default `int` arguments
 and result. tests/test_abi.py compiles halda.h and compares every struct's size and field offsets, and every
 prototype's arity and result type, with this module; tests/test_boxes.py does the same for halda_boxes.h.
 """
@@ -239,4 +239,20 @@ WIDE_PROTOTYPES = {
     **_with_host("halda_solve_change_subsets_wide", *_table, c_int32, POINTER(HaldaChangeSubsetsWideC),
                  POINTER(HaldaChangeSubsetFrontierWideC)),
     "halda_change_subsets_wide_launch_bytes": (c_int64, [c_int32] * 4 + [c_int64]),
+}
+
+# include/halda_partition.h, the companion header of exact replica partitioning: its structs and prototypes,
+# applied by load_library with the others (tests/test_partition.py holds them to that header)
+class HaldaPartitionC(ctypes.Structure):
+    _fields_ = [("max_groups", c_int32), ("criterion", c_int32)]
+
+
+class HaldaPartitionFrontierC(ctypes.Structure):
+    _fields_ = _ptrs("status", "value", "group_mask", "group_obj", "group_k")
+
+
+PARTITION_STRUCTS = {HaldaPartitionC: "halda_partition", HaldaPartitionFrontierC: "halda_partition_frontier"}
+PARTITION_PROTOTYPES = {
+    **_with_host("halda_solve_partition", *_table, POINTER(HaldaPartitionC), *_ks, POINTER(HaldaPartitionFrontierC)),
+    "halda_partition_bytes": (c_int64, [c_int32, c_int32]),
 }
