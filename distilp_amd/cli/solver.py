@@ -245,13 +245,15 @@ def select_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: flo
     return out
 
 
-def replica_lines(devices: List[DeviceProfile], model: ModelProfile, replicas: int, criterion: str) -> List[str]:
-    """--replicas R [--criterion max|sum]: one line per point of halda_partition_frontier, r = 1 .. R, device
-    names in the fleet's order (kv_bits "4bit" like the solve above)."""
+def replica_lines(devices: List[DeviceProfile], model: ModelProfile, replicas: int, criterion: str,
+                  route: str = "masks") -> List[str]:
+    """--replicas R [--criterion max|sum] [--replica-route masks|classes|auto]: one line per point of
+    halda_partition_frontier, r = 1 .. R, device names in the fleet's order (kv_bits "4bit" like the solve above)."""
     from ..solver.partition import halda_partition_frontier
 
     out = []
-    for r, pt in enumerate(halda_partition_frontier(devices, model, replicas, criterion, kv_bits="4bit"), 1):
+    for r, pt in enumerate(halda_partition_frontier(devices, model, replicas, criterion, kv_bits="4bit",
+                                                      route=route), 1):
         if pt.groups is None:
             out.append(f"replicas {r}: infeasible")
             continue
@@ -354,6 +356,10 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--replicas", type=int, metavar="R",
                    help="After the solution, print for every r up to R the best split of the fleet into r independent "
                         "pipelines (at most 20 devices, R up to 8)")
+    o.add_argument("--replica-route", choices=("masks", "classes", "auto"), default="masks",
+                   help="With --replicas: enumerate device sets (masks, default: at most 20 devices), or groups by how "
+                        "many devices of each kind they take (classes: up to 256 devices of at most 8 kinds with equal "
+                        "profiles); auto takes masks up to 20 devices and classes beyond")
     o.add_argument("--criterion", choices=("max", "sum"), default="max",
                    help="With --replicas: price a split by its slowest pipeline (max, default; the other pipelines are "
                         "only held at or below it) or by the sum of its pipelines' objectives (sum)")
@@ -474,7 +480,7 @@ def main(argv=None) -> int:
             print(line)
     if args.replicas is not None:
         try:
-            lines = replica_lines(devices, model, args.replicas, args.criterion)
+            lines = replica_lines(devices, model, args.replicas, args.criterion, args.replica_route)
         except ValueError as e:
             print(f"error: --replicas: {e}", file=sys.stderr)
             return 2

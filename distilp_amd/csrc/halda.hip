@@ -37,6 +37,7 @@
 #include "halda_boxes.h"
 #include "halda_wide.h"
 #include "halda_partition.h"
+#include "halda_partition_classes.h"
 #include "halda_launch.hpp"
 #include "halda_stage.hpp"
 
@@ -5070,6 +5071,343 @@ int halda_solve_partition_host(void *ctx, const halda_model *model, const halda_
     const std::array<stage::Copy, 5> back = {{{fh->status, o_st, 4 * pts},
                                               {fh->value, o_v, 8 * pts},
                                               {fh->group_mask, o_gm, 4 * slots},
+                                              {fh->group_obj, o_go, 8 * slots},
+                                              {fh->group_k, o_gk, 4 * slots}}};
+    rc = download(back, base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- replica partitioning by device class
+// halda_solve_partition_classes (include/halda_partition_classes.h): solve_partition's plan with count vectors
+// for masks. Every code of every fleet is an item (code m of fleet f: item item_off[f] + m - 1), solved in
+// launches of at most kSubsetsChunkDevices listed devices cut at item boundaries
+// (halda_partition_classes_index_kernel writes the lists, the sub-fleet entry's expansion route solves them into
+// the val and k planes); then one halda_partition_classes_level_kernel launch per level and one
+// halda_partition_classes_trace_kernel. The planes and item arrays live in the context's sel_buf.
+constexpr int kPcMaxDevices = 256;
+constexpr int64_t kPcMaxCodes = int64_t(1) << 20;  // HALDA_SUBSETS_MAX items per fleet, as the mask route
+constexpr int64_t kPcMaxPairs = int64_t(1) << 32;  // pair evaluations per level and fleet
+constexpr int64_t kPcLdsCodes = 8192;              // both planes of 8192 doubles fill 128 KiB of LDS
+
+// The codes of a fleet of C classes of cnt[c] devices, or -1 (and why) outside the gate.
+static int64_t pc_codes(const int32_t *cnt, int C, std::string *why) {
+    const auto no = [&](const std::string &m) {
+        if (why) *why = m;
+        return int64_t(-1);
+    };
+    if (C < 1 || C > kPcMaxClasses) return no("has " + std::to_string(C) + " classes (1..8)");
+    int64_t M = 0, codes = 1, pairs = 1;
+    for (int c = 0; c < C; ++c) {
+        if (cnt[c] < 1 || cnt[c] > kPcMaxDevices) return no("has a class of " + std::to_string(cnt[c]) + " devices");
+        M += cnt[c];
+        codes = std::min(codes * (cnt[c] + 1), 2 * kPcMaxCodes);
+        pairs = std::min(pairs * ((int64_t(cnt[c]) + 1) * (cnt[c] + 2) / 2), 2 * kPcMaxPairs);
+    }
+    if (M > kPcMaxDevices) return no("has " + std::to_string(M) + " devices (1..256)");
+    if (codes > kPcMaxCodes) return no("has more than 2^20 codes");
+    if (pairs > kPcMaxPairs) return no("has more than 2^32 pair evaluations per level");
+    return codes;
+}
+
+int64_t halda_partition_classes_bytes(const int32_t *counts, int32_t n_classes, int32_t max_groups) {
+    if (!counts || max_groups < 1 || max_groups > kPartMaxGroups) return -1;
+    const int64_t codes = pc_codes(counts, n_classes, nullptr);
+    // per code: val (8), k (4), two best planes (16) and an arg entry (4) per level r = 2 .. max_groups
+    return codes < 0 ? -1 : codes * (28 + 4 * int64_t(max_groups - 1));
+}
+
+// The fewest and the most devices of the codes a .. b of F (1 <= a <= b): a walk from the top class down over
+// four states -- on both bounds, on a only, on b only, free of both -- each with its best digit sum so far.
+static void pc_len_range(const PcFleet &F, uint32_t a, uint32_t b, int *lmin, int *lmax) {
+    for (int pass = 0; pass < 2; ++pass) {
+        const bool mx = pass == 1;
+        const int none = mx ? -1 : INT32_MAX;
+        const auto better = [&](int x, int y) { return mx ? std::max(x, y) : std::min(x, y); };
+        int both = 0, lo = none, hi = none, fr = none;
+        for (int c = F.C - 1; c >= 0; --c) {
+            const int cnt = F.cnt[c], da = int((a / uint32_t(F.stride[c])) % uint32_t(cnt + 1)),
+                      db = int((b / uint32_t(F.stride[c])) % uint32_t(cnt + 1));
+            int nboth = none, nlo = none, nhi = none, nfr = none;
+            if (fr != none) nfr = fr + (mx ? cnt : 0);
+            if (lo != none) {
+                nlo = lo + da;
+                if (da < cnt) nfr = better(nfr, lo + (mx ? cnt : da + 1));
+            }
+            if (hi != none) {
+                nhi = hi + db;
+                if (db > 0) nfr = better(nfr, hi + (mx ? db - 1 : 0));
+            }
+            if (both != none) {
+                if (da == db) {
+                    nboth = both + da;
+                } else {  // (da < db: a <= b and the classes above agree)
+                    nlo = both + da;
+                    nhi = both + db;
+                    if (db - da >= 2) nfr = both + (mx ? db - 1 : da + 1);
+                }
+            }
+            both = nboth, lo = nlo, hi = nhi, fr = nfr;
+        }
+        int best = none;
+        for (const int x : {both, lo, hi, fr})
+            if (x != none) best = better(best, x);
+        if (mx) *lmax = std::max(*lmax, best);
+        else *lmin = std::min(*lmin, best);
+    }
+}
+
+extern "C++" {
+template <int Op, bool Lds>
+static int launch_pc_level(const PcArgs &P, const PartLevel &L, unsigned grid, size_t lds, hipStream_t s) {
+    if (lds)
+        HIP_TRY(Ctx::ensure_lds(reinterpret_cast<const void *>(halda_partition_classes_level_kernel<Op, Lds>), int64_t(lds)));
+    hipLaunchKernelGGL((halda_partition_classes_level_kernel<Op, Lds>), dim3(grid), dim3(256), lds, s, P, L);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+}  // extern "C++"
+
+// The gate and the fleets' records from the host class ids: fl[f] and the class orders in perm.
+static int pc_plan(int64_t nf, const int32_t *cls, const int64_t *dev_off, int R, int crit, std::vector<PcFleet> *fl_,
+                   std::vector<int32_t> *perm_, int64_t *items_, int64_t *listed_, int64_t *max_codes_) {
+    if (R < 1 || R > kPartMaxGroups) return fail(HALDA_E_ARG, "halda_partition_classes: max_groups must be in 1..8");
+    if (crit != kPartMax && crit != kPartSum)
+        return fail(HALDA_E_ARG, "halda_partition_classes: criterion must be 0 (max) or 1 (sum)");
+    if (dev_off[0] != 0) return fail(HALDA_E_ARG, "halda_partition_classes: dev_off[0] must be 0");
+    std::vector<PcFleet> &fl = *fl_;
+    fl.assign(size_t(nf), PcFleet{});
+    int64_t items = 0, listed = 0, Mmax = 0, max_codes = 0;
+    for (int64_t f = 0; f < nf; ++f) {
+        const int64_t d0 = dev_off[f], M = dev_off[f + 1] - d0;
+        const std::string who = "halda_solve_partition_classes: fleet " + std::to_string(f) + " ";
+        if (M < 1 || M > kPcMaxDevices) return fail(HALDA_E_ARG, who + "has " + std::to_string(M) + " devices (1..256)");
+        PcFleet &F = fl[f];
+        for (int64_t i = 0; i < M; ++i) {
+            const int32_t id = cls[d0 + i];
+            if (id < 0 || id > F.C || id >= kPcMaxClasses)
+                return fail(HALDA_E_ARG, who + (id >= kPcMaxClasses || F.C >= kPcMaxClasses
+                                                    ? "has more than 8 classes"
+                                                    : "has class ids not numbered by first occurrence"));
+            if (id == F.C) ++F.C;
+            ++F.cnt[id];
+        }
+        std::string why;
+        const int64_t codes = pc_codes(F.cnt, F.C, &why);
+        if (codes < 0) return fail(HALDA_E_ARG, who + why);
+        F.item_off = items;
+        F.list_off = listed;
+        F.n_codes = int32_t(codes);
+        F.M = int32_t(M);
+        F.perm_off = int32_t(d0);
+        int32_t stride = 1, start = 0;
+        for (int c = 0; c < kPcMaxClasses; ++c) {
+            F.stride[c] = stride;
+            F.start[c] = start;
+            stride *= F.cnt[c] + 1;
+            start += F.cnt[c];
+        }
+        items += codes - 1;
+        listed += pc_digits_below(F, uint32_t(codes));
+        Mmax = std::max(Mmax, M);
+        max_codes = std::max(max_codes, codes);
+    }
+    if (R > Mmax)
+        return fail(HALDA_E_ARG, "halda_partition_classes: max_groups " + std::to_string(R) + " is beyond the " +
+                                     std::to_string(Mmax) + " devices of the largest fleet");
+    // the class orders: class-major, ascending index within a class
+    std::vector<int32_t> &perm = *perm_;
+    perm.assign(size_t(dev_off[nf]), 0);
+    for (int64_t f = 0; f < nf; ++f) {
+        int32_t at[kPcMaxClasses];
+        for (int c = 0; c < kPcMaxClasses; ++c) at[c] = fl[f].start[c];
+        for (int64_t i = 0; i < fl[f].M; ++i) perm[size_t(dev_off[f] + at[cls[dev_off[f] + i]]++)] = int32_t(i);
+    }
+    *items_ = items;
+    *listed_ = listed;
+    *max_codes_ = max_codes;
+    return HALDA_OK;
+}
+
+static int solve_partition_classes(void *ctx, const halda_model *model, const halda_fleets *table, const int32_t *cls,
+                                   const int64_t *dev_off, int R, int crit, const int32_t *ks, int32_t n_k,
+                                   const halda_partition_classes_frontier *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int nf = table->n_fleets;
+    if (!frontier->status || !frontier->value || !frontier->group_code || !frontier->group_obj || !frontier->group_k)
+        return fail(HALDA_E_ARG, "halda_partition_classes_frontier: NULL");
+    if (n_k <= 0 || n_k > 1024) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (model->L < 1) return fail(HALDA_E_ARG, "model.L < 1");
+    for (int j = 0; j < n_k; ++j)
+        if (ks[j] < 1 || (j && ks[j] <= ks[j - 1])) return fail(HALDA_E_ARG, "ks must be ascending, unique, > 0");
+    if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    std::vector<PcFleet> fl;
+    std::vector<int32_t> perm;
+    int64_t items = 0, listed = 0, max_codes = 0;
+    if (const int rc = pc_plan(nf, cls, dev_off, R, crit, &fl, &perm, &items, &listed, &max_codes)) return rc;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    // the listed devices in front of item g (g = items: all of them)
+    auto listed_before = [&](int64_t g) -> int64_t {
+        if (g >= items) return listed;
+        int f = nf - 1;
+        while (fl[f].item_off > g) --f;
+        return fl[f].list_off + pc_digits_below(fl[f], uint32_t(g - fl[f].item_off) + 1);
+    };
+    // launches of at most kSubsetsChunkDevices listed devices (an item lists at most 256: every launch has items)
+    struct Chunk { int64_t a, n, l0, nd; int lmin, lmax; };
+    std::vector<Chunk> chunks;
+    int64_t max_items = 0, max_dev = 0;
+    for (int64_t a = 0; a < items;) {
+        const int64_t l0 = listed_before(a);
+        int64_t lo = a + 1, hi = items;  // the largest b with listed_before(b) - l0 within the cap
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo + 1) / 2;
+            if (listed_before(mid) - l0 <= kSubsetsChunkDevices) lo = mid;
+            else hi = mid - 1;
+        }
+        Chunk ch{a, lo - a, l0, listed_before(lo) - l0, kPcMaxDevices, 0};
+        for (int f = 0; f < nf; ++f) {
+            const int64_t b0 = std::max(a, fl[f].item_off), b1 = std::min(lo, fl[f].item_off + fl[f].n_codes - 1);
+            if (b0 < b1) pc_len_range(fl[f], uint32_t(b0 - fl[f].item_off) + 1, uint32_t(b1 - fl[f].item_off), &ch.lmin, &ch.lmax);
+        }
+        chunks.push_back(ch);
+        max_items = std::max(max_items, ch.n);
+        max_dev = std::max(max_dev, ch.nd);
+        a = lo;
+    }
+    stage::Bump lay;
+    const size_t n8 = 8 * size_t(items), n4 = 4 * size_t(items), fl_bytes = sizeof(PcFleet) * fl.size();
+    const size_t o_fl = lay.take(fl_bytes), o_perm = lay.take(4 * perm.size()), o_val = lay.take(n8), o_k = lay.take(n4),
+                 o_b0 = lay.take(n8), o_b1 = lay.take(n8), o_arg = lay.take(n4 * size_t(R - 1)),
+                 o_pt = lay.take(8 * size_t(nf) * R), o_par = lay.take(4 * size_t(max_items)),
+                 o_soff = lay.take(8 * size_t(max_items + 1)), o_sidx = lay.take(4 * size_t(max_dev)),
+                 o_w = lay.take(4 * size_t(max_dev)), o_n = lay.take(4 * size_t(max_dev));
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sel_buf, &c->sel_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
+    }
+    char *base = reinterpret_cast<char *>(c->sel_buf);
+    // (pageable sources: the copies are staged before the call returns)
+    HIP_TRY(hipMemcpyAsync(base + o_fl, fl.data(), fl_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_perm, perm.data(), 4 * perm.size(), hipMemcpyHostToDevice, s));
+    PcArgs P;
+    P.fl = reinterpret_cast<const PcFleet *>(base + o_fl);
+    P.perm = reinterpret_cast<const int32_t *>(base + o_perm);
+    P.n_items = items;
+    P.n_fleets = nf;
+    P.R = R;
+    double *val = reinterpret_cast<double *>(base + o_val);
+    int32_t *kpl = reinterpret_cast<int32_t *>(base + o_k);
+    c->fleet_timed = false;
+    for (const Chunk &ch : chunks) {
+        halda_subfleets I;
+        I.n_items = int32_t(ch.n);
+        I.min_devices = ch.lmin;
+        I.max_devices = ch.lmax;
+        I.parent = reinterpret_cast<const int32_t *>(base + o_par);
+        I.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
+        I.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
+        hipLaunchKernelGGL(halda_partition_classes_index_kernel, dim3(unsigned((ch.n + 3) / 4)), dim3(256), 0, s, P, ch.a,
+                           ch.l0, int32_t(ch.n), reinterpret_cast<int32_t *>(base + o_par),
+                           reinterpret_cast<int64_t *>(base + o_soff), reinterpret_cast<int32_t *>(base + o_sidx));
+        HIP_TRY(hipGetLastError());
+        halda_fleet_result out = {};
+        out.best_k = kpl + ch.a;
+        out.obj_value = val + ch.a;
+        out.w = reinterpret_cast<int32_t *>(base + o_w);
+        out.n = reinterpret_cast<int32_t *>(base + o_n);
+        // the sub-fleet entry's expansion route, unedited, on the items just written
+        const lrec::PathOverride expand(c->knob[lrec::kSubfleets], 1, /*keep_route=*/true);
+        const int rc = solve_subfleets(ctx, model, table, &I, ks, n_k, &out, s, ch.nd);
+        if (rc != HALDA_OK) return rc;
+    }
+    // the levels: LDS source where both planes of every fleet fit 128 KiB
+    const bool lds = max_codes <= kPcLdsCodes;
+    const size_t lds_bytes = lds ? 16 * size_t(max_codes) : 0;
+    double *bp[2] = {reinterpret_cast<double *>(base + o_b0), reinterpret_cast<double *>(base + o_b1)};
+    for (int r = 2; r <= R; ++r) {
+        PartLevel L;
+        L.val = val;
+        L.prev = r == 2 ? val : bp[(r - 1) & 1];
+        L.best = bp[r & 1];
+        L.arg = reinterpret_cast<uint32_t *>(base + o_arg) + size_t(r - 2) * size_t(items);
+        L.pt = reinterpret_cast<double *>(base + o_pt);
+        L.r = r;
+        L.full_only = r == R;
+        // LDS: workgroups per fleet -- about 32 codes a workgroup, no more workgroups than fill the device
+        L.bpf = L.full_only ? 1 : int(std::max<int64_t>(1, std::min<int64_t>(max_codes / 32, c->cus / nf)));
+        const int64_t waves = L.full_only ? nf : items;
+        const unsigned grid = lds ? unsigned(nf) * unsigned(L.bpf)
+                                  : unsigned(std::min<int64_t>((waves + 3) / 4, int64_t(c->cus) * 8));
+        int rc;
+        if (crit == kPartSum)
+            rc = lds ? launch_pc_level<kPartSum, true>(P, L, grid, lds_bytes, s)
+                     : launch_pc_level<kPartSum, false>(P, L, grid, 0, s);
+        else
+            rc = lds ? launch_pc_level<kPartMax, true>(P, L, grid, lds_bytes, s)
+                     : launch_pc_level<kPartMax, false>(P, L, grid, 0, s);
+        if (rc != HALDA_OK) return rc;
+    }
+    const PartFrontier O{frontier->status, frontier->value, frontier->group_code, frontier->group_obj, frontier->group_k};
+    hipLaunchKernelGGL(halda_partition_classes_trace_kernel, dim3(unsigned((nf * R + 255) / 256)), dim3(256), 0, s, P,
+                       static_cast<const double *>(val), static_cast<const int32_t *>(kpl),
+                       reinterpret_cast<const uint32_t *>(base + o_arg), reinterpret_cast<const double *>(base + o_pt), O);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+int halda_solve_partition_classes(void *ctx, const halda_model *model, const halda_fleets *fleets,
+                                  const halda_partition_classes *classes, const int32_t *ks, int32_t n_k,
+                                  halda_partition_classes_frontier *frontier, void *stream) {
+    if (!ctx || !model || !fleets || !classes || !ks || !frontier)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/classes/ks/frontier");
+    if (fleets->n_fleets <= 0) return HALDA_OK;
+    if (!classes->cls || !classes->dev_off) return fail(HALDA_E_ARG, "halda_partition_classes has a NULL array");
+    return solve_partition_classes(ctx, model, fleets, classes->cls, classes->dev_off, classes->max_groups,
+                                   classes->criterion, ks, n_k, frontier, stream);
+}
+
+int halda_solve_partition_classes_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                                       const halda_partition_classes *classes, const int32_t *ks, int32_t n_k,
+                                       halda_partition_classes_frontier *fh) {
+    if (!ctx || !model || !th || !classes || !ks || !fh)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/classes/ks/frontier");
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (th->n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!classes->cls) return fail(HALDA_E_ARG, "halda_partition_classes has a NULL array");
+    if (!fh->status || !fh->value || !fh->group_code || !fh->group_obj || !fh->group_k)
+        return fail(HALDA_E_ARG, "halda_partition_classes_frontier: NULL");
+    const int R = classes->max_groups;
+    if (R < 1 || R > kPartMaxGroups) return fail(HALDA_E_ARG, "halda_partition_classes: max_groups must be in 1..8");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    const size_t pts = size_t(nf) * size_t(R), slots = 8 * pts;
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    const size_t o_st = lay.take(4 * pts), o_v = lay.take(8 * pts), o_gm = lay.take(4 * slots),
+                 o_go = lay.take(8 * slots), o_gk = lay.take(4 * slots);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    halda_partition_classes_frontier fd;
+    fd.status = reinterpret_cast<int32_t *>(base + o_st);
+    fd.value = reinterpret_cast<double *>(base + o_v);
+    fd.group_code = reinterpret_cast<uint32_t *>(base + o_gm);
+    fd.group_obj = reinterpret_cast<double *>(base + o_go);
+    fd.group_k = reinterpret_cast<int32_t *>(base + o_gk);
+    rc = solve_partition_classes(ctx, model, &d, classes->cls, th->dev_off, R, classes->criterion, ks, n_k, &fd, s);
+    if (rc != HALDA_OK) return rc;
+    const std::array<stage::Copy, 5> back = {{{fh->status, o_st, 4 * pts},
+                                              {fh->value, o_v, 8 * pts},
+                                              {fh->group_code, o_gm, 4 * slots},
                                               {fh->group_obj, o_go, 8 * slots},
                                               {fh->group_k, o_gk, 4 * slots}}};
     rc = download(back, base, s);

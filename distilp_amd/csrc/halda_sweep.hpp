@@ -4707,3 +4707,252 @@ __global__ HALDA_PART_FN __launch_bounds__(256) void halda_partition_trace_kerne
         O.group_k[int64_t(i) * 8 + g] = T ? k[o + T] : 0;
     }
 }
+
+// ---------------------------------------------------------------- replica partitioning by device class
+// halda_solve_partition_classes (include/halda_partition_classes.h): a fleet of up to 256 devices of at most 8
+// classes. A group is a count vector g, 0 <= g_c <= cnt_c, written as its mixed-radix code sum g_c stride_c
+// (stride_{c+1} = stride_c (cnt_c + 1)), so code(S - T) = code(S) - code(T). Code m >= 1 of fleet f is item
+// fl[f].item_off + m - 1, and the per-item planes, the level record, the two sources and the point arrays are
+// the mask section's (PartLevel, PartGlobalSrc / PartLdsSrc, PartFrontier with the code in group_mask).
+constexpr int kPcMaxClasses = 8;
+
+struct PcFleet {
+    int64_t item_off;               // the fleet's first item (code 1)
+    int64_t list_off;               // listed devices of every item in front of it
+    int32_t n_codes;                // prod (cnt_c + 1): codes 1 .. n_codes - 1 are its items
+    int32_t M;                      // its devices
+    int32_t perm_off;               // its class order in PcArgs.perm
+    int32_t C;                      // its classes
+    int32_t cnt[kPcMaxClasses];     // class sizes, 0 past C
+    int32_t stride[kPcMaxClasses];  // stride_c, n_codes past C
+    int32_t start[kPcMaxClasses];   // position of class c's first device in class order
+};
+
+struct PcArgs {
+    const PcFleet *fl;    // [n_fleets]
+    const int32_t *perm;  // every fleet's devices (local indices) class-major, ascending within a class
+    int64_t n_items;      // sum over fleets of n_codes - 1
+    int32_t n_fleets, R;
+};
+
+// stride_{c+1}, with n_codes past the last class
+HALDA_PART_FN __host__ __device__ inline uint32_t pc_next_stride(const PcFleet &F, int c) {
+    return uint32_t(c + 1 < kPcMaxClasses ? F.stride[c + 1] : F.n_codes);
+}
+
+// The listed devices of the codes below m (m <= n_codes): the digit sum of 0 .. m - 1, digit by digit. Digit c
+// runs 0 .. cnt_c in blocks of stride_c codes; `full` whole periods, then d whole blocks and e codes of block d.
+HALDA_PART_FN __host__ __device__ inline int64_t pc_digits_below(const PcFleet &F, uint32_t m) {
+    int64_t t = 0;
+#pragma unroll
+    for (int c = 0; c < kPcMaxClasses; ++c) {
+        const uint32_t s = uint32_t(F.stride[c]), b = uint32_t(F.cnt[c]) + 1, q = m / s, full = q / b, d = q - full * b;
+        const uint32_t e = m - q * s;
+        t += int64_t(full) * s * (int64_t(b) * (b - 1) / 2) + int64_t(s) * (int64_t(d) * (d - 1) / 2) + int64_t(d) * e;
+    }
+    return t;
+}
+
+// The fleet of item g: the last one whose item_off is <= g.
+HALDA_PART_FN __device__ inline int pc_fleet_of(const PcArgs &P, int64_t g) {
+    int lo = 0, hi = P.n_fleets - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (P.fl[mid].item_off <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// halda_partition_classes_index_kernel: one wave per item of the launch [i0, i0 + n) writes its code's list --
+// the first g_c devices of every class, in class order -- as an item of halda_solve_subfleets. Lanes run over
+// the list positions (four rounds at 256 devices); l0 is the listed devices in front of item i0.
+__global__ HALDA_PART_FN __launch_bounds__(256) void halda_partition_classes_index_kernel(PcArgs P, int64_t i0, int64_t l0, int32_t n,
+                                                                            int32_t *parent, int64_t *sub_off,
+                                                                            int32_t *sub_idx) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * 4 + int(threadIdx.x >> 6));
+    if (i >= n) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t g = i0 + i;
+    const int f = pc_fleet_of(P, g);
+    const PcFleet pf = P.fl[f];
+    const uint32_t code = uint32_t(g - pf.item_off) + 1;
+    const int64_t so = pf.list_off + pc_digits_below(pf, code) - l0;
+    int dig[kPcMaxClasses], len = 0;
+#pragma unroll
+    for (int c = 0; c < kPcMaxClasses; ++c) {
+        dig[c] = int((code / uint32_t(pf.stride[c])) % (uint32_t(pf.cnt[c]) + 1));
+        len += dig[c];
+    }
+    for (int j = lane; j < len; j += 64) {
+        int p = 0, a = 0;  // a: the list positions in front of class c
+#pragma unroll
+        for (int c = 0; c < kPcMaxClasses; ++c) {
+            if (j >= a && j < a + dig[c]) p = pf.start[c] + j - a;
+            a += dig[c];
+        }
+        sub_idx[so + j] = P.perm[pf.perm_off + p];
+    }
+    if (lane == 0) {
+        parent[i] = f;
+        sub_off[i] = so;
+        if (i == n - 1) sub_off[i + 1] = so + len;
+    }
+}
+
+// The wave's minimum for one S (wave-uniform) at level r: +inf / 0 where S has fewer than r devices. The
+// candidates T are the points of the box [1 .. S_c0] x prod over c > c0 of [0 .. S_c] but S itself, c0 the
+// lowest class of S: candidate i has the digits of i in the radices rad_c0 = S_c0, rad_c = S_c + 1 (1 below
+// c0 and past the last class), class c0 least significant, so S is candidate n - 1 and the codes ascend with i.
+// Lane l takes i = l, l + 64, ...: the digits of 64 in these radices are added to its digit vector with
+// carries, and code(T) follows each carry by wrap_c = stride_{c+1} - rad_c stride_c. No division in the loop.
+template <int Op, class Src>
+HALDA_PART_FN __device__ inline void pc_wave_min(const PcFleet &F, const Src &src, uint32_t S, int r, int lane, double *v_out,
+                                   uint32_t *t_out) {
+    uint32_t rad[kPcMaxClasses], st[kPcMaxClasses], wrap[kPcMaxClasses], d[kPcMaxClasses];
+    uint32_t n = 1, devs = 0, base = 0, stepcode = 0, tcode = 0;
+    bool below = true;  // no class of S seen yet
+#pragma unroll
+    for (int c = 0; c < kPcMaxClasses; ++c) {
+        const uint32_t s = uint32_t(F.stride[c]), sc = (S / s) % (uint32_t(F.cnt[c]) + 1);
+        const bool first = below && sc > 0;
+        below = below && sc == 0;
+        rad[c] = first ? sc : sc + 1;
+        if (first) base = s;
+        wrap[c] = pc_next_stride(F, c) - rad[c] * s;
+        devs += sc;
+        n *= rad[c];
+    }
+    *v_out = kInf;
+    *t_out = 0;
+    if (int(devs) < r) return;
+    uint32_t ql = uint32_t(lane), qs = 64;
+#pragma unroll
+    for (int c = 0; c < kPcMaxClasses; ++c) {
+        const uint32_t s = uint32_t(F.stride[c]);
+        const uint32_t nl = ql / rad[c], ns = qs / rad[c];
+        d[c] = ql - nl * rad[c];
+        st[c] = qs - ns * rad[c];
+        ql = nl;
+        qs = ns;
+        tcode += d[c] * s;
+        stepcode += st[c] * s;
+    }
+    tcode += base;
+    double v = kInf;
+    uint32_t t = 0xFFFFFFFFu;
+    for (uint32_t i = uint32_t(lane); i + 1 < n; i += 64) {
+        part_min(v, t, part_op<Op>(src.val(tcode), src.prev(S - tcode)), tcode);
+        uint32_t carry = 0;
+        tcode += stepcode;
+#pragma unroll
+        for (int c = 0; c < kPcMaxClasses; ++c) {
+            if (c < F.C) {
+                const uint32_t x = d[c] + st[c] + carry;
+                carry = x >= rad[c] ? 1u : 0u;
+                d[c] = carry ? x - rad[c] : x;
+                tcode += carry ? wrap[c] : 0u;
+            }
+        }
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double v2 = part_shfl_xor(v, s, lane);
+        const uint32_t t2 = uint32_t(__builtin_amdgcn_ds_bpermute((lane ^ s) << 2, int(t)));
+        part_min(v, t, v2, t2);
+    }
+    *v_out = v;
+    *t_out = t;
+}
+
+template <int Op, class Src>
+HALDA_PART_FN __device__ inline void pc_one(const PcArgs &P, const PartLevel &L, const PcFleet &F, const Src &src, int f, int64_t o,
+                              uint32_t S, int lane) {
+    double v;
+    uint32_t t;
+    pc_wave_min<Op>(F, src, S, L.r, lane, &v, &t);
+    if (lane == 0) {
+        L.best[o + S] = v;
+        L.arg[o + S] = t;
+        if (S == uint32_t(F.n_codes) - 1) L.pt[int64_t(f) * P.R + L.r - 1] = v;
+    }
+}
+
+// halda_partition_classes_level_kernel: level r of every fleet on a persistent grid, one wave per (fleet, S)
+// at a time. Lds (every fleet of the call has at most 8192 codes): workgroup b serves fleet b / bpf; it copies
+// the fleet's val and best_{r-1} into LDS once (coalesced; the one barrier is reached by every thread), then
+// its four waves walk the codes 1 + 4 (b % bpf) + wave, stepping by 4 bpf. Otherwise the waves of the grid
+// stride over the call's items and read the planes in global memory. The level before is complete: it was the
+// launch before. The last level computes the full count vectors only.
+template <int Op, bool Lds>
+__global__ HALDA_PART_FN __launch_bounds__(256) void halda_partition_classes_level_kernel(PcArgs P, PartLevel L) {
+    const int lane = int(threadIdx.x & 63);
+    const int wv = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+    if constexpr (Lds) {
+        extern __shared__ double pc_lds[];
+        const int f = int(blockIdx.x) / L.bpf, j = int(blockIdx.x) - f * L.bpf;
+        const PcFleet pf = P.fl[f];
+        const uint32_t n = uint32_t(pf.n_codes);
+        const int64_t o = pf.item_off - 1;
+        double *lv = pc_lds, *lp = pc_lds + n;
+        for (uint32_t m = 1 + threadIdx.x; m < n; m += 256) {
+            lv[m] = L.val[o + m];
+            lp[m] = L.prev[o + m];
+        }
+        __syncthreads();
+        const PartLdsSrc src{lv, lp};
+        if (L.full_only) {
+            if (j == 0 && wv == 0) pc_one<Op>(P, L, pf, src, f, o, n - 1, lane);
+        } else {
+            for (uint32_t S = 1 + 4 * uint32_t(j) + uint32_t(wv); S < n; S += 4 * uint32_t(L.bpf))
+                pc_one<Op>(P, L, pf, src, f, o, S, lane);
+        }
+    } else {
+        const int64_t w0 = int64_t(blockIdx.x) * 4 + wv, nw = int64_t(gridDim.x) * 4;
+        if (L.full_only) {
+            for (int64_t f = w0; f < P.n_fleets; f += nw) {
+                const PcFleet pf = P.fl[f];
+                const PartGlobalSrc src{L.val, L.prev, pf.item_off - 1};
+                pc_one<Op>(P, L, pf, src, int(f), src.o, uint32_t(pf.n_codes) - 1, lane);
+            }
+        } else {
+            for (int64_t g = w0; g < P.n_items; g += nw) {
+                const int f = pc_fleet_of(P, g);
+                const PcFleet pf = P.fl[f];
+                const PartGlobalSrc src{L.val, L.prev, pf.item_off - 1};
+                pc_one<Op>(P, L, pf, src, f, src.o, uint32_t(g - pf.item_off) + 1, lane);
+            }
+        }
+    }
+}
+
+// halda_partition_classes_trace_kernel: one thread per (fleet, r) walks arg_r, arg_{r-1}, ... from the full
+// code, subtracting the winning codes, and writes the point; the last group is what is left. arg holds the
+// planes of r = 2 .. R, n_items entries each.
+__global__ HALDA_PART_FN __launch_bounds__(256) void halda_partition_classes_trace_kernel(PcArgs P, const double *val, const int32_t *k,
+                                                                            const uint32_t *arg, const double *pt,
+                                                                            PartFrontier O) {
+    const int i = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (i >= P.n_fleets * P.R) return;
+    const int f = i / P.R, r = i - f * P.R + 1;
+    const int64_t o = P.fl[f].item_off - 1;
+    const uint32_t full = uint32_t(P.fl[f].n_codes) - 1;
+    double v = kInf;
+    if (P.fl[f].M >= r) v = r == 1 ? val[o + full] : pt[i];
+    const bool ok = v < kInf;
+    O.status[i] = ok ? HALDA_STATUS_OPTIMAL : HALDA_STATUS_INFEASIBLE;
+    O.value[i] = ok ? v : kInf;
+    uint32_t S = full;
+    for (int g = 0; g < 8; ++g) {
+        uint32_t T = 0;
+        if (ok && g < r && S) {
+            const int level = r - g;  // the groups still to place
+            // (a finite point's T is a non-empty part of S; the clamp keeps every index inside the fleet)
+            T = level >= 2 ? arg[int64_t(level - 2) * P.n_items + o + S] : S;
+            if (T > S) T = S;
+            S -= T;
+        }
+        O.group_mask[int64_t(i) * 8 + g] = T;
+        O.group_obj[int64_t(i) * 8 + g] = T ? val[o + T] : kInf;
+        O.group_k[int64_t(i) * 8 + g] = T ? k[o + T] : 0;
+    }
+}

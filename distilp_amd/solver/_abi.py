@@ -1,6 +1,7 @@
 """The C ABI of libhalda (include/halda.h, and include/halda_boxes.h beside it) as ctypes declarations: every
 struct, in header order, and the prototype of every function. `_libhalda.load_library` applies PROTOTYPES,
-BOXES_PROTOTYPES, WIDE_PROTOTYPES (include/halda_wide.h) and PARTITION_PROTOTYPES (include/halda_partition.h) to the library it opens, so no call can reach a function with ctypes' default `int` arguments
+BOXES_PROTOTYPES, WIDE_PROTOTYPES (include/halda_wide.h) PARTITION_PROTOTYPES (include/halda_partition.h) and PARTITION_CLASSES_PROTOTYPES
+(include/halda_partition_classes.h) to the library it opens, so no call can reach a function with ctypes' default `int` arguments
 and result. tests/test_abi.py compiles halda.h and compares every struct's size and field offsets, and every
 prototype's arity and result type, with this module; tests/test_boxes.py does the same for halda_boxes.h.
 """
@@ -255,4 +256,22 @@ PARTITION_STRUCTS = {HaldaPartitionC: "halda_partition", HaldaPartitionFrontierC
 PARTITION_PROTOTYPES = {
     **_with_host("halda_solve_partition", *_table, POINTER(HaldaPartitionC), *_ks, POINTER(HaldaPartitionFrontierC)),
     "halda_partition_bytes": (c_int64, [c_int32, c_int32]),
+}
+
+# include/halda_partition_classes.h, partitioning by device class: its structs and prototypes, applied by
+# load_library with the others (tests/test_partition_classes.py holds them to that header)
+class HaldaPartitionClassesC(ctypes.Structure):
+    _fields_ = [("max_groups", c_int32), ("criterion", c_int32)] + _ptrs("cls", "dev_off")
+
+
+class HaldaPartitionClassesFrontierC(ctypes.Structure):
+    _fields_ = _ptrs("status", "value", "group_code", "group_obj", "group_k")
+
+
+PARTITION_CLASSES_STRUCTS = {HaldaPartitionClassesC: "halda_partition_classes",
+                             HaldaPartitionClassesFrontierC: "halda_partition_classes_frontier"}
+PARTITION_CLASSES_PROTOTYPES = {
+    **_with_host("halda_solve_partition_classes", *_table, POINTER(HaldaPartitionClassesC), *_ks,
+                 POINTER(HaldaPartitionClassesFrontierC)),
+    "halda_partition_classes_bytes": (c_int64, [_vp, c_int32, c_int32]),
 }

@@ -15,6 +15,14 @@ The GPU work is one child process under a time limit; the parent prints one JSON
 file.
 
     python tools/partition_ab.py --out profiles/partition_ab.json
+
+--classes measures halda_solve_partition_classes instead, by the same events, legs and medians: on class-sorted
+fleets both routes admit (4 kinds x 4 and 4 x 5 devices) the class route against the mask route -- call (R = 4),
+solve (R = 1) and levels (their difference) of each, and whether the raw statuses and values are equal bit for bit
+-- and beyond the mask gate the class route alone: 4 x 16 = 64 devices (83,521 codes, global source), 2 x 128 = 256
+devices on the 320-layer model, 3 x 8 = 24 devices (LDS source).
+
+    python tools/partition_ab.py --classes --out profiles/partition_classes_ab.json
 """
 
 from __future__ import annotations
@@ -32,6 +40,10 @@ REPO = Path(__file__).resolve().parent.parent
 SHAPES = (("a_64x8", 64, 8, 2, 5, 3), ("b_8x13", 8, 13, 1, 3, 3), ("c_1x16", 1, 16, 1, 3, 3),
           ("d_1x20", 1, 20, 1, 2, 2))  # name, fleets, M, warm, reps, rounds
 R = 4
+# --classes: name, class sizes, model layers, also the mask route, warm, reps, rounds
+CLASS_SHAPES = (("e_4x4", (4, 4, 4, 4), 80, True, 2, 5, 3), ("f_4x5", (5, 5, 5, 5), 80, True, 1, 2, 2),
+                ("g_4x16", (16, 16, 16, 16), 80, False, 1, 3, 3), ("h_2x128", (128, 128), 320, False, 1, 3, 3),
+                ("i_3x8", (8, 8, 8), 80, False, 2, 5, 3))
 
 
 def recurrence(val, M, R):
@@ -189,17 +201,115 @@ def child(only) -> None:
     print(json.dumps(out))
 
 
+def child_classes(only) -> None:
+    sys.path.insert(0, str(REPO))
+    import numpy as np
+    import torch
+
+    torch.cuda.init()  # torch's HIP runtime first
+    from distilp_amd.common import DeviceProfile, ModelProfileSplit
+    from distilp_amd.solver import partition as pt
+    from distilp_amd.solver._libhalda import get_context, last_error
+    from distilp_amd.solver.fleets import BYTE_FIELDS, F64_FIELDS, _fleets_struct, fleet_table, model_struct
+    from distilp_amd.synth import load_model_dict, synth_fleet
+
+    base = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
+    dev = torch.device("cuda", 0)
+    ctx = get_context(0)
+    lib = ctx.lib
+    stream = torch.cuda.Stream(dev)
+    sp = ctypes.c_void_p(stream.cuda_stream)
+    out = {"gpu": torch.cuda.get_device_name(0)}
+    fields = ("dev_off", "os_class", "flags") + F64_FIELDS + BYTE_FIELDS
+    i32, f64 = torch.int32, torch.float64
+
+    for name, counts, L, both, warm, reps, rounds in CLASS_SHAPES:
+        if only and name not in only:
+            continue
+        model = base if L == base.L else base.model_copy(update={"L": L})
+        ks = sorted(k for k in range(1, model.L) if model.L % k == 0)
+        karr, m = np.asarray(ks, np.int32), model_struct(model, 0.5)
+        kinds = [DeviceProfile.model_validate(d) for d in synth_fleet(7700 + len(counts), len(counts))]
+        fleet = [kinds[c] for c, n in enumerate(counts) for _ in range(n)]  # class-sorted
+        table = fleet_table([fleet], model)
+        cls, cnt, _ = pt.device_classes(table, 0)
+        assert tuple(cnt.tolist()) == counts
+        off = np.ascontiguousarray(table.dev_off, np.int64)
+        arrs = {f: torch.from_numpy(np.ascontiguousarray(getattr(table, f))).to(dev) for f in fields}
+        fs = _fleets_struct(table, lambda f: arrs[f].data_ptr())
+
+        def frontier():
+            return [torch.empty(R, dtype=i32, device=dev), torch.empty(R, dtype=f64, device=dev),
+                    torch.empty(R * 8, dtype=i32, device=dev), torch.empty(R * 8, dtype=f64, device=dev),
+                    torch.empty(R * 8, dtype=i32, device=dev)]
+
+        fr_c, fr_m = frontier(), frontier()
+        frc = pt.HaldaPartitionClassesFrontierC(*[t.data_ptr() for t in fr_c])
+        frm = pt.HaldaPartitionFrontierC(*[t.data_ptr() for t in fr_m])
+
+        def leg(kind):
+            route, groups = kind.split("_")
+            r = R if groups == "call" else 1
+            ts = []
+            for rep in range(warm + reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                if route == "classes":
+                    part = pt.HaldaPartitionClassesC(r, 0, cls.ctypes.data, off.ctypes.data)
+                    rc = lib.halda_solve_partition_classes(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(part),
+                                                           karr.ctypes.data, len(ks), ctypes.byref(frc), sp)
+                else:
+                    part = pt.HaldaPartitionC(r, 0)
+                    rc = lib.halda_solve_partition(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(part),
+                                                   karr.ctypes.data, len(ks), ctypes.byref(frm), sp)
+                if rc != 0:
+                    raise RuntimeError(f"{kind} failed ({rc}): {last_error(lib)}")
+                e1.record(stream)
+                stream.synchronize()
+                if rep >= warm:
+                    ts.append(e0.elapsed_time(e1))
+            return statistics.median(ts)
+
+        legs = ("classes_call", "classes_solve") + (("masks_call", "masks_solve") if both else ())
+        rnd = {k: [] for k in legs}
+        for _ in range(rounds):  # alternate the legs
+            for kind in legs:
+                rnd[kind].append(leg(kind))
+        codes = int(np.prod(np.asarray(counts) + 1))
+        rec = {"workload": f"{len(counts)} classes x {counts[0]} devices = {len(fleet)} devices, L = {L}, R = {R}, "
+                           f"{codes - 1} codes, {len(ks)} k",
+               "source": "lds" if codes <= pt.LDS_CODES else "global",
+               **{f"{k}_event_ms": statistics.median(rnd[k]) for k in legs}, **{f"{k}_rounds_ms": rnd[k] for k in legs}}
+        rec["classes_levels_event_ms"] = rec["classes_call_event_ms"] - rec["classes_solve_event_ms"]
+        leg("classes_call")  # leave the R = 4 points in the frontiers
+        rec["classes_status"] = fr_c[0].cpu().numpy().tolist()
+        rec["classes_value"] = fr_c[1].cpu().numpy().tolist()
+        if both:
+            leg("masks_call")
+            rec["masks_levels_event_ms"] = rec["masks_call_event_ms"] - rec["masks_solve_event_ms"]
+            rec["masks"] = (1 << len(fleet)) - 1
+            rec["same_bits"] = bool(fr_c[0].cpu().numpy().tobytes() == fr_m[0].cpu().numpy().tobytes()
+                                    and fr_c[1].cpu().numpy().tobytes() == fr_m[1].cpu().numpy().tobytes())
+        out[name] = rec
+        del arrs
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", help="also write the JSON line to this file")
     ap.add_argument("--timeout", type=float, default=500.0, help="time limit of the GPU child process, seconds")
     ap.add_argument("--only", nargs="+", help="shape names to run (default: all)")
+    ap.add_argument("--classes", action="store_true",
+                    help="measure halda_solve_partition_classes (against the mask route where both admit the fleet)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        child(args.only)
+        (child_classes if args.classes else child)(args.only)
         return 0
-    cmd = [sys.executable, str(Path(__file__).resolve()), "--child"] + (["--only"] + args.only if args.only else [])
+    cmd = ([sys.executable, str(Path(__file__).resolve()), "--child"] + (["--classes"] if args.classes else [])
+           + (["--only"] + args.only if args.only else []))
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
     sys.stderr.write(p.stderr)
     if p.returncode != 0:
