@@ -35,6 +35,8 @@ without it at that plan's k that takes at most P layers off the survivors (halda
 point), `lose NAME: p=..., loaded=..., released=..., obj=..., regret=...`, or `lose NAME: infeasible`.
 --route {wave,wide,auto} (default wave) picks the GPU route of --select-devices, --scale-in, --failover and
 --move-frontier: wide serves fleets of up to 256 devices, auto takes wave wherever its gate admits the call.
+--route wide is also honoured by --cpu-only, --max-move and --reload-frontier: their solves inside a box run on the
+workgroup kernel (halda_solve_fleets_boxes_wide); with any other value they call what they always called.
 --cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
 halda_solve_bounded) and prints the usual output for that solve. Without these flags the output is unchanged.
 """
@@ -138,7 +140,7 @@ def incumbent_lines(devices: List[DeviceProfile], model: ModelProfile, plan, res
 
 
 def within_line(devices: List[DeviceProfile], model: ModelProfile, plan, max_move: int,
-                max_move_n: Optional[int] = None) -> str:
+                max_move_n: Optional[int] = None, route: str = "auto") -> str:
     """--max-move D: the best plan at the incumbent's k at most D layers per device away from it
     (halda_solve_bounded inside move_bounds' box), or "infeasible" when the box holds no plan. With
     --max-move-n Dn the box also keeps every n_i within Dn of the incumbent's (move_box)."""
@@ -147,11 +149,12 @@ def within_line(devices: List[DeviceProfile], model: ModelProfile, plan, max_mov
     k, w, n = plan
     if max_move_n is None:
         head = f"within {max_move}"
-        r = halda_solve_bounded_batch([devices], model, [move_bounds(w, max_move)], [k], kv_bits="4bit")[0]
+        r = halda_solve_bounded_batch([devices], model, [move_bounds(w, max_move)], [k], kv_bits="4bit",
+                                      route=route)[0]
     else:
         head = f"within {max_move} (n within {max_move_n})"
         r = halda_solve_bounded_batch([devices], model, [move_box(w, n, max_move, max_move_n)], [k],
-                                      kv_bits="4bit")[0]
+                                      kv_bits="4bit", route=route)[0]
     if r is None:
         return f"{head}: infeasible"
     moved = sum(abs(int(a) - int(b)) for a, b in zip(r.w, w))
@@ -177,13 +180,15 @@ def frontier_lines(devices: List[DeviceProfile], model: ModelProfile, plan, budg
     return out
 
 
-def reload_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_seconds: Optional[float]) -> List[str]:
+def reload_lines(devices: List[DeviceProfile], model: ModelProfile, plan, max_seconds: Optional[float],
+                 route: Optional[str] = None) -> List[str]:
     """--reload-frontier [SECONDS]: one line per point of halda_reload_frontier around the incumbent (kv_bits
     "4bit" like the solve above)."""
     from ..solver.boxes import halda_reload_frontier
 
     out = []
-    for j, pt in enumerate(halda_reload_frontier(devices, model, plan, max_seconds, kv_bits="4bit")):
+    extra = {} if route is None else {"route": route}
+    for j, pt in enumerate(halda_reload_frontier(devices, model, plan, max_seconds, kv_bits="4bit", **extra)):
         if pt.plan is None:
             out.append(f"reload {j}: infeasible")
         else:
@@ -347,7 +352,9 @@ def _parser() -> argparse.ArgumentParser:
                    help="After the solution, print the best sub-fleet with exactly d devices left out for every "
                         "d up to D (default: every subset), and the selection over them")
     o.add_argument("--route", choices=("wave", "wide", "auto"), default="wave",
-                   help="With --select-devices, --scale-in, --failover or --move-frontier: the GPU route -- wave "
+                   help="With --cpu-only, --max-move or --reload-frontier: wide solves inside the box on the workgroup "
+                        "kernel (fleets of up to 256 devices), any other value as before. "
+                        "With --select-devices, --scale-in, --failover or --move-frontier: the GPU route -- wave "
                         "(default: fleets of up to 64 devices), wide (up to 256 devices) or auto (wave where its gate "
                         "admits the call)")
     o.add_argument("--keep", nargs="+", metavar="NAME_OR_INDEX", default=[],
@@ -437,12 +444,15 @@ def main(argv=None) -> int:
 
     if not args.quiet:
         print(f"\n{bar}\nRunning HALDA solver...\n{bar}")
+    # --route wide reaches the box-taking entries too (--cpu-only, --max-move, --reload-frontier): the workgroup
+    # kernel of halda_solve_fleets_boxes_wide; any other value leaves their calls as they were
+    wide = {"route": "wide"} if args.route == "wide" else {}
     if n_max is None:
         result = halda_solve(devices, model, mip_gap=args.mip_gap, plot=not args.no_plot, kv_bits="4bit")
     else:
         from ..solver.bounds import halda_solve_bounded
 
-        result = halda_solve_bounded(devices, model, n_max=n_max, kv_bits="4bit")
+        result = halda_solve_bounded(devices, model, n_max=n_max, kv_bits="4bit", **wide)
 
     if args.quiet:
         print(f"k={result.k}, obj={result.obj_value:.6f}")
@@ -491,9 +501,9 @@ def main(argv=None) -> int:
             print(line)
         if args.max_move is not None:
             if args.max_move_n is None:
-                print(within_line(devices, model, incumbent, args.max_move))
+                print(within_line(devices, model, incumbent, args.max_move, **wide))
             else:
-                print(within_line(devices, model, incumbent, args.max_move, args.max_move_n))
+                print(within_line(devices, model, incumbent, args.max_move, args.max_move_n, **wide))
         if args.move_frontier is not None:
             try:
                 lines = frontier_lines(devices, model, incumbent, args.move_frontier, args.route)
@@ -505,7 +515,7 @@ def main(argv=None) -> int:
         if args.reload_frontier is not None:
             try:
                 lines = reload_lines(devices, model, incumbent,
-                                     None if args.reload_frontier == float("inf") else args.reload_frontier)
+                                     None if args.reload_frontier == float("inf") else args.reload_frontier, **wide)
             except ValueError as e:
                 print(f"error: --reload-frontier: {e}", file=sys.stderr)
                 return 2

@@ -35,6 +35,7 @@
 
 #include "halda.h"
 #include "halda_boxes.h"
+#include "halda_boxes_wide.h"
 #include "halda_wide.h"
 #include "halda_partition.h"
 #include "halda_partition_classes.h"
@@ -60,6 +61,7 @@ bool in_host_block(const void *p, size_t bytes) {
 #include "halda_prims.hpp"
 #include "halda_solve.hpp"
 #include "halda_sweep.hpp"
+#include "halda_boxes_wide.hpp"
 #include "halda_rank.hpp"
 
 // ------------------------------------------------------------------ host side
@@ -3216,6 +3218,145 @@ int halda_solve_fleets_boxes_host(void *ctx, const halda_model *model, const hal
     const halda_boxes db = {boxes->n_box, bdev(0), bdev(1), bdev(2), bdev(3)};
     halda_fleet_result r = stage::bind_result(base, R, *out_h);
     rc = solve_boxes(ctx, model, &d, ks, n_k, &db, &r, s, nd);
+    if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- many boxes beyond one wave
+// halda_solve_fleets_boxes_wide (include/halda_boxes_wide.h): halda_sweep_boxes_wide_kernel, one 256-thread
+// workgroup per (box, fleet) on a persistent grid; the gate is fleets of 1 .. 256 devices, n_box in 1 .. 65535,
+// n_k <= 64, n_box * n_fleets * n_k < 2^31, the LDS slice within the LDS budget and one workgroup's workspace
+// slice within the global-table budget. No x / c. The grid and the workspace are launch_wide's.
+int halda_boxes_wide_bytes(int32_t max_devices, int32_t max_R, int32_t any_k_gt_1, int64_t *lds, int64_t *global) {
+    if (max_devices < 1 || max_R < 0 || !lds || !global)
+        return fail(HALDA_E_ARG, "halda_boxes_wide_bytes: max_devices < 1, max_R < 0 or a NULL result");
+    if (max_devices > 4096 || max_R > (1 << 24)) {  // far outside the gate; no overflow below
+        *lds = *global = INT64_MAX;
+        return HALDA_OK;
+    }
+    const BoxesWideSlice sl = boxes_wide_slice(max_devices, max_R, any_k_gt_1 != 0);
+    *lds = sl.lds;
+    *global = sl.global;
+    return HALDA_OK;
+}
+
+// The longest row of a call: R = W - sum wlo <= L / ks[0] - min_devices (ks ascends, every wlo >= 1).
+static int boxes_wide_max_r(const halda_model &model, const halda_fleets &F, const int32_t *ks) {
+    return std::max(0, model.L / ks[0] - F.min_devices);
+}
+
+static int check_boxes_wide_args(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                                 int32_t n_k, const halda_boxes *boxes, const halda_fleet_result *out,
+                                 const char *who_c) {
+    const std::string who = who_c;
+    if (!ctx || !model || !fleets || !ks || !boxes || !out)
+        return fail(HALDA_E_ARG, who + ": NULL ctx/model/fleets/ks/boxes/out");
+    if (boxes->n_box < 1 || boxes->n_box > 65535) return fail(HALDA_E_ARG, who + ": n_box must be in 1..65535");
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    if (const int rc = check_fleets_args(model, fleets, ks, n_k, out)) return rc;
+    if (out->x || out->c || out->x_off) return fail(HALDA_E_ARG, who + ": x / c are not produced, pass NULL");
+    if (F.max_devices > kWideMaxM)
+        return fail(HALDA_E_ARG, who + ": every fleet must have 1 .. " + std::to_string(kWideMaxM) + " devices");
+    if (n_k > 64) return fail(HALDA_E_ARG, who + ": n_k must be <= 64");
+    if (int64_t(boxes->n_box) * F.n_fleets * n_k >= (int64_t(1) << 31))
+        return fail(HALDA_E_ARG, who + ": n_box * n_fleets * n_k must be < 2^31");
+    const int max_r = boxes_wide_max_r(*model, F, ks);
+    if (max_r > (1 << 24)) return fail(HALDA_E_ARG, who + ": the slice exceeds the LDS budget");
+    const BoxesWideSlice sl = boxes_wide_slice(F.max_devices, max_r, ks[n_k - 1] > 1);
+    if (sl.lds > kLdsBudget)
+        return fail(HALDA_E_ARG, who + ": the slice of " + std::to_string(sl.lds) + " B exceeds the LDS budget of " +
+                                     std::to_string(kLdsBudget) + " B");
+    if (sl.global > kGlobalTableBudget)
+        return fail(HALDA_E_ARG, who + ": the workspace slice of " + std::to_string(sl.global) +
+                                     " B exceeds the global-table budget of " + std::to_string(kGlobalTableBudget) +
+                                     " B");
+    return HALDA_OK;
+}
+
+int halda_solve_fleets_boxes_wide(void *ctx, const halda_model *model, const halda_fleets *fleets, const int32_t *ks,
+                                  int32_t n_k, const halda_boxes *boxes, halda_fleet_result *out, void *stream) {
+    if (const int rc = check_boxes_wide_args(ctx, model, fleets, ks, n_k, boxes, out, "halda_solve_fleets_boxes_wide"))
+        return rc;
+    const halda_fleets &F = *fleets;
+    if (F.n_fleets <= 0) return HALDA_OK;
+    Ctx *c = static_cast<Ctx *>(ctx);
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    const int max_r = boxes_wide_max_r(*model, F, ks);
+    const BoxesWideSlice sl = boxes_wide_slice(F.max_devices, max_r, ks[n_k - 1] > 1);
+    SweepArgs A = {};
+    static_cast<halda_model &>(A.Mo) = *model;
+    A.Mo.bvo = model_bvo(*model);
+    A.F = F;
+    A.n_k = n_k;
+    for (int j = 0; j < n_k; ++j) {
+        A.ks[j] = ks[j];
+        A.Ws[j] = model->L / ks[j];
+    }
+    A.out = FleetOut(*out);
+    A.outs = (out->obj_by_k ? kOutObk : 0) | (out->status ? kOutSt : 0);
+    A.mmax = F.max_devices;
+    A.r1max = max_r + 1;
+    A.uM = F.min_devices == F.max_devices ? F.max_devices : 0;
+    A.gstride = (sl.global + 255) & ~int64_t(255);
+    const void *fn = reinterpret_cast<const void *>(halda_sweep_boxes_wide_kernel);
+    HIP_TRY(Ctx::ensure_lds(fn, sl.lds));
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kWideThreads, size_t(sl.lds)));
+    const int64_t items = int64_t(boxes->n_box) * F.n_fleets;
+    const unsigned grid = unsigned(std::max<int64_t>(
+        1, std::min<int64_t>({int64_t(c->cus) * std::max(1, per_cu), items, kGlobalTableBudget / A.gstride})));
+    const size_t gneed = size_t(A.gstride) * size_t(grid);
+    if (gneed > c->gtab_bytes) {
+        if (c->gtab) HIP_TRY(hipFree(c->gtab));
+        c->gtab = nullptr;
+        c->gtab_bytes = 0;
+        HIP_TRY(hipMalloc(&c->gtab, gneed));
+        c->gtab_bytes = gneed;
+    }
+    // the global tables are per context: this launch runs after their previous user on another stream
+    if (const int rc = order_after_previous(c, s)) return rc;
+    A.gtab = static_cast<unsigned char *>(c->gtab);
+    const BoxesWideArgs Bs{boxes->w_min, boxes->w_max, boxes->n_min, boxes->n_max, boxes->n_box};
+    hipLaunchKernelGGL(halda_sweep_boxes_wide_kernel, dim3(grid), dim3(kWideThreads), size_t(sl.lds), s, A, Bs);
+    HIP_TRY(hipGetLastError());
+    return HALDA_OK;
+}
+
+// The host variant on the staging layer: the table once, each bound array that was passed once, the
+// n_box * n_fleets result rows back (lay_table / lay_result, as halda_solve_fleets_boxes_host lays them).
+int halda_solve_fleets_boxes_wide_host(void *ctx, const halda_model *model, const halda_fleets *fh, const int32_t *ks,
+                                       int32_t n_k, const halda_boxes *boxes, halda_fleet_result *out_h) {
+    if (const int rc =
+            check_boxes_wide_args(ctx, model, fh, ks, n_k, boxes, out_h, "halda_solve_fleets_boxes_wide_host"))
+        return rc;
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int64_t nf = fh->n_fleets, nb = boxes->n_box;
+    if (nf <= 0) return HALDA_OK;
+    const int64_t nd = fh->dev_off[nf];
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    const int32_t *bsrc[4] = {boxes->w_min, boxes->w_max, boxes->n_min, boxes->n_max};
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    size_t o_b[4];
+    for (int a = 0; a < 4; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nb * nd) : 0;
+    const stage::ResultSlots R = stage::lay_result(lay, *out_h, nb * nf, nb * nd, size_t(nb) * nf * n_k, 0);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *fh, s);
+    for (int a = 0; a < 4 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nb * nd, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*fh, base, T);
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    const halda_boxes db = {boxes->n_box, bdev(0), bdev(1), bdev(2), bdev(3)};
+    halda_fleet_result r = stage::bind_result(base, R, *out_h);
+    rc = halda_solve_fleets_boxes_wide(ctx, model, &d, ks, n_k, &db, &r, s);
     if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));

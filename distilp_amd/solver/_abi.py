@@ -1,6 +1,6 @@
 """The C ABI of libhalda (include/halda.h, and include/halda_boxes.h beside it) as ctypes declarations: every
 struct, in header order, and the prototype of every function. `_libhalda.load_library` applies PROTOTYPES,
-BOXES_PROTOTYPES, WIDE_PROTOTYPES (include/halda_wide.h) PARTITION_PROTOTYPES (include/halda_partition.h) and PARTITION_CLASSES_PROTOTYPES
+BOXES_PROTOTYPES, BOXES_WIDE_PROTOTYPES (include/halda_boxes_wide.h), WIDE_PROTOTYPES (include/halda_wide.h) PARTITION_PROTOTYPES (include/halda_partition.h) and PARTITION_CLASSES_PROTOTYPES
 (include/halda_partition_classes.h) to the library it opens, so no call can reach a function with ctypes' default `int` arguments
 and result. tests/test_abi.py compiles halda.h and compares every struct's size and field offsets, and every
 prototype's arity and result type, with this module; tests/test_boxes.py does the same for halda_boxes.h.
@@ -204,6 +204,14 @@ BOXES_STRUCTS = {HaldaBoxesC: "halda_boxes"}
 BOXES_PROTOTYPES = {
     **_with_host("halda_solve_fleets_boxes", *_table, *_ks, POINTER(HaldaBoxesC), _out),
     **_knob("boxes"),
+}
+
+# include/halda_boxes_wide.h, the companion header of the workgroup route of the many-boxes entry (it takes
+# halda_boxes.h's struct): its prototypes, applied by load_library with the others (tests/test_boxes_wide.py holds
+# them to that header)
+BOXES_WIDE_PROTOTYPES = {
+    **_with_host("halda_solve_fleets_boxes_wide", *_table, *_ks, POINTER(HaldaBoxesC), _out),
+    "halda_boxes_wide_bytes": (c_int, [c_int32] * 3 + [POINTER(c_int64)] * 2),
 }
 
 # include/halda_wide.h, the companion header of the workgroup routes of the move budget and the change frontier

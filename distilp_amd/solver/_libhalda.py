@@ -16,7 +16,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from ._abi import BOXES_PROTOTYPES, EXPORTS, PROTOTYPES, HaldaBatchC, HaldaResultC  # noqa: F401 -- EXPORTS: the binding's surface
+from ._abi import BOXES_PROTOTYPES, BOXES_WIDE_PROTOTYPES, EXPORTS, PROTOTYPES, HaldaBatchC, HaldaResultC  # noqa: F401 -- EXPORTS: the binding's surface
 from ._abi import PARTITION_CLASSES_PROTOTYPES, PARTITION_PROTOTYPES, WIDE_PROTOTYPES
 
 LIB_PATH = Path(os.environ.get("HALDA_LIB", Path(__file__).resolve().parent.parent / "libhalda.so"))
@@ -70,7 +70,7 @@ def load_library(path: Path | str | None = None):
         lib = ctypes.CDLL(str(p))
         if lib.halda_version() != ABI_VERSION:
             raise HaldaUnavailable(f"{p} has ABI {lib.halda_version()}, this binding needs {ABI_VERSION}: rebuild it")
-        for name, (restype, argtypes) in {**PROTOTYPES, **BOXES_PROTOTYPES, **WIDE_PROTOTYPES, **PARTITION_PROTOTYPES,
+        for name, (restype, argtypes) in {**PROTOTYPES, **BOXES_PROTOTYPES, **BOXES_WIDE_PROTOTYPES, **WIDE_PROTOTYPES, **PARTITION_PROTOTYPES,
                                           **PARTITION_CLASSES_PROTOTYPES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -228,7 +228,16 @@ def halda_solve_bounded_batch(fleets: Sequence[Sequence[DeviceProfile]], model: 
     any of them None, or None for no bounds), in ONE GPU call (halda_solve_fleets_boxed_host where some fleet
     has an n list, else halda_solve_fleets_bounded_host). One HALDAResult per fleet, None where no k is feasible within the bounds.
     `route`: "auto" (the context's bounds path), "general", or "tables" -- one table launch for small fleets
-    and k > 1 where the fused launch does not apply (at most 64 devices per fleet; general elsewhere)."""
+    and k > 1 where the fused launch does not apply (at most 64 devices per fleet; general elsewhere), or
+    "wide" -- the workgroup kernel of boxes.py (halda_solve_fleets_boxes_wide: fleets of up to 256 devices, the
+    bounds as its one box; ValueError outside boxes.check_gate_wide), obj_value priced by one evaluation call."""
+    if route == "wide":
+        from .boxes import halda_solve_boxes_batch  # (boxes.py imports this module)
+
+        fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
+        if len(bounds) != len(fleets):
+            raise ValueError(f"{len(bounds)} bounds for {len(fleets)} fleets")
+        return halda_solve_boxes_batch(fleets, model, [list(bounds)], k_candidates, kv_bits, device, "wide")[0]
     check_route(route)
     kv_factor = kv_bits_to_factor(kv_bits)
     fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
@@ -260,7 +269,8 @@ def halda_solve_bounded(devs: Sequence[DeviceProfile], model: ModelProfile, w_mi
     """halda_solve with every device's layer count kept in [w_min_i, w_max_i] and, with n_min / n_max, its GPU
     share in [n_min_i, n_max_i]; RuntimeError, as halda_solve raises it, when no k is feasible within the
     bounds. `route`: as halda_solve_bounded_batch."""
-    check_route(route)
+    if route != "wide":
+        check_route(route)
     devs = list(devs)
     if n_min is not None or n_max is not None:
         b = (w_min, w_max, n_min, n_max)

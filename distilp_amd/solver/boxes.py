@@ -27,14 +27,14 @@ import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
 from ._abi import HaldaBoxesC, HaldaFleetResultC
-from ._libhalda import get_context, last_route, ptr, set_path
+from ._libhalda import STATUS_INFEASIBLE, STATUS_OPTIMAL, get_context, last_route, ptr, set_path
 from .bounds import INT32_MAX, Bounds, _check_entry
-from .budget import check_incumbent
-from .coefficients import HALDAResult
+from .budget import GLOBAL_BUDGET, LDS_BUDGET, _align16, check_incumbent
+from .coefficients import HALDAResult, assign_sets
 from .fleets import FleetSolve, FleetTable, _host_struct, fleet_constants, fleet_table, model_struct, open_x_offsets
 from .halda import _batch_k_list, _batch_results, _positive_ks
 from .lower import kv_bits_to_factor
-from .plans import Incumbent
+from .plans import Incumbent, evaluate_table
 from .subfleets import ItemTable
 
 MAX_BOXES = 65535  # halda_solve_fleets_boxes: blockIdx.y is the box
@@ -137,14 +137,150 @@ def _solve_planes(table: FleetTable, model: ModelProfile, pos: List[int], planes
     return res, nb, ext
 
 
+# ------------------------------------------------------------------ route "wide": the workgroup kernel
+WIDE_MAX_DEVICES = 256  # one thread per device of a 256-thread workgroup
+WIDE_MAX_K = 64         # the k list travels in the kernel arguments
+ROUTES = (None, "wide")  # None: halda_solve_fleets_boxes, as before the route keyword existed
+
+
+def check_boxes_route(route) -> None:
+    if route not in ROUTES:
+        raise ValueError(f"route: {route!r} is not one of {ROUTES}")
+
+
+def boxes_wide_bytes(max_devices: int, max_R: int, any_k_gt_1: bool):
+    """(lds, global) of one workgroup of halda_sweep_boxes_wide_kernel (csrc/halda_boxes_wide.hpp boxes_wide_slice,
+    the figures halda_boxes_wide_bytes returns). LDS: two value planes of max_R + 1 doubles, two row buffers of 256
+    doubles per table (G, and H for some k > 1), per device wlo, the reduction slots, the per-k objectives.
+    Workspace: G and H as max_devices rows of max_R + 1 doubles, one arg-min uint16 per (device, state), the plan
+    row and its n."""
+    M, S, kc = int(max_devices), int(max_R) + 1, bool(any_k_gt_1)
+    o = _align16(2 * S * 8)
+    o = _align16(o + 2 * 256 * 8)
+    o = _align16(o + (2 * 256 * 8 if kc else 0))
+    o = _align16(o + M * 4)
+    o = _align16(o + 2 * 4 * 8)
+    lds = _align16(o + 64 * 8)
+    g = _align16(M * S * 8)
+    g = _align16(g + (M * S * 8 if kc else 0))
+    g = _align16(g + M * S * 2)
+    g = _align16(g + M * 2)
+    return lds, _align16(g + M * 4)
+
+
+def check_gate_wide(max_devices: int, min_devices: int, n_box: int, n_fleets: int, ks: Sequence[int], L: int) -> None:
+    """The gate of route "wide" (halda_solve_fleets_boxes_wide's), from the shapes alone: ValueError outside it.
+    `ks`: the positive k of the call, ascending."""
+    if min_devices < 1 or max_devices > WIDE_MAX_DEVICES:
+        raise ValueError(f"route 'wide' needs fleets of 1 .. {WIDE_MAX_DEVICES} devices, got {min_devices} .. "
+                         f"{max_devices}")
+    if not 1 <= n_box <= MAX_BOXES:
+        raise ValueError(f"{n_box} boxes: 1 .. {MAX_BOXES} in one call")
+    if not 1 <= len(ks) <= WIDE_MAX_K:
+        raise ValueError(f"{len(ks)} k candidates on route 'wide': 1 .. {WIDE_MAX_K} in one call")
+    if n_box * n_fleets * len(ks) >= 2**31:
+        raise ValueError(f"{n_box} boxes x {n_fleets} fleets x {len(ks)} k on route 'wide': the product must be < 2^31")
+    max_R = max(0, int(L) // int(ks[0]) - int(min_devices))
+    lds, glob = boxes_wide_bytes(max_devices, max_R, int(ks[-1]) > 1)
+    if lds > LDS_BUDGET:
+        raise ValueError(f"rows of {max_R + 1} entries need {lds} B of LDS per fleet on route 'wide', beyond the "
+                         f"{LDS_BUDGET} B budget")
+    if glob > GLOBAL_BUDGET:
+        raise ValueError(f"rows of {max_R + 1} entries on fleets of up to {max_devices} devices need {glob} B of "
+                         f"workspace per fleet, beyond the {GLOBAL_BUDGET} B budget")
+
+
+def _check_planes(planes, nd: int):
+    planes = [None if p is None else np.ascontiguousarray(p, np.int32) for p in planes]
+    if len(planes) != 4:
+        raise ValueError(f"planes: {len(planes)} arrays, expected (w_min, w_max, n_min, n_max)")
+    shapes = {p.shape for p in planes if p is not None}
+    if not shapes:
+        raise ValueError("planes: every array is None, the number of boxes is unknown")
+    if len(shapes) != 1 or len(next(iter(shapes))) != 2 or next(iter(shapes))[1] != nd:
+        raise ValueError(f"planes: shapes {sorted(shapes)}, expected one [n_box, {nd}]")
+    return planes, int(next(iter(shapes))[0])
+
+
+def _solve_planes_wide(table: FleetTable, model: ModelProfile, pos: List[int], planes, kv_factor: float,
+                       device: int) -> Tuple[FleetSolve, int]:
+    """One halda_solve_fleets_boxes_wide_host call, then ONE halda_eval_plans call that prices every returned
+    plan: (the FleetSolve of all n_box * n_fleets (box, fleet) rows, box-major, without x / c, n_box). obj_by_k is
+    the kernel's (halda_eval_plans' device-formed bits of each k's plan); obj_value is re-formed on the host from
+    the evaluation's x / c as every entry of this package forms it, so it equals halda_evaluate_plan's of the
+    returned (k, w, n) bit for bit. The kernel returns the plan of its best k alone (ascending k, strict "<" on
+    the device-formed objectives): that plan is the one candidate the host-formed value is taken on."""
+    nf, nd, nk = table.n_fleets, table.n_devices, len(pos)
+    planes, nb = _check_planes(planes, nd)
+    sizes = table.sizes()
+    check_gate_wide(int(sizes.max()), int(sizes.min()), nb, nf, pos, int(model.L))
+    ctx = get_context(device)
+    res = FleetSolve(best_k=np.zeros(nb * nf, np.int32), obj_value=np.zeros(nb * nf), w=np.zeros(nb * nd, np.int32),
+                     n=np.zeros(nb * nd, np.int32), obj_by_k=np.zeros((nb * nf, nk)),
+                     status=np.zeros((nb * nf, nk), np.int32), ks=pos)
+    r = HaldaFleetResultC(*(ptr(a) for a in (res.best_k, res.obj_value, res.w, res.n, res.obj_by_k, res.status)),
+                          None, None, None)
+    fs, keep = _host_struct(table)
+    bx = HaldaBoxesC(nb, *(ptr(p) for p in planes))
+    karr = np.asarray(pos, np.int32)
+    m = model_struct(model, kv_factor)
+    ctx.call("halda_solve_fleets_boxes_wide_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, nk,
+             ctypes.byref(bx), ctypes.byref(r))
+    del keep
+    if (res.best_k > 0).any():
+        rows = _box_rows(table, nb)
+        ev = evaluate_table(rows, model, res.best_k, res.w, res.n, kv_factor, device).evaluations(rows, model)
+        res.obj_value[:] = [e.obj_value if k > 0 else np.inf for e, k in zip(ev, res.best_k)]
+    return res, nb
+
+
+def _box_rows(table: FleetTable, nb: int) -> FleetTable:
+    """The (box, fleet) rows as a table of n_box * n_fleets fleets, box-major: the table's fields once per box."""
+    nd = table.n_devices
+    off = (table.dev_off[None, :-1] + nd * np.arange(nb, dtype=np.int64)[:, None]).ravel()
+    names = [f for f in FleetTable.__dataclass_fields__ if f != "dev_off"]
+    return FleetTable(dev_off=np.append(off, nb * nd).astype(np.int64),
+                      **{f: np.ascontiguousarray(np.tile(getattr(table, f), nb)) for f in names})
+
+
+def _wide_results(fleets, table: FleetTable, res: FleetSolve, nb: int) -> List[List[Optional[HALDAResult]]]:
+    """out[b][f] of a wide solve: a HALDAResult, or None where no k is feasible inside box b. A status other than
+    OPTIMAL / INFEASIBLE raises, as _batch_results raises it."""
+    bad = (res.status != STATUS_OPTIMAL) & (res.status != STATUS_INFEASIBLE)
+    if bad.any():
+        i, j = map(int, np.argwhere(bad)[0])
+        raise RuntimeError(f"libhalda rejected the (box {i // table.n_fleets}, fleet {i % table.n_fleets}, "
+                           f"k={res.ks[j]}) MILP with status {int(res.status[i, j])}")
+    nf, nd = table.n_fleets, table.n_devices
+    sets = [assign_sets(list(d)) for d in fleets]
+    out = []
+    for b in range(nb):
+        row = []
+        for f in range(nf):
+            k = int(res.best_k[b * nf + f])
+            a, e = b * nd + int(table.dev_off[f]), b * nd + int(table.dev_off[f + 1])
+            row.append(None if k == 0 else HALDAResult(w=[int(v) for v in res.w[a:e]], n=[int(v) for v in res.n[a:e]],
+                                                       k=k, obj_value=float(res.obj_value[b * nf + f]), sets=sets[f]))
+        out.append(row)
+    return out
+
+
 def solve_boxes_table(table: FleetTable, model: ModelProfile, pos: List[int], planes, kv_factor: float,
-                      device: int = 0) -> List[FleetSolve]:
+                      device: int = 0, route: Optional[str] = None) -> List[FleetSolve]:
     """One halda_solve_fleets_boxes_host call on a packed table. `planes` = (w_min, w_max, n_min, n_max), each
     int32 [n_box, n_devices] or None (no bound on that side in any box). Per box the FleetSolve
     (want_x="open") of its slice: views of one result buffer, with the box's x / c rows from 0 and the per-table
-    x_off."""
-    res, nb, ext = _solve_planes(table, model, pos, planes, kv_factor, device)
+    x_off. route="wide": one halda_solve_fleets_boxes_wide_host call (fleets of up to 256 devices, check_gate_wide)
+    and one evaluation call; the slices then hold no x / c and obj_value is the host-formed objective."""
+    check_boxes_route(route)
     nf, nd = table.n_fleets, table.n_devices
+    if route == "wide":
+        res, nb = _solve_planes_wide(table, model, pos, planes, kv_factor, device)
+        return [FleetSolve(best_k=res.best_k[b * nf:(b + 1) * nf], obj_value=res.obj_value[b * nf:(b + 1) * nf],
+                           w=res.w[b * nd:(b + 1) * nd], n=res.n[b * nd:(b + 1) * nd],
+                           obj_by_k=res.obj_by_k[b * nf:(b + 1) * nf], status=res.status[b * nf:(b + 1) * nf], ks=pos)
+                for b in range(nb)]
+    res, nb, ext = _solve_planes(table, model, pos, planes, kv_factor, device)
     xsel = res.x_off[:nf * len(pos)]  # box 0's offsets are the table's own
     return [FleetSolve(best_k=res.best_k[b * nf:(b + 1) * nf], obj_value=res.obj_value[b * nf:(b + 1) * nf],
                        w=res.w[b * nd:(b + 1) * nd], n=res.n[b * nd:(b + 1) * nd],
@@ -154,14 +290,19 @@ def solve_boxes_table(table: FleetTable, model: ModelProfile, pos: List[int], pl
 
 def halda_solve_boxes_batch(fleets: Sequence[Sequence[DeviceProfile]], model: ModelProfile,
                             boxes: Sequence[Sequence[Bounds]], k_candidates: Optional[Iterable[int]] = None,
-                            kv_bits: str = "8bit", device: int = 0) -> List[List[Optional[HALDAResult]]]:
+                            kv_bits: str = "8bit", device: int = 0,
+                            route: Optional[str] = None) -> List[List[Optional[HALDAResult]]]:
     """Many fleets under many boxes, the fleets packed once and every box in ONE GPU call
     (halda_solve_fleets_boxes_host). `boxes[b]` is what halda_solve_bounded_batch takes as `bounds`: one entry
     per fleet, each None, (w_min, w_max) or (w_min, w_max, n_min, n_max). out[b][f] is a HALDAResult, or None
     where no k is feasible inside box b, and equals
     halda_solve_bounded_batch(fleets, model, boxes[b], k_candidates, kv_bits, route="tables")[f] bit for bit.
     ValueError before any packing or GPU work for an empty box list, more than 65,535 boxes, a box without one
-    entry per fleet, or a bad entry (bounds._check_entry's rules)."""
+    entry per fleet, or a bad entry (bounds._check_entry's rules).
+    route="wide": the workgroup kernel (halda_solve_fleets_boxes_wide: fleets of up to 256 devices, at most 64 k,
+    check_gate_wide -- ValueError outside it, before packing) and one evaluation call that prices every returned
+    plan; out[b][f].obj_value is then halda_evaluate_plan's of the returned plan, bit for bit."""
+    check_boxes_route(route)
     kv_factor = kv_bits_to_factor(kv_bits)
     fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
     boxes = check_boxes(boxes, [len(d) for d in fleets])
@@ -173,9 +314,15 @@ def halda_solve_boxes_batch(fleets: Sequence[Sequence[DeviceProfile]], model: Mo
     if not Ks:
         return [[None] * len(fleets) for _ in boxes]
     pos = _positive_ks(Ks)
+    if route == "wide" and pos:
+        sizes = [len(d) for d in fleets]
+        check_gate_wide(max(sizes), min(sizes), len(boxes), len(fleets), pos, int(model.L))
     table = fleet_table(fleets, model)
     if not pos:
         return [[None] * len(fleets) for _ in boxes]
+    if route == "wide":
+        res, nb = _solve_planes_wide(table, model, pos, box_planes(table, boxes, checked=True), kv_factor, device)
+        return _wide_results(fleets, table, res, nb)
     res, nb, _ = _solve_planes(table, model, pos, box_planes(table, boxes, checked=True), kv_factor, device)
     # the (box, fleet) rows seen as n_box * n_fleets fleets: the table's extents, classes and constants once per box
     nf, nd = table.n_fleets, table.n_devices
@@ -188,14 +335,16 @@ def halda_solve_boxes_batch(fleets: Sequence[Sequence[DeviceProfile]], model: Mo
 
 def halda_solve_boxes(devs: Sequence[DeviceProfile], model: ModelProfile, boxes: Sequence[Bounds],
                       k_candidates: Optional[Iterable[int]] = None, kv_bits: str = "8bit",
-                      device: int = 0) -> List[Optional[HALDAResult]]:
+                      device: int = 0, route: Optional[str] = None) -> List[Optional[HALDAResult]]:
     """halda_solve_boxes_batch for one fleet: `boxes[b]` is None, (w_min, w_max) or (w_min, w_max, n_min, n_max);
-    out[b] is the best plan inside box b, None where it holds none."""
+    out[b] is the best plan inside box b, None where it holds none. route: as halda_solve_boxes_batch."""
+    check_boxes_route(route)
     try:
         boxes = [[b] for b in boxes]
     except TypeError:
         raise ValueError(f"boxes: {boxes!r} is not a sequence of boxes") from None
-    return [r[0] for r in halda_solve_boxes_batch([list(devs)], model, boxes, k_candidates, kv_bits, device)]
+    extra = {} if route is None else {"route": route}  # (no route: the call as it always was)
+    return [r[0] for r in halda_solve_boxes_batch([list(devs)], model, boxes, k_candidates, kv_bits, device, **extra)]
 
 
 def reload_caps(w0: Sequence[int], s_disk: Sequence[float], W: int, max_points: int = 256,
@@ -253,7 +402,7 @@ class ReloadPoint:
 
 def halda_reload_frontier(devs: Sequence[DeviceProfile], model: ModelProfile, incumbent: Incumbent,
                           max_seconds: Optional[float] = None, max_points: int = 256, kv_bits: str = "8bit",
-                          device: int = 0) -> List[ReloadPoint]:
+                          device: int = 0, route: Optional[str] = None) -> List[ReloadPoint]:
     """The best plan reachable in T seconds of reload, for every T at which the answer can change.
 
     At the incumbent's k (W = L // k), point j is the optimum inside w_max = w0 + caps[j] of
@@ -265,7 +414,9 @@ def halda_reload_frontier(devs: Sequence[DeviceProfile], model: ModelProfile, in
     strictly improve keeps the previous point's plan (which its caps also admit), halda_move_frontier's rule.
     seconds = t[j] * (k * b_layer); seconds_used is formed from the same quotients gained_i / s_disk_i, so it
     never exceeds seconds by rounding. ValueError before any GPU work for a missing or malformed incumbent (as
-    halda_move_frontier), a bad max_points or a negative max_seconds."""
+    halda_move_frontier), a bad max_points or a negative max_seconds. route: halda_solve_boxes' ("wide": fleets
+    of up to 256 devices in one launch)."""
+    check_boxes_route(route)
     devs = list(devs)
     kv_bits_to_factor(kv_bits)
     k, w0, _ = check_incumbent(incumbent, len(devs), int(model.L))
@@ -279,7 +430,7 @@ def halda_reload_frontier(devs: Sequence[DeviceProfile], model: ModelProfile, in
                           None if max_seconds is None else max_seconds / group)
     boxes: list = [(None, [a + int(c) for a, c in zip(w0, row)]) for row in caps]
     boxes.append(None)
-    res = halda_solve_boxes(devs, model, boxes, [k], kv_bits, device)
+    res = halda_solve_boxes(devs, model, boxes, [k], kv_bits, device, **({} if route is None else {"route": route}))
     free = res[-1]
     out: List[ReloadPoint] = []
     best: Optional[HALDAResult] = None

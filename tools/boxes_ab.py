@@ -16,6 +16,16 @@ The GPU work is one child process under a time limit; the parent prints one JSON
 to a file.
 
     python tools/boxes_ab.py --out profiles/boxes_ab.json
+
+--wide: the workgroup entry halda_solve_fleets_boxes_wide (one launch of halda_sweep_boxes_wide_kernel) against
+halda_solve_fleets_boxes on the same resident arrays, timed the same way. Beyond one wave the latter is its loop route
+(one general-route halda_solve_fleets_boxed call per box): 1 fleet x 100 devices x 64 boxes on 160 layers at
+ks = [1] and at ks = [2] (W = 80 < 100 devices: every box settles INFEASIBLE on the status ladder), 1 x 70 x 64 boxes
+at ks = [2] (feasible), 1 x 256 x 8 boxes on 320 layers. In-gate, against the table route: 256 x 16 x 8 boxes at
+ks = [2] on 80 layers. End to end, wall clock: halda_reload_frontier(route="wide") of a 100-device fleet against the
+default route.
+
+    python tools/boxes_ab.py --wide --out profiles/boxes_wide_ab.json
 """
 
 from __future__ import annotations
@@ -155,17 +165,132 @@ def child() -> None:
     print(json.dumps(out))
 
 
+def child_wide() -> None:
+    sys.path.insert(0, str(REPO))
+    import numpy as np
+    import torch
+
+    torch.cuda.init()  # torch's HIP runtime first
+    from distilp_amd.common import DeviceProfile, ModelProfileSplit
+    from distilp_amd.solver import boxes as bx
+    from distilp_amd.solver import halda_reload_frontier
+    from distilp_amd.solver._abi import HaldaBoxesC, HaldaFleetResultC
+    from distilp_amd.solver._libhalda import get_context, last_error
+    from distilp_amd.solver.bounds import halda_solve_bounded
+    from distilp_amd.solver.fleets import BYTE_FIELDS, F64_FIELDS, _fleets_struct, fleet_table, model_struct, solve_table
+    from distilp_amd.synth import load_model_dict, synth_fleet
+
+    base_model = ModelProfileSplit.model_validate(load_model_dict()).to_model_profile()
+    dev = torch.device("cuda", 0)
+    ctx = get_context(0)
+    lib = ctx.lib
+    stream = torch.cuda.Stream(dev)
+    legs = ("wide", "base")
+    out = {"gpu": torch.cuda.get_device_name(0), "reps": REPS, "rounds": ROUNDS}
+    fields = ("dev_off", "os_class", "flags") + F64_FIELDS + BYTE_FIELDS
+
+    def fleet(seed, M):
+        return [DeviceProfile.model_validate(d) for d in synth_fleet(seed, M)]
+
+    for name, nf, M, nb, ks, L in (("a_1x100_64boxes_k1_L160", 1, 100, 64, [1], 160),
+                                   ("b_1x100_64boxes_k2_L160", 1, 100, 64, [2], 160),
+                                   ("b2_1x70_64boxes_k2_L160", 1, 70, 64, [2], 160),
+                                   ("c_1x256_8boxes_k1_L320", 1, 256, 8, [1], 320),
+                                   ("d_256x16_8boxes_k2_L80", 256, 16, 8, [2], 80)):
+        model = base_model.model_copy(update={"L": L})
+        table = fleet_table([fleet(1000 + M + s, M) for s in range(nf)], model)
+        karr = np.asarray(ks, np.int32)
+        inc = solve_table(table.perturbed(np.random.default_rng(7)), model, ks, 0.5)
+        w0 = np.maximum(1, inc.w.astype(np.int64))  # (an infeasible k leaves zeros: the ladder starts at 1)
+        hi = np.stack([w0 + j for j in range(nb)]).astype(np.int32)  # box j: every device may gain j layers
+        arrs = {f: torch.from_numpy(np.ascontiguousarray(getattr(table, f))).to(dev) for f in fields}
+        fs = _fleets_struct(table, lambda f: arrs[f].data_ptr())
+        nd = table.n_devices
+        i32, f64 = torch.int32, torch.float64
+        o = [torch.empty(nb * nf, dtype=i32, device=dev), torch.empty(nb * nf, dtype=f64, device=dev),
+             torch.empty(nb * nd, dtype=i32, device=dev), torch.empty(nb * nd, dtype=i32, device=dev)]
+        bt = torch.from_numpy(hi).to(dev)
+        r = HaldaFleetResultC(*[t.data_ptr() for t in o], None, None, None, None, None)
+        bs = HaldaBoxesC(nb, None, bt.data_ptr(), None, None)
+        m = model_struct(model, 0.5)
+
+        def leg(kind):
+            fn = lib.halda_solve_fleets_boxes_wide if kind == "wide" else lib.halda_solve_fleets_boxes
+            ts = []
+            for rep in range(WARM + REPS):
+                for t in o:
+                    t.fill_(-7)
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                rc = fn(ctx.ctx, ctypes.byref(m), ctypes.byref(fs), karr.ctypes.data, len(ks), ctypes.byref(bs),
+                        ctypes.byref(r), ctypes.c_void_p(stream.cuda_stream))
+                if rc != 0:
+                    raise RuntimeError(f"{kind} failed ({rc}): {last_error(lib)}")
+                e1.record(stream)
+                stream.synchronize()
+                if rep >= WARM:
+                    ts.append(e0.elapsed_time(e1))
+            route = "wide" if kind == "wide" else bx.last_boxes_route(ctx)
+            return statistics.median(ts), route, [t.cpu().numpy().copy() for t in o]
+
+        rounds = {k: [] for k in legs}
+        res, routes = {}, {}
+        for _ in range(ROUNDS):  # alternate the legs
+            for kind in legs:
+                ms_med, routes[kind], res[kind] = leg(kind)
+                rounds[kind].append(ms_med * 1e3)
+        med = {k: statistics.median(rounds[k]) for k in legs}
+        a, b = res["wide"], res["base"]
+        fin = np.isfinite(b[1])
+        rel = float(np.max(np.abs(a[1][fin] - b[1][fin]) / np.maximum(1.0, np.abs(b[1][fin])), initial=0.0))
+        out[name] = {"workload": f"{nf} fleets x {M} devices x {nb} boxes, ks = {ks}, L = {L}", "routes": routes,
+                     "same_best_k": bool(np.array_equal(a[0], b[0])),
+                     "same_feasible": bool(np.array_equal(np.isfinite(a[1]), fin)), "max_rel_obj_diff": rel,
+                     "feasible": int((a[0] > 0).sum()), "slices": nb * nf, "base_over_wide": med["base"] / med["wide"],
+                     **{f"{k}_event_us": med[k] for k in legs}, **{f"{k}_rounds_us": rounds[k] for k in legs}}
+
+    # end to end: the reload frontier of one 100-device fleet on 160 layers, route "wide" against the default route
+    model = base_model.model_copy(update={"L": 160})
+    devs = fleet(2000, 100)
+    old = halda_solve_bounded(fleet(3000, 100), model, k_candidates=[1], kv_bits="4bit")
+    inc = (1, list(old.w), list(old.n))
+
+    def timed(fn):
+        res = fn()
+        ts = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            res = fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts), ts, res
+
+    got = {}
+    for _ in range(2):  # alternate: the second round's figures are kept
+        got["wide"] = timed(lambda: halda_reload_frontier(devs, model, inc, kv_bits="4bit", route="wide"))
+        got["default"] = timed(lambda: halda_reload_frontier(devs, model, inc, kv_bits="4bit"))
+    pw, pd = got["wide"][2], got["default"][2]
+    out["e_end_to_end_reload_frontier_1x100_k1_L160"] = {
+        "points": len(pw), "wide_ms": got["wide"][0], "wide_all_ms": got["wide"][1], "default_ms": got["default"][0],
+        "default_all_ms": got["default"][1], "default_over_wide": got["default"][0] / got["wide"][0],
+        "max_rel_obj_diff": max((abs(a.obj_value - b.obj_value) / max(1.0, abs(b.obj_value)) for a, b in zip(pw, pd)),
+                                default=0.0) if len(pw) == len(pd) else None}
+    print(json.dumps(out))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", help="also write the JSON line to this file")
     ap.add_argument("--timeout", type=float, default=400.0, help="time limit of the GPU child process, seconds")
+    ap.add_argument("--wide", action="store_true",
+                    help="time halda_solve_fleets_boxes_wide against halda_solve_fleets_boxes (see above)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        child()
+        (child_wide if args.wide else child)()
         return 0
-    p = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child"], capture_output=True, text=True,
-                       timeout=args.timeout)
+    p = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child"] + (["--wide"] if args.wide else []),
+                       capture_output=True, text=True, timeout=args.timeout)
     sys.stderr.write(p.stderr)
     if p.returncode != 0:
         return p.returncode
