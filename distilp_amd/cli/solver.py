@@ -37,6 +37,10 @@ point), `lose NAME: p=..., loaded=..., released=..., obj=..., regret=...`, or `l
 --move-frontier: wide serves fleets of up to 256 devices, auto takes wave wherever its gate admits the call.
 --route wide is also honoured by --cpu-only, --max-move and --reload-frontier: their solves inside a box run on the
 workgroup kernel (halda_solve_fleets_boxes_wide); with any other value they call what they always called.
+--leave-one-out-bounded (with --cpu-only or --max-move) prints, after everything else, one
+`without NAME (bounded): k=K, obj=OBJ` line per device (or `without NAME (bounded): infeasible`): the fleet without
+that device inside the survivors' part of the box those flags built (halda_leave_one_out with bounds=; with
+--max-move at the incumbent's k). --leave-one-out itself is unchanged.
 --cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
 halda_solve_bounded) and prints the usual output for that solve. Without these flags the output is unchanged.
 """
@@ -93,6 +97,34 @@ def leave_one_out_lines(devices: List[DeviceProfile], model: ModelProfile, mip_g
     without it (halda_leave_one_out, kv_bits "4bit" like the solve above)."""
     res = halda_leave_one_out(devices, model, mip_gap=mip_gap, kv_bits="4bit")
     return [f"without {d.name}: " + ("infeasible" if r is None else f"k={r.k}, obj={r.obj_value:.6f}")
+            for d, r in zip(devices, res)]
+
+
+def bounded_box(n_max: Optional[List[int]], plan, max_move: Optional[int], max_move_n: Optional[int]):
+    """The box the main output's bounded solves ran in, as one bounds entry: --cpu-only's n_max, --max-move's
+    move box around the incumbent `plan` (with --max-move-n its n side too), both where both were given (the
+    lower n_max of the two per device)."""
+    from ..solver.bounds import move_bounds, move_box
+
+    w_min = w_max = n_min = None
+    n_hi = None if n_max is None else list(n_max)
+    if max_move is not None:
+        _, w, n = plan
+        if max_move_n is None:
+            w_min, w_max = move_bounds(w, max_move)
+        else:
+            w_min, w_max, n_min, box_hi = move_box(w, n, max_move, max_move_n)
+            n_hi = box_hi if n_hi is None else [min(a, b) for a, b in zip(n_hi, box_hi)]
+    return (w_min, w_max) if n_min is None and n_hi is None else (w_min, w_max, n_min, n_hi)
+
+
+def leave_one_out_bounded_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: float, box,
+                                k: Optional[int] = None) -> List[str]:
+    """--leave-one-out-bounded: one line per dropped device -- the best k and obj_value of the fleet without it
+    inside the survivors' part of `box` (halda_leave_one_out with bounds=; at the incumbent's k alone when the
+    box is a move box around it)."""
+    res = halda_leave_one_out(devices, model, None if k is None else [k], mip_gap=mip_gap, kv_bits="4bit", bounds=box)
+    return [f"without {d.name} (bounded): " + ("infeasible" if r is None else f"k={r.k}, obj={r.obj_value:.6f}")
             for d, r in zip(devices, res)]
 
 
@@ -324,6 +356,9 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--no-plot", action="store_true", help="Disable plotting of k vs objective curve")
     o.add_argument("--leave-one-out", action="store_true",
                    help="After the solution, print the best k and objective of the fleet without each device")
+    o.add_argument("--leave-one-out-bounded", action="store_true",
+                   help="With --cpu-only or --max-move: after everything else, print the best k and objective of the "
+                        "fleet without each device inside the same bounds (with --max-move: at that plan's k)")
     o.add_argument("--kv-sweep", nargs="+", metavar="BITS", choices=("4bit", "8bit", "fp16", "bf16"),
                    help="After the solution, print the best k and objective at each KV precision (e.g. 4bit 8bit fp16)")
     o.add_argument("--n-kv-sweep", nargs="+", type=int, metavar="N",
@@ -400,6 +435,8 @@ def main(argv=None) -> int:
         parser.error("--max-move-n requires --max-move")
     if args.max_move_n is not None and args.max_move_n < 0:
         parser.error("--max-move-n must be >= 0")
+    if args.leave_one_out_bounded and not args.cpu_only and args.max_move is None:
+        parser.error("--leave-one-out-bounded requires --cpu-only or --max-move")
     if args.move_frontier is not None and not args.evaluate_solution:
         parser.error("--move-frontier requires --evaluate-solution")
     if args.move_frontier is not None and args.move_frontier < 0:
@@ -538,6 +575,11 @@ def main(argv=None) -> int:
                 return 2
             for line in lines:
                 print(line)
+    if args.leave_one_out_bounded:
+        box = bounded_box(n_max, incumbent, args.max_move, args.max_move_n)
+        k = incumbent[0] if args.max_move is not None else None
+        for line in leave_one_out_bounded_lines(devices, model, args.mip_gap, box, k):
+            print(line)
     return 0
 
 

@@ -36,6 +36,7 @@
 #include "halda.h"
 #include "halda_boxes.h"
 #include "halda_boxes_wide.h"
+#include "halda_subfleets_boxed.h"
 #include "halda_wide.h"
 #include "halda_partition.h"
 #include "halda_partition_classes.h"
@@ -166,6 +167,8 @@ struct Ctx {
     size_t fleet_scratch_bytes = 0;
     uint8_t *sub_tab = nullptr;     // halda_solve_subfleets: the expanded table of the expansion route
     size_t sub_tab_bytes = 0;
+    int32_t *sub_bnd = nullptr;     // halda_solve_subfleets_boxed: the expansion route's gathered bound arrays
+    size_t sub_bnd_bytes = 0;
     uint8_t *sel_buf = nullptr;     // halda_solve_subsets: combo lists, per-(d, fleet) records, per-candidate results
     size_t sel_bytes = 0;
     int64_t scale_chunk = 0;        // halda_set_change_subsets_chunk: a launch's scratch cap (0: the default)
@@ -176,6 +179,9 @@ struct Ctx {
     // 2 expansion; subsets: 1 fused, 2 expansion, 3 mixed; variants: 1 fused, 2 loop; plans: 1 fused, 2 two
     // launches; bounds: 1 fused, 2 general, 3 table launch; boxes: 1 register launch, 3 table launch, 2 loop.
     lrec::Knob knob[lrec::kFamilies];
+    // halda_solve_subfleets_boxed's own (include/halda_subfleets_boxed.h): path 0 automatic, 1 always expansion;
+    // routes 1 register launch, 3 table launch, 2 expansion
+    lrec::Knob sub_box;
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -791,12 +797,17 @@ int finish(Ctx *c, hipStream_t s, lrec::Record r) {
 // Step two: evf0, the family's kernel (`enqueue` launches it and answers its status), evf1, the record and the
 // family's route. An error leaves the route and the record as they were.
 template <class Enqueue>
-int launch_one(Ctx *c, hipStream_t s, lrec::Record r, lrec::Family family, int route, Enqueue &&enqueue) {
+int launch_one(Ctx *c, hipStream_t s, lrec::Record r, lrec::Knob &knob, int route, Enqueue &&enqueue) {
     if (c->timing) HIP_TRY(hipEventRecord(c->evf0, s));
     int rc = enqueue();
     if (rc == HALDA_OK) rc = finish(c, s, r);
-    if (rc == HALDA_OK) c->knob[family].route = route;
+    if (rc == HALDA_OK) knob.route = route;
     return rc;
+}
+
+template <class Enqueue>
+int launch_one(Ctx *c, hipStream_t s, lrec::Record r, lrec::Family family, int route, Enqueue &&enqueue) {
+    return launch_one(c, s, r, c->knob[family], route, std::forward<Enqueue>(enqueue));
 }
 
 // halda_set_<family>_path / halda_last_<family>_route (the admissible paths: lrec::kKnobRules)
@@ -1313,6 +1324,7 @@ void halda_free(void *ctx) {
     if (c->fleet_scratch) (void)hipFree(c->fleet_scratch);
     if (c->gtab) (void)hipFree(c->gtab);
     if (c->sub_tab) (void)hipFree(c->sub_tab);
+    if (c->sub_bnd) (void)hipFree(c->sub_bnd);
     if (c->sel_buf) (void)hipFree(c->sel_buf);
     if (c->var_desc) (void)hipFree(c->var_desc);
     for (auto &x : c->sws) {
@@ -2118,6 +2130,43 @@ int halda_solve_fleets_host(void *ctx, const halda_model *model, const halda_fle
 int halda_set_subfleets_path(void *ctx, int path) { return set_family_path(ctx, lrec::kSubfleets, path); }
 int halda_last_subfleets_route(void *ctx, int *route) { return last_family_route(ctx, lrec::kSubfleets, route); }
 
+// The expansion routes' first step (halda_solve_subfleets, halda_solve_subfleets_boxed): the listed devices as a
+// compact table (16 double and 2 byte arrays of nd entries) in the context's grow-only sub_tab, after the previous
+// user of the context's shared scratch. *X: that table under V's shape summary, its dev_off the items' sub_off;
+// *nd_: its devices. total: sub_off[n_items] when the caller knows it, -1 to read it back where needed.
+static int expand_items(Ctx *c, const halda_fleets &table, const halda_subfleets &I, const halda_fleets &V,
+                        int64_t total, hipStream_t s, halda_fleets *X_, int64_t *nd_) {
+    int64_t nd = total >= 0 ? total : int64_t(I.n_items) * I.max_devices;
+    if (total < 0 && I.min_devices != I.max_devices) {
+        HIP_TRY(hipMemcpyAsync(&nd, I.sub_off + I.n_items, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (nd < int64_t(I.n_items) * I.min_devices || nd > int64_t(I.n_items) * I.max_devices)
+            return fail(HALDA_E_ARG, "halda_subfleets: sub_off[n_items] does not fit min_devices / max_devices");
+    }
+    const size_t nd8 = (size_t(nd) * 8 + 255) & ~size_t(255), nd1 = (size_t(nd) + 255) & ~size_t(255);
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sub_tab, &c->sub_tab_bytes, 16 * nd8 + 2 * nd1);
+        if (rc != HALDA_OK) return rc;
+    }
+    const SubArgs S{I.parent, I.sub_off, I.sub_idx};
+    ExpandOut E;
+    for (int a = 0; a < 16; ++a) E.f[a] = reinterpret_cast<double *>(c->sub_tab + nd8 * size_t(a));
+    E.os_class = c->sub_tab + 16 * nd8;
+    E.flags = E.os_class + nd1;
+    hipLaunchKernelGGL(halda_expand_subfleets_kernel, dim3(unsigned((I.n_items + 3) / 4)), dim3(256), 0, s, table, S,
+                       int(I.n_items), E);
+    HIP_TRY(hipGetLastError());
+    halda_fleets X = V;
+    X.dev_off = I.sub_off;
+    X.os_class = E.os_class;
+    X.flags = E.flags;
+    for (int a = 0; a < stage::kFields; ++a) X.*stage::kField[a] = E.f[a];
+    *X_ = X;
+    *nd_ = nd;
+    return HALDA_OK;
+}
+
 // total: sub_off[n_items] when the caller knows it (the host variant), -1 to read it back where needed
 static int solve_subfleets(void *ctx, const halda_model *model, const halda_fleets *table,
                            const halda_subfleets *items, const int32_t *ks, int32_t n_k, halda_fleet_result *out,
@@ -2154,32 +2203,10 @@ static int solve_subfleets(void *ctx, const halda_model *model, const halda_flee
             });
         }
     }
-    // expansion: the listed devices as a compact table (16 double and 2 byte arrays of nd entries)
-    int64_t nd = total >= 0 ? total : int64_t(I.n_items) * I.max_devices;
-    if (total < 0 && I.min_devices != I.max_devices) {
-        HIP_TRY(hipMemcpyAsync(&nd, I.sub_off + I.n_items, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (nd < int64_t(I.n_items) * I.min_devices || nd > int64_t(I.n_items) * I.max_devices)
-            return fail(HALDA_E_ARG, "halda_subfleets: sub_off[n_items] does not fit min_devices / max_devices");
-    }
-    const size_t nd8 = (size_t(nd) * 8 + 255) & ~size_t(255), nd1 = (size_t(nd) + 255) & ~size_t(255);
-    {
-        int rc = order_after_previous(c, s);
-        if (rc == HALDA_OK) rc = grow(&c->sub_tab, &c->sub_tab_bytes, 16 * nd8 + 2 * nd1);
-        if (rc != HALDA_OK) return rc;
-    }
-    ExpandOut E;
-    for (int a = 0; a < 16; ++a) E.f[a] = reinterpret_cast<double *>(c->sub_tab + nd8 * size_t(a));
-    E.os_class = c->sub_tab + 16 * nd8;
-    E.flags = E.os_class + nd1;
-    hipLaunchKernelGGL(halda_expand_subfleets_kernel, dim3(unsigned((I.n_items + 3) / 4)), dim3(256), 0, s, *table, S,
-                       int(I.n_items), E);
-    HIP_TRY(hipGetLastError());
-    halda_fleets X = V;
-    X.dev_off = I.sub_off;
-    X.os_class = E.os_class;
-    X.flags = E.flags;
-    for (int a = 0; a < stage::kFields; ++a) X.*stage::kField[a] = E.f[a];
+    // expansion: the ordinary sweep on the listed devices as a compact table
+    halda_fleets X;
+    int64_t nd = 0;
+    if (const int rc = expand_items(c, *table, I, V, total, s, &X, &nd)) return rc;
     c->knob[lrec::kSubfleets].route = 2;
     return halda_solve_fleets(ctx, model, &X, ks, n_k, out, s);
 }
@@ -3218,6 +3245,196 @@ int halda_solve_fleets_boxes_host(void *ctx, const halda_model *model, const hal
     const halda_boxes db = {boxes->n_box, bdev(0), bdev(1), bdev(2), bdev(3)};
     halda_fleet_result r = stage::bind_result(base, R, *out_h);
     rc = solve_boxes(ctx, model, &d, ks, n_k, &db, &r, s, nd);
+    if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- sub-fleets under boxes
+// halda_solve_subfleets_boxed (include/halda_subfleets_boxed.h): items (parent fleet, index list, box) solved as
+// the fleets of their listed devices under the box's entries for those devices, every output bit for bit what
+// halda_solve_fleets_boxed writes for the materialised list with gathered bounds under bounds path 3.
+// Register route (1): every list of one length <= kK1MaxM and the boxed entry's fused gate over (n_items, that
+// length) -> halda_sweep_subfleets_box_kernel. Table route (3): else under path 3's table gate over the lists'
+// shape summary -> halda_sweep_subfleets_box_tables_kernel on plan_sweep's slice. Neither uses context scratch.
+// Expansion route (2; everything else and every call on path 1; the specification of the other two):
+// halda_expand_subfleets_kernel writes the compact table into sub_tab, halda_expand_sub_bounds_kernel the arrays
+// that were passed into sub_bnd (both grow-only, per context, after order_after_previous), and
+// halda_solve_fleets_boxed runs on them under bounds path 3, which is put back on return.
+int halda_set_subfleets_boxed_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path != 0 && path != 1)
+        return fail(HALDA_E_ARG, "sub-fleets boxed path must be 0 (automatic) or 1 (always expand)");
+    c->sub_box.path = path;
+    return HALDA_OK;
+}
+
+int halda_last_subfleets_boxed_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->sub_box.route;
+    return HALDA_OK;
+}
+
+static int check_sub_boxes(const halda_sub_boxes *boxes) {
+    if (!boxes) return fail(HALDA_E_ARG, "halda_solve_subfleets_boxed: NULL boxes");
+    if (boxes->n_box < 1 || boxes->n_box > 65535) return fail(HALDA_E_ARG, "n_box must be in 1..65535");
+    return HALDA_OK;
+}
+
+// total: sub_off[n_items] when the caller knows it (the host variant), -1 to read it back where needed
+static int solve_subfleets_boxed(void *ctx, const halda_model *model, const halda_fleets *table,
+                                 const halda_subfleets *items, const int32_t *ks, int32_t n_k,
+                                 const halda_sub_boxes *boxes, halda_fleet_result *out, void *stream, int64_t total) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !table || !items || !ks || !out)
+        return fail(HALDA_E_ARG, "halda_solve_subfleets_boxed: NULL ctx/model/table/items/ks/out");
+    {
+        const int rc = check_sub_boxes(boxes);
+        if (rc != HALDA_OK) return rc;
+    }
+    const halda_subfleets &I = *items;
+    if (I.n_items <= 0) return HALDA_OK;
+    if (!I.parent || !I.sub_off || !I.sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (table->n_fleets <= 0) return fail(HALDA_E_ARG, "halda_solve_subfleets_boxed: the table has no fleets");
+    // the items seen as a batch of fleets: the table's arrays under the items' count and length summary
+    halda_fleets V = *table;
+    V.n_fleets = I.n_items;
+    V.min_devices = I.min_devices;
+    V.max_devices = I.max_devices;
+    {
+        const int rc = check_fleets_args(model, &V, ks, n_k, out);
+        if (rc != HALDA_OK) return rc;
+    }
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    const halda_sub_boxes &B = *boxes;
+    const SubArgs S{I.parent, I.sub_off, I.sub_idx};
+    const SubBoxArgs X{B.w_min, B.w_max, B.n_min, B.n_max, B.item_box, table->n_fleets};
+    // the fused kernels index (item, k) instances with 32 bits
+    if (c->sub_box.path == 0 && c->fleets_fused && n_k <= 64 && int64_t(I.n_items) * n_k < (int64_t(1) << 31)) {
+        SweepPlan p;
+        const int rc = plan_sweep(c, *model, V, ks, n_k, *out, &p);
+        if (rc != HALDA_OK) return rc;
+        SweepArgs &A = p.A;
+        if (p.kind == kRegAlone && A.uM > 0 && A.uM <= kK1MaxM) {
+            begin_one(c, A);  // every item is solved in the one launch: nothing is flagged or handed back
+            return launch_one(c, s, lrec::Record::reg_alone, c->sub_box, 1, [&]() -> int {
+                hipLaunchKernelGGL(halda_sweep_subfleets_box_kernel, dim3(p.grid1), dim3(p.block1), 0, s, A, S, X);
+                return launched();
+            });
+        }
+        if (V.min_devices >= 1 && V.max_devices <= kK1MaxM && p.slice <= kLdsBudget) {
+            begin_one(c, A);
+            const void *fn = reinterpret_cast<const void *>(halda_sweep_subfleets_box_tables_kernel);
+            int per_cu = 0;
+            HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
+            const unsigned grid =
+                unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, int64_t(I.n_items))));
+            return launch_one(c, s, lrec::Record::tables_alone, c->sub_box, 3, [&]() -> int {
+                hipLaunchKernelGGL(halda_sweep_subfleets_box_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, A,
+                                   S, X);
+                return launched();
+            });
+        }
+    }
+    // expansion: the compact table, then the passed bound arrays gathered into the same layout
+    halda_fleets E;
+    int64_t nd = 0;
+    if (const int rc = expand_items(c, *table, I, V, total, s, &E, &nd)) return rc;
+    const int32_t *bsrc[4] = {B.w_min, B.w_max, B.n_min, B.n_max};
+    const size_t nd4 = (size_t(nd) * 4 + 255) & ~size_t(255);
+    if (const int rc = grow(&c->sub_bnd, &c->sub_bnd_bytes, 4 * nd4)) return rc;
+    SubBoundsOut G;
+    for (int a = 0; a < 4; ++a)
+        G.a[a] = bsrc[a] ? reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(c->sub_bnd) + nd4 * size_t(a)) : nullptr;
+    if (bsrc[0] || bsrc[1] || bsrc[2] || bsrc[3]) {
+        hipLaunchKernelGGL(halda_expand_sub_bounds_kernel, dim3(unsigned((I.n_items + 3) / 4)), dim3(256), 0, s, *table,
+                           S, X, int(I.n_items), G);
+        HIP_TRY(hipGetLastError());
+    }
+    const halda_box one = {G.a[0], G.a[1], G.a[2], G.a[3]};
+    const lrec::PathOverride tables(c->knob[lrec::kBounds], 3);  // (put back on return)
+    c->sub_box.route = 2;
+    return halda_solve_fleets_boxed(ctx, model, &E, ks, n_k, &one, out, s);
+}
+
+int halda_solve_subfleets_boxed(void *ctx, const halda_model *model, const halda_fleets *table,
+                                const halda_subfleets *items, const int32_t *ks, int32_t n_k,
+                                const halda_sub_boxes *boxes, halda_fleet_result *out, void *stream) {
+    return solve_subfleets_boxed(ctx, model, table, items, ks, n_k, boxes, out, stream, -1);
+}
+
+// The host variant on halda_stage.hpp's layouts: the parent table crosses PCIe once, each bound array that was
+// passed once (all n_box planes), the item arrays and item_box once; the results over the items come back.
+int halda_solve_subfleets_boxed_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                                     const halda_subfleets *ih, const int32_t *ks, int32_t n_k,
+                                     const halda_sub_boxes *boxes, halda_fleet_result *out_h) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !ih || !ks || !out_h)
+        return fail(HALDA_E_ARG, "halda_solve_subfleets_boxed_host: NULL ctx/model/table/items/ks/out");
+    {
+        const int rc = check_sub_boxes(boxes);
+        if (rc != HALDA_OK) return rc;
+    }
+    if (ih->n_items <= 0) return HALDA_OK;
+    if (!ih->parent || !ih->sub_off || !ih->sub_idx) return fail(HALDA_E_ARG, "halda_subfleets has a NULL array");
+    if (th->n_fleets <= 0 || !th->dev_off) return fail(HALDA_E_ARG, "halda_solve_subfleets_boxed_host: empty table");
+    if (n_k <= 0) return fail(HALDA_E_ARG, "n_k must be in 1..1024");
+    if (!out_h->best_k || !out_h->obj_value || !out_h->w || !out_h->n)
+        return fail(HALDA_E_ARG, "halda_fleet_result: NULL");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf], n = ih->n_items, nb = boxes->n_box;
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    int64_t lmin = 0, lmax = 0;
+    {
+        const int rc = check_items_host(*th, *ih, &lmin, &lmax);
+        if (rc != HALDA_OK) return rc;
+    }
+    if (lmax > 4096) return fail(HALDA_E_ARG, "halda_subfleets: a list of more than 4096 devices");
+    if ((ih->min_devices || ih->max_devices) && (lmin != ih->min_devices || lmax != ih->max_devices))
+        return fail(HALDA_E_ARG, "halda_subfleets: min_devices / max_devices are not the lists' shortest and longest "
+                                 "length (" + std::to_string(lmin) + ", " + std::to_string(lmax) + ")");
+    if (boxes->item_box)
+        for (int64_t i = 0; i < n; ++i)
+            if (boxes->item_box[i] < 0 || boxes->item_box[i] >= nb)
+                return fail(HALDA_E_ARG, "halda_sub_boxes: item " + std::to_string(i) + " has box " +
+                                             std::to_string(boxes->item_box[i]) + " outside the call's " +
+                                             std::to_string(nb) + " boxes");
+    const int64_t tot = ih->sub_off[n];
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    // layout: the parent table, the planes that were passed, the item arrays and item_box, the results
+    const int32_t *bsrc[4] = {boxes->w_min, boxes->w_max, boxes->n_min, boxes->n_max};
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    size_t o_b[4];
+    for (int a = 0; a < 4; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nb * nd) : 0;
+    const stage::ItemsLayout IL = stage::lay_items(lay, n, tot);
+    const size_t o_ib = boxes->item_box ? lay.take(4 * n) : 0;
+    const bool xsel = stage::compact(*out_h);
+    const size_t xs = stage::xc_extent(ih->sub_off, n, n_k, 1, lmax, xsel ? out_h->x_off : nullptr);
+    const stage::ResultSlots R = stage::lay_result(lay, *out_h, n, tot, size_t(n) * n_k, xs);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    for (int a = 0; a < 4 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nb * nd, s);
+    if (rc == HALDA_OK) rc = upload(base, IL, *ih, s);
+    if (rc == HALDA_OK && boxes->item_box) rc = upload(base, o_ib, boxes->item_box, 4 * n, s);
+    if (rc == HALDA_OK && xsel) rc = upload(base, R.x_off, out_h->x_off, 8 * R.n_inst, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    halda_subfleets di = stage::rebase(*ih, base, IL);
+    di.min_devices = int32_t(lmin);
+    di.max_devices = int32_t(lmax);
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    const halda_sub_boxes db = {boxes->n_box, bdev(0), bdev(1), bdev(2), bdev(3),
+                                boxes->item_box ? reinterpret_cast<const int32_t *>(base + o_ib) : nullptr};
+    halda_fleet_result r = stage::bind_result(base, R, *out_h);
+    rc = solve_subfleets_boxed(ctx, model, &d, &di, ks, n_k, &db, &r, s, tot);
     if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));

@@ -2337,6 +2337,122 @@ __global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_bo
     else boxes_tables<BoundRec>(A, Bs, smem);
 }
 
+// ---------------------------------------------------------------- sub-fleets under boxes
+// halda_solve_subfleets_boxed: an item is (parent fleet, list of local device indices, box) -- the fleet of the
+// listed devices in list order, list position j under the box's entry for parent device idx[j]. The boxes are
+// halda_boxes planes in the PARENT table's device layout (box b's entry for table device g at b * nd + g, nd =
+// dev_off[table fleets]); outputs are halda_solve_subfleets' (per item; w / n at sub_off[i] + j). A.F is the
+// parent table under the items' count and length summary, as halda_sweep_subfleets_kernel takes it.
+struct SubBoxArgs {
+    const int32_t *w_min, *w_max, *n_min, *n_max;  // [n_box * dev_off[table_fleets]]; any may be NULL
+    const int32_t *item_box;                       // [n_items], NULL: box 0 for every item
+    int table_fleets;                              // the parent table's fleets (A.F.n_fleets is the item count)
+};
+
+// bounded_lane's gathered form: the lane's device is table device g (not d0 + lane) and its bounds lie at bg in
+// the bound arrays; d0 is where the item's w / n go. The 18 field loads and the up-to-four 4-byte bound loads
+// depend on g / bg alone, so they issue together as bounded_lane's do. kBox: the n pair too.
+template <bool kBox>
+__device__ inline BoundedLane bounded_lane_at(const SweepArgs &A, const SubBoxArgs &X, int lane, int64_t g, int64_t bg,
+                                              int64_t d0, int M) {
+    BoundedLane in;
+    const bool kl = lane < A.n_k;
+    in.kj = A.ks[kl ? lane : 0];
+    in.Wj = kl ? A.Ws[lane] : 0;
+    in.d0 = d0;
+    in.M = M;
+    in.mf = load_fields(A.F, g);
+    in.wmn = X.w_min ? X.w_min[bg] : 0;
+    in.wmx = X.w_max ? X.w_max[bg] : 0x7fffffff;
+    in.nmn = 0;
+    in.nmx = 0x7fffffff;
+    if constexpr (kBox) {
+        in.nmn = X.n_min ? X.n_min[bg] : 0;
+        in.nmx = X.n_max ? X.n_max[bg] : 0x7fffffff;
+    }
+    return in;
+}
+
+// One item on either fused route. Wave-uniform through the scalar cache (the item arrays, item_box and dev_off are
+// read-only to the kernel): the item's list offset, its parent's first device, its box and the plane stride. Lane
+// j's list entry is the first vector round trip (lanes past the list read entry 0, as bounded_lane's read device
+// 0), the fields and bounds of device dev_off[parent] + idx the second. From there the lane is bounded_fleet's,
+// unedited: the same code on the same values as the materialised list's own boxed launch, hence the same bits.
+template <class Rec, bool kTables>
+__device__ inline void sub_box_item(const SweepArgs &A, const SubArgs &S, const SubBoxArgs &X, int i, int64_t nd,
+                                    const WaveCtx &w, int lane) {
+    const int64_t so = sload_i64(S.sub_off + i);
+    const int M = kTables ? int(sload_i64(S.sub_off + i + 1) - so) : A.uM;
+    const int64_t base = sload_i64(A.F.dev_off + sload_i32(S.parent + i));
+    const int64_t plane = X.item_box ? int64_t(sload_i32(X.item_box + i)) * nd : 0;
+    const int64_t g = base + S.sub_idx[so + (lane < M ? lane : 0)];
+    bounded_fleet<Rec, kTables>(A, i, w, Wave(lane),
+                                bounded_lane_at<std::is_same<Rec, BoxRec>::value>(A, X, lane, g, plane + g, so, M));
+}
+
+// The register form -- one wave per item, kSweepWavesPerBlock per workgroup, every list of A.uM <= kK1MaxM
+// devices; the host sends only item batches the boxed entry's fused gate admits (plan_sweep's kRegAlone over
+// (n_items, A.uM)). The record type is the launch's, chosen once (wave-uniform): a box record when an n array
+// was passed, else a bound record, as halda_solve_fleets_boxed chooses its kernel.
+__global__ __launch_bounds__(64 * kSweepWavesPerBlock, HALDA_SWEEP_WAVES_PER_SIMD) void halda_sweep_subfleets_box_kernel(
+    SweepArgs A, SubArgs S, SubBoxArgs X) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * kSweepWavesPerBlock + int(threadIdx.x >> 6));
+    if (i >= A.F.n_fleets) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t nd = sload_i64(A.F.dev_off + X.table_fleets);
+    __shared__ uint8_t dparg[kSweepWavesPerBlock][64 * kDpLanes];
+    WaveCtx w = {};
+    w.dparg = dparg[threadIdx.x >> 6];
+    if (X.n_min || X.n_max) sub_box_item<BoxRec, false>(A, S, X, i, nd, w, lane);
+    else sub_box_item<BoundRec, false>(A, S, X, i, nd, w, lane);
+}
+
+// The table form: one wave per workgroup on a persistent grid with the table kernel's LDS slice (plan_sweep's for
+// the unbounded batch of the lists' shapes: it depends on no bound, so one slice serves every box), items dealt
+// b, b + grid, ... -- the leave-one-out items of one parent are adjacent, so neighbouring workgroups read the same
+// table lines from L2. Lists of any lengths 1 .. kK1MaxM, every k. The record type is chosen outside the item
+// loop (one loop per type: the choice inside it costs the boxes table kernel its spills).
+template <class Rec>
+__device__ inline void sub_box_tables(const SweepArgs &A, const SubArgs &S, const SubBoxArgs &X, unsigned char *smem) {
+    const int lane = threadIdx.x;
+    const WaveCtx w = wave_ctx(smem, make_slice(A.mmax, A.r1max, A.tab, A.tab_kc));
+    const int64_t nd = sload_i64(A.F.dev_off + X.table_fleets);
+    const int n = A.F.n_fleets;
+    for (int64_t it = blockIdx.x; it < n; it += gridDim.x) sub_box_item<Rec, true>(A, S, X, int(it), nd, w, lane);
+}
+
+__global__ __launch_bounds__(64, HALDA_SOLVE_WAVES_PER_SIMD) void halda_sweep_subfleets_box_tables_kernel(
+    SweepArgs A, SubArgs S, SubBoxArgs X) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (X.n_min || X.n_max) sub_box_tables<BoxRec>(A, S, X, smem);
+    else sub_box_tables<BoundRec>(A, S, X, smem);
+}
+
+// halda_expand_sub_bounds_kernel: the expansion route's second gather, beside halda_expand_subfleets_kernel -- one
+// wave per item copies, for each bound array that was passed, its box's entries of the listed devices into a
+// compact array in the items' layout (entry sub_off[i] + j), on which the boxed entry then runs.
+struct SubBoundsOut {
+    int32_t *a[4];  // w_min, w_max, n_min, n_max of the compact table; NULL where the input is
+};
+
+__global__ __launch_bounds__(256) void halda_expand_sub_bounds_kernel(halda_fleets T, SubArgs S, SubBoxArgs X,
+                                                                        int n_items, SubBoundsOut E) {
+    const int i = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * 4 + int(threadIdx.x >> 6));
+    if (i >= n_items) return;
+    const int lane = int(threadIdx.x & 63);
+    const int64_t so = sload_i64(S.sub_off + i);
+    const int len = int(sload_i64(S.sub_off + i + 1) - so);
+    const int64_t nd = sload_i64(T.dev_off + X.table_fleets);
+    const int64_t at = sload_i64(T.dev_off + sload_i32(S.parent + i)) +
+                       (X.item_box ? int64_t(sload_i32(X.item_box + i)) * nd : 0);
+    const int32_t *src[4] = {X.w_min, X.w_max, X.n_min, X.n_max};
+    for (int j = lane; j < len; j += 64) {
+        const int64_t bg = at + S.sub_idx[so + j];
+        for (int a = 0; a < 4; ++a)
+            if (src[a]) E.a[a][so + j] = src[a][bg];
+    }
+}
+
 // ---------------------------------------------------------------- total move budget (halda_solve_fleets_budget)
 // The fixed-k problem at the incumbent's k with sum_i |w_i - w0_i| <= B added: the constraint couples the
 // devices, so it is not a narrowing of column bounds. Both plans sum to W, hence sum |delta| = 2 sum delta+;

@@ -206,6 +206,19 @@ BOXES_PROTOTYPES = {
     **_knob("boxes"),
 }
 
+# include/halda_subfleets_boxed.h, the companion header of sub-fleets under boxes: halda_boxes' fields and the
+# items' box indices; applied by load_library with the others (tests/test_subfleets_bounded.py holds them to
+# that header)
+class HaldaSubBoxesC(ctypes.Structure):
+    _fields_ = [("n_box", c_int32)] + _ptrs("w_min", "w_max", "n_min", "n_max", "item_box")
+
+
+SUBBOX_STRUCTS = {HaldaSubBoxesC: "halda_sub_boxes"}
+SUBBOX_PROTOTYPES = {
+    **_with_host("halda_solve_subfleets_boxed", *_table, _items, *_ks, POINTER(HaldaSubBoxesC), _out),
+    **_knob("subfleets_boxed"),
+}
+
 # include/halda_boxes_wide.h, the companion header of the workgroup route of the many-boxes entry (it takes
 # halda_boxes.h's struct): its prototypes, applied by load_library with the others (tests/test_boxes_wide.py holds
 # them to that header)

@@ -25,7 +25,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..common import DeviceProfile, ModelProfile
-from ._abi import BYTE_FIELDS, F64_FIELDS, HaldaFleetResultC, HaldaSubfleetsC
+from ._abi import BYTE_FIELDS, F64_FIELDS, HaldaFleetResultC, HaldaSubBoxesC, HaldaSubfleetsC
 from ._libhalda import get_context, last_route, ptr, set_path
 from .coefficients import HALDAResult
 from .fleets import (_PACKER, DEV_CPU_RATE, DEV_HEAD, FleetSolve, FleetTable, _host_struct, _scratch,
@@ -193,11 +193,14 @@ def check_item_heads(fleets, table: FleetTable, parent: np.ndarray, heads: np.nd
 
 
 def solve_items(table: FleetTable, parent: np.ndarray, sub_off: np.ndarray, sub_idx: np.ndarray,
-                model: ModelProfile, pos: List[int], kv_factor: float, device: int = 0, fleets=None
-                ) -> List[Optional[HALDAResult]]:
+                model: ModelProfile, pos: List[int], kv_factor: float, device: int = 0, fleets=None,
+                boxed=None) -> List[Optional[HALDAResult]]:
     """One halda_solve_subfleets_host call: the parent table and the item arrays go to the GPU, the items'
     x / c of the k that can be optimal come back (open_x_offsets over the list lengths), and halda.py's
-    _batch_results builds each HALDAResult from them and the items' constants and classes (item_table)."""
+    _batch_results builds each HALDAResult from them and the items' constants and classes (item_table).
+    boxed = (planes, item_box): the call is halda_solve_subfleets_boxed_host instead -- `planes` the four
+    [n_box, n_devices] int32 arrays of boxes.box_planes over the parent table (None: no bound on that side),
+    `item_box` int32 [n] -- and the results are the items' best plans inside their boxes."""
     gt = item_table(table, parent, sub_off, sub_idx, model)
     if fleets is not None:
         check_item_heads(fleets, table, parent, gt.heads, model)
@@ -225,14 +228,23 @@ def solve_items(table: FleetTable, parent: np.ndarray, sub_off: np.ndarray, sub_
     it = HaldaSubfleetsC(n, int(lens.min()), int(lens.max()), ptr(parent), ptr(sub_off), ptr(sub_idx))
     karr = np.asarray(pos, np.int32)
     m = model_struct(model, kv_factor)
-    ctx.call("halda_solve_subfleets_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it),
-             karr.ctypes.data, nk, ctypes.byref(r))
+    if boxed is None:
+        ctx.call("halda_solve_subfleets_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it),
+                 karr.ctypes.data, nk, ctypes.byref(r))
+    else:
+        planes, item_box = boxed
+        n_box = next(int(a.shape[0]) for a in planes if a is not None)
+        bx = HaldaSubBoxesC(n_box, *(ptr(a) for a in planes), ptr(item_box))
+        ctx.call("halda_solve_subfleets_boxed_host", ctx.ctx, ctypes.byref(m), ctypes.byref(fs), ctypes.byref(it),
+                 karr.ctypes.data, nk, ctypes.byref(bx), ctypes.byref(r))
     del keep
     return _batch_results(gt, res, pos, model, consts=gt.consts)
 
 
-def _solve_arrays(fleets, model, parent, sub_off, sub_idx, k_candidates, kv_bits, device):
-    """The items (validated arrays) over `fleets`, chunk by chunk: each parent packed once."""
+def _solve_arrays(fleets, model, parent, sub_off, sub_idx, k_candidates, kv_bits, device, boxed=None):
+    """The items (validated arrays) over `fleets`, chunk by chunk: each parent packed once. boxed = (boxes,
+    item_box): boxes.check_boxes' result over `fleets` and the items' box indices (subfleets_bounded.py); the
+    planes are written once, from the one packed table."""
     Ks = _batch_k_list(model, k_candidates)  # halda_solve_batch's k list and k rules
     kv_factor = kv_bits_to_factor(kv_bits)
     n = len(parent)
@@ -243,13 +255,19 @@ def _solve_arrays(fleets, model, parent, sub_off, sub_idx, k_candidates, kv_bits
     if not pos:
         return [None] * n
     chunks = plan_chunks(np.diff(sub_off), SUBFLEET_CHUNK_DEVICES)
+    planes = item_box = None
+    if boxed is not None:
+        from .boxes import box_planes  # (boxes.py imports this module)
+
+        planes, item_box = box_planes(table, boxed[0], checked=True), np.ascontiguousarray(boxed[1], np.int32)
     if len(chunks) == 1:  # the usual call: the result builder's list as it is
-        return solve_items(table, parent, sub_off, sub_idx, model, pos, kv_factor, device, fleets)
+        return solve_items(table, parent, sub_off, sub_idx, model, pos, kv_factor, device, fleets,
+                           None if boxed is None else (planes, item_box))
     out: List[Optional[HALDAResult]] = []
     for a, b in chunks:
         lo, hi = int(sub_off[a]), int(sub_off[b])
         out.extend(solve_items(table, parent[a:b], sub_off[a:b + 1] - lo, sub_idx[lo:hi], model, pos, kv_factor,
-                               device, fleets))
+                               device, fleets, None if boxed is None else (planes, item_box[a:b])))
     return out
 
 
@@ -297,12 +315,20 @@ def halda_leave_one_out_batch(
     mip_gap: Optional[float] = 1e-4,
     kv_bits: str = "8bit",
     device: int = 0,
+    bounds=None,
 ) -> List[List[Optional[HALDAResult]]]:
     """Per fleet, the list whose entry i is `halda_solve_batch` of the fleet without device i (None where
     no k is feasible; [None] for a one-device fleet), all fleets' lists in one GPU call per chunk of
-    SUBFLEET_CHUNK_DEVICES listed devices."""
+    SUBFLEET_CHUNK_DEVICES listed devices. bounds: one entry per fleet as halda_solve_bounded_batch takes them
+    (None, (w_min, w_max) or (w_min, w_max, n_min, n_max)); entry i is then the best plan of the fleet without
+    device i inside the survivors' part of the fleet's box (halda_solve_subfleets_bounded)."""
     fleets = fleets if isinstance(fleets, (list, tuple)) else list(fleets)
     sizes = [len(d) for d in fleets]
+    boxed = None
+    if bounds is not None:
+        from .subfleets_bounded import check_one_box  # (it imports this module)
+
+        boxed = check_one_box(bounds, sizes)
     parent, sub_off, sub_idx = leave_one_out_items(sizes)
     # The output lists are made BEFORE the solve and filled by index afterwards: the result builder makes its
     # ~9 containers per result with the cyclic GC paused (fleetpack.c results), so the first container
@@ -310,7 +336,11 @@ def halda_leave_one_out_batch(
     # halda_solve_batch returns the builder's list as it is; this entry allocates nothing after it either.
     n_f = len(sizes)
     out = [[None] * M for M in sizes]
-    flat = _solve_arrays(fleets, model, parent, sub_off, sub_idx, k_candidates, kv_bits, device)
+    if boxed is None:
+        flat = _solve_arrays(fleets, model, parent, sub_off, sub_idx, k_candidates, kv_bits, device)
+    else:
+        flat = _solve_arrays(fleets, model, parent, sub_off, sub_idx, k_candidates, kv_bits, device,
+                             (boxed, np.zeros(len(parent), np.int32)))
     a = 0
     for f in range(n_f):
         M = sizes[f]
@@ -329,10 +359,14 @@ def halda_leave_one_out(
     mip_gap: Optional[float] = 1e-4,
     kv_bits: str = "8bit",
     device: int = 0,
+    bounds=None,
 ) -> List[Optional[HALDAResult]]:
     """The plan if device i drops out, for every i: entry i is `halda_solve_batch` of the fleet without
-    device i (None where no k is feasible). A one-device fleet gives [None]."""
-    return halda_leave_one_out_batch([list(devs)], model, k_candidates, mip_gap, kv_bits, device)[0]
+    device i (None where no k is feasible). A one-device fleet gives [None]. bounds: the fleet's box (None,
+    (w_min, w_max) or (w_min, w_max, n_min, n_max)); entry i then stays inside the survivors' part of it."""
+    if bounds is None:
+        return halda_leave_one_out_batch([list(devs)], model, k_candidates, mip_gap, kv_bits, device)[0]
+    return halda_leave_one_out_batch([list(devs)], model, k_candidates, mip_gap, kv_bits, device, [bounds])[0]
 
 
 def halda_select_devices(
@@ -343,6 +377,7 @@ def halda_select_devices(
     kv_bits: str = "8bit",
     device: int = 0,
     _solve_lists: Optional[Callable[[List[List[int]]], List[Optional[HALDAResult]]]] = None,
+    bounds=None,
 ) -> Tuple[List[int], HALDAResult]:
     """Which devices to leave out: greedy backward elimination on top of leave-one-out. Starting from the
     full fleet, each round solves the kept devices without each one of them and drops the device whose
@@ -350,12 +385,19 @@ def halda_select_devices(
     when no removal improves or one device is left. Returns (kept indices into `devs`, ascending; the
     HALDAResult of that sub-fleet, indexed within the kept list). A heuristic over subsets (at most
     M (M + 1) / 2 of them), not the optimum over all 2^M. RuntimeError when neither the fleet nor any
-    sub-fleet met on the way is feasible. `_solve_lists` (tests): the solve of a list of index lists."""
+    sub-fleet met on the way is feasible. `_solve_lists` (tests): the solve of a list of index lists.
+    bounds: the fleet's box (None, (w_min, w_max) or (w_min, w_max, n_min, n_max)); every sub-fleet of the walk
+    is then solved inside its devices' part of the box (halda_solve_subfleets_bounded), the greedy rule unchanged."""
     devs = list(devs)
     if not devs:
         raise IndexError("list index out of range")  # the reference's kappa on an empty fleet
 
     def on_gpu(lists):
+        if bounds is not None:
+            from .subfleets_bounded import halda_solve_subfleets_bounded  # (it imports this module)
+
+            return halda_solve_subfleets_bounded([devs], model, [(0, s) for s in lists], [[bounds]], k_candidates,
+                                                 kv_bits, device)
         return halda_solve_subfleets([devs], model, [(0, s) for s in lists], k_candidates, mip_gap, kv_bits, device)
 
     solve = _solve_lists or on_gpu
