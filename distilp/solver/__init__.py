@@ -21,6 +21,7 @@ from distilp_amd.solver import (ReloadPoint, halda_reload_frontier, halda_solve_
 from distilp_amd.solver import (PartitionPoint, halda_partition, halda_partition_frontier,  # noqa: F401
                                 halda_partition_frontier_batch)
 from distilp_amd.solver import halda_solve_subfleets_bounded  # noqa: F401
+from distilp_amd.solver import halda_subset_frontier_boxes  # noqa: F401
 
 __all__ = ["halda_solve", "HALDAResult"]
 

@@ -41,6 +41,9 @@ workgroup kernel (halda_solve_fleets_boxes_wide); with any other value they call
 `without NAME (bounded): k=K, obj=OBJ` line per device (or `without NAME (bounded): infeasible`): the fleet without
 that device inside the survivors' part of the box those flags built (halda_leave_one_out with bounds=; with
 --max-move at the incumbent's k). --leave-one-out itself is unchanged.
+--select-devices-bounded [D] (with --cpu-only or --max-move, honouring --keep) prints, last of all, the exact
+selection inside those bounds: `drop d (bounded): dropped=[...], k=..., obj=...` or `drop d (bounded): infeasible`
+per point, then `selected (bounded): kept=[...]`. --select-devices itself is unchanged.
 --cpu-only NAME_OR_INDEX ... solves with those devices' GPUs unused (n_max = 0 on them,
 halda_solve_bounded) and prints the usual output for that solve. Without these flags the output is unchanged.
 """
@@ -282,6 +285,28 @@ def select_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: flo
     return out
 
 
+def select_bounded_lines(devices: List[DeviceProfile], model: ModelProfile, mip_gap: float, max_drop: Optional[int],
+                         keep: Sequence[int], box, k: Optional[int] = None) -> List[str]:
+    """--select-devices-bounded [D] [--keep ...]: select_lines inside `box` (halda_subset_frontier with bounds=:
+    a kept device stays under its own entry of the box, a dropped device's entry does not apply; at the
+    incumbent's k alone when the box is a move box around it)."""
+    from ..solver.subsets import halda_subset_frontier, select_point
+
+    pts = halda_subset_frontier(devices, model, max_drop, keep or None, None if k is None else [k], mip_gap=mip_gap,
+                                kv_bits="4bit", bounds=box)
+    out = []
+    for d, pt in enumerate(pts):
+        if pt.result is None:
+            out.append(f"drop {d} (bounded): infeasible")
+        else:
+            out.append(f"drop {d} (bounded): dropped=[{', '.join(devices[i].name for i in pt.dropped)}], "
+                       f"k={pt.result.k}, obj={pt.obj_value:.6f}")
+    best = select_point(pts)
+    out.append("selected (bounded): infeasible" if best is None
+               else f"selected (bounded): kept=[{', '.join(devices[i].name for i in best.kept)}]")
+    return out
+
+
 def replica_lines(devices: List[DeviceProfile], model: ModelProfile, replicas: int, criterion: str,
                   route: str = "masks") -> List[str]:
     """--replicas R [--criterion max|sum] [--replica-route masks|classes|auto]: one line per point of
@@ -366,6 +391,9 @@ def _parser() -> argparse.ArgumentParser:
     o.add_argument("--evaluate-solution", metavar="FILE",
                    help="After the solution, price the plan of a --save-solution JSON on this fleet: its objective "
                         "(or why it is infeasible), its regret against the solution and the layers that would move")
+    o.add_argument("--select-devices-bounded", nargs="?", type=int, const=-1, default=None, metavar="D",
+                   help="With --cpu-only or --max-move: after everything else, the exact selection over every sub-fleet "
+                        "that leaves out at most D devices (default: any number) inside the same bounds; honours --keep")
     o.add_argument("--max-move", type=int, metavar="D",
                    help="With --evaluate-solution: also print the best plan at that plan's k that moves at most D "
                         "layers per device away from it")
@@ -453,8 +481,10 @@ def main(argv=None) -> int:
         parser.error("--scale-in requires --evaluate-solution and --failover")
     if args.scale_in is not None and args.scale_in < 0:
         parser.error("--scale-in must be >= 0")
-    if args.keep and args.select_devices is None and args.scale_in is None:
-        parser.error("--keep requires --select-devices or --scale-in")
+    if args.select_devices_bounded is not None and not args.cpu_only and args.max_move is None:
+        parser.error("--select-devices-bounded requires --cpu-only or --max-move")
+    if args.keep and args.select_devices is None and args.scale_in is None and args.select_devices_bounded is None:
+        parser.error("--keep requires --select-devices, --select-devices-bounded or --scale-in")
     n_max = None
     if args.cpu_only:
         try:
@@ -579,6 +609,18 @@ def main(argv=None) -> int:
         box = bounded_box(n_max, incumbent, args.max_move, args.max_move_n)
         k = incumbent[0] if args.max_move is not None else None
         for line in leave_one_out_bounded_lines(devices, model, args.mip_gap, box, k):
+            print(line)
+    if args.select_devices_bounded is not None:
+        box = bounded_box(n_max, incumbent, args.max_move, args.max_move_n)
+        try:
+            lines = select_bounded_lines(devices, model, args.mip_gap,
+                                         None if args.select_devices_bounded == -1 else args.select_devices_bounded,
+                                         pick_indices(devices, args.keep), box,
+                                         incumbent[0] if args.max_move is not None else None)
+        except (ValueError, IndexError) as e:
+            print(f"error: --select-devices-bounded: {e}", file=sys.stderr)
+            return 2
+        for line in lines:
             print(line)
     return 0
 

@@ -37,6 +37,7 @@
 #include "halda_boxes.h"
 #include "halda_boxes_wide.h"
 #include "halda_subfleets_boxed.h"
+#include "halda_subsets_boxed.h"
 #include "halda_wide.h"
 #include "halda_partition.h"
 #include "halda_partition_classes.h"
@@ -63,6 +64,7 @@ bool in_host_block(const void *p, size_t bytes) {
 #include "halda_solve.hpp"
 #include "halda_sweep.hpp"
 #include "halda_boxes_wide.hpp"
+#include "halda_subsets_box.hpp"
 #include "halda_rank.hpp"
 
 // ------------------------------------------------------------------ host side
@@ -182,6 +184,10 @@ struct Ctx {
     // halda_solve_subfleets_boxed's own (include/halda_subfleets_boxed.h): path 0 automatic, 1 always expansion;
     // routes 1 register launch, 3 table launch, 2 expansion
     lrec::Knob sub_box;
+    // halda_solve_subsets_boxed's own (include/halda_subsets_boxed.h): path 0 automatic, 1 always expansion;
+    // routes 1 register launch, 3 table launch, 2 expansion, 4 mixed by d; and its launches' item cap (0: default)
+    lrec::Knob sel_box;
+    int64_t sel_box_chunk = 0;
     halda_batch last_lowered = {};
     halda_result last_solved = {};
     bool have_lowered = false;
@@ -2358,11 +2364,18 @@ struct SubsetLaunch {
     int lmin, lmax;         // expansion: the shortest and longest list of the launch
 };
 
-// sizes: every fleet's device count (host); keep: host masks or NULL
-static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets *table, const int32_t *sizes,
-                         const halda_subsets *subsets, const int32_t *ks, int32_t n_k,
-                         halda_subset_frontier *frontier, void *stream) {
-    Ctx *c = static_cast<Ctx *>(ctx);
+// halda_solve_subsets' argument checks and gate, from the shapes alone (halda_solve_subsets_boxed takes them word
+// for word). sizes: every fleet's device count (host). Out: per fleet its droppable devices, their count q and the
+// most it may drop, min(max_drop, q, M - 1); *uniform: every fleet of one size.
+struct SubsetGate {
+    std::vector<uint64_t> drop;
+    std::vector<int> qs, Df;
+    bool uniform = true;
+};
+
+static int subsets_gate(const halda_model *model, const halda_fleets *table, const int32_t *sizes,
+                        const halda_subsets *subsets, const int32_t *ks, int32_t n_k,
+                        const halda_subset_frontier *frontier, SubsetGate *G) {
     const int nf = table->n_fleets, D = subsets->max_drop;
     const uint64_t *keep = subsets->keep_mask;
     if (!frontier->status || !frontier->obj || !frontier->dropped_mask || !frontier->best_k)
@@ -2373,9 +2386,11 @@ static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets
     for (int j = 0; j < n_k; ++j)
         if (ks[j] < 1 || (j && ks[j] <= ks[j - 1])) return fail(HALDA_E_ARG, "ks must be ascending, unique, > 0");
     if (!stage::complete(*table)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
-    // the gate, from the shapes alone
-    std::vector<uint64_t> drop(nf);
-    std::vector<int> qs(nf), Df(nf);
+    std::vector<uint64_t> &drop = G->drop;
+    std::vector<int> &qs = G->qs, &Df = G->Df;
+    drop.assign(nf, 0);
+    qs.assign(nf, 0);
+    Df.assign(nf, 0);
     int Dmax = -1;
     bool uniform = true;
     for (int f = 0; f < nf; ++f) {
@@ -2400,6 +2415,21 @@ static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets
     if (D > Dmax)
         return fail(HALDA_E_ARG, "halda_subsets: max_drop " + std::to_string(D) + " is beyond min(q, M - 1) = " +
                                      std::to_string(Dmax) + " of every fleet");
+    G->uniform = uniform;
+    return HALDA_OK;
+}
+
+// sizes: every fleet's device count (host); keep: host masks or NULL
+static int solve_subsets(void *ctx, const halda_model *model, const halda_fleets *table, const int32_t *sizes,
+                         const halda_subsets *subsets, const int32_t *ks, int32_t n_k,
+                         halda_subset_frontier *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int nf = table->n_fleets, D = subsets->max_drop;
+    SubsetGate gate;
+    if (const int rc = subsets_gate(model, table, sizes, subsets, ks, n_k, frontier, &gate)) return rc;
+    const std::vector<uint64_t> &drop = gate.drop;
+    const std::vector<int> &qs = gate.qs, &Df = gate.Df;
+    const bool uniform = gate.uniform;
     hipStream_t s = nullptr;
     if (const int rc = enter(c, stream, &s)) return rc;
     // the combo lists of every (q, d) in use, and the records per (d, fleet)
@@ -3436,6 +3466,327 @@ int halda_solve_subfleets_boxed_host(void *ctx, const halda_model *model, const 
     halda_fleet_result r = stage::bind_result(base, R, *out_h);
     rc = solve_subfleets_boxed(ctx, model, &d, &di, ks, n_k, &db, &r, s, tot);
     if (rc == HALDA_OK) rc = download(stage::result_copies(R, *out_h), base, s);
+    if (rc != HALDA_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return HALDA_OK;
+}
+
+// ---------------------------------------------------------------- exact device selection under boxes
+// halda_solve_subsets_boxed (include/halda_subsets_boxed.h): halda_solve_subsets' candidates, each priced under
+// every box as halda_solve_subfleets_boxed prices item (fleet, kept list, box), and the frontier over (box, fleet,
+// d). The host lays out what solve_subsets lays out (one SubsetFleet per (d, fleet), one combo list per (q, d)),
+// uploads both once and works d by d; an item is (fleet, box, candidate), candidate innermost
+// (halda_subsets_box.hpp). Per d, from the shapes alone: the register route (every fleet of one size, the boxed
+// entry's fused gate over the d's items), else the table route (the lists' unbounded slice within the LDS
+// budget), else expansion (halda_subsets_box_index_kernel, then solve_subfleets_boxed on its expansion path, in
+// chunks of at most kSubsetsChunkDevices listed devices cut at candidate boundaries). A launch takes at most
+// sel_box_chunk items and is followed by halda_subsets_box_pick_kernel. Everything lives in the context's
+// grow-only sel_buf (order_after_previous).
+int halda_set_subsets_boxed_path(void *ctx, int path) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (path != 0 && path != 1)
+        return fail(HALDA_E_ARG, "subsets boxed path must be 0 (automatic) or 1 (always expand)");
+    c->sel_box.path = path;
+    return HALDA_OK;
+}
+
+int halda_last_subsets_boxed_route(void *ctx, int *route) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !route) return fail(HALDA_E_ARG, "NULL ctx/route");
+    *route = c->sel_box.route;
+    return HALDA_OK;
+}
+
+int halda_set_subsets_boxed_chunk(void *ctx, int64_t items) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c) return fail(HALDA_E_ARG, "NULL ctx");
+    if (items < 0 || items > kSubsetsFusedChunk)
+        return fail(HALDA_E_ARG, "subsets boxed chunk must be 0 (the default) or 1 .. 2^22 items");
+    c->sel_box_chunk = items;
+    return HALDA_OK;
+}
+
+static int check_boxes_arg(const halda_boxes *boxes) {
+    if (!boxes) return fail(HALDA_E_ARG, "halda_solve_subsets_boxed: NULL boxes");
+    if (boxes->n_box < 1 || boxes->n_box > 65535) return fail(HALDA_E_ARG, "n_box must be in 1..65535");
+    return HALDA_OK;
+}
+
+struct SubsetBoxLaunch {
+    int d, route;           // 1 register, 3 table, 2 expansion
+    int64_t i0, n, l0, nd;  // first item, items; expansion: listed devices in front of it, its listed devices
+    int lmin, lmax;         // the shortest and longest list (table: of the d, expansion: of the launch)
+    int64_t cmax;           // register: item slots per (fleet, box) group
+};
+
+// sizes: every fleet's device count (host); keep: host masks or NULL
+static int solve_subsets_boxed(void *ctx, const halda_model *model, const halda_fleets *table, const int32_t *sizes,
+                               const halda_subsets *subsets, const int32_t *ks, int32_t n_k, const halda_boxes *boxes,
+                               halda_subset_frontier *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    const int nf = table->n_fleets, D = subsets->max_drop;
+    const int64_t nb = boxes->n_box;
+    SubsetGate gate;
+    if (const int rc = subsets_gate(model, table, sizes, subsets, ks, n_k, frontier, &gate)) return rc;
+    hipStream_t s = nullptr;
+    if (const int rc = enter(c, stream, &s)) return rc;
+    const int64_t chunk = c->sel_box_chunk > 0 ? c->sel_box_chunk : kSubsetsFusedChunk;
+    const bool may_fuse = c->sel_box.path == 0 && c->fleets_fused && n_k <= 64;
+    std::vector<uint64_t> combos;
+    std::vector<int64_t> coff(65 * 64, -1);
+    std::vector<SubsetFleet> recs(size_t(D + 1) * nf);
+    std::vector<SubsetBoxLaunch> launches;
+    int64_t max_items = 0, max_dev = 0;
+    bool any_fused = false;
+    unsigned routes = 0;  // bit r: some d took route r
+    for (int d = 0; d <= D; ++d) {
+        SubsetFleet *R = recs.data() + size_t(d) * nf;
+        int64_t cmax = 0, items = 0, devs = 0;
+        int lmin = 64, lmax = 0;
+        for (int f = 0; f < nf; ++f) {
+            SubsetFleet &r = R[f];
+            r = SubsetFleet{};
+            r.drop_mask = gate.drop[f];
+            r.M = sizes[f];
+            r.cnt = d <= gate.Df[f] ? int32_t(binom_sat(gate.qs[f], d)) : 0;
+            // the compact numbering, per box: the kernels scale both offsets by n_box
+            r.item_off = items;
+            r.list_off = devs;
+            if (r.cnt > 0) {
+                int64_t &o = coff[size_t(gate.qs[f]) * 64 + d];
+                if (o < 0) {
+                    o = int64_t(combos.size());
+                    subset_combos(gate.qs[f], d, combos);
+                }
+                r.combo_off = o;
+                lmin = std::min(lmin, sizes[f] - d);
+                lmax = std::max(lmax, sizes[f] - d);
+            }
+            cmax = std::max<int64_t>(cmax, r.cnt);
+            items += r.cnt;
+            devs += int64_t(r.cnt) * (sizes[f] - d);
+        }
+        const int64_t padded = cmax * nf * nb, total = items * nb;
+        int route = 2;
+        if (may_fuse && gate.uniform && padded < (int64_t(1) << 31)) {
+            halda_fleets V = *table;
+            V.n_fleets = int32_t(std::min(padded, chunk));
+            V.min_devices = V.max_devices = sizes[0] - d;
+            halda_fleet_result o = {};
+            SweepPlan p;
+            if (const int rc = plan_sweep(c, *model, V, ks, n_k, o, &p)) return rc;
+            if (p.kind == kRegAlone && p.A.uM > 0 && p.A.uM <= kK1MaxM) route = 1;
+        }
+        if (route == 2 && may_fuse && total < (int64_t(1) << 31) && lmin >= 1 && lmax <= kK1MaxM) {
+            halda_fleets V = *table;
+            V.n_fleets = int32_t(std::min(total, chunk));
+            V.min_devices = lmin;
+            V.max_devices = lmax;
+            halda_fleet_result o = {};
+            SweepPlan p;
+            if (const int rc = plan_sweep(c, *model, V, ks, n_k, o, &p)) return rc;
+            if (p.slice <= kLdsBudget) route = 3;
+        }
+        routes |= 1u << route;
+        if (route != 2) {
+            const int64_t all = route == 1 ? padded : total;
+            for (int64_t a = 0; a < all; a += chunk)
+                launches.push_back(SubsetBoxLaunch{d, route, a, std::min(chunk, all - a), 0, 0, lmin, lmax, cmax});
+            max_items = std::max(max_items, std::min(chunk, all));
+            any_fused = true;
+            continue;
+        }
+        // expansion: fleet f's n_box * cnt items of sizes[f] - d listed devices each, in chunks of at most `chunk`
+        // items and kSubsetsChunkDevices listed devices (an item is never split)
+        int f = 0;
+        int64_t a = 0;
+        while (a < total) {
+            SubsetBoxLaunch L{d, 2, a, 0, 0, 0, 64, 0, 0};
+            while (R[f].cnt == 0 || (R[f].item_off + R[f].cnt) * nb <= a) ++f;
+            L.l0 = R[f].list_off * nb + (a - R[f].item_off * nb) * (sizes[f] - d);
+            int64_t b = a;
+            for (int g = f; g < nf && b < total; ++g) {
+                if (R[g].cnt == 0) continue;
+                const int len = sizes[g] - d;
+                const int64_t left = (R[g].item_off + R[g].cnt) * nb - b;
+                const int64_t take = std::min({left, (kSubsetsChunkDevices - L.nd) / len, chunk - L.n});
+                if (take <= 0) break;
+                L.n += take;
+                L.nd += take * len;
+                L.lmin = std::min(L.lmin, len);
+                L.lmax = std::max(L.lmax, len);
+                b += take;
+                if (take < left) break;
+            }
+            launches.push_back(L);
+            max_items = std::max(max_items, L.n);
+            max_dev = std::max(max_dev, L.nd);
+            a = b;
+        }
+    }
+    // scratch: combos, records, per-item results, then the fused ring or the expansion's item arrays and w / n
+    stage::Bump lay;
+    const size_t o_combo = lay.take(8 * combos.size()), o_rec = lay.take(sizeof(SubsetFleet) * recs.size()),
+                 o_obj = lay.take(8 * size_t(max_items)), o_bk = lay.take(4 * size_t(max_items)),
+                 o_par = lay.take(4 * size_t(max_items)), o_ibox = lay.take(4 * size_t(max_items)),
+                 o_soff = lay.take(8 * size_t(max_items + 1));
+    const size_t wn = std::max<size_t>(size_t(max_dev), any_fused ? size_t(kSubsetsRing) * 64 : 0);
+    const size_t o_sidx = lay.take(4 * size_t(max_dev)), o_w = lay.take(4 * wn), o_n = lay.take(4 * wn);
+    {
+        int rc = order_after_previous(c, s);
+        if (rc == HALDA_OK) rc = grow(&c->sel_buf, &c->sel_bytes, lay.off);
+        if (rc != HALDA_OK) return rc;
+    }
+    char *base = reinterpret_cast<char *>(c->sel_buf);
+    // (pageable sources: the copies are staged before the calls return)
+    HIP_TRY(hipMemcpyAsync(base + o_combo, combos.data(), 8 * combos.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(base + o_rec, recs.data(), sizeof(SubsetFleet) * recs.size(), hipMemcpyHostToDevice, s));
+    halda_fleet_result out = {};
+    out.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+    out.obj_value = reinterpret_cast<double *>(base + o_obj);
+    out.w = reinterpret_cast<int32_t *>(base + o_w);
+    out.n = reinterpret_cast<int32_t *>(base + o_n);
+    const SubsetFrontier FR{frontier->status, frontier->obj, frontier->dropped_mask, frontier->best_k};
+    const SubBoxArgs X{boxes->w_min, boxes->w_max, boxes->n_min, boxes->n_max, nullptr, nf};
+    c->fleet_timed = false;
+    for (const SubsetBoxLaunch &L : launches) {
+        SubsetArgs U = {};
+        U.fl = reinterpret_cast<const SubsetFleet *>(base + o_rec) + size_t(L.d) * nf;
+        U.combos = reinterpret_cast<const uint64_t *>(base + o_combo);
+        U.i0 = L.i0;
+        U.n = int32_t(L.n);
+        U.n_fleets = nf;
+        U.d = L.d;
+        if (L.route != 2) {
+            U.cmax = L.route == 1 ? int32_t(L.cmax) : 0;
+            halda_fleets V = *table;
+            V.n_fleets = int32_t(L.n);
+            V.min_devices = L.route == 1 ? sizes[0] - L.d : L.lmin;
+            V.max_devices = L.route == 1 ? sizes[0] - L.d : L.lmax;
+            SweepPlan p;
+            if (const int rc = plan_sweep(c, *model, V, ks, n_k, out, &p)) return rc;
+            // The route was decided on min(items, chunk) fleets and this plan is for L.n of them: plan_sweep's
+            // kRegAlone and slice depend on the list shapes alone, not on the fleet count. Held here, so that an
+            // edit to its small-batch rule cannot launch the register kernel on a table plan.
+            if (L.route == 1 ? p.kind != kRegAlone : p.slice > kLdsBudget)
+                return fail(HALDA_E_ARG, "halda_solve_subsets_boxed: a launch's plan left the route chosen for its d");
+            // (no events, no record, and fleet_timed as an expansion launch of this call may have left it)
+            stamp(c, p.A, nullptr, c->hb_flag);
+            c->have_lowered = false;
+            if (L.route == 1) {
+                hipLaunchKernelGGL(halda_sweep_subsets_box_kernel,
+                                   dim3(unsigned((L.n + kSweepWavesPerBlock - 1) / kSweepWavesPerBlock)),
+                                   dim3(64 * kSweepWavesPerBlock), 0, s, p.A, U, X, int(nb), kSubsetsRing - 1);
+            } else {
+                const void *fn = reinterpret_cast<const void *>(halda_sweep_subsets_box_tables_kernel);
+                int per_cu = 0;
+                HIP_TRY(c->occupancy(fn, p.slice, &per_cu));  // also raises the kernel's dynamic-LDS limit
+                const unsigned grid = unsigned(std::max<int64_t>(1, std::min<int64_t>(int64_t(c->cus) * per_cu, L.n)));
+                hipLaunchKernelGGL(halda_sweep_subsets_box_tables_kernel, dim3(grid), dim3(64), size_t(p.slice), s, p.A,
+                                   U, X, int(nb), kSubsetsRing - 1);
+            }
+            HIP_TRY(hipGetLastError());
+        } else {
+            U.l0 = L.l0;
+            halda_subfleets I;
+            I.n_items = int32_t(L.n);
+            I.min_devices = L.lmin;
+            I.max_devices = L.lmax;
+            I.parent = reinterpret_cast<const int32_t *>(base + o_par);
+            I.sub_off = reinterpret_cast<const int64_t *>(base + o_soff);
+            I.sub_idx = reinterpret_cast<const int32_t *>(base + o_sidx);
+            hipLaunchKernelGGL(halda_subsets_box_index_kernel, dim3(unsigned((L.n + 3) / 4)), dim3(256), 0, s, U, int(nb),
+                               reinterpret_cast<int32_t *>(base + o_par), reinterpret_cast<int64_t *>(base + o_soff),
+                               reinterpret_cast<int32_t *>(base + o_sidx), reinterpret_cast<int32_t *>(base + o_ibox));
+            HIP_TRY(hipGetLastError());
+            // the sub-fleet boxed entry's expansion route, unedited, on the items just written
+            const halda_sub_boxes SB = {boxes->n_box, boxes->w_min, boxes->w_max, boxes->n_min, boxes->n_max,
+                                        reinterpret_cast<const int32_t *>(base + o_ibox)};
+            const lrec::PathOverride expand(c->sub_box, 1, /*keep_route=*/true);
+            if (const int rc = solve_subfleets_boxed(ctx, model, table, &I, ks, n_k, &SB, &out, s, L.nd)) return rc;
+        }
+        hipLaunchKernelGGL(halda_subsets_box_pick_kernel, dim3(unsigned(nf), unsigned(nb)), dim3(256), 0, s, U, int(nb),
+                           static_cast<const double *>(out.obj_value), static_cast<const int32_t *>(out.best_k), FR,
+                           D + 1);
+        HIP_TRY(hipGetLastError());
+    }
+    c->sel_box.route = routes == (1u << 1) ? 1 : routes == (1u << 2) ? 2 : routes == (1u << 3) ? 3 : 4;
+    return HALDA_OK;
+}
+
+int halda_solve_subsets_boxed(void *ctx, const halda_model *model, const halda_fleets *fleets,
+                              const halda_subsets *subsets, const int32_t *ks, int32_t n_k, const halda_boxes *boxes,
+                              halda_subset_frontier *frontier, void *stream) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !fleets || !subsets || !ks || !frontier)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/ks/frontier");
+    if (const int rc = check_boxes_arg(boxes)) return rc;
+    const int64_t nf = fleets->n_fleets;
+    if (nf <= 0) return HALDA_OK;
+    if (!fleets->dev_off) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    std::vector<int32_t> sizes(size_t(nf), fleets->max_devices);
+    if (fleets->min_devices != fleets->max_devices) {
+        HIP_TRY(hipSetDevice(c->device));
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+        std::vector<int64_t> off(size_t(nf) + 1);
+        HIP_TRY(hipMemcpyAsync(off.data(), fleets->dev_off, 8 * (nf + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int64_t f = 0; f < nf; ++f)
+            sizes[f] = int32_t(std::max<int64_t>(-1, std::min<int64_t>(off[f + 1] - off[f], 65)));
+    }
+    return solve_subsets_boxed(ctx, model, fleets, sizes.data(), subsets, ks, n_k, boxes, frontier, stream);
+}
+
+int halda_solve_subsets_boxed_host(void *ctx, const halda_model *model, const halda_fleets *th,
+                                   const halda_subsets *subsets, const int32_t *ks, int32_t n_k,
+                                   const halda_boxes *boxes, halda_subset_frontier *fh) {
+    Ctx *c = static_cast<Ctx *>(ctx);
+    if (!c || !model || !th || !subsets || !ks || !fh)
+        return fail(HALDA_E_ARG, "NULL ctx/model/fleets/subsets/ks/frontier");
+    if (const int rc = check_boxes_arg(boxes)) return rc;
+    if (th->n_fleets <= 0) return HALDA_OK;
+    if (!stage::complete(*th)) return fail(HALDA_E_ARG, "halda_fleets has a NULL array");
+    if (!fh->status || !fh->obj || !fh->dropped_mask || !fh->best_k)
+        return fail(HALDA_E_ARG, "halda_subset_frontier: NULL");
+    if (subsets->max_drop < 0 || subsets->max_drop > 63)
+        return fail(HALDA_E_ARG, "halda_subsets: max_drop must be in 0..63");
+    const int64_t nf = th->n_fleets, nd = th->dev_off[nf], nb = boxes->n_box;
+    if (nd < nf) return fail(HALDA_E_ARG, "bad device count");
+    std::vector<int32_t> sizes(size_t(nf), 0);
+    for (int64_t f = 0; f < nf; ++f)
+        sizes[f] = int32_t(std::max<int64_t>(-1, std::min<int64_t>(th->dev_off[f + 1] - th->dev_off[f], 65)));
+    // layout: the table, the planes that were passed, the frontier
+    const int32_t *bsrc[4] = {boxes->w_min, boxes->w_max, boxes->n_min, boxes->n_max};
+    const size_t pts = size_t(nb) * size_t(nf) * size_t(subsets->max_drop + 1);
+    stage::Bump lay;
+    const stage::TableLayout T = stage::lay_table(lay, nf, nd);
+    size_t o_b[4];
+    for (int a = 0; a < 4; ++a) o_b[a] = bsrc[a] ? lay.take(4 * nb * nd) : 0;
+    const size_t o_st = lay.take(4 * pts), o_obj = lay.take(8 * pts), o_mask = lay.take(8 * pts), o_bk = lay.take(4 * pts);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_scratch(c, lay.off);
+    char *base = static_cast<char *>(c->scratch);
+    if (rc == HALDA_OK) rc = upload(base, T, *th, s);
+    for (int a = 0; a < 4 && rc == HALDA_OK; ++a)
+        if (bsrc[a]) rc = upload(base, o_b[a], bsrc[a], 4 * nb * nd, s);
+    if (rc != HALDA_OK) return rc;
+    const halda_fleets d = stage::rebase(*th, base, T);
+    auto bdev = [&](int a) { return bsrc[a] ? reinterpret_cast<const int32_t *>(base + o_b[a]) : nullptr; };
+    const halda_boxes db = {boxes->n_box, bdev(0), bdev(1), bdev(2), bdev(3)};
+    halda_subset_frontier fd;
+    fd.status = reinterpret_cast<int32_t *>(base + o_st);
+    fd.obj = reinterpret_cast<double *>(base + o_obj);
+    fd.dropped_mask = reinterpret_cast<uint64_t *>(base + o_mask);
+    fd.best_k = reinterpret_cast<int32_t *>(base + o_bk);
+    rc = solve_subsets_boxed(ctx, model, &d, sizes.data(), subsets, ks, n_k, &db, &fd, s);
+    if (rc != HALDA_OK) return rc;
+    const std::array<stage::Copy, 4> back = {{{fh->status, o_st, 4 * pts},
+                                              {fh->obj, o_obj, 8 * pts},
+                                              {fh->dropped_mask, o_mask, 8 * pts},
+                                              {fh->best_k, o_bk, 4 * pts}}};
+    rc = download(back, base, s);
     if (rc != HALDA_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return HALDA_OK;

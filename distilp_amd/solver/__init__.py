@@ -20,6 +20,7 @@ from .scale import (ScalePoint, halda_scale_in, halda_scale_in_frontier, halda_s
 from .subfleets import (halda_leave_one_out, halda_leave_one_out_batch, halda_select_devices,  # noqa: F401
                         halda_solve_subfleets)
 from .subfleets_bounded import halda_solve_subfleets_bounded  # noqa: F401
+from .subsets_bounded import halda_subset_frontier_boxes  # noqa: F401
 from .subsets import (SubsetPoint, halda_select_devices_exact, halda_subset_frontier,  # noqa: F401
                       halda_subset_frontier_batch)
 from .variants import halda_context_sweep, halda_solve_variants, model_grid  # noqa: F401
@@ -36,6 +37,6 @@ __all__ = ["halda_solve", "halda_solve_batch", "halda_solve_fleets", "halda_solv
            "halda_scale_in_frontier", "halda_scale_in_frontier_batch", "halda_scale_in", "halda_scale_out_frontier",
            "ScalePoint", "halda_solve_boxes", "halda_solve_boxes_batch", "reload_caps", "halda_reload_frontier",
            "ReloadPoint", "ILPResult", "halda_partition_frontier", "halda_partition_frontier_batch",
-           "halda_partition", "PartitionPoint", "halda_solve_subfleets_bounded"]
+           "halda_partition", "PartitionPoint", "halda_solve_subfleets_bounded", "halda_subset_frontier_boxes"]
 
 __version__ = "0.1.2"  # the reference's solver module reports 0.1.2 (solver/__init__.py:13)

@@ -219,6 +219,16 @@ SUBBOX_PROTOTYPES = {
     **_knob("subfleets_boxed"),
 }
 
+# include/halda_subsets_boxed.h, the companion header of exact selection under boxes (it takes halda.h's
+# halda_subsets / halda_subset_frontier and halda_boxes.h's halda_boxes): its prototypes, applied by load_library
+# with the others (tests/test_subsets_bounded.py holds them to that header)
+SUBSETS_BOXED_PROTOTYPES = {
+    **_with_host("halda_solve_subsets_boxed", *_table, POINTER(HaldaSubsetsC), *_ks, POINTER(HaldaBoxesC),
+                 POINTER(HaldaSubsetFrontierC)),
+    **_knob("subsets_boxed"),
+    "halda_set_subsets_boxed_chunk": (c_int, [_vp, c_int64]),
+}
+
 # include/halda_boxes_wide.h, the companion header of the workgroup route of the many-boxes entry (it takes
 # halda_boxes.h's struct): its prototypes, applied by load_library with the others (tests/test_boxes_wide.py holds
 # them to that header)

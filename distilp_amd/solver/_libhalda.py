@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from ._abi import BOXES_PROTOTYPES, BOXES_WIDE_PROTOTYPES, EXPORTS, PROTOTYPES, HaldaBatchC, HaldaResultC  # noqa: F401 -- EXPORTS: the binding's surface
-from ._abi import PARTITION_CLASSES_PROTOTYPES, PARTITION_PROTOTYPES, SUBBOX_PROTOTYPES, WIDE_PROTOTYPES
+from ._abi import PARTITION_CLASSES_PROTOTYPES, PARTITION_PROTOTYPES, SUBBOX_PROTOTYPES, SUBSETS_BOXED_PROTOTYPES, WIDE_PROTOTYPES
 
 LIB_PATH = Path(os.environ.get("HALDA_LIB", Path(__file__).resolve().parent.parent / "libhalda.so"))
 
@@ -71,7 +71,8 @@ def load_library(path: Path | str | None = None):
         if lib.halda_version() != ABI_VERSION:
             raise HaldaUnavailable(f"{p} has ABI {lib.halda_version()}, this binding needs {ABI_VERSION}: rebuild it")
         for name, (restype, argtypes) in {**PROTOTYPES, **BOXES_PROTOTYPES, **BOXES_WIDE_PROTOTYPES, **WIDE_PROTOTYPES, **PARTITION_PROTOTYPES,
-                                          **PARTITION_CLASSES_PROTOTYPES, **SUBBOX_PROTOTYPES}.items():
+                                          **PARTITION_CLASSES_PROTOTYPES, **SUBBOX_PROTOTYPES,
+                                          **SUBSETS_BOXED_PROTOTYPES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         if path is None:
@@ -100,7 +101,8 @@ def ptr(a) -> Optional[int]:
 ROUTES = {"subfleets": ("none", "fused", "expand"), "subsets": ("none", "fused", "expand", "mixed"),
           "variants": ("none", "fused", "loop"), "plans": ("none", "fused", "two_launch"),
           "bounds": ("none", "fused", "general", "tables"), "boxes": ("none", "register", "loop", "tables"),
-          "subfleets_boxed": ("none", "register", "expand", "tables")}
+          "subfleets_boxed": ("none", "register", "expand", "tables"),
+          "subsets_boxed": ("none", "register", "expand", "tables", "mixed")}
 
 
 def set_path(ctx: "HaldaContext", family: str, path: int) -> None:

@@ -231,6 +231,50 @@ def _frontier_by_lists(M: int, slots: Sequence[int], D: int, solve: SolveLists) 
     return pts
 
 
+def selection_gate(fleets: List[list], keep, max_drop, route: str = "wave") -> Tuple[List[List[int]], int, List[int]]:
+    """The gate of a selection call, before any packing: (per fleet its droppable devices, max_drop as an int, per
+    fleet the most it may drop). The errors are halda_subset_frontier_batch's."""
+    if keep is not None and len(keep) != len(fleets):
+        raise ValueError(f"{len(keep)} keep entries for {len(fleets)} fleets")
+    slots, lim = [], []
+    for f, devs in enumerate(fleets):
+        if not devs:
+            raise IndexError("list index out of range")  # the reference's kappa on an empty fleet
+        if route == "wave" and len(devs) > MAX_DEVICES:
+            raise ValueError(f"exact selection needs fleets of at most {MAX_DEVICES} devices, fleet {f} has "
+                             f"{len(devs)}")
+        slots.append((droppable if route == "wave" else droppable_wide)(len(devs), None if keep is None else keep[f]))
+        lim.append(min(len(slots[f]), len(devs) - 1))
+    if not fleets:
+        return [], 0, []
+    D = check_max_drop(max_drop, max(lim) if route == "wave" else min(max(lim), MAX_DROP))
+    Df = [min(D, x) for x in lim]
+    for f in range(len(fleets)):
+        check_count(len(slots[f]), Df[f])
+    return slots, D, Df
+
+
+def check_candidate_heads(fleets, table, slots, Df, model) -> None:
+    """The packer's error that depends on kappa's head, for every head a candidate can have."""
+    par, hd = [], []
+    for f in range(len(fleets)):
+        o = int(table.dev_off[f])
+        for i in possible_heads(table.flags[o:o + len(fleets[f])], slots[f], Df[f]):
+            par.append(f)
+            hd.append(o + i)
+    check_item_heads(fleets, table, np.asarray(par, np.int64), np.asarray(hd, np.int64), model)
+
+
+def keep_mask_array(fleets, slots, keep, route: str = "wave") -> Optional[np.ndarray]:
+    """halda_subsets.keep_mask (route "wide": keep_words per fleet), or None where nothing is kept."""
+    if keep is None or not any(len(slots[f]) < len(fleets[f]) for f in range(len(fleets))):
+        return None
+    if route == "wide":
+        return np.asarray([keep_words(len(fleets[f]), slots[f]) for f in range(len(fleets))], np.uint64)
+    return np.asarray([sum(1 << i for i in range(len(fleets[f])) if i not in set(slots[f]))
+                       for f in range(len(fleets))], np.uint64)
+
+
 def solve_subsets_table(table, model: ModelProfile, pos: List[int], kv_factor: float, max_drop: int,
                         keep_masks: Optional[np.ndarray], device: int = 0, route: str = "wave"):
     """One halda_solve_subsets_host call on a packed table: (status, obj, dropped_mask, best_k), each
@@ -276,6 +320,7 @@ def halda_subset_frontier_batch(
     device: int = 0,
     _solve_lists: Optional[Callable[[int, List[List[int]]], List[Optional[HALDAResult]]]] = None,
     route: str = "wave",
+    bounds=None,
 ) -> List[List[SubsetPoint]]:
     """Per fleet its selection frontier: one SubsetPoint per d = 0 .. min(max_drop, q, M - 1), q the fleet's
     droppable devices (max_drop None: every d the fleet admits -- with nothing kept, every non-empty
@@ -286,26 +331,28 @@ def halda_subset_frontier_batch(
     keep index out of range or an empty fleet. `_solve_lists(f, lists)` (tests): the solve of index lists of
     fleet f, in place of the GPU. route: "wave" (default) is this call; "wide" takes fleets of up to 256 devices
     (ValueError beyond, for max_drop above 63 and for a keep index out of range); "auto" is "wave" where every
-    fleet has at most 64 devices and "wide" elsewhere."""
+    fleet has at most 64 devices and "wide" elsewhere.
+    bounds: one entry per fleet as halda_solve_bounded_batch takes them (None, (w_min, w_max) or (w_min, w_max,
+    n_min, n_max) over the fleet's devices): the exact selection inside that box (subsets_bounded.py) -- a kept
+    device stays under its own entry, a dropped device's entry does not apply, and each point's `result` is
+    halda_solve_subfleets_bounded's. The wave route only: ValueError for bounds on route "wide" (and on "auto"
+    where it resolves to "wide"). bounds=None calls exactly what was called before the keyword existed."""
     fleets = [list(d) for d in fleets]
     route = pick_route(route, [len(d) for d in fleets])
-    if keep is not None and len(keep) != len(fleets):
-        raise ValueError(f"{len(keep)} keep entries for {len(fleets)} fleets")
-    slots, lim = [], []
-    for f, devs in enumerate(fleets):
-        if not devs:
-            raise IndexError("list index out of range")  # the reference's kappa on an empty fleet
-        if route == "wave" and len(devs) > MAX_DEVICES:
-            raise ValueError(f"exact selection needs fleets of at most {MAX_DEVICES} devices, fleet {f} has "
-                             f"{len(devs)}")
-        slots.append((droppable if route == "wave" else droppable_wide)(len(devs), None if keep is None else keep[f]))
-        lim.append(min(len(slots[f]), len(devs) - 1))
+    if bounds is not None:
+        from .subfleets_bounded import check_one_box  # (these import this module)
+        from .subsets_bounded import frontier_boxes_batch
+
+        if route == "wide":
+            raise ValueError("bounds: exact selection under layer bounds serves the wave route only (fleets of at most "
+                             f"{MAX_DEVICES} devices), not route 'wide'")
+        check_one_box(bounds, [len(d) for d in fleets])
+        hook = None if _solve_lists is None else (lambda items: [_solve_lists(f, [kept])[0] for f, kept, _ in items])
+        return frontier_boxes_batch(fleets, model, [list(bounds)], max_drop, keep, k_candidates, kv_bits, device,
+                                    hook)[0]
+    slots, D, Df = selection_gate(fleets, keep, max_drop, route)
     if not fleets:
         return []
-    D = check_max_drop(max_drop, max(lim) if route == "wave" else min(max(lim), MAX_DROP))
-    Df = [min(D, x) for x in lim]
-    for f in range(len(fleets)):
-        check_count(len(slots[f]), Df[f])
     if _solve_lists is not None:
         return [_frontier_by_lists(len(fleets[f]), slots[f], Df[f], lambda ls, f=f: _solve_lists(f, ls))
                 for f in range(len(fleets))]
@@ -315,21 +362,8 @@ def halda_subset_frontier_batch(
     table = fleet_table(fleets, model, _reuse=True)
     if not pos:
         return [[_NO_POINT] * (Df[f] + 1) for f in range(len(fleets))]
-    # the packer's error that depends on kappa's head, for every head a candidate can have
-    par, hd = [], []
-    for f in range(len(fleets)):
-        o = int(table.dev_off[f])
-        for i in possible_heads(table.flags[o:o + len(fleets[f])], slots[f], Df[f]):
-            par.append(f)
-            hd.append(o + i)
-    check_item_heads(fleets, table, np.asarray(par, np.int64), np.asarray(hd, np.int64), model)
-    masks = None
-    if keep is not None and any(len(slots[f]) < len(fleets[f]) for f in range(len(fleets))):
-        if route == "wide":
-            masks = np.asarray([keep_words(len(fleets[f]), slots[f]) for f in range(len(fleets))], np.uint64)
-        else:
-            masks = np.asarray([sum(1 << i for i in range(len(fleets[f])) if i not in set(slots[f]))
-                                for f in range(len(fleets))], np.uint64)
+    check_candidate_heads(fleets, table, slots, Df, model)
+    masks = keep_mask_array(fleets, slots, keep, route)
     status, _, dmask, _ = solve_subsets_table(table, model, pos, kv_factor, D, masks, device, route)
     items, at = [], {}
     for f in range(len(fleets)):
@@ -369,12 +403,15 @@ def halda_subset_frontier(
     device: int = 0,
     _solve_lists: Optional[SolveLists] = None,
     route: str = "wave",
+    bounds=None,
 ) -> List[SubsetPoint]:
     """The selection frontier of one fleet: point d is the best sub-fleet with exactly d of the droppable
     devices (all but `keep`) left out, d = 0 .. max_drop (None: min(q, M - 1), every candidate there is).
     Point 0 is the full fleet. Each point's `result` equals
     `halda_solve_subfleets([devs], model, [(0, kept)])[0]` bit for bit. ValueError for max_drop beyond
-    min(q, M - 1); otherwise the errors of halda_subset_frontier_batch. route: as there."""
+    min(q, M - 1); otherwise the errors of halda_subset_frontier_batch. route: as there. bounds: the fleet's box
+    (None, (w_min, w_max) or (w_min, w_max, n_min, n_max)); the frontier is then the exact selection inside it and
+    each point's `result` halda_solve_subfleets_bounded's (wave route only: ValueError with route "wide")."""
     devs = list(devs)
     if not devs:
         raise IndexError("list index out of range")
@@ -382,7 +419,8 @@ def halda_subset_frontier(
         check_max_drop(max_drop, min(len(droppable(len(devs), keep)), len(devs) - 1))
     hook = None if _solve_lists is None else (lambda f, ls: _solve_lists(ls))
     return halda_subset_frontier_batch([devs], model, max_drop, None if keep is None else [keep], k_candidates,
-                                       mip_gap, kv_bits, device, hook, route)[0]
+                                       mip_gap, kv_bits, device, hook, route,
+                                       bounds=None if bounds is None else [bounds])[0]
 
 
 def select_point(points: Sequence[SubsetPoint]) -> Optional[SubsetPoint]:
@@ -406,13 +444,16 @@ def halda_select_devices_exact(
     device: int = 0,
     _solve_lists: Optional[SolveLists] = None,
     route: str = "wave",
+    bounds=None,
 ) -> Tuple[List[int], HALDAResult]:
     """Which devices to use: the optimum over every sub-fleet that leaves out at most max_drop of the
     droppable devices (None: over all of them), not halda_select_devices' greedy walk. Returns (kept
     indices into `devs`, ascending; the HALDAResult of that sub-fleet, indexed within the kept list).
-    RuntimeError when no sub-fleet is feasible. route: as in halda_subset_frontier_batch."""
+    RuntimeError when no sub-fleet is feasible. route: as in halda_subset_frontier_batch. bounds: the fleet's box,
+    as halda_subset_frontier takes it -- the optimum over the sub-fleets inside it (a device to pin AND keep goes in
+    `keep`; wave route only)."""
     best = select_point(halda_subset_frontier(devs, model, max_drop, keep, k_candidates, mip_gap, kv_bits, device,
-                                              _solve_lists, route))
+                                              _solve_lists, route, bounds=bounds))
     if best is None:
         raise RuntimeError("No feasible MILP found for any k this round.")
     return list(best.kept), best.result

@@ -6,7 +6,8 @@ wrote into the gfx950 code object (read with the ROCm LLVM tools, as tests/test_
     python tools/kernel_meta.py NEW.so --against OLD.so --out profiles/kernel_meta.json
 
 With --against, the output holds both builds and the list of kernels whose metadata differs or that only one
-build has; DESIGN.md cites it where it says the existing kernels are unchanged.
+build has; DESIGN.md cites it where it says the existing kernels are unchanged. --brief records, of the two
+builds, only the kernels that are new, gone or changed, and how many were compared.
 """
 
 from __future__ import annotations
@@ -47,6 +48,7 @@ def main() -> int:
     ap.add_argument("lib")
     ap.add_argument("--against", help="an older build to compare with")
     ap.add_argument("--out", help="also write the JSON to this file")
+    ap.add_argument("--brief", action="store_true", help="with --against: leave the unchanged kernels' tables out")
     args = ap.parse_args()
     new = kernel_meta(args.lib)
     res = {"kernels": new}
@@ -55,6 +57,11 @@ def main() -> int:
         res = {"this_build": new, "parent_build": old,
                "only_in_this_build": sorted(set(new) - set(old)), "only_in_parent_build": sorted(set(old) - set(new)),
                "changed": sorted(k for k in set(new) & set(old) if new[k] != old[k])}
+        if args.brief:
+            moved = set(res["only_in_this_build"]) | set(res["only_in_parent_build"]) | set(res["changed"])
+            res["compared"] = len(set(new) & set(old))
+            res["this_build"] = {k: v for k, v in new.items() if k in moved}
+            res["parent_build"] = {k: v for k, v in old.items() if k in moved}
     text = json.dumps(res, indent=1)
     print(text)
     if args.out:
